@@ -13,7 +13,12 @@ Workload = BASELINE.json's north star, configs[2]: SuperPointNet_gauss2_ssmall (
 (`--arch sp` = configs[1]).  A step is one full pair-training step on one batch of synthetic pairs already resident in
 HBM: 2 forwards (separate BatchNorm statistics), label ops, detector / sparse-descriptor / segmentation losses with
 on-device index sampling, multi-task loss, backward, gradient all-reduce (N > 1, overlapped with the tail of the
-backward pass), Adam.  Rank 0 prints ONE JSON line.
+backward pass), Adam.  Every step (warm-up and timed) starts from the same weights - one device copy of the flat parameter
+vector per step - so the forward and backward of every step compute the same function of the same inputs (the Adam moments
+and BatchNorm running statistics carry on: nothing in a training-mode step reads them before it updates them).  Carried from
+step to step, the weights would amplify the commit-order noise of the floating-point atomics (~1e-6): Adam maps a gradient that
+is pure rounding noise to an update of up to lr, and after 25 steps two runs differ by several per cent in their gradients.
+Rank 0 prints ONE JSON line.
 
 `roofline`: the dominant kernel of the step, conv_wino4_kernel (3x3 forward + data-gradient convolutions of the 240x320 /
 120x160 / 60x80 maps, Winograd F(4x4,3x3) in fp32), timed live with HIP events on the launch stream inside the library
@@ -29,6 +34,9 @@ rank 0, N = 1 only: batch 32, 1 warm-up + 3 timed steps.  `bf16` (fp32 line, N =
 the bf16 path (conv algorithm 12), 5 + 20 steps after the fp32 measurement, with its own `roofline` (bound "hbm": algorithmic bytes
 of the dominant kernel against 8 TB/s, PMC traffic from two more child passes); `--dtype bf16` makes that path the line.  `export`: BASELINE configs[4] beside the headline - 3 timed
 steps of 8 images (4 ssp_export_points calls of 2 images x 100 views, 480x640) after everything else; never part of `value`.
+`--dump-outputs DIR`: rank 0 writes the arrays of the last timed step (scalars, gradients, Adam moments, BatchNorm running
+statistics; float32 .npy, ~20 MB) to DIR, so that two builds run with the same arguments can be compared (dump_outputs); two runs
+of one build agree to the rounding of the atomics (bit for bit under SSP_DETERMINISTIC=1).
 """
 import argparse
 import csv
@@ -208,7 +216,10 @@ def side_block(Engine, what, arch, conv_algo, B, H, W, dev, sample, args, headli
     eng.set_conv_algo(conv_algo)
     eng.load_state_dict(synth.default_init_state_dict(layer_table(arch), seed=0))
 
+    start = eng.params.clone()  # every step starts from these weights (module docstring)
+
     def step(it):
+        eng.params.copy_(start)
         eng.zero_grad()
         eng.pair_step(sample, indices=None, seed=(it * 1000003 + 1), train=True, lambda_loss=1.0, lamda_d=1.0, multi_task=True, dense=dense)
         eng.adam_step(args.lr)
@@ -241,6 +252,30 @@ def side_block(Engine, what, arch, conv_algo, B, H, W, dev, sample, args, headli
     del eng
     torch.cuda.empty_cache()
     return blk
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: the arrays the timed path's last step computed, as float32 .npy files.  The inputs are seeded
+    (synth.make_pair, default_init_state_dict, the per-step sampler seeds) and every step starts from the same weights, so two
+    builds run with the same arguments can be compared file by file.  scalars: the SSP_N_SCALARS floats pair_step returns
+    (SCALAR_NAMES first); grads: the flat gradient bucket (parameters in param_layout order, then eta); adam_m / adam_v: the Adam
+    moments after the update, which with the step count and the weights the step started from determine it; bn_running: the
+    running statistics after the step.  The updated parameters themselves are not written: where a gradient is pure rounding noise (a convolution bias in
+    front of BatchNorm has a true gradient of 0), Adam's first step moves the weight by a noise-signed amount of up to lr, so they
+    differ from run to run by more than rounding at a few dozen elements.  Returns {name: shape}."""
+    import numpy as np
+    arrays = {"scalars": eng.scalars, "grads": eng.grads, "adam_m": eng.adam_m, "adam_v": eng.adam_v, "bn_running": eng.bn_running}
+    arrays = {k: v.detach().to("cpu", copy=True).float().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def parse_args(argv=None):
@@ -279,7 +314,13 @@ def parse_args(argv=None):
                          "segmentation head)")
     ap.add_argument("--no-bf16", action="store_true",
                     help="skip the `bf16` block of the fp32 line (BASELINE configs[3] per GPU: the same step on the bf16 path, conv algorithm 12)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32, rank 0): "
+                         "the step's scalars, its gradient bucket, the Adam moments after its update and the BatchNorm running "
+                         "statistics")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.dtype is not None:
         args.conv_algo = {"f32": 1, "bf16": 12}[args.dtype]
     return args
@@ -490,7 +531,10 @@ def main():
 
     PROF_EVERY = 4  # HIP events bracket the 3x3 launches of every 4th timed step (all of them cost ~1.7 % of the step)
 
+    start = eng.params.clone()  # every step starts from these weights (module docstring)
+
     def step(it):
+        eng.params.copy_(start)
         if profiling[0]:
             eng.profile_pause((it - args.warmup) % PROF_EVERY != 0)
         kw = dict(indices=None, seed=(it * 1000003 + rank * 7919 + 1), train=True, lambda_loss=1.0, lamda_d=1.0,
@@ -549,6 +593,7 @@ def main():
         dt = float(t.item())
 
     if rank == 0:
+        dumped = dump_outputs(eng, args.dump_outputs) if args.dump_outputs else None
         scal = dict(zip(SCALAR_NAMES, eng.scalars.cpu().tolist()))
         pairs_s = world * B * args.steps / dt
         prec = PRECISION.get(args.conv_algo, ("f32", "fp32"))
@@ -566,6 +611,8 @@ def main():
                # executes 1/4 resp. 16/36 of these multiplies, so it may exceed 1); the hardware fraction is roofline.frac
                "step_algorithmic_tflops_vs_fp32_mfma_peak": round(pairs_s * GFLOP_PER_PAIR[arch] / 1e3 / (PEAK_FP32_MFMA_TF * world), 4),
                "final_loss": round(scal["loss"], 4), "build_id": ssp.lib.build_id()[:16]}
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         # what explains this box (boxes of one pool differ by +-3 % in pairs/s): the shader clock the device sustains under fp32
         # matrix-core load right before and right after the timed region (ssp_clock_probe: 5 ms on every CU, 2400 MHz is the part's
         # maximum) and the socket's power cap / draw at start as rocm-smi reports them

@@ -361,6 +361,32 @@ def test_bench_dtype_flag_selects_the_conv_algorithm():
     assert b.parse_args([]).arch == "ssp" and b.parse_args([]).batch == 32  # the north-star workload is the default
 
 
+def test_bench_dump_outputs_writes_the_step_arrays(tmp_path):
+    """bench.py --dump-outputs DIR: the engine's step outputs land in DIR/<name>.npy as float32, within the 64 MB budget at the
+    benchmark's largest model; --steps must be positive (it is the number of timed steps)."""
+    import types
+    from semantic_superpoint_amd import lib as L
+    b = _load_bench()
+    assert b.parse_args(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path) and b.parse_args([]).dump_outputs is None
+    with pytest.raises(SystemExit):
+        b.parse_args(["--steps", "0"])
+    _, n = L.param_layout("SuperPointNet_gauss2_ssmall")
+    _, nb = L.bn_layout("SuperPointNet_gauss2_ssmall")
+    g = torch.Generator().manual_seed(0)
+    eng = types.SimpleNamespace(scalars=torch.rand(L.N_SCALARS, generator=g), bn_running=torch.rand(2 * nb, generator=g),
+                                **{k: torch.rand(n + 3, generator=g) for k in ("grads", "params", "adam_m", "adam_v")})
+    d = tmp_path / "out"
+    shapes = b.dump_outputs(eng, str(d))
+    assert sorted(shapes) == sorted(p.stem for p in d.glob("*.npy")) == ["adam_m", "adam_v", "bn_running", "grads", "scalars"]
+    total = 0
+    for k, shp in shapes.items():
+        a = np.load(d / (k + ".npy"))
+        assert a.dtype == np.float32 and list(a.shape) == shp
+        assert np.array_equal(a, getattr(eng, k).numpy()), k
+        total += a.nbytes
+    assert total <= 64 << 20
+
+
 def test_lds_layouts_are_conflict_free_under_the_lane_group_model():
     """The LDS layouts of the pipelined Winograd conv against the ds_read_b128 lane-group model of MI355X_MICROARCH.md
     (tools/lds_conflicts.py restates the kernel's offset formulas): fragment reads and the 8x32-tile transform reads take
