@@ -352,6 +352,41 @@ int ssp_detector_heatmap(ssp_handle* h, int slot, float* heat_dev, void* stream)
 int ssp_op_heatmap_nms(const float* heat_dev, const ssp_export_params* p, int n_maps, void* workspace_dev,
                        const float* labels_dev, float* nms_map_dev, float* pr_dev, void* stream);
 
+/* ---- descriptor export (export.py:66-190 export_descriptor; Val_model_heatmap.py:33-186) ------------------------
+ * ssp_describe_points: after ssp_forward(slot, train = 0) on n images (eval-mode BatchNorm, Val_model_heatmap.py:65),
+ *   the per-image body of get_pts_desc_from_agent (export.py:126-142) for the first n images of the slot:
+ *     run                 -> flattenDetection of the slot's detector logits (utils/utils.py:515-560)
+ *     heatmap_to_pts      -> getPtsFromHeatmap (models/model_wrap.py:266-293): threshold (fp32), greedy NMS, border
+ *                            removal, descending confidence (ties: lower row-major index), top_k when p->top_k > 0
+ *     soft_argmax_points  -> models/model_wrap.py:212-249 when p->subpixel (sx, sy of the rows, as ssp_export_points)
+ *     desc_to_sparseDesc  -> sample_desc_from_points (models/model_wrap.py:295-313) at the INTEGER points: bilinear
+ *                            grid_sample (align_corners=True, zeros padding) of the slot's L2-normalised coarse
+ *                            descriptor, x_n = x / (W/2) - 1, then divided by the fp32 L2 norm of the sampled vector.
+ *                            Image k samples its OWN map (the reference's grid has batch 1: an extension for n > 1).
+ *   p->n_views is ignored (>= 1); p->height / width must equal the slot's forward.  cap = ssp_export_max_points(p):
+ *   pts_dev [n][cap][5] rows (x, y, confidence, sx, sy), count_dev [n], desc_dev [n][cap][256] (rows < count written).
+ *   Returns -1 for a slot without a forward that computed descriptors, or shapes that do not match it.
+ *   workspace_dev: ssp_describe_workspace_bytes(p, n) bytes.
+ * ssp_op_sample_descriptors: the sampling step alone on a public NCHW desc [b,256,hc,wc] at explicit points
+ *   xy [b][cap][2] (x, y) with counts [b] (clamped to cap) -> out [b][cap][256].
+ * ssp_match_two_way: PointTracker.nn_match_two_way (models/model_wrap.py:451-497) for n_pairs pairs.  Pair p matches
+ *   desc1 + p*pair_stride*cap*256 (count1[p*pair_stride] rows of 256 unit vectors) against desc2 likewise:
+ *   dot = D1^T D2 in fp32 (matrix cores), d = sqrt(2 - 2 clip(dot, -1, 1)), row / column argmin of d (first index on
+ *   ties, as np.argmin), keep = d_row < nn_thresh && colargmin[rowargmin[i]] == i.  match_dev [n_pairs][cap][3] =
+ *   (i, j, d) as floats in ascending i, n_match_dev [n_pairs]; an empty side gives 0 matches.  pair_stride = 2 matches
+ *   the interleaved (image, warped image) output of ssp_describe_points.  cap <= SSP_MATCH_MAX_POINTS; nn_thresh < 0 is
+ *   refused (the reference raises ValueError).  workspace_dev: ssp_match_workspace_bytes(cap, n_pairs) bytes. */
+#define SSP_MATCH_MAX_POINTS 4096
+size_t ssp_describe_workspace_bytes(const ssp_export_params* p, int n);
+int ssp_describe_points(ssp_handle* h, int slot, const ssp_export_params* p, int n, void* workspace_dev, float* pts_dev,
+                        int32_t* count_dev, float* desc_dev, void* stream);
+int ssp_op_sample_descriptors(const float* desc_nchw_dev, int b, int hc, int wc, const float* xy_dev,
+                              const int32_t* counts_dev, int cap, float* out_dev, void* stream);
+size_t ssp_match_workspace_bytes(int cap, int n_pairs);
+int ssp_match_two_way(const float* desc1_dev, const int32_t* count1_dev, const float* desc2_dev, const int32_t* count2_dev,
+                      int cap, int n_pairs, int pair_stride, float nn_thresh, void* workspace_dev, float* match_dev,
+                      int32_t* n_match_dev, void* stream);
+
 /* BatchNorm2d(train) (+ReLU (+MaxPool2d(2))) backward. y: raw conv output NHWC; dout: gradient wrt the activated
  * (and pooled) output; stats4 = scale|shift|mean|invstd ([4*C]); dgamma/dbeta/dbias are accumulated;
  * sums_dev: double [SSP_NREP][2*C] scratch. */

@@ -121,6 +121,17 @@ struct PointsWork {       // device scratch of one image (ssp_export_workspace_b
   int32_t* counters;      // [1] = number of kept points inside the border band
 };
 
+// Batched launches (ssp_describe_points): blockIdx.y selects image `img` of n heatmaps [n][H*W] whose scratch is laid out
+// array by array (state, cand: [n][H*W], keys: [n][cap2], counters: [n][16]).  Single-image launches have gridDim.y = 1.
+__device__ __forceinline__ PointsWork points_work_of(PointsWork w, int img, int hw, int cap2) {
+  w.state += (size_t)img * hw;
+  w.cand[0] += (size_t)img * hw;
+  w.cand[1] += (size_t)img * hw;
+  w.keys += (size_t)img * cap2;
+  w.counters += 16 * img;
+  return w;
+}
+
 enum { ST_EMPTY = 0, ST_UNDECIDED = 1, ST_KEPT = 2 };
 
 // 5x5 soft-argmax around pixel (x, y) of the zero-padded heatmap: utils/losses.py:64-91 extract_patch_from_points,
@@ -190,8 +201,10 @@ __device__ __forceinline__ void push_kept(const PointsWork& w, int i, int x, int
 }
 
 // state[i] = heat[i] >= thresh (NaN compares false); also clears the sort keys
-__global__ __launch_bounds__(256) void nms_init_kernel(const float* __restrict__ heat, float thresh, PointsWork w, int HW,
+__global__ __launch_bounds__(256) void nms_init_kernel(const float* __restrict__ heat, float thresh, PointsWork w0, int HW,
                                                        int cap2) {
+  const PointsWork w = points_work_of(w0, blockIdx.y, HW, cap2);
+  heat += (size_t)blockIdx.y * HW;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < cap2) w.keys[i] = 0ull;
   if (i >= HW) return;
@@ -205,8 +218,10 @@ __global__ __launch_bounds__(256) void nms_init_kernel(const float* __restrict__
 // progress for `max_idle` passes (its neighbours are not resident) gives up; nms_points_kernel finishes the rest.
 constexpr int NMS_TILE = 32, NMS_MAX_HALO = 8, NMS_PITCH_MAX = NMS_TILE + 2 * NMS_MAX_HALO;
 
-__global__ __launch_bounds__(1024) void nms_tiles_kernel(const float* __restrict__ heat, PointsWork w, int H, int W, int dist,
+__global__ __launch_bounds__(1024) void nms_tiles_kernel(const float* __restrict__ heat, PointsWork w0, int H, int W, int dist,
                                                          int border, int cap2, int max_idle) {
+  const PointsWork w = points_work_of(w0, blockIdx.y, H * W, cap2);
+  heat += (size_t)blockIdx.y * H * W;
   __shared__ float sv[NMS_PITCH_MAX * NMS_PITCH_MAX];
   __shared__ uint8_t ss[NMS_PITCH_MAX * NMS_PITCH_MAX];
   __shared__ int pending, progress;
@@ -271,10 +286,15 @@ __global__ __launch_bounds__(1024) void nms_tiles_kernel(const float* __restrict
 // One block of 1024 threads per heatmap: finishes whatever the tiled rounds left undecided (everything when
 // dist > NMS_MAX_HALO), then border removal, descending bitonic sort, soft-argmax refinement and top-k.
 // pts: [cap][5] = (x, y, confidence, soft-argmax x in [0,4], soft-argmax y in [0,4]); the host adds (sx - 2, sy - 2)
-// in float64 like models/model_wrap.py:245.  count: number of rows written.
-__global__ __launch_bounds__(1024) void nms_points_kernel(const float* __restrict__ heat, PointsWork w, int H, int W,
+// in float64 like models/model_wrap.py:245.  count: number of rows written.  Batched: image blockIdx.y writes
+// pts[img][cap][5] and count[img].
+__global__ __launch_bounds__(1024) void nms_points_kernel(const float* __restrict__ heat, PointsWork w0, int H, int W,
                                                           int dist, int border, int top_k, int subpixel, int cap,
                                                           int cap2, float* __restrict__ pts, int32_t* __restrict__ count) {
+  const PointsWork w = points_work_of(w0, blockIdx.y, H * W, cap2);
+  heat += (size_t)blockIdx.y * H * W;
+  pts += (size_t)blockIdx.y * cap * 5;
+  count += blockIdx.y;
   __shared__ int n_next;
   const int tid = threadIdx.x;
   if (tid == 0) n_next = 0;

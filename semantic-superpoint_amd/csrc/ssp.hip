@@ -35,6 +35,7 @@
 #include "dense_loss.hip.h"
 #include "pair_kernels.hip.h"
 #include "export_kernels.hip.h"
+#include "describe_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "backward_tail.hip.h"
 
@@ -161,6 +162,7 @@ struct Slot {
   size_t stats_bytes;
   int N, H, W;
   bool bsums_dirty;
+  bool has_desc;    // the last forward wrote `desc` (the detector-only forward of ssp_export_points does not)
 };
 
 struct ssp_handle {
@@ -1977,6 +1979,7 @@ static int run_forward(ssp_handle* h, const SlotSet& SS, const float* const* xs,
   for (int k = 0; k < SS.n; ++k) {
     Slot& S = *SS.s[k];
     S.N = N; S.H = H; S.W = W; S.x = xs[k];
+    S.has_desc = !detector_only;
     for (int l = 0; l < 8; ++l) S.act_valid[l] = false;   // (rewritten by this forward where a layer uses it)
     S.bsums_dirty = false;
   }
@@ -3423,6 +3426,106 @@ int ssp_export_points(ssp_handle* h, const ssp_export_params* p, int n_images, c
     HIPCHK(hipGetLastError());
     CHK(heatmap_points(agg, p, w.pw, pts_dev[k], count_dev[k], st));
   }
+  return 0;
+}
+
+// ---- descriptor export (export.py:66-190): keypoints, sparse descriptors, two-way matching ----
+struct DescribeWs {
+  float* heat;  // [n][H*W]
+  PointsWork pw;  // state, cand: [n][H*W]; keys: [n][cap2]; counters: [n][16] (points_work_of)
+  size_t bytes;
+};
+static DescribeWs describe_carve(const ssp_export_params* p, int n, void* base) {
+  Carver c{reinterpret_cast<char*>(base), 0};
+  const size_t hw = (size_t)p->height * p->width;
+  DescribeWs w;
+  w.heat = c.take<float>(hw * n);
+  w.pw.state = c.take<uint8_t>(hw * n);
+  w.pw.cand[0] = c.take<int32_t>(hw * n);
+  w.pw.cand[1] = c.take<int32_t>(hw * n);
+  w.pw.keys = c.take<uint64_t>((size_t)export_cap2(p) * n);
+  w.pw.counters = c.take<int32_t>((size_t)16 * n);
+  w.bytes = align_up(c.off, 256);
+  return w;
+}
+
+size_t ssp_describe_workspace_bytes(const ssp_export_params* p, int n) {
+  if (export_check(p) || n < 1) return 0;
+  return describe_carve(p, n, nullptr).bytes;
+}
+
+int ssp_describe_points(ssp_handle* h, int slot, const ssp_export_params* p, int n, void* workspace_dev, float* pts_dev,
+                        int32_t* count_dev, float* desc_dev, void* stream) {
+  if (!h || !h->bound) return fail(-1, "handle not bound");
+  CHK(export_check(p));
+  if (slot < 0 || slot > 1) return fail(-1, "describe_points: slot must be 0 or 1");
+  if (!workspace_dev || !pts_dev || !count_dev || !desc_dev) return fail(-1, "describe_points: null pointer");
+  Slot& S = h->slot[slot];
+  if (S.N <= 0 || !S.has_desc) return fail(-1, "describe_points: slot %d holds no forward with descriptors", slot);
+  if (n < 1 || n > S.N || p->height != S.H || p->width != S.W)
+    return fail(-1, "describe_points: %d images of %dx%d do not match the slot's forward (%d of %dx%d)", n, p->height,
+                p->width, S.N, S.H, S.W);
+  hipStream_t st = (hipStream_t)stream;
+  const DescribeWs w = describe_carve(p, n, workspace_dev);
+  const int Hc = S.H / 8, Wc = S.W / 8, ncells = n * Hc * Wc, hw = S.H * S.W;
+  const int cap = ssp_export_max_points(p), cap2 = export_cap2(p);
+  HIPCHK(hipMemsetAsync(w.pw.counters, 0, (size_t)16 * n * sizeof(int32_t), st));
+  hipLaunchKernelGGL(flatten_detection_kernel, dim3(cdiv(ncells, 4)), dim3(256), 0, st, S.Y[L_PB], S.bn[L_PB].scale,
+                     S.bn[L_PB].shift, (const float*)nullptr, w.heat, ncells, Hc, Wc, (long)Hc * Wc * S.y_cs[L_PB],
+                     (long)S.y_cs[L_PB], 1L);
+  hipLaunchKernelGGL(nms_init_kernel, dim3(cdiv(std::max(hw, cap2), 256), n), dim3(256), 0, st, w.heat, p->conf_thresh, w.pw,
+                     hw, cap2);
+  if (p->nms_dist <= NMS_MAX_HALO)
+    hipLaunchKernelGGL(nms_tiles_kernel, dim3(cdiv(p->width, NMS_TILE) * cdiv(p->height, NMS_TILE), n), dim3(1024), 0, st,
+                       w.heat, w.pw, p->height, p->width, p->nms_dist, p->border_remove, cap2, 512);
+  hipLaunchKernelGGL(nms_points_kernel, dim3(1, n), dim3(1024), 0, st, w.heat, w.pw, p->height, p->width, p->nms_dist,
+                     p->border_remove, p->top_k, p->subpixel, cap, cap2, pts_dev, count_dev);
+  hipLaunchKernelGGL(sample_desc_kernel, dim3(cdiv(cap, 4), n), dim3(256), 0, st, S.desc, (long)Hc * Wc * 256, 256L, 1L,
+                     Hc, Wc, (const float*)pts_dev, 5, (const int32_t*)count_dev, cap, desc_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_op_sample_descriptors(const float* desc_nchw_dev, int b, int hc, int wc, const float* xy_dev,
+                              const int32_t* counts_dev, int cap, float* out_dev, void* stream) {
+  if (!desc_nchw_dev || !xy_dev || !counts_dev || !out_dev) return fail(-1, "sample_descriptors: null pointer");
+  if (b < 1 || hc < 1 || wc < 1 || cap < 0) return fail(-1, "sample_descriptors: b, hc, wc >= 1 and cap >= 0 required");
+  if (cap == 0) return 0;
+  hipLaunchKernelGGL(sample_desc_kernel, dim3(cdiv(cap, 4), b), dim3(256), 0, (hipStream_t)stream, desc_nchw_dev,
+                     (long)256 * hc * wc, 1L, (long)hc * wc, hc, wc, xy_dev, 2, counts_dev, cap, out_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+static int match_check(int cap, int n_pairs, int pair_stride) {
+  if (cap < 1 || cap > SSP_MATCH_MAX_POINTS || n_pairs < 1 || pair_stride < 1)
+    return fail(-1, "match_two_way: 1 <= cap <= %d, n_pairs >= 1, pair_stride >= 1 required (cap %d)", SSP_MATCH_MAX_POINTS,
+                cap);
+  return 0;
+}
+
+size_t ssp_match_workspace_bytes(int cap, int n_pairs) {
+  if (match_check(cap, n_pairs, 1)) return 0;
+  return align_up((size_t)2 * n_pairs * cap * sizeof(uint64_t), 256);
+}
+
+int ssp_match_two_way(const float* desc1_dev, const int32_t* count1_dev, const float* desc2_dev, const int32_t* count2_dev,
+                      int cap, int n_pairs, int pair_stride, float nn_thresh, void* workspace_dev, float* match_dev,
+                      int32_t* n_match_dev, void* stream) {
+  CHK(match_check(cap, n_pairs, pair_stride));
+  if (!(nn_thresh >= 0.f)) return fail(-1, "match_two_way: nn_thresh must be non-negative");
+  if (!desc1_dev || !count1_dev || !desc2_dev || !count2_dev || !workspace_dev || !match_dev || !n_match_dev)
+    return fail(-1, "match_two_way: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  uint64_t* rowmin = reinterpret_cast<uint64_t*>(workspace_dev);
+  uint64_t* colmin = rowmin + (size_t)n_pairs * cap;
+  HIPCHK(hipMemsetAsync(rowmin, 0xFF, (size_t)2 * n_pairs * cap * sizeof(uint64_t), st));
+  const int t = cdiv(cap, MATCH_TILE);
+  hipLaunchKernelGGL(match_dist_kernel, dim3(t, t, n_pairs), dim3(256), 0, st, desc1_dev, count1_dev, desc2_dev, count2_dev,
+                     cap, pair_stride, rowmin, colmin);
+  hipLaunchKernelGGL(match_compact_kernel, dim3(n_pairs), dim3(1024), 0, st, (const uint64_t*)rowmin, (const uint64_t*)colmin,
+                     count1_dev, count2_dev, cap, pair_stride, nn_thresh, match_dev, n_match_dev);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 

@@ -9,8 +9,16 @@ plus `HomoAdaptExporter`, the fused MI355X path the loop uses: one ssp_export_po
 (forward of the detector head over the views in train-mode BatchNorm, softmax -> depth-to-space, masked un-warp
 accumulation, greedy NMS, soft-argmax refinement, top-k) with no host round trip before the final point list.
 
-Every arithmetic step runs in libssp_hip.so; tensors must live on a HIP device (no CPU fallback).  The descriptor
-export of the reference (`export_descriptor`, `run(onlyHeatmap=False)`) is outside this path and raises.
+The descriptor export (keypoints, sparse descriptors and two-way matches of image pairs):
+  PointTracker(max_length=2, nn_thresh).nn_match_two_way / update / get_matches / get_mscores / clear_desc
+                                                                     models/model_wrap.py:451-597
+  export_descriptor(config, output_dir, args)                        export.py:66-190
+with `Val_model_heatmap` (Val_model_heatmap.py) as the per-image front end and `DescriptorExporter`, the fused path the
+loop uses: ONE eval forward over the 2P images of P pairs, keypoints + sparse descriptors (ssp_describe_points) and the
+matcher (ssp_match_two_way) on the device, then one read of the counts and sized copies.
+
+Every arithmetic step runs in libssp_hip.so; tensors must live on a HIP device (no CPU fallback).  The dense-descriptor
+branch of SuperPointFrontend_torch.run (`onlyHeatmap=False`) is not provided and raises.
 """
 import logging
 import os
@@ -217,3 +225,231 @@ def export_detector_homoAdapt_gpu(config, output_dir, args):
         with open(save_output / "export.txt", "a") as f:
             f.write("output pairs: %d\n" % count)
     return count
+
+
+class PointTracker(object):
+    """models/model_wrap.py:416-597 for two-frame tracks (max_length=2, as export_descriptor uses it): the two-way
+    nearest-neighbour matcher runs on the device (ssp_match_two_way).  Track bookkeeping beyond the last pair of frames
+    (get_tracks / draw_tracks) is not provided."""
+
+    def __init__(self, max_length, nn_thresh, device=None):
+        if max_length < 2:
+            raise ValueError("max_length must be greater than or equal to 2.")
+        if max_length != 2:
+            raise NotImplementedError("PointTracker keeps the last two frames only (max_length=2)")
+        self.maxl = max_length
+        self.nn_thresh = nn_thresh
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.all_pts = [np.zeros((2, 0)) for _ in range(self.maxl)]
+        self.last_desc = None
+        self.track_count = 0
+        self.max_score = 9999
+        self.matches = None
+        self.last_pts = None
+        self.mscores = None
+
+    def nn_match_two_way(self, desc1, desc2, nn_thresh):
+        """desc1 [D,N1], desc2 [D,N2] unit columns -> float64 [3,L] (index in desc1, index in desc2, distance), rows of
+        desc1 ascending.  Same checks and order as models/model_wrap.py:451-497 (an empty side returns before the
+        nn_thresh check)."""
+        assert desc1.shape[0] == desc2.shape[0]
+        if desc1.shape[1] == 0 or desc2.shape[1] == 0:
+            return np.zeros((3, 0))
+        if nn_thresh < 0.0:
+            raise ValueError("'nn_thresh' should be non-negative")
+        if desc1.shape[0] != 256:
+            raise ValueError("the device matcher takes 256-dimensional descriptors")
+        n1, n2 = desc1.shape[1], desc2.shape[1]
+        cap = max(n1, n2)
+        if cap > L.MATCH_MAX_POINTS:
+            raise ValueError("at most %d descriptors per side (got %d)" % (L.MATCH_MAX_POINTS, cap))
+        f32 = dict(dtype=torch.float32, device=self.device)
+        d1 = torch.zeros(1, cap, 256, **f32)
+        d2 = torch.zeros(1, cap, 256, **f32)
+        d1[0, :n1] = torch.from_numpy(np.ascontiguousarray(desc1.T, dtype=np.float32)).to(self.device)
+        d2[0, :n2] = torch.from_numpy(np.ascontiguousarray(desc2.T, dtype=np.float32)).to(self.device)
+        c1 = torch.tensor([n1], dtype=torch.int32, device=self.device)
+        c2 = torch.tensor([n2], dtype=torch.int32, device=self.device)
+        m, nm = L.op_match_two_way(d1, c1, d2, c2, nn_thresh)
+        matches = _matches_to_numpy(m[0], int(nm.item()))
+        self.mscores = matches
+        return matches
+
+    def get_matches(self):
+        return self.matches
+
+    def get_mscores(self):
+        return self.mscores
+
+    def clear_desc(self):
+        self.last_desc = None
+
+    def update(self, pts, desc):
+        """pts [3,N] points, desc [D,N] descriptors of the next frame.  After it, get_matches() is [4,L]
+        (x0, y0, x1, y1) of the mutual matches with the previous frame (models/model_wrap.py:521-597)."""
+        if pts is None or desc is None:
+            print("PointTracker: Warning, no points were added to tracker.")
+            return
+        assert pts.shape[1] == desc.shape[1]
+        if self.last_desc is None:
+            self.last_desc = np.zeros((desc.shape[0], 0))
+        self.all_pts.pop(0)
+        self.all_pts.append(pts)
+        matches = self.nn_match_two_way(self.last_desc, desc, self.nn_thresh)
+        self.matches = matches
+        if self.last_pts is not None:
+            id1 = self.last_pts[:, matches[0, :].astype(int)]
+            id2 = pts[:2, :][:, matches[1, :].astype(int)]
+            self.matches = np.concatenate((id1, id2), axis=0)
+        self.last_desc = desc.copy()
+        self.last_pts = pts[:2, :].copy()
+
+    def get_tracks(self, min_length):
+        raise NotImplementedError("PointTracker keeps no tracks here: use get_matches() after the second update")
+
+    def draw_tracks(self, out, tracks):
+        raise NotImplementedError("PointTracker keeps no tracks here: use get_matches() after the second update")
+
+
+def _matches_to_numpy(m, n):
+    """Device rows (i, j, score) -> the reference's float64 [3,L]."""
+    a = m[:n].cpu().numpy().astype(np.float64)
+    return a.T.copy() if n else np.zeros((3, 0))
+
+
+def _image_2d(t):
+    t = torch.as_tensor(t)
+    while t.dim() > 2:
+        assert t.shape[0] == 1, "one image per entry"
+        t = t[0]
+    return t
+
+
+class DescriptorExporter:
+    """Fused descriptor export of image PAIRS on one GPU.  `net` is one of this package's model drop-ins (its Engine
+    is created / grown for 2 x batch_pairs x H x W on first use).  Eval-mode BatchNorm computes every image on its own,
+    but the engine picks its convolution kernels by batch size (last-bit differences in the heatmap move points that sit
+    at the threshold), so the forward always runs over 2 x batch_pairs images, zero-padded: a pair's result does not
+    depend on how many pairs share its call."""
+
+    def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, border_remove=4, batch_pairs=16):
+        if nn_thresh < 0.0:
+            raise ValueError("'nn_thresh' should be non-negative")
+        self.net, self.device = net, torch.device(device)
+        self.conf_thresh, self.nms_dist, self.subpixel = conf_thresh, nms_dist, bool(subpixel)
+        self.nn_thresh, self.border_remove = nn_thresh, border_remove
+        self.batch_pairs = int(batch_pairs)
+
+    def run_device(self, pairs):
+        """pairs: list of (image, warped_image), each [H,W] / [1,H,W] / [1,1,H,W].  Returns the device tensors of the
+        batch: {"pts": [2P,cap,5], "count": [2P], "desc": [2P,cap,256], "match": [P,cap,3], "n_match": [P]} (image
+        2p = pair p's image, 2p + 1 its warped image); no host synchronisation."""
+        if not 1 <= len(pairs) <= self.batch_pairs:
+            raise ValueError("1 to %d pairs per call (got %d)" % (self.batch_pairs, len(pairs)))
+        ims = []
+        for a, b in pairs:
+            ims += [_image_2d(a), _image_2d(b)]
+        n = len(ims)
+        h, w = ims[0].shape
+        x = torch.zeros(2 * self.batch_pairs, 1, h, w, dtype=torch.float32, device=self.device)
+        x[:n, 0] = torch.stack([t.to(self.device, torch.float32) for t in ims])
+        eng = self.net.engine(x.shape[0], h, w, self.device)
+        with torch.no_grad():
+            eng.forward(x, slot=0, train=False, want=())
+        o = eng.describe_points(0, n, conf_thresh=self.conf_thresh, nms_dist=self.nms_dist, subpixel=self.subpixel,
+                                border_remove=self.border_remove)
+        o["match"], o["n_match"] = L.op_match_two_way(o["desc"], o["count"], o["desc"][1:], o["count"][1:],
+                                                      self.nn_thresh, pair_stride=2, n_pairs=len(pairs))
+        return o
+
+    def __call__(self, pairs, homographies=None):
+        """Returns one `pred` dict per pair with the keys and layouts of export.py:145-183: image, warped_image,
+        prob / warped_prob (float64 [N,3], subpixel when enabled), desc / warped_desc (float32 [N,256], sampled at the
+        integer points), matches (float64 [L,4] = x0, y0, x1, y1) and homography when given."""
+        o = self.run_device(pairs)
+        counts = o["count"].cpu().numpy()
+        n_match = o["n_match"].cpu().numpy()
+        preds = []
+        for p, (a, b) in enumerate(pairs):
+            pred = {}
+            probs = []
+            for k, tag in ((2 * p, ""), (2 * p + 1, "warped_")):
+                c = int(counts[k])
+                prob = L.points_to_numpy(o["pts"][k], torch.tensor(c), self.subpixel)
+                pred[tag + "prob"] = prob
+                pred[tag + "desc"] = o["desc"][k, :c].cpu().numpy()
+                probs.append(prob)
+            pred["image"] = _image_2d(a).detach().cpu().numpy()
+            pred["warped_image"] = _image_2d(b).detach().cpu().numpy()
+            m = _matches_to_numpy(o["match"][p], int(n_match[p]))
+            idx0, idx1 = m[0].astype(int), m[1].astype(int)
+            pred["matches"] = np.concatenate((probs[0][idx0, :2], probs[1][idx1, :2]), axis=1)
+            if homographies is not None:
+                pred["homography"] = np.asarray(homographies[p])
+            preds.append(pred)
+        return preds
+
+
+def export_descriptor(config, output_dir, args, test_loader=None, pairs_per_flush=16):
+    """export.py:66-190: keypoints, descriptors and matches of (image, warped_image) pairs, one `<count>.npz` per pair
+    under output_dir/checkpoints/../predictions.  The front end is `Val_model_heatmap` of this package (config["model"]:
+    name, params, pretrained, nms, detection_threshold, nn_thresh, subpixel.enable).  test_loader: any iterable of
+    samples with "image", "warped_image" ([1,1,H,W]) and "homography"; default = the HOST repository's
+    utils.loader.dataLoader_test, as in the reference.  Pairs are batched `pairs_per_flush` at a time and sharded over
+    ranks when torch.distributed is initialised (rank r writes the pairs i with i % world == r, named by i)."""
+    import yaml
+    from .Val_model_heatmap import Val_model_heatmap
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("export_descriptor needs a HIP device: there is no CPU fallback")
+    rank, world = 0, 1
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+    os.makedirs(output_dir, exist_ok=True)
+    if rank == 0:
+        with open(os.path.join(output_dir, "config.yml"), "w") as f:
+            yaml.dump(config, f, default_flow_style=False)
+    save_path = Path(output_dir) / "checkpoints"
+    os.makedirs(save_path, exist_ok=True)
+    save_output = save_path / "../predictions"
+    os.makedirs(save_output, exist_ok=True)
+
+    mcfg = config["model"]
+    subpixel = bool(mcfg.get("subpixel", {}).get("enable", False))
+    patch_size = mcfg.get("subpixel", {}).get("patch_size", 5)
+    if subpixel and patch_size != 5:
+        raise ValueError("the device soft-argmax implements the 5x5 patch of the reference configs")
+    if test_loader is None:
+        from utils.loader import dataLoader_test as dataLoader  # the reference's own loader (export.py:100-104)
+        test_loader = dataLoader(config, dataset=config["data"]["dataset"])["test_loader"]
+    agent = Val_model_heatmap(mcfg, device=device)
+    agent.loadModel()
+    exporter = DescriptorExporter(agent.net, device, agent.conf_thresh, agent.nms_dist, subpixel, agent.nn_thresh,
+                                  agent.border_remove, batch_pairs=pairs_per_flush)
+    pending, count = [], 0
+
+    def flush():
+        nonlocal count
+        if not pending:
+            return
+        preds = exporter([(s["image"], s["warped_image"]) for _, s in pending],
+                         homographies=[_squeeze_np(s["homography"]) for _, s in pending])
+        for (i, _), pred in zip(pending, preds):
+            np.savez_compressed(Path(save_output, "{}.npz".format(i)), **pred)
+            count += 1
+        pending.clear()
+
+    for i, sample in enumerate(test_loader):
+        if i % world != rank:
+            continue
+        pending.append((i, sample))
+        if len(pending) == pairs_per_flush:
+            flush()
+    flush()
+    logging.info("output pairs: %d", count)
+    return count
+
+
+def _squeeze_np(t):
+    return (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).squeeze()

@@ -73,7 +73,11 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_pair_step_phase", "ssp_grad_early_offset", "ssp_pair_step_graph", "ssp_handle_set_conv_algo",
            "ssp_op_detector_loss", "ssp_debug_occupancy", "ssp_sample_indices_cell", "ssp_op_warp_labels_px",
            "ssp_op_warp_labels_full_px", "ssp_profile_read_kernel", "ssp_op_label_quantize", "ssp_profile_pause", "ssp_op_conv_bf16", "ssp_op_conv_wgrad_bf16", "ssp_op_bn_bwd_bf16", "ssp_build_id",
-           "ssp_set_deterministic", "ssp_get_deterministic", "ssp_clock_probe", "ssp_op_sem_loss"]
+           "ssp_set_deterministic", "ssp_get_deterministic", "ssp_clock_probe", "ssp_op_sem_loss",
+           "ssp_describe_workspace_bytes", "ssp_describe_points", "ssp_op_sample_descriptors", "ssp_match_workspace_bytes",
+           "ssp_match_two_way"]
+
+MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 
 
 def load_library(path=None):
@@ -191,6 +195,17 @@ def load_library(path=None):
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
     lib.ssp_op_dense_loss.argtypes = [vp, vp, vp, vp, i, i, i, f, f, i, f, vp, C.c_size_t, vp, vp, vp, vp]
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_describe_workspace_bytes.argtypes = [ep, i]
+        lib.ssp_describe_workspace_bytes.restype = C.c_size_t
+        lib.ssp_describe_points.argtypes = [vp, i, ep, i, vp, vp, vp, vp, vp]
+        lib.ssp_op_sample_descriptors.argtypes = [vp, i, i, i, vp, vp, i, vp, vp]
+        lib.ssp_match_workspace_bytes.argtypes = [i, i]
+        lib.ssp_match_workspace_bytes.restype = C.c_size_t
+        lib.ssp_match_two_way.argtypes = [vp, vp, vp, vp, i, i, i, f, vp, vp, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
     _lib = lib
     return lib
 
@@ -612,6 +627,31 @@ class Engine:
             _check(self.lib.ssp_export_points(self.h, C.byref(p), k, arr(views), arr(masks), arr(unwarp_h),
                                               arr(self._export_ws[:k]), arr(hm), arr(pts), arr(cnt), _stream()))
         return [{"pts": pts[j], "count": cnt[j], "heatmap": hm[j]} for j in range(k)]
+
+    def describe_points(self, slot, n, conf_thresh=0.015, nms_dist=4, subpixel=True, top_k=0, border_remove=4):
+        """Keypoints + sparse descriptors of the first n images of the last EVAL forward in `slot` (Val_model_heatmap's
+        run / heatmap_to_pts / soft_argmax_points / desc_to_sparseDesc, export.py:126-142).  Returns device tensors
+        {"pts": [n,cap,5] rows (x, y, conf, sx, sy), "count": [n] int32, "desc": [n,cap,256]}; no host synchronisation."""
+        hh, ww = self.height, self.width
+        x = getattr(self, "_x", [None, None])[slot]
+        if x is not None:
+            hh, ww = x.shape[-2], x.shape[-1]
+        p = SspExportParams(1, hh, ww, float(np.float32(conf_thresh)), int(nms_dist), int(border_remove), int(top_k or 0),
+                            int(bool(subpixel)))
+        wsb = self.lib.ssp_describe_workspace_bytes(C.byref(p), int(n))
+        cap = self.lib.ssp_export_max_points(C.byref(p))
+        if wsb == 0 or cap < 0:
+            _check(-1)
+        if getattr(self, "_describe_ws", None) is None or self._describe_ws.numel() < wsb:
+            self._describe_ws = torch.empty(wsb, dtype=torch.uint8, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        pts = torch.empty(n, cap, 5, **f32)
+        cnt = torch.zeros(n, dtype=torch.int32, device=self.device)
+        desc = torch.empty(n, cap, 256, **f32)
+        with torch.cuda.device(self.device):
+            _check(self.lib.ssp_describe_points(self.h, int(slot), C.byref(p), int(n), _ptr(self._describe_ws), _ptr(pts),
+                                                _ptr(cnt), _ptr(desc), _stream()))
+        return {"pts": pts, "count": cnt, "desc": desc}
 
     def detector_heatmap(self, slot, n, hh, ww):
         """flattenDetection of the detector logits left in `slot` by the last forward / pair step -> [n,1,hh,ww]."""
@@ -1043,6 +1083,52 @@ def op_soft_argmax_points(heatmap, xy):
     with torch.cuda.device(heatmap.device):
         _check(lib.ssp_op_soft_argmax_points(_ptr(heatmap), _ptr(xy), _ptr(out), xy.shape[0], H, W, _stream()))
     return out
+
+
+def op_sample_descriptors(desc, xy, counts=None):
+    """sample_desc_from_points (models/model_wrap.py:295-313) on the device: desc [B,256,Hc,Wc] (the L2-normalised coarse
+    descriptor), xy [B,cap,2] float32 points (x, y) in pixels, counts [B] int32 (default: all cap).  Image b samples its own
+    map.  Returns [B,cap,256] unit rows (rows >= counts[b] are undefined)."""
+    lib = load_library()
+    _need_gpu(desc, "desc")
+    _need_gpu(xy, "xy")
+    B, D, hc, wc = desc.shape
+    assert D == 256 and desc.dtype == torch.float32 and xy.dtype == torch.float32 and xy.shape[0] == B and xy.shape[2] == 2
+    cap = xy.shape[1]
+    if counts is None:
+        counts = torch.full((B,), cap, dtype=torch.int32, device=desc.device)
+    _need_gpu(counts, "counts")
+    assert counts.dtype == torch.int32 and counts.numel() == B
+    out = torch.empty(B, cap, 256, dtype=torch.float32, device=desc.device)
+    with torch.cuda.device(desc.device):
+        _check(lib.ssp_op_sample_descriptors(_ptr(desc), B, hc, wc, _ptr(xy), _ptr(counts), cap, _ptr(out), _stream()))
+    return out
+
+
+def op_match_two_way(desc1, count1, desc2, count2, nn_thresh, pair_stride=1, n_pairs=None):
+    """PointTracker.nn_match_two_way (models/model_wrap.py:451-497) for P pairs on the device.  desc1, desc2:
+    [P*pair_stride, cap, 256] unit rows, count1, count2: [P*pair_stride] int32 (pair p uses entry p*pair_stride).
+    Returns (match [P,cap,3] rows (i, j, score) in ascending i, n_match [P] int32) as device tensors."""
+    lib = load_library()
+    if nn_thresh < 0.0:
+        raise ValueError("'nn_thresh' should be non-negative")
+    for t, nm in ((desc1, "desc1"), (desc2, "desc2"), (count1, "count1"), (count2, "count2")):
+        _need_gpu(t, nm)
+    cap = desc1.shape[1]
+    assert desc1.shape[1:] == (cap, 256) and desc2.shape[1:] == (cap, 256), "both sides need the same [cap,256] rows"
+    assert count1.dtype == torch.int32 and count2.dtype == torch.int32
+    P = n_pairs if n_pairs is not None else desc1.shape[0] // pair_stride
+    assert (P - 1) * pair_stride < min(desc1.shape[0], desc2.shape[0], count1.numel(), count2.numel())
+    wsb = lib.ssp_match_workspace_bytes(cap, P)
+    if wsb == 0:
+        _check(-1)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=desc1.device)
+    match = torch.empty(P, cap, 3, dtype=torch.float32, device=desc1.device)
+    n_match = torch.empty(P, dtype=torch.int32, device=desc1.device)
+    with torch.cuda.device(desc1.device):
+        _check(lib.ssp_match_two_way(_ptr(desc1), _ptr(count1), _ptr(desc2), _ptr(count2), cap, P, int(pair_stride),
+                                     float(np.float32(nn_thresh)), _ptr(ws), _ptr(match), _ptr(n_match), _stream()))
+    return match, n_match
 
 
 def points_to_numpy(pts, count, subpixel):
