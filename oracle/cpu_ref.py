@@ -381,12 +381,14 @@ def norm_pts(pts, shape_wh):
     return pts / torch.as_tensor(shape_wh).float() * 2 - 1
 
 
-def descriptor_loss_sparse_given(desc_a, desc_b, idx, lamda_d=1.0, n_non=100, dist="cos", method="2d"):
+def descriptor_loss_sparse_given(desc_a, desc_b, idx, lamda_d=1.0, n_non=100, dist="cos", method="2d", hinge=None):
     """Deterministic half of descriptor_loss_sparse (sparse_loss.py:219-254) for one image given
     the sampled indices.  desc_* [D,Hc,Wc].  Returns (loss, pos, neg).
     method: "2d" = bilinear grid_sample at normPts (pixelwise_contrastive_loss.py:160-184), anything else ("1d") =
     index_select at the integer cell (:185-188).  dist: "cos" = hinge on the dot product (:200-204, :247-256), anything else
-    ("euclidean") = squared distance of the matches (:205-206) and (max(0, ||a - b|| - M))^2 of the non-matches (:249-258)."""
+    ("euclidean") = squared distance of the matches (:205-206) and (max(0, ||a - b|| - M))^2 of the non-matches (:249-258).
+    hinge (test hook, not reference behaviour; dist "cos" only): {"pos": 0/1 [n_match], "neg": 0/1 [n_match * n_non]} dictates
+    which hinge terms are active (and so the count that normalises the non-match sum), like the forced ReLU gates of forward."""
     D, Hc, Wc = desc_a.shape
     wh = (Wc, Hc)
     flat_a = desc_a.reshape(D, Hc * Wc).t()
@@ -399,30 +401,36 @@ def descriptor_loss_sparse_given(desc_a, desc_b, idx, lamda_d=1.0, n_non=100, di
     else:  # sparse_loss.py:224-226,234-236: uv_to_1d, index_select
         da = flat_a[(idx["uv_a"][:, 0] + idx["uv_a"][:, 1] * Wc).long()]
         db = flat_b[(idx["uv_b"][:, 0] + idx["uv_b"][:, 1] * Wc).long()]
+    if hinge is not None and dist != "cos":
+        raise ValueError("forced hinges need dist 'cos'")
     if dist == "cos":
-        pos = torch.clamp(1.0 - (da * db).sum(-1), min=0).sum() / da.shape[0]
+        t = 1.0 - (da * db).sum(-1)
+        pos = (torch.clamp(t, min=0) if hinge is None else t * hinge["pos"].to(t.dtype)).sum() / da.shape[0]
     else:
         pos = (da - db).pow(2).sum() / da.shape[0]
     # non matches: sparse_loss.py:96-100,245-246 ; pixelwise_contrastive_loss.py:238-263 (M = 0.2, invert=True)
     ia = (idx["uv_a"][:, 0] + idx["uv_a"][:, 1] * Wc).long().repeat_interleave(n_non)
     ib = idx["nm_b"].long()
     if dist == "cos":
-        nm = torch.clamp((flat_a[ia] * flat_b[ib]).sum(-1) - 0.2, min=0)
+        t = (flat_a[ia] * flat_b[ib]).sum(-1) - 0.2
+        nm = torch.clamp(t, min=0) if hinge is None else t * hinge["neg"].to(t.dtype)
     else:
         nm = torch.clamp((flat_a[ia] - flat_b[ib]).norm(2, 1) - 0.2, min=0).pow(2)
-    nnz = int((nm != 0).sum())
+    nnz = int((nm != 0).sum()) if hinge is None else int(hinge["neg"].sum())
     neg = nm.sum() / (nnz + 1)  # sparse_loss.py:154
     return lamda_d * pos + neg, pos, neg
 
 
 def batch_descriptor_loss_sparse(desc, desc_w, homographies, indices=None, lamda_d=1.0, n_match=1000,
-                                 n_non=100, np_rng=np.random, torch_gen=None, dist="cos", method="2d"):
-    """sparse_loss.py:267-284.  `indices` (list per image) overrides sampling."""
+                                 n_non=100, np_rng=np.random, torch_gen=None, dist="cos", method="2d", hinges=None):
+    """sparse_loss.py:267-284.  `indices` (list per image) overrides sampling; `hinges` (list per image, test hook): the
+    forced hinge terms of descriptor_loss_sparse_given."""
     ls, ps, ns, used = [], [], [], []
     for i in range(desc.shape[0]):
         idx = indices[i] if indices is not None else sample_sparse_indices(
             homographies[i].float(), desc.shape[2], desc.shape[3], n_match, n_non, np_rng, torch_gen)
-        l, p, n = descriptor_loss_sparse_given(desc[i], desc_w[i], idx, lamda_d, n_non, dist, method)
+        l, p, n = descriptor_loss_sparse_given(desc[i], desc_w[i], idx, lamda_d, n_non, dist, method,
+                                               None if hinges is None else hinges[i])
         ls.append(l), ps.append(p), ns.append(n), used.append(idx)
     return torch.stack(ls).mean(), torch.stack(ps).mean(), torch.stack(ns).mean(), used
 
@@ -440,8 +448,11 @@ def multi_task_loss(eta, det, pos, neg, sem=None):
 # --------------------------------------------------------------------------------------
 def pair_losses(sd, eta, sample, arch="SuperPointNet_gauss2", indices=None, lambda_loss=1.0, lamda_d=1.0,
                 multi_task=True, gaussian=True, n_match=1000, n_non=100, np_rng=np.random, torch_gen=None,
-                train=True, dense=None, forced=None, operand_dtype=None, warped_pair=True, sparse_dist="cos", sparse_method="2d"):
+                train=True, dense=None, forced=None, operand_dtype=None, warped_pair=True, sparse_dist="cos", sparse_method="2d",
+                forced_hinges=None):
     """Forward of both views + all losses.  Returns (loss, scalars dict, aux dict).
+    forced / forced_hinges (test hooks): the ReLU gates and max-pool winners of each view (forward) and the active hinge terms
+    of the sparse descriptor loss per image (descriptor_loss_sparse_given) dictated by the caller.
     sparse_dist / sparse_method: model.sparse_loss.params.dist / method (sparse_loss.py:76-77; every shipped config: cos / 2d).
     dense: None (sparse descriptor loss) or the dict of model.dense_loss.params (Train_model_heatmap_all.py:131-137).
     warped_pair=False: the single-view branch (`data.warped_pair.enable: false`, :207; the shipped
@@ -473,7 +484,7 @@ def pair_losses(sd, eta, sample, arch="SuperPointNet_gauss2", indices=None, lamb
     elif lambda_loss > 0:
         loss_desc, pos, neg, used = batch_descriptor_loss_sparse(
             out["desc"], out_w["desc"], sample["homographies"], indices, lamda_d, n_match, n_non, np_rng, torch_gen,
-            sparse_dist, sparse_method)
+            sparse_dist, sparse_method, forced_hinges)
     else:
         loss_desc, pos, neg, used = zero, zero, zero, None
     if multi_task:

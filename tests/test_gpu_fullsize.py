@@ -10,42 +10,11 @@ import torch
 
 from oracle import cpu_ref as C
 from tests import golden_util as G
+from tests.gate_util import _dev, _engine, _gate_flip_case, _hip_gates, _idx_to_dev, _noisy, _oracle_indices, _rel, _to_dev
 
 pytestmark = pytest.mark.gpu
 ARCHS = {"sp": "SuperPointNet_gauss2", "ssp": "SuperPointNet_gauss2_ssmall"}
 SCALARS = ("loss", "loss_det", "loss_det_warp", "loss_desc", "loss_sem", "loss_sem_warp", "positive_dist", "negative_dist")
-
-
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X (run through gpurun)"
-    return torch.device("cuda:0")
-
-
-def _engine(arch, B, H, W, sd, **kw):
-    from semantic_superpoint_amd.lib import Engine
-    e = Engine(arch, B, H, W, _dev(), **kw)
-    e.load_state_dict(sd)
-    return e
-
-
-def _to_dev(sample):
-    return {k: v.to(_dev()).contiguous() for k, v in sample.items()}
-
-
-def _idx_to_dev(idx, Wc):
-    ma = torch.stack([(i["uv_a"][:, 0] + i["uv_a"][:, 1] * Wc) for i in idx]).to(torch.int32)
-    mb = torch.stack([(i["uv_b"][:, 0] + i["uv_b"][:, 1] * Wc) for i in idx]).to(torch.int32)
-    nm = torch.stack([i["nm_b"] for i in idx]).to(torch.int32)
-    return ma.to(_dev()).contiguous(), mb.to(_dev()).contiguous(), nm.to(_dev()).contiguous()
-
-
-def _rel(a, b):
-    a, b = a.double().reshape(-1), b.double().reshape(-1)
-    return float((a - b).norm() / (b.norm() + 1e-30)), float((a - b).abs().max() / (b.abs().max() + 1e-30))
-
-
-def _noisy(arch):  # conv biases feeding a BatchNorm: exact gradient 0, both sides hold rounding noise
-    return {c + ".bias" for c, bn, _, _, _ in C.layer_table(arch) if bn is not None}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -121,79 +90,6 @@ def test_full_size_step_golden(tag, algo):
 # ------------------------------------------------------------------------------------------------
 # (iii) gate flips are the ONLY source of the end-to-end gradient differences
 # ------------------------------------------------------------------------------------------------
-def _hip_gates(e, arch, slot, B, H, W):
-    """ReLU gates and max-pool winners of the HIP forward in `slot`, recomputed from its raw convolution outputs and
-    BatchNorm affine (float64 gives the exact sign of the fp32 fma; rounding to fp32 reproduces the pooled values)."""
-    t = C.layer_table(arch)
-    relu, pool = {}, {}
-    nheads = 3 if arch.endswith("ssmall") else 2
-    res = [(H, W), (H, W), (H // 2, W // 2), (H // 2, W // 2), (H // 4, W // 4), (H // 4, W // 4), (H // 8, W // 8),
-           (H // 8, W // 8)]
-    for l in range(8):
-        hh, ww = res[l]
-        c = t[l][3]
-        y = e.debug_buffer(slot, "Y%d" % l, (B, hh, ww, c)).double()
-        z = (y * e.debug_buffer(slot, "scale%d" % l, (c,)).double() + e.debug_buffer(slot, "shift%d" % l, (c,)).double())
-        z = z.permute(0, 3, 1, 2).cpu()  # NCHW
-        relu[t[l][0]] = (z > 0)
-        if l in (1, 3, 5):  # pooled on the way into layer l + 1
-            a = torch.relu(z.float())
-            win = a.view(B, c, hh // 2, 2, ww // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, c, hh // 2, ww // 2, 4)
-            pool[l + 1] = win.argmax(dim=4)  # first maximum, like torch's max_pool2d and the HIP routing
-    hc, wc = H // 8, W // 8
-    yh = e.debug_buffer(slot, "Y8", (B, hc, wc, 256 * nheads)).double()
-    for k, (name, l) in enumerate((("convPa", 8), ("convDa", 10), ("convDS", 12))[:nheads]):
-        z = yh[..., 256 * k:256 * (k + 1)] * e.debug_buffer(slot, "scale%d" % l, (256,)).double() + \
-            e.debug_buffer(slot, "shift%d" % l, (256,)).double()
-        relu[name] = (z.permute(0, 3, 1, 2).cpu() > 0)
-    return {"relu": relu, "pool": pool}
-
-
-def _gate_flip_case(arch, B, H, W, sd, sample, used, algo, loss_kw, plain_grads, forced_tol=1e-4, plain_tol=5e-3):
-    """(a) HIP vs the plain oracle gradients `plain_grads`: statistical agreement (gate flips of activations within rounding
-    distance of 0 perturb the gradient).  (b) HIP vs the oracle evaluated WITH THE HIP PATH'S ReLU gates and max-pool
-    winners: agreement to `forced_tol` relative L2 per tensor (and 10 x that per element of max|ref|) -> the flips are the
-    whole difference.  Returns (worst plain, worst forced, worst 64-element slice error against the forced oracle)."""
-    single = "warped_img" not in sample
-    nv = 1 if single else 2
-    e = _engine(arch, B, H, W, sd)
-    if algo is not None:
-        e.set_conv_algo(algo)
-    e.zero_grad()
-    e.pair_step(_to_dev(sample), indices=None if used is None else _idx_to_dev(used, W // 8), train=True, **loss_kw)
-    torch.cuda.synchronize()
-    gd = {k: v.cpu().clone() for k, v in e.grad_dict().items()}
-    forced = tuple(_hip_gates(e, arch, v, B, H, W) for v in range(nv))
-    nflip = ngates = 0
-    for v in range(nv):
-        for k, z in _oracle_preacts(sd, sample, arch, v).items():
-            nflip += int((forced[v]["relu"][k] != (z > 0)).sum())
-            ngates += z.numel()
-    tsd = C.to_torch(sd, requires_grad=True)
-    eta = torch.tensor([1.0, 2.0, 1.0], requires_grad=True)
-    okw = {k: v for k, v in loss_kw.items() if k in ("lambda_loss", "lamda_d", "multi_task", "gaussian")}
-    loss, _, _ = C.pair_losses(tsd, eta, sample, arch, indices=used, forced=forced, warped_pair=not single, **okw)
-    loss.backward()
-    worst_plain, worst_forced, worst_slice = (0.0, ""), (0.0, ""), (0.0, "")
-    for k in C.param_keys(arch):
-        if k in _noisy(arch) or tsd[k].grad is None:
-            continue
-        l2p, _ = _rel(gd[k], plain_grads[k])
-        l2f, mxf = _rel(gd[k], tsd[k].grad)
-        sl = float((gd[k].reshape(-1)[:64] - tsd[k].grad.reshape(-1)[:64]).abs().max() / (tsd[k].grad.abs().max() + 1e-30))
-        worst_plain, worst_forced = max(worst_plain, (l2p, k)), max(worst_forced, (max(l2f, 0.1 * mxf), k))
-        worst_slice = max(worst_slice, (sl, k))
-    print("%s %dx%d algo %s%s: gate flips %d of %d; worst rel-L2: plain %.2e (%s), gates forced %.2e (%s); worst 64-element "
-          "slice vs the forced oracle %.2e of max|grad| (%s)"
-          % (arch, H, W, algo, " single view" if single else "", nflip, ngates, worst_plain[0], worst_plain[1], worst_forced[0],
-             worst_forced[1], worst_slice[0], worst_slice[1]))
-    assert worst_plain[0] <= plain_tol, ("plain oracle", worst_plain, "flipped gates: %d" % nflip)
-    assert worst_forced[0] <= forced_tol, ("gates forced", worst_forced, "flipped gates: %d" % nflip)
-    if eta.grad is not None:
-        assert (gd["eta"] - eta.grad).abs().max() < 1e-5
-    return worst_plain, worst_forced, worst_slice
-
-
 @pytest.mark.parametrize("tag", ["sp", "ssp"])
 def test_gradient_differences_are_gate_flips_only(tag):
     """120x160, B = 2, default kernels (every 3x3 layer on F(2x2,3x3) at this size)."""
@@ -235,28 +131,6 @@ def test_gate_flips_only_under_the_benchmarked_kernels_240x320(tag):
 
 # 64-element slices of the algorithm-10 gradients against the forced-gate oracle at 240x320: 2 x the residual measured on the GPU box
 FORCED_SLICE_TOL_W4 = 3e-5  # measured 1.44e-5 (sp), 1.18e-5 (ssp); per-tensor rel-L2 2.34e-5
-
-
-def _oracle_preacts(sd, sample, arch, view):
-    """Pre-activation signs of the oracle's own forward (to count the flipped gates)."""
-    import torch.nn.functional as F
-    tsd = C.to_torch(sd)
-    x = sample["image"] if view == 0 else sample["warped_img"]
-    t = C.layer_table(arch)
-    out, h = {}, x
-    with torch.no_grad():
-        for i, (conv, bn, cin, cout, k) in enumerate(t[:8]):
-            if i in (2, 4, 6):
-                h = F.max_pool2d(h, 2)
-            y = F.conv2d(h, tsd[conv + ".weight"], tsd[conv + ".bias"], padding=1)
-            z = F.batch_norm(y, None, None, tsd[bn + ".weight"], tsd[bn + ".bias"], training=True, eps=1e-5)
-            out[conv] = z
-            h = F.relu(z)
-        for conv, bn in (("convPa", "bnPa"), ("convDa", "bnDa"), ("convDS", "bnS1")):
-            if conv + ".weight" in tsd:
-                y = F.conv2d(h, tsd[conv + ".weight"], tsd[conv + ".bias"], padding=1)
-                out[conv] = F.batch_norm(y, None, None, tsd[bn + ".weight"], tsd[bn + ".bias"], training=True, eps=1e-5)
-    return out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -318,16 +192,6 @@ def test_bench_size_properties(tag):
             first, last = (v, last) if it == 0 else (first, v)
     assert last["loss"] < first["loss"] - 0.05, (first["loss"], last["loss"])
     assert bool(torch.isfinite(e.params).all())
-
-
-def _oracle_indices(idx, Wc):
-    """Device-sampled (match_a, match_b, nonmatch_b) -> the per-image index dicts of cpu_ref.Trainer."""
-    ma, mb, nm = (t.cpu().long() for t in idx)
-    out = []
-    for i in range(ma.shape[0]):
-        out.append({"uv_a": torch.stack((ma[i] % Wc, ma[i] // Wc), dim=1).float(),
-                    "uv_b": torch.stack((mb[i] % Wc, mb[i] // Wc), dim=1).float(), "nm_b": nm[i]})
-    return out
 
 
 def _np_sd(sd):

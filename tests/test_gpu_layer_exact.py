@@ -1,0 +1,253 @@
+"""GPU: layer-exact, teacher-forced checks of the fp32 training forward and the gates-forced backward at the benchmarked size.
+
+  * test_fp32_forward_chain_teacher_forced: after a training-mode pair step, every layer of BOTH views (slot v = view v) is
+    re-evaluated in fp64 from the HIP path's OWN stored input of that layer: operand = relu(fma(Y_prev, scale, shift)) in fp32
+    (2x2 max-pooled where the network pools), fp64 products and sums of the fp32 weights, + bias.  Every stored output element
+    must satisfy |Y - Y64| <= tau * ((|W| (*) |A|) + |b|), (*) the same convolution in fp64 on absolute values: a bound that does
+    not depend on the activation scale.  A single product term dropped or doubled costs ~1/576 of the bound on a 64-channel
+    3x3 layer, so any tau below 1e-4 catches it.  The BatchNorm affine must be the fp64 batch statistics of the stored output;
+    the raw pooled copies must be the exact per-channel max (min where gamma < 0) of the stored output's 2x2 windows.
+  * test_gate_flips_only_at_the_benchmarked_size: the proof of tests/test_gpu_fullsize.py (gradient differences are ReLU /
+    max-pool gate flips only) at B = 32, 240x320, the default algorithm, on bench.py's inputs and the device-sampled indices.
+  * Both run one separate profiled step of the same configuration and assert that the kernels they claim to cover launched:
+    if the dispatch predicates move, these tests fail instead of silently covering other kernels."""
+import os
+import time
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import cpu_ref as C
+from tests.gate_util import _dev, _engine, _gate_flip_case, _oracle_indices
+
+pytestmark = pytest.mark.gpu
+ARCHS = {"sp": "SuperPointNet_gauss2", "ssp": "SuperPointNet_gauss2_ssmall"}
+
+# tau per kernel family: 4 x the worst ratio |Y - Y64| / ((|W| (*) |A|) + |b|) measured on the MI355X over every configuration
+# of test_fp32_forward_chain_teacher_forced (both views, all checked images)
+TAU = {
+    "conv0_direct": 4 * 3.21e-7,   # conv0_direct_kernel (Cin = 1): measured 3.202e-7
+    "direct": 4 * 3.23e-7,         # conv_mfma_kernel (algorithm 0): measured 3.229e-7
+    "f2x2": 4 * 2.31e-7,           # conv_wino_pipe_kernel / conv_wino_p2_kernel, F(2x2,3x3): measured 2.303e-7 (pipe: convDa, B = 32)
+    "f4x4": 4 * 4.44e-6,           # conv_wino4_kernel, F(4x4,3x3): measured 4.434e-6
+    "pointwise": 4 * 3.46e-7,      # conv1x1_group_kernel (algorithm 0: conv_mfma_kernel<1>): measured 3.457e-7
+}
+FAMILY = {"conv0_direct": "conv0_direct", "direct": "direct", "pipe": "f2x2", "p2": "f2x2", "wino4": "f4x4", "pointwise": "pointwise"}
+# the gates-forced proof at B = 32 (ReLU gates, max-pool winners and descriptor-loss hinges forced): per-tensor rel-L2 bound and
+# 64-element slices at 2 x the residual measured on the MI355X.  The 5e-5 of the 240x320, B = 2 algorithm-10 case does not hold
+# here: measured 7.18e-5 (sp) / 7.00e-5 (ssp), both on inc.conv.conv.3.weight, the end of a backward chain summing 16x the terms
+FORCED_TOL_B32 = 1e-4
+FORCED_SLICE_TOL_B32 = 9e-5   # measured 2.99e-5 (sp), 4.37e-5 (ssp)
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _kernel(algo, layer, ks, nprob, N, H, W, cin, cout):
+    """The forward kernel of one layer of a pair step: a mirror of w4_eligible / conv_uses_p2 of csrc/ssp.hip (handle: the
+    device's CU count).  The profiled step of each test checks the kernels this predicts did launch."""
+    if layer == 0:
+        return "conv0_direct"
+    if ks == 1:
+        return "pointwise"
+    if algo == 0 or cin % 16:
+        return "direct"
+    n_cu = torch.cuda.get_device_properties(_dev()).multi_processor_count
+    if algo == 10 or (algo in (1, 11) and cin % 8 == 0 and cin <= 256):
+        wide = _cdiv(H, 16) * 16 * _cdiv(W, 32) * 32 <= _cdiv(H, 32) * 32 * _cdiv(W, 16) * 16
+        items = nprob * N * _cdiv(H, 16 if wide else 32) * _cdiv(W, 32 if wide else 16) * _cdiv(cout, 64)
+        if algo == 10 or (H * W >= 60 * 80 and 4 * items >= 16 * n_cu):
+            return "wino4"
+    w1 = W % 32 == 0
+    items = nprob * N * _cdiv(H, 8 if w1 else 32) * _cdiv(W, 32 if w1 else 8) * _cdiv(cout, 64)
+    return "p2" if items < 4 * n_cu else "pipe"
+
+
+def _sd_tensor(sd, k):
+    v = sd[k]
+    return (v.detach().cpu() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v))).float()
+
+
+def _inputs(tag, B, H, W, flip_gamma):
+    from semantic_superpoint_amd import synth
+    from semantic_superpoint_amd.lib import layer_table
+    arch = ARCHS[tag]
+    sd = synth.default_init_state_dict(layer_table(arch), seed=0)   # bench.py's weights and inputs
+    if flip_gamma:  # negative BatchNorm scales on every third channel: the min branch of the raw pooled copies
+        for _, bn, _, _, _ in C.layer_table(arch):
+            if bn is not None:
+                g = sd[bn + ".weight"].clone()
+                g[::3] = -g[::3]
+                sd[bn + ".weight"] = g
+    sample = synth.make_pair(B, H, W, _dev(), seed=100, semantic=(tag == "ssp"))
+    return arch, sd, sample
+
+
+def _profiled_kernels(e, sample, indices):
+    """One separate pair step with every 3x3 forward / data-gradient / weight-gradient launch timed per kernel."""
+    e.zero_grad()
+    e.profile_enable("conv3x3_every")
+    e.pair_step(sample, indices=indices, train=True)
+    torch.cuda.synchronize()
+    k = e.profile_read_kernels()
+    e.profile_enable("none")
+    return k
+
+
+def _conv_ratio(y, a, w, b, pad):
+    """max over the elements of |Y - Y64| / ((|W| (*) |A|) + |b|) (fp64 reference from the fp32 operand a and weights w)."""
+    ad, wd, bd = a.double(), w.double(), b.double()
+    ex = F.conv2d(ad, wd, bd, padding=pad)
+    mag = F.conv2d(ad.abs(), wd.abs(), bd.abs(), padding=pad)
+    return float(((y.double() - ex).abs() / mag.clamp_min(1e-300)).max())
+
+
+class _Chain:
+    def __init__(self, e, arch, sd, B, H, W, algo, imgs):
+        self.e, self.arch, self.sd, self.B, self.H, self.W, self.algo, self.imgs = e, arch, sd, B, H, W, algo, imgs
+        self.t = C.layer_table(arch)
+        self.worst = {}
+
+    def res(self, l):
+        s = 0 if l < 2 else 1 if l < 4 else 2 if l < 6 else 3
+        return self.H >> s, self.W >> s
+
+    def conv(self, v, l, y_sel, a_sel, kernel):
+        conv, _, cin, cout, k = self.t[l]
+        r = _conv_ratio(y_sel, a_sel, _sd_tensor(self.sd, conv + ".weight"), _sd_tensor(self.sd, conv + ".bias"), k // 2)
+        fam = FAMILY[kernel]
+        self.worst[fam] = max(self.worst.get(fam, (0.0, "")), (r, "%s view %d (%s)" % (conv, v, kernel)))
+        assert r <= TAU[fam], (conv, "view", v, kernel, r, TAU[fam])
+
+    def affine(self, v, l, y):
+        """the engine's BatchNorm affine of layer l = the fp64 batch statistics of its stored (full-batch) output y (NCHW)"""
+        _, bn, _, cout, _ = self.t[l]
+        yd = y.double()
+        mean = yd.mean(dim=(0, 2, 3))
+        var = (yd - mean.view(1, -1, 1, 1)).square().mean(dim=(0, 2, 3))
+        del yd
+        sc = _sd_tensor(self.sd, bn + ".weight").double() * (var + 1e-5).rsqrt()
+        sh = _sd_tensor(self.sd, bn + ".bias").double() - mean * sc
+        msc = self.e.debug_buffer(v, "scale%d" % l, (cout,)).cpu().double()
+        msh = self.e.debug_buffer(v, "shift%d" % l, (cout,)).cpu().double()
+        assert (msc - sc).abs().max() <= 1e-5 * float(sc.abs().max()), ("scale", l, "view", v)
+        assert (msh - sh).abs().max() <= 1e-5 * max(1.0, float(sh.abs().max())), ("shift", l, "view", v)
+        return msc.float(), msh.float()
+
+    @staticmethod
+    def operand(y, sc, sh):  # one fp32 fma per element (exact product in fp64, one rounding), ReLU
+        return F.relu((y.double() * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1)).float())
+
+    def view(self, v, x):
+        e, t, B, H, W, imgs = self.e, self.t, self.B, self.H, self.W, self.imgs
+        nprob = 2
+        y = e.debug_buffer(v, "Y0", (B, H, W, 64)).cpu().permute(0, 3, 1, 2)
+        self.conv(v, 0, y[imgs], x[imgs], "conv0_direct")
+        prev = y
+        for l in range(1, 8):
+            conv, bn, cin, cout, k = t[l]
+            sc, sh = self.affine(v, l - 1, prev)
+            hl, wl = self.res(l)
+            a = self.operand(prev[imgs], sc, sh)
+            if l in (2, 4, 6):
+                a = F.max_pool2d(a, 2)
+                # Apool[l - 1]: the raw pooled copy the producing kernel wrote (per-channel max / min by the sign of gamma of the
+                # stored tensor; conv_wino_pipe_kernel and conv_wino4_kernel), else the activated pooled tensor bn_relu_pool_kernel
+                # materialised for this layer's direct read
+                raw = e.debug_buffer(v, "A%d" % (l - 1), (B, hl, wl, cin)).cpu().permute(0, 3, 1, 2)
+                gam = _sd_tensor(self.sd, t[l - 1][1] + ".weight").view(1, -1, 1, 1)
+                prod = _kernel(self.algo, l - 1, 3, nprob, B, 2 * hl, 2 * wl, t[l - 1][2], t[l - 1][3])
+                if prod in ("pipe", "wino4"):
+                    want = torch.where(gam >= 0, F.max_pool2d(prev, 2), -F.max_pool2d(-prev, 2))
+                    assert torch.equal(raw, want), ("raw pooled copy", l - 1, "view", v, prod)
+                    assert torch.equal(self.operand(raw[imgs], sc, sh), a), ("pooled operand", l - 1, "view", v)
+                else:  # (fmaf in the kernel, fp64-then-fp32 here: a double rounding may differ by one ulp)
+                    assert torch.allclose(raw[imgs], a, rtol=2.0 ** -23, atol=0.0), ("activated pooled input", l - 1, "view", v, prod)
+            y = e.debug_buffer(v, "Y%d" % l, (B, hl, wl, cout)).cpu().permute(0, 3, 1, 2)
+            self.conv(v, l, y[imgs], a, _kernel(self.algo, l, k, nprob, B, hl, wl, cin, cout))
+            prev = y
+        sc7, sh7 = self.affine(v, 7, prev)
+        x4 = self.operand(prev[imgs], sc7, sh7)
+        nheads = 3 if self.arch.endswith("ssmall") else 2
+        Hc, Wc = H // 8, W // 8
+        yh = e.debug_buffer(v, "Y8", (B, Hc, Wc, 256 * nheads)).cpu().permute(0, 3, 1, 2)   # [Pa | Da | DS] raw outputs
+        for hk, (l3, l1) in enumerate(((8, 9), (10, 11), (12, 13))[:nheads]):
+            conv, bn, cin, cout, k = t[l3]
+            y3 = yh[:, 256 * hk:256 * hk + 256]
+            self.conv(v, l3, y3[imgs], x4, _kernel(self.algo, l3, 3, nprob, B, Hc, Wc, cin, 256 * nheads))
+            sc, sh = self.affine(v, l3, y3)
+            a = self.operand(y3[imgs], sc, sh)
+            cout1 = t[l1][3]
+            cs = {65: 80, 256: 256}.get(cout1, (cout1 + 3) // 4 * 4)
+            o = e.debug_buffer(v, "Y%d" % l1, (B, Hc, Wc, cs)).cpu().permute(0, 3, 1, 2)[:, :cout1]
+            self.conv(v, l1, o[imgs], a, _kernel(self.algo, l1, 1, nprob, B, Hc, Wc, 256, cout1))
+
+
+# B = 32: the conv checks run on a subset of the images of each view (the first two, the middle one and the last two: the first
+# and the last rounds of the persistent tile loops); the BatchNorm statistics and the pooled copies are checked on the full batch
+CHAIN_CASES = [
+    # tag, B, H, W, algorithm, kernels that must launch in the profiled step
+    ("sp", 32, 240, 320, 1, ("conv_wino4_kernel", "conv_wino_pipe_kernel", "conv_wino_p2_kernel", "wgrad_wino_kernel")),
+    ("ssp", 32, 240, 320, 1, ("conv_wino4_kernel", "conv_wino_pipe_kernel", "conv_wino_p2_kernel", "wgrad_wino_kernel")),
+    ("ssp", 2, 240, 320, 1, ("conv_wino_pipe_kernel",)),   # the 240x320 layers on the first-generation kernel
+    ("ssp", 3, 40, 56, 1, ("conv_wino_p2_kernel",)),       # odd tile counts, 5x7 cells
+    ("ssp", 2, 64, 96, 0, ()),                             # direct implicit GEMM
+    ("sp", 2, 64, 96, 10, ("conv_wino4_kernel",)),         # F(4x4,3x3) on every 3x3 layer
+]
+
+
+@pytest.mark.parametrize("tag,B,H,W,algo,launched", CHAIN_CASES, ids=["%s-B%d-%dx%d-algo%d" % c[:5] for c in CHAIN_CASES])
+def test_fp32_forward_chain_teacher_forced(tag, B, H, W, algo, launched):
+    torch.set_num_threads(min(int(os.environ.get("OMP_NUM_THREADS", "16")), 16))
+    t0 = time.perf_counter()
+    arch, sd, sample = _inputs(tag, B, H, W, flip_gamma=B < 32)
+    e = _engine(arch, B, H, W, sd)
+    if algo != 1:
+        e.set_conv_algo(algo)
+    e.zero_grad()
+    e.pair_step(sample, indices=None, seed=7, train=True)
+    torch.cuda.synchronize()
+    imgs = [0, 1, B // 2, B - 2, B - 1] if B >= 32 else list(range(B))
+    ch = _Chain(e, arch, sd, B, H, W, algo, imgs)
+    for v, key in enumerate(("image", "warped_img")):
+        ch.view(v, sample[key].cpu())
+    print("%s B=%d %dx%d algo %d: worst |Y - Y64| / bound per family: %s (%.1f s)" % (
+        tag, B, H, W, algo, ", ".join("%s %.3e [%s]" % (f, r, where) for f, (r, where) in sorted(ch.worst.items())),
+        time.perf_counter() - t0))
+    kern = _profiled_kernels(e, sample, e._last_idx)
+    print("profiled step: %s" % {k: v["launches"] for k, v in kern.items()})
+    for name in launched:
+        assert kern.get(name, {}).get("launches", 0) > 0, (name, "did not launch", sorted(kern))
+    if algo == 0:
+        assert not any(k.startswith("conv_wino") for k in kern), sorted(kern)
+
+
+@pytest.mark.parametrize("tag", ["sp", "ssp"])
+def test_gate_flips_only_at_the_benchmarked_size(tag):
+    """B = 32, 240x320, default algorithm, bench.py's inputs and the device-sampled indices: against the oracle evaluated with
+    the HIP path's ReLU gates, max-pool winners and active descriptor-loss hinges, every gradient tensor agrees to FORCED_TOL_B32
+    relative L2 and every 64-element slice to 2 x the measured residual (the plain-oracle leg is test_bench_size_step_vs_oracle).
+    Without the forced hinges the descriptor head differs by 3e-3 (convDa.weight): a few dozen of the step's 3.2 M non-match dot
+    products lie within 1e-5 of the margin, and the HIP loss is exact on its own descriptors (rel-L2 9e-7 of dL/d desc)."""
+    torch.set_num_threads(min(int(os.environ.get("OMP_NUM_THREADS", "16")), 16))
+    B, H, W = 32, 240, 320
+    arch, sd, sample = _inputs(tag, B, H, W, flip_gamma=False)
+    e = _engine(arch, B, H, W, sd)
+    e.zero_grad()
+    e.pair_step(sample, indices=None, seed=7, train=True)
+    idx = e._last_idx
+    kern = _profiled_kernels(e, sample, idx)
+    print("profiled step: %s" % {k: v["launches"] for k, v in kern.items()})
+    for name in ("conv_wino4_kernel", "conv_wino_pipe_kernel", "conv_wino_p2_kernel", "wgrad_wino_kernel"):
+        assert kern.get(name, {}).get("launches", 0) > 0, (name, "did not launch", sorted(kern))
+    used = _oracle_indices(idx, W // 8)
+    del e, idx
+    torch.cuda.empty_cache()
+    np_sd = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
+    cpu = {k: v.cpu() for k, v in sample.items() if k != "cell_homographies"}
+    _, _, ws = _gate_flip_case(arch, B, H, W, np_sd, cpu, used, None, dict(lambda_loss=1.0, lamda_d=1.0, multi_task=True), None,
+                               forced_tol=FORCED_TOL_B32, force_hinges=True)
+    assert ws[0] <= FORCED_SLICE_TOL_B32, ws

@@ -31,12 +31,16 @@ def _ref_input(x_nhwc, in_mode, sc, sh):
                                                 "wgrad_f3x3_4x4"])
 def conv_algo(request):
     """ssp_set_conv_algo: every convolution / weight-gradient operator test runs under the fp32 implementations
-    (1 = default: software-pipelined Winograd; 0 = direct implicit GEMM; [2 = Winograd without the software pipeline, 5 = the
-    pipelined kernel with LDS-staged weights and 3 / 7 / 8 = the bf16-operand experiments inside the Winograd kernels are compiled
-    out of the shipped library: SSP_LEGACY_ALGOS];
-    6 = the second-generation pipelined Winograd kernel: two independent 4-wave workgroups per CU;
+    (1 = default: the default dispatch of the 3x3 Winograd convolutions, which for a handle-less operator call (256 CUs assumed)
+    picks by shape - conv_wino4_kernel where w4_eligible holds, else the second-generation conv_wino_p2_kernel below 4 x 256
+    F(2x2,3x3) tile-block items (conv_uses_p2), else the first-generation conv_wino_pipe_kernel; the kernel each case reaches
+    is named beside it in CONV_CASES / DGRAD_CASES; 0 = direct implicit GEMM; [2 = Winograd without the software pipeline,
+    5 = the pipelined kernel with LDS-staged weights and 3 / 7 / 8 = the bf16-operand experiments inside the Winograd kernels are
+    compiled out of the shipped library: SSP_LEGACY_ALGOS];
+    6 = the second-generation pipelined Winograd kernel (two independent 4-wave workgroups per CU) on every 3x3 Winograd case;
     10 = Winograd F(4x4,3x3) (conv_wino4_kernel) on every 3x3 convolution it can run, F(2x2,3x3) elsewhere;
-    11 = algorithm 1 with the Winograd F(3x3,4x4) weight gradient, wgrad_wino4_kernel (opt-in: correct, not faster))."""
+    11 = algorithm 1 with the Winograd F(3x3,4x4) weight gradient, wgrad_wino4_kernel (opt-in: correct, not faster)).
+    The id "winograd_pipelined" of algorithm 1 names the default dispatch: every kernel it can pick is a pipelined Winograd kernel."""
     from semantic_superpoint_amd import lib as L
     L.set_conv_algo(request.param)
     yield request.param
@@ -45,23 +49,31 @@ def conv_algo(request):
 
 CONV_CASES = [
     # N, H, W, cin, cout, ks, in_mode   (H,W = conv resolution; the input is 2H x 2W for in_mode 2)
-    (2, 16, 64, 64, 64, 3, 1),    # wide tiles (8x32), full tiles
-    (1, 12, 32, 64, 128, 3, 0),   # wide, partial tile rows, 2 cout blocks
-    (2, 8, 32, 64, 64, 3, 2),     # wide + pooled input
-    (2, 30, 40, 128, 128, 3, 1),  # narrow tiles (32x8): the 30x40 layers
-    (1, 8, 24, 64, 128, 3, 2),    # narrow + pooled input
-    (2, 6, 8, 128, 256, 3, 1),    # heads on a tiny map
-    (2, 30, 40, 256, 65, 1, 1),   # convPb: 1x1, cout tail
-    (1, 4, 6, 256, 256, 1, 1),    # convDb
-    (1, 16, 32, 256, 133, 1, 0),  # 1x1 raw input, wide
-    (3, 7, 9, 40, 200, 1, 1),     # 1x1: partial 32-channel chunk under BatchNorm-on-load, 7 n-tiles = two grouped problems, ragged pixels
-    (1, 3, 5, 300, 20, 1, 0),     # 1x1: ten chunks, one partial n-tile, 15 pixels
-    (1, 9, 11, 64, 64, 3, 1),     # odd map: partial 2x2 Winograd tiles at the right / bottom edge
-    (2, 14, 20, 32, 64, 3, 0),    # 32 input channels (four 8-channel stages), narrow partial tiles
-    (1, 8, 32, 48, 70, 3, 1),     # Cin = 48, cout tail (70 = 64 + 6)
-    (3, 10, 64, 16, 64, 3, 0),    # Cin = 16: two stages per tile, many tiles per block
-    (2, 50, 70, 64, 128, 3, 1),   # several F(4x4,3x3) tile blocks per image, partial at both edges (32x16 blocks: 50 = 3 x 16 + 2)
-    (1, 70, 50, 32, 64, 3, 0),    # the 16x32 block shape of F(4x4,3x3) (70 = 2 x 32 + 6, 50 = 3 x 16 + 2)
+    # kernel reached under algorithm 1 (handle-less: w4_eligible / conv_uses_p2 with 256 CUs; in_mode 2 and Cin % 16 != 0: direct;
+    # 1x1: conv1x1_group)
+    (2, 16, 64, 64, 64, 3, 1),    # p2: wide tiles (8x32), full tiles
+    (1, 12, 32, 64, 128, 3, 0),   # p2: wide, partial tile rows, 2 cout blocks
+    (2, 8, 32, 64, 64, 3, 2),     # direct: wide + pooled input
+    (2, 30, 40, 128, 128, 3, 1),  # p2: narrow tiles (32x8): the 30x40 layers
+    (1, 8, 24, 64, 128, 3, 2),    # direct: narrow + pooled input
+    (2, 6, 8, 128, 256, 3, 1),    # p2: heads on a tiny map
+    (2, 30, 40, 256, 65, 1, 1),   # conv1x1_group: convPb: 1x1, cout tail
+    (1, 4, 6, 256, 256, 1, 1),    # conv1x1_group: convDb
+    (1, 16, 32, 256, 133, 1, 0),  # conv1x1_group: 1x1 raw input, wide
+    (3, 7, 9, 40, 200, 1, 1),     # conv1x1_group: partial 32-channel chunk under BatchNorm-on-load, 7 n-tiles = two grouped problems, ragged pixels
+    (1, 3, 5, 300, 20, 1, 0),     # conv1x1_group: ten chunks, one partial n-tile, 15 pixels
+    (1, 9, 11, 64, 64, 3, 1),     # p2: odd map: partial 2x2 Winograd tiles at the right / bottom edge
+    (2, 14, 20, 32, 64, 3, 0),    # p2: 32 input channels (four 8-channel stages), narrow partial tiles
+    (1, 8, 32, 48, 70, 3, 1),     # p2: Cin = 48, cout tail (70 = 64 + 6)
+    (3, 10, 64, 16, 64, 3, 0),    # p2: Cin = 16: two stages per tile, many tiles per block
+    (2, 50, 70, 64, 128, 3, 1),   # p2 (algorithm 10: several F(4x4,3x3) tile blocks per image, partial at both edges: 50 = 3 x 16 + 2)
+    (1, 70, 50, 32, 64, 3, 0),    # p2 (algorithm 10: the 16x32 block shape of F(4x4,3x3): 70 = 2 x 32 + 6, 50 = 3 x 16 + 2)
+    # pipe: >= 1024 first-generation tile-block items (8x32 / 32x8 tiles x 64-channel blocks: >= 4 rounds of the 256 persistent
+    # blocks) on maps below the 60x80 pixels of w4_eligible
+    (24, 60, 64, 64, 200, 3, 1),  # pipe, wide 8x32: 1536 items (6 per block), partial bottom tile row (60 = 7 x 8 + 4), cout 200 = 3 x 64 + 8
+    (32, 36, 128, 64, 128, 3, 0), # pipe, wide 8x32, raw input: 1280 items, partial bottom tile row (36 = 4 x 8 + 4)
+    (16, 56, 84, 64, 200, 3, 1),  # pipe, narrow 32x8: 1408 items, partial tiles at the right (84 = 10 x 8 + 4) and bottom (56 = 32 + 24)
+    (64, 56, 84, 16, 68, 3, 0),   # pipe, narrow 32x8, raw input, Cin = 16: 2816 items (11 per block, like the heads at B = 32), cout 68 = 64 + 4
 ]
 
 
@@ -88,8 +100,21 @@ def test_conv_forward(N, H, W, cin, cout, ks, mode, conv_algo):
     assert (stats[cout:].cpu() - q_ref).abs().max() < 1e-4 * q_ref.abs().max()
 
 
-@pytest.mark.parametrize("N,H,W,cin,cout,ks", [(2, 16, 32, 64, 64, 3), (1, 30, 40, 128, 256, 3), (2, 6, 8, 256, 65, 1),
-                                                 (1, 8, 32, 64, 128, 3), (2, 30, 40, 256, 133, 1), (1, 5, 7, 256, 256, 1)])
+DGRAD_CASES = [
+    # N, H, W, cin, cout, ks of the FORWARD conv; the data gradient is a conv of Cin = cout (padded to 4) -> cout = cin.
+    # Kernel under algorithm 1 (handle-less), as in CONV_CASES:
+    (2, 16, 32, 64, 64, 3),       # p2
+    (1, 30, 40, 128, 256, 3),     # p2
+    (2, 6, 8, 256, 65, 1),        # conv1x1_group
+    (1, 8, 32, 64, 128, 3),       # p2
+    (2, 30, 40, 256, 133, 1),     # conv1x1_group
+    (1, 5, 7, 256, 256, 1),       # conv1x1_group
+    (32, 36, 128, 128, 64, 3),    # pipe, wide 8x32: 1280 items, partial bottom tile row
+    (16, 56, 84, 200, 80, 3),     # pipe, narrow 32x8: 1408 items, partial right / bottom tiles, 200 = 3 x 64 + 8 output channels
+]
+
+
+@pytest.mark.parametrize("N,H,W,cin,cout,ks", DGRAD_CASES)
 def test_conv_dgrad(N, H, W, cin, cout, ks, conv_algo):
     """data gradient = conv with transposed/flipped weights; `cin/cout` are those of the FORWARD conv."""
     from semantic_superpoint_amd import lib as L

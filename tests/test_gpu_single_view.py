@@ -148,7 +148,7 @@ def test_single_view_gradients_golden(tag, algo):
 def test_single_view_gradient_differences_are_gate_flips_only():
     """The 8e-3 slice differences above are ReLU / max-pool gate flips: against the oracle evaluated with the HIP path's own
     gates every gradient tensor of the single-view step agrees to 1e-4 (tests/test_gpu_fullsize.py::_gate_flip_case)."""
-    from tests.test_gpu_fullsize import _gate_flip_case
+    from tests.gate_util import _gate_flip_case
     g = G.load("g13_single_view_kendall_120x160.npz")
     sample = G.g13_sample(g)
     sd = C.init_state_dict(ARCH, seed=37)
