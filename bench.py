@@ -20,6 +20,11 @@ step to step, the weights would amplify the commit-order noise of the floating-p
 is pure rounding noise to an update of up to lr, and after 25 steps two runs differ by several per cent in their gradients.
 Rank 0 prints ONE JSON line.
 
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the steps, writes --dump-outputs and
+prints the line (with the `roofline` of the timed steps' own HIP events and the shader clock around them; neither takes a run
+of its own).  `--full` adds every other measurement: the socket power from rocm-smi, the PMC child runs of `roofline.traffic` /
+`mfma_busy`, `cpu_baseline` and the `sp`, `bf16` and `export` blocks; its --no-* options drop single legs of it.
+
 `roofline`: the dominant kernel of the step, conv_wino4_kernel (3x3 forward + data-gradient convolutions of the 240x320 /
 120x160 / 60x80 maps, Winograd F(4x4,3x3) in fp32), timed live with HIP events on the launch stream inside the library
 (ssp_profile_enable) over the timed region.  `achieved` / `frac` are the multiplies EXECUTED on the matrix cores per second
@@ -27,12 +32,13 @@ against the fp32 MFMA peak - the hardware fraction; `algorithmic_tflops` / `algo
 FLOPs (Winograd executes 1/4 resp. 16/36 of them, so that ratio may exceed 1).  `roofline.kernels` holds the same numbers
 for every 3x3 kernel of the step (conv_wino4, conv_wino_pipe, conv_wino_p2, wgrad_wino...), `mfma_busy` the PMC ratio
 SQ_VALU_MFMA_BUSY_CYCLES / 1024 SIMDs : GRBM_GUI_ACTIVE / 8 XCDs, `traffic` the HBM bytes per launch (2 x FETCH_SIZE +
-WRITE_SIZE, FETCH doubled per MI355X_MICROARCH.md) - all three from rocprofv3 PMC child runs of this command made BEFORE
-this process touches the GPU (`--traffic live`, the default at N = 1 when rocprofv3 is on PATH; null if that fails).
-`cpu_baseline`: the oracle (oracle/cpu_ref.py, a restatement pinned against the reference) timed on this host's cores,
-rank 0, N = 1 only: batch 32, 1 warm-up + 3 timed steps.  `bf16` (fp32 line, N = 1): BASELINE configs[3] per GPU - the same step on
+WRITE_SIZE, FETCH doubled per MI355X_MICROARCH.md) - the last two from rocprofv3 PMC child runs of this command made BEFORE
+this process touches the GPU (`--traffic live`, the default of --full at N = 1 when rocprofv3 is on PATH; null if that fails
+or without them).
+`cpu_baseline` (--full): the oracle (oracle/cpu_ref.py, a restatement pinned against the reference) timed on this host's cores,
+rank 0, N = 1 only: batch 32, 1 warm-up + 3 timed steps.  `bf16` (--full, fp32 line, N = 1): BASELINE configs[3] per GPU - the same step on
 the bf16 path (conv algorithm 12), 5 + 20 steps after the fp32 measurement, with its own `roofline` (bound "hbm": algorithmic bytes
-of the dominant kernel against 8 TB/s, PMC traffic from two more child passes); `--dtype bf16` makes that path the line.  `export`: BASELINE configs[4] beside the headline - 3 timed
+of the dominant kernel against 8 TB/s, PMC traffic from two more child passes); `--dtype bf16` makes that path the line.  `export` (--full): BASELINE configs[4] beside the headline - 3 timed
 steps of 8 images (4 ssp_export_points calls of 2 images x 100 views, 480x640) after everything else; never part of `value`.
 `--dump-outputs DIR`: rank 0 writes the arrays of the last timed step (scalars, gradients, Adam moments, BatchNorm running
 statistics; float32 .npy, ~20 MB) to DIR, so that two builds run with the same arguments can be compared (dump_outputs); two runs
@@ -288,6 +294,9 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--height", type=int, default=240)
     ap.add_argument("--width", type=int, default=320)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: rocm-smi power state, the PMC child runs of roofline.traffic "
+                         "(--traffic auto), cpu_baseline and the sp / bf16 / export blocks (N = 1); the --no-* options below drop legs of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--lr", type=float, default=0.001)
@@ -306,7 +315,7 @@ def parse_args(argv=None):
                     help="N > 1: one blocking all-reduce after the whole backward instead of the overlapped split bucket")
     ap.add_argument("--traffic", default="auto", choices=["auto", "live", "none"],
                     help="roofline.traffic: live = two rocprofv3 --pmc child runs of this command (FETCH_SIZE, WRITE_SIZE) "
-                         "before the timed run; auto = live when N = 1, rocprofv3 is on PATH and the roofline leg is on")
+                         "before the timed run; auto = live under --full when N = 1, rocprofv3 is on PATH and the roofline leg is on")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # the profiled child of --traffic live
     ap.add_argument("--no-export", action="store_true", help="skip the `export` block (BASELINE configs[4], 3 calls at 100 x 480x640)")
     ap.add_argument("--no-sp", action="store_true",
@@ -463,14 +472,17 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 
-    power = power_state() if (rank == 0 and not args.pmc_child) else None   # (a child process: nothing here has touched the GPU)
-    pmc, pmc_note = {}, "not collected"
-    want_live = args.traffic == "live" or (args.traffic == "auto" and not args.no_roofline and not args.pmc_child)
+    # everything beside the headline runs under --full only (module docstring)
+    power = power_state() if (args.full and rank == 0 and not args.pmc_child) else None   # (a child process: nothing here has touched the GPU)
+    pmc, pmc_note = {}, "not collected" if args.full else "not collected (the PMC child runs belong to --full)"
+    want_live = args.traffic == "live" or (args.traffic == "auto" and args.full and not args.no_roofline and not args.pmc_child)
     pmc16 = {}
     pmc_export = None
-    want_bf16_block = (world == 1 and rank == 0 and args.conv_algo == 1 and not args.no_bf16 and not args.pmc_child)
+    side = args.full and world == 1 and rank == 0 and not args.pmc_child
+    want_bf16_block = side and args.conv_algo == 1 and not args.no_bf16
     # BASELINE configs[1] (SuperPointNet_gauss2, no semantic head) beside the configs[2] headline
-    want_sp_block = (world == 1 and rank == 0 and args.conv_algo == 1 and args.arch == "ssp" and not args.no_sp and not args.pmc_child)
+    want_sp_block = side and args.conv_algo == 1 and args.arch == "ssp" and not args.no_sp
+    want_export_block = side and not args.no_export
     pmc_sp = {}
     if want_live and world == 1:
         pmc, pmc_note = live_pmc(args)  # child processes; this process has not touched the GPU yet
@@ -479,7 +491,7 @@ def main():
         if want_sp_block:    # the SP step's own counters (same kernels, one 3x3 head less per launch group)
             sp_args = argparse.Namespace(**dict(vars(args), arch="sp"))
             pmc_sp, _ = live_pmc(sp_args)
-        if not args.no_export and rank == 0:  # ... and of the export block's convolutions (one call, two images)
+        if want_export_block:  # ... and of the export block's convolutions (one call, two images)
             import bench_export
             pmc_export = bench_export.export_pmc("sp", 100, 480, 640)
 
@@ -636,7 +648,7 @@ def main():
                 out["roofline"] = rl
             eng.profile_enable("none")
             profiling[0] = False
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(arch, H, W, batch=B)
             if (H, W, B) == (240, 320, 32) and arch in REFERENCE_CPU_CONTAINER:
                 ref = REFERENCE_CPU_CONTAINER[arch]
@@ -663,7 +675,7 @@ def main():
                                          pairs_s, pmc16, pmc_note, dense, cpu_ref_line=cpu_line)
             except Exception as e:  # the headline line must survive a failure of the side measurement
                 out["bf16"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_export and not args.pmc_child:
+        if want_export_block:
             # BASELINE configs[4] next to the headline (never part of `value`): the training engine is released first
             try:
                 import bench_export

@@ -361,6 +361,44 @@ def test_bench_dtype_flag_selects_the_conv_algorithm():
     assert b.parse_args([]).arch == "ssp" and b.parse_args([]).batch == 32  # the north-star workload is the default
 
 
+def test_bench_plain_run_leaves_the_side_measurements_to_full(tmp_path):
+    """A plain bench.py run does what its headline needs: it starts neither the rocm-smi power query nor the rocprofv3 PMC child
+    runs of roofline.traffic, and its line carries no cpu_baseline / sp / bf16 / export block; --full starts both tools.
+    Stand-ins on PATH log their calls and fail (the benchmark survives both failing).  Without a GPU both runs then stop
+    with the 'needs an MI355X' message; with one they run a tiny step."""
+    import json
+    import subprocess
+    assert not _load_bench().parse_args([]).full
+    log = tmp_path / "calls.log"
+    bindir = tmp_path / "bin"
+    bindir.mkdir()
+    for tool in ("rocm-smi", "rocprofv3"):
+        (bindir / tool).write_text("#!/bin/sh\necho %s >> '%s'\nexit 1\n" % (tool, log))
+        (bindir / tool).chmod(0o755)
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["PATH"] = str(bindir) + os.pathsep + env.get("PATH", "")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--batch", "2",
+           "--height", "64", "--width", "96"]
+
+    def run(*extra):
+        if log.exists():
+            log.unlink()
+        r = subprocess.run(cmd + list(extra), env=env, capture_output=True, text=True, timeout=600)
+        if torch.cuda.is_available():
+            assert r.returncode == 0, r.stderr[-2000:]
+        else:
+            assert r.returncode != 0 and "needs an MI355X" in r.stderr
+        return r, (sorted(set(log.read_text().split())) if log.exists() else [])
+
+    r, calls = run()
+    assert calls == []
+    if torch.cuda.is_available():
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["value"] > 0 and not {"power", "cpu_baseline", "sp", "bf16", "export"} & set(line)
+    _, calls = run("--full", "--no-cpu-baseline", "--no-sp", "--no-bf16", "--no-export")
+    assert calls == ["rocm-smi", "rocprofv3"]
+
+
 def test_bench_dump_outputs_writes_the_step_arrays(tmp_path):
     """bench.py --dump-outputs DIR: the engine's step outputs land in DIR/<name>.npy as float32, within the 64 MB budget at the
     benchmark's largest model; --steps must be positive (it is the number of timed steps)."""

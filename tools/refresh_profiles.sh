@@ -7,12 +7,12 @@ O=$R/gpurun_out/refresh
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 Q="--no-cpu-baseline --traffic none --no-export --no-bf16 --no-sp"   # (the fp32 passes must not run the in-process side blocks)
-# ---- the driver's command, timed; then the single-configuration lines ----
-( time python3 $R/bench.py > $O/bench_default_run.json 2> $O/bench_default_run.err ) 2> $O/bench_default_run.time
-python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-export --no-bf16 --no-sp > $O/bench_ssp.json 2>/dev/null
-python3 $R/bench.py --arch sp --steps 20 --warmup 5 --no-cpu-baseline --no-export --no-bf16 > $O/bench_sp.json 2>/dev/null
-python3 $R/bench.py --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-export > $O/bench_ssp_bf16.json 2>/dev/null
-python3 $R/bench.py --arch sp --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-export > $O/bench_sp_bf16.json 2>/dev/null
+# ---- the full line (every block), timed; then the single-configuration lines ----
+( time python3 $R/bench.py --full > $O/bench_default_run.json 2> $O/bench_default_run.err ) 2> $O/bench_default_run.time
+python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-export --no-bf16 --no-sp > $O/bench_ssp.json 2>/dev/null
+python3 $R/bench.py --full --arch sp --steps 20 --warmup 5 --no-cpu-baseline --no-export --no-bf16 > $O/bench_sp.json 2>/dev/null
+python3 $R/bench.py --full --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-export > $O/bench_ssp_bf16.json 2>/dev/null
+python3 $R/bench.py --full --arch sp --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-export > $O/bench_sp_bf16.json 2>/dev/null
 python3 $R/bench.py --steps 20 --warmup 5 $Q --no-roofline --graph > $O/bench_ssp_graph.json 2>/dev/null
 python3 $R/bench.py --steps 20 --warmup 5 $Q --no-roofline > $O/bench_ssp_eager.json 2>/dev/null
 python3 $R/bench.py --conv-algo 0 --steps 10 --warmup 3 $Q > $O/bench_ssp_direct.json 2>/dev/null
