@@ -229,7 +229,17 @@ struct ssp_handle {
   struct ProfKernel { double flops = 0, exec_flops = 0, bytes = 0; int64_t launches = 0; } prof_k[SSP_PROF_K_COUNT];
   std::vector<unsigned char> ev_kernel;  // kernel bucket of event pair i (ev_pool[2 i], ev_pool[2 i + 1])
   int n_cu;
+  // test hook (ssp_debug_backward_taps): the fp32 backward copies per-layer gradients into a caller-owned device arena
+  float* tap_arena = nullptr;
+  unsigned tap_mask = 0;
+  unsigned tap_route[16] = {};  // per-layer record of the path the last backward pass took (TAP_*; host bookkeeping, always kept)
+  int tap_wk = 0, tap_dk = 0;   // kernel kind of the last launch_wgrad / launch_conv of the handle (TAP_WG_* / TAP_DG_*)
 };
+
+// route bits of ssp_debug_backward_tap (include/ssp_hip.h)
+enum { TAP_BSUMS_FUSED = 1, TAP_APPLY_FUSED = 2, TAP_SUMS_LAZY = 4, TAP_WG_SHIFT = 4, TAP_DG_SHIFT = 8 };
+enum { TAP_WG_FUSED12 = 1, TAP_WG_WINO = 2, TAP_WG_WINO4 = 3, TAP_WG_DIRECT = 4, TAP_WG_GROUPED = 5, TAP_WG_L0 = 6 };
+enum { TAP_DG_WINO4 = 1, TAP_DG_PIPE = 2, TAP_DG_P2 = 3, TAP_DG_DIRECT = 4, TAP_DG_GROUPED = 5, TAP_DG_OTHER = 6 };
 
 struct AlgoScope {  // makes the handle's conv algorithm the current one for the duration of an entry point
   int prev;
@@ -709,6 +719,7 @@ static int launch_conv(ssp_handle* h, const ConvCall& c, hipStream_t st, int pro
   // large maps: tools/archive/conv_probe.py)
   const bool p2 = conv_uses_p2(h, c);
   const bool w4 = conv_uses_w4(h, c);
+  if (h) h->tap_dk = w4 ? TAP_DG_WINO4 : p2 ? TAP_DG_P2 : (c.wino && pipe_algo()) ? TAP_DG_PIPE : c.wino ? TAP_DG_OTHER : TAP_DG_DIRECT;
   if (c.pool_out[0] != nullptr) {
     if (!conv_writes_pool(h, c)) return fail(-3, "pooled raw output needs the first-generation pipelined Winograd kernel");
     a.pool_out[0] = c.pool_out[0]; a.pool_out[1] = c.pool_out[1]; a.pool_gamma = c.pool_gamma;
@@ -1148,6 +1159,7 @@ static int launch_wgrad(ssp_handle* h, const WgradCall& c, float* partial, size_
   const int pairs = a.ncib * a.ncob;
   const int taps = wino ? WC : c.ks * c.ks;  // 64 x 64 slabs per partial block
   const bool fused12 = c.fuse_apply && wino && !wino4;  // wgrad_wino_fused_kernel applies the right-hand product of G^T M G itself: 12-component slabs
+  if (h) h->tap_wk = fused12 ? TAP_WG_FUSED12 : wino4 ? TAP_WG_WINO4 : wino ? TAP_WG_WINO : TAP_WG_DIRECT;
   const size_t slab = wino4 ? (size_t)WG4_SLAB : fused12 ? (size_t)12 * 4096 : (size_t)taps * 4096;  // floats per partial block
   int nsplit = ((wino ? 1 : 2) * n_cu) / pairs / 8 * 8;  // blocks per CU; multiple of 8: blocks sharing tiles share an XCD
   if (nsplit < 1) nsplit = 1;
@@ -1838,6 +1850,44 @@ struct SlotSet {
   Slot* s[2];
 };
 
+// ---- backward taps (test hook, ssp_debug_backward_taps): copies of per-layer gradients into a caller-owned arena ----
+// floats of tap (layer l, which: 0 = dOut, 1 = dY) at the handle's maximum batch; 0 = no such tap.  Encoder layer l: dOut = the
+// gradient wrt its (pooled) activation, dY = wrt its conv output (none for layer 0); L_PA: the whole [cells][hcs] tensors of
+// the 3x3 heads; L_PB / L_DB: dY of the pointwise heads
+static size_t tap_floats(const ssp_handle* h, int l, int which) {
+  const size_t B = h->cfg.max_batch, cells = B * (h->cfg.height / 8) * (h->cfg.width / 8);
+  if (l < 8) {
+    int lh, lw; layer_res(l, h->cfg.height, h->cfg.width, lh, lw);
+    const bool pool_after = l == 1 || l == 3 || l == 5;
+    if (which == 1) return l == 0 ? 0 : B * lh * lw * h->L[l].cout;
+    return B * (pool_after ? (size_t)(lh / 2) * (lw / 2) : (size_t)lh * lw) * h->L[l].cout;
+  }
+  if (l == L_PA) return cells * 256 * h->nheads;
+  if (which == 1 && l == L_PB) return cells * 80;
+  if (which == 1 && l == L_DB) return cells * 256;
+  return 0;
+}
+// offset of tap (slot, l, which) in the arena of layer mask `mask`: slot-major, then layer, then which; slot 2 gives the size
+static size_t tap_offset(const ssp_handle* h, unsigned mask, int slot, int l, int which) {
+  size_t off = 0;
+  for (int s = 0; s < 2; ++s)
+    for (int m = 0; m < 16; ++m)
+      for (int w = 0; w < 2; ++w) {
+        if (s == slot && m == l && w == which) return off;
+        if (mask >> m & 1) off += tap_floats(h, m, w);
+      }
+  return off;
+}
+static int tap_copy(ssp_handle* h, const SlotSet& SS, int l, int which, float* const* src, size_t n, hipStream_t st) {
+  if (h->tap_arena == nullptr || !(h->tap_mask >> l & 1)) return 0;
+  if (n > tap_floats(h, l, which)) return fail(-3, "backward tap %d/%d: %zu floats exceed its arena slice", l, which, n);
+  for (int k = 0; k < SS.n; ++k) {
+    float* dst = h->tap_arena + tap_offset(h, h->tap_mask, (int)(SS.s[k] - h->slot), l, which);
+    HIPCHK(hipMemcpyAsync(dst, src[k], n * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  return 0;
+}
+
 // a layer whose finalize was left to its reader (ssp_handle::fin_pending) and whose reader cannot do it: the launch after all
 static int bn_finalize_pending(ssp_handle* h, const SlotSet& SS, int l, int train, hipStream_t st) {
   if (l < 0 || !h->fin_pending[l]) return 0;
@@ -2097,6 +2147,7 @@ static int bn_layer_backward(ssp_handle* h, const SlotSet& SS, int l, const floa
   }
   const bool fused = h->bsums_fused[l];  // pass 1 already sits in bsums (conv_layer_backward of the layer above)
   h->bsums_fused[l] = false;
+  if (fused) h->tap_route[l] |= TAP_BSUMS_FUSED;
   h->apply_fused[l] = false;             // set below only by the branches that leave pass 2 to the weight gradient
   const bool raw_pool = pool_after && l < 8 && SS.s[0]->pool_raw[l];
   if ((fused || raw_pool) && pool_after)  // S2 of gamma == 0 channels comes from a scan over Y (bn_bwd_sums_kernel)
@@ -2113,6 +2164,7 @@ static int bn_layer_backward(ssp_handle* h, const SlotSet& SS, int l, const floa
     hipLaunchKernelGGL(bn_bwd_sums_kernel<float>, dim3(cdiv(64 * 32, 256)), dim3(256), 0, st, a0, a1, SS.n, dg, db);
     hipLaunchKernelGGL(bn_bwd_apply_l0_kernel<float>, dim3(nb2, SS.n), dim3(256), l0_lds_bytes(W), st, a0, a1, P(h, d.w_off), P(h, d.b_off),
                        Gd(h, d.w_off));
+    h->tap_route[0] |= TAP_WG_L0 << TAP_WG_SHIFT;
   } else if (relu && pool_after && have_pool && d.cout % 4 == 0 && d_cs == d.cout && d_co == 0) {
     // pass 1 from the pooled activation (1/4 of Y's bytes), pass 2 over Y
     const long npix = (long)N * (H / 2) * (W / 2);
@@ -2241,6 +2293,7 @@ static int conv_layer_backward(ssp_handle* h, const SlotSet& SS, int l, int src,
     // bn_layer_backward(l) ran the sums only: dOut of the pooled activation still sits in gP (= din, which the data-gradient
     // conv overwrites AFTER the weight gradient has consumed it: same stream), dY is produced into dy[] by the weight gradient
     h->apply_fused[l] = false;
+    h->tap_route[l] |= TAP_APPLY_FUSED;
     w.fuse_apply = true;
     w.fuse_pool = (l == 1 || l == 3 || l == 5);
     w.dout_cs = d.cout; w.dout_co = 0; w.f_gamma = P(h, d.g_off); w.f_ycs = A.y_cs[l];
@@ -2252,13 +2305,18 @@ static int conv_layer_backward(ssp_handle* h, const SlotSet& SS, int l, int src,
     }
     if (h->sums_lazy[l]) {
       h->sums_lazy[l] = false;
+      h->tap_route[l] |= TAP_SUMS_LAZY;
       w.f_lazy = 1; w.f_count = (double)N * H * W; w.f_dgamma = Gd(h, d.g_off); w.f_dbeta = Gd(h, d.be_off); w.f_dbias = Gd(h, d.b_off);
       for (int k = 0; k < SS.n; ++k) w.f_bsums[k] = SS.s[k]->bn[l].bsums;
     }
   }
-  if (!skip_wgrad) CHK(launch_wgrad(h, w, h->partial, h->partial_floats, h->n_cu, st));
+  if (!skip_wgrad) {
+    CHK(launch_wgrad(h, w, h->partial, h->partial_floats, h->n_cu, st));
+    h->tap_route[l] |= (unsigned)h->tap_wk << TAP_WG_SHIFT;
+  }
   if (skip_dgrad) return 0;  // the caller runs the data gradient itself (the grouped pointwise launch of the heads)
   CHK(launch_conv(h, c, st, d.ks == 3 ? SSP_PROF_CONV3X3_DGRAD : 0));
+  h->tap_route[l] |= (unsigned)h->tap_dk << TAP_DG_SHIFT;
   return 0;
 }
 
@@ -2562,13 +2620,17 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
       int lh, lw; layer_res(l, H, W, lh, lw);
       const bool pool_after = (l == 1 || l == 3 || l == 5);
       const int C = h->L[l].cout;
+      CHK(tap_copy(h, SS, l, 0, gP, (size_t)N * (pool_after ? (lh / 2) * (lw / 2) : lh * lw) * C, st));
       CHK(bn_layer_backward(h, SS, l, gP, C, 0, true, pool_after, gQ, C, 0, N, lh, lw, st));
       if (l > 0) CHK(conv_layer_backward(h, SS, l, l - 1, gQ, C, 0, gP, h->L[l].cin, 0, N, lh, lw, layer_in_mode(l), st));
+      if (l > 0) CHK(tap_copy(h, SS, l, 1, gQ, (size_t)N * lh * lw * C, st));
     }
     return flush_wgrad_reduce(h, st);  // the pending Winograd weight-gradient slabs -> OIHW gradients, one launch
   };
+  if (h->tap_arena != nullptr && bf16_path()) return fail(-3, "backward taps cover the fp32 backward only (not conv algorithm 12)");
   if (part == 2) return encoder(EARLY_SPLIT_LAYER - 1, 0);
-  for (int l = 0; l < 16; ++l) h->bsums_fused[l] = h->apply_fused[l] = false;  // (a failed / aborted pass must not leave a flag behind)
+  for (int l = 0; l < 16; ++l) h->bsums_fused[l] = h->apply_fused[l] = false;
+  for (int l = 0; l < 16; ++l) h->tap_route[l] = 0;  // (a failed / aborted pass must not leave a flag behind)
   for (int k = 0; k < SS.n; ++k) {
     Slot& S = *SS.s[k];
     // the forward's single memset of the statistics region also cleared the backward sums; clear them again only
@@ -2644,12 +2706,14 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
   if (has_semi) {
     if (!pair) CHK(bn_layer_backward(h, SS, L_PB, dsemi, 80, 0, false, false, gQ, 80, 0, N, Hc, Wc, st));
     CHK(conv_layer_backward(h, SS, L_PB, L_PA, gQ, 80, 0, dact, hcs, 0, N, Hc, Wc, 1, st, grouped, gw));
+    CHK(tap_copy(h, SS, L_PB, 1, gQ, ncells_all * 80, st));
     if (grouped) add_dgrad(L_PB, gQ, 80, 0);
     if (gw) add_wgrad(L_PB, gQ, 80);
   }
   if (has_desc) {
     if (!pair) CHK(bn_layer_backward(h, SS, L_DB, draw_desc, 256, 0, false, false, gQd, 256, 0, N, Hc, Wc, st));
     CHK(conv_layer_backward(h, SS, L_DB, L_DA, gQd, 256, 0, dact, hcs, 256, N, Hc, Wc, 1, st, grouped, gw));
+    CHK(tap_copy(h, SS, L_DB, 1, gQd, ncells_all * 256, st));
     if (grouped) add_dgrad(L_DB, gQd, 256, 256);
     if (gw) add_wgrad(L_DB, gQd, 256);
   }
@@ -2673,10 +2737,16 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
   if (gw && nw > 0) CHK(launch_g1_wgrad(Lw, nw, SS.n, (long)ncells_all, h->g1_partial, h->g1_partial_slabs, h->n_cu, st,
                                         tail_merge_env() ? &h->tail : nullptr));
   if (grouped && ng > 0) CHK(launch_g1(Lg, ng, SS.n, (long)ncells_all, 0, h->n_cu, st));
+  for (int l : {L_PB, L_DB, L_SOUT}) {
+    const bool ran = l == L_PB ? has_semi : l == L_DB ? has_desc : has_sem;
+    if (ran && gw) h->tap_route[l] |= TAP_WG_GROUPED << TAP_WG_SHIFT;
+    if (ran && grouped) h->tap_route[l] |= TAP_DG_GROUPED << TAP_DG_SHIFT;
+  }
   // ---- 3x3 heads: BN+ReLU backward gP -> gQ [cells][hcs]; weight gradients; ONE data-gradient conv over the
   // concatenated dY channels (sums the heads' contributions) gQ -> gP [cells][128] ----
   {
     const int heads[3] = {L_PA, L_DA, L_DS};
+    CHK(tap_copy(h, SS, L_PA, 0, gP, ncells_all * hcs, st));   // dOut of the 3x3 heads, [cells][hcs]
     BnSumsQueue sums_queue;   // the heads' replica reductions in one launch where nothing else is left of their BatchNorm backward
     for (int hk = 0; hk < h->nheads; ++hk)
       CHK(bn_layer_backward(h, SS, heads[hk], gP, hcs, 256 * hk, true, false, gQ, hcs, 256 * hk, N, Hc, Wc, st, &sums_queue));
@@ -2693,6 +2763,7 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
       }
       if (h->apply_fused[heads[hk]]) {  // bn_layer_backward above left the APPLY pass to this launch
         h->apply_fused[heads[hk]] = false;
+        h->tap_route[heads[hk]] |= TAP_APPLY_FUSED;
         w.fuse_apply = true; w.fuse_pool = false;
         w.dout_cs = hcs; w.dout_co = 0; w.f_gamma = P(h, d.g_off); w.f_ycs = hcs;
         for (int k = 0; k < SS.n; ++k) {
@@ -2704,12 +2775,15 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
         }
         if (h->sums_lazy[heads[hk]]) {
           h->sums_lazy[heads[hk]] = false;
+          h->tap_route[heads[hk]] |= TAP_SUMS_LAZY;
           w.f_lazy = 1; w.f_count = (double)N * Hc * Wc; w.f_dgamma = Gd(h, d.g_off); w.f_dbeta = Gd(h, d.be_off); w.f_dbias = Gd(h, d.b_off);
           for (int k = 0; k < SS.n; ++k) w.f_bsums[k] = SS.s[k]->bn[heads[hk]].bsums;
         }
       }
       CHK(launch_wgrad(h, w, h->partial, h->partial_floats, h->n_cu, st));
+      h->tap_route[heads[hk]] |= (unsigned)h->tap_wk << TAP_WG_SHIFT;
     }
+    CHK(tap_copy(h, SS, L_PA, 1, gQ, ncells_all * hcs, st));   // dY of the 3x3 heads, [cells][hcs]
     ConvCall c;
     c.in = gQ[0]; c.in_cs = hcs; c.in_co = 0; c.cin = hcs; c.wpk = h->wpk_heads_bwd; c.bias = nullptr; c.wino = wino_ok(3, hcs);
     c.allow_w4 = false;
@@ -2719,6 +2793,7 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
     if (SS.n == 2) { c.nprob = 2; c.in2 = gQ[1]; c.out2 = gP[1]; }
     setup_bnr(h, SS, 7, false, c);
     CHK(launch_conv(h, c, st, SSP_PROF_CONV3X3_DGRAD));
+    for (int hk = 0; hk < h->nheads; ++hk) h->tap_route[heads[hk]] |= (unsigned)h->tap_dk << TAP_DG_SHIFT;
   }
   // ---- encoder ----
   if (part == 1) return encoder(7, EARLY_SPLIT_LAYER);
@@ -2861,6 +2936,8 @@ static int pair_step_impl(ssp_handle* h, const ssp_pair_inputs* in, float* scala
   if (!in || !scalars_dev) return fail(-1, "null argument");
   if (phase < 0 || phase > 2) return fail(-1, "pair-step phase must be 0, 1 or 2");
   AlgoScope algo(h);
+  if (h->tap_arena != nullptr && bf16_path() && in->train)
+    return fail(-1, "backward taps cover the fp32 backward only: conv algorithm 12 refuses to run with them on");
   // Single-view step (`data.warped_pair.enable: false`, Train_model_heatmap_all.py:207,237-262,330-332 - the branch the shipped
   // configs/magicpoint_shapes_pair.yaml takes): warped_image_dev == NULL.  One forward, detector (+ segmentation) loss of the
   // image only, loss_det_warp = loss_sem_warp = 0; the descriptor loss needs a pair (:343 asserts).
@@ -3093,6 +3170,7 @@ int ssp_pair_step_graph(ssp_handle* h, const ssp_pair_inputs* in, float* scalars
   if (!in || !scalars_dev) return fail(-1, "null argument");
   hipStream_t st = (hipStream_t)stream;
   if (st == nullptr) return fail(-1, "ssp_pair_step_graph needs a non-default stream (stream capture)");
+  if (h->tap_arena != nullptr) return fail(-1, "ssp_pair_step_graph: backward taps are on (ssp_debug_backward_taps); they need the eager step");
   // key = everything a captured launch depends on except the seed (kept in device memory)
   std::vector<unsigned char> key(sizeof(ssp_pair_inputs) + sizeof(void*) + 4 * sizeof(int));
   {
@@ -3682,6 +3760,29 @@ int ssp_debug_occupancy(int which) {
 
 int ssp_debug_conv_knobs(int ablate, int grid) {
   g_dbg_ablate = ablate; g_dbg_grid = grid;
+  return 0;
+}
+
+// test hook: backward taps (tap_floats / tap_offset / tap_copy); arena_dev == NULL switches them off
+int ssp_debug_backward_taps(ssp_handle* h, float* arena_dev, size_t arena_floats, unsigned layer_mask) {
+  if (!h) return fail(-1, "bad argument");
+  h->tap_arena = nullptr; h->tap_mask = 0;
+  if (arena_dev == nullptr) return 0;
+  const unsigned mask = layer_mask & 0xffffu;
+  const size_t need = tap_offset(h, mask, 2, 0, 0);
+  if (arena_floats < need) return fail(-1, "backward-tap arena holds %zu floats, the layer mask needs %zu", arena_floats, need);
+  h->tap_arena = arena_dev; h->tap_mask = mask;
+  return 0;
+}
+size_t ssp_debug_backward_tap_floats(const ssp_handle* h, unsigned layer_mask) {
+  return h ? tap_offset(h, layer_mask & 0xffffu, 2, 0, 0) : 0;
+}
+int ssp_debug_backward_tap(ssp_handle* h, int slot, int layer, int which, size_t* offset, size_t* nfloats, unsigned* route) {
+  if (!h || slot < 0 || slot > 1 || layer < 0 || layer >= 16 || which < 0 || which > 1) return fail(-1, "bad argument");
+  const size_t n = h->tap_arena != nullptr && (h->tap_mask >> layer & 1) ? tap_floats(h, layer, which) : 0;
+  if (offset) *offset = n ? tap_offset(h, h->tap_mask, slot, layer, which) : 0;
+  if (nfloats) *nfloats = n;
+  if (route) *route = h->tap_route[layer];
   return 0;
 }
 

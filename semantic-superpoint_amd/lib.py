@@ -75,7 +75,7 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_op_warp_labels_full_px", "ssp_profile_read_kernel", "ssp_op_label_quantize", "ssp_profile_pause", "ssp_op_conv_bf16", "ssp_op_conv_wgrad_bf16", "ssp_op_bn_bwd_bf16", "ssp_build_id",
            "ssp_set_deterministic", "ssp_get_deterministic", "ssp_clock_probe", "ssp_op_sem_loss",
            "ssp_describe_workspace_bytes", "ssp_describe_points", "ssp_op_sample_descriptors", "ssp_match_workspace_bytes",
-           "ssp_match_two_way"]
+           "ssp_match_two_way", "ssp_debug_backward_taps", "ssp_debug_backward_tap_floats", "ssp_debug_backward_tap"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 
@@ -164,6 +164,11 @@ def load_library(path=None):
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
     lib.ssp_debug_buffer.argtypes = [vp, i, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    if hasattr(lib, "ssp_debug_backward_taps"):  # (an A/B library of an older revision, SSP_HIP_LIB, lacks the taps)
+        lib.ssp_debug_backward_taps.argtypes = [vp, vp, C.c_size_t, C.c_uint]
+        lib.ssp_debug_backward_tap_floats.argtypes = [vp, C.c_uint]
+        lib.ssp_debug_backward_tap_floats.restype = C.c_size_t
+        lib.ssp_debug_backward_tap.argtypes = [vp, i, i, i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint)]
     lib.ssp_debug_conv_knobs.argtypes = [i, i]
     lib.ssp_debug_occupancy.argtypes = [i]
     lib.ssp_set_conv_algo.argtypes = [i]
@@ -357,6 +362,7 @@ class Engine:
         self.bn_running = torch.cat([torch.zeros(self.n_bn_ch, **f32), torch.ones(self.n_bn_ch, **f32)])
         self.nbt = torch.zeros(len(self.bns), dtype=torch.int64, device=self.device)
         self.ws_bytes = self.lib.ssp_workspace_bytes(h)
+        self._tap_arena = None   # debug_backward_taps
         self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
         self.scalars = torch.zeros(N_SCALARS, **f32)
         self.adam_t = 0
@@ -671,6 +677,35 @@ class Engine:
         off = p.value - base
         assert 0 <= off and off + numel * es <= self.ws_bytes
         return self.workspace[off:off + numel * es].view(dtype).view(*shape).clone()
+
+    def debug_backward_taps(self, layers):
+        """Test hook: switch the backward taps on for the layers in `layers` (iterable of layer indices; 8 = the three 3x3 heads)
+        with a fresh device arena owned by this engine, or off (`layers` empty / None)."""
+        mask = 0
+        for l in layers or ():
+            mask |= 1 << int(l)
+        self._tap_arena = None
+        if mask == 0:
+            _check(self.lib.ssp_debug_backward_taps(self.h, None, 0, 0))
+            return
+        n = int(self.lib.ssp_debug_backward_tap_floats(self.h, mask))
+        self._tap_arena = torch.zeros(n, dtype=torch.float32, device=self.device)
+        _check(self.lib.ssp_debug_backward_taps(self.h, _ptr(self._tap_arena), n, mask))
+
+    def backward_route(self, layer):
+        """Route record of `layer` in the last backward pass (include/ssp_hip.h, ssp_debug_backward_tap)."""
+        r = C.c_uint()
+        _check(self.lib.ssp_debug_backward_tap(self.h, 0, layer, 0, None, None, C.byref(r)))
+        return r.value
+
+    def backward_tap(self, slot, layer, which, shape):
+        """Test hook: host copy of one backward tap (which: 0 = dOut, 1 = dY) of the last step as a tensor of `shape` (NHWC, the
+        step's batch: a prefix of the tap's max_batch slice)."""
+        off, n = C.c_size_t(), C.c_size_t()
+        _check(self.lib.ssp_debug_backward_tap(self.h, slot, layer, which, C.byref(off), C.byref(n), None))
+        numel = int(np.prod(shape))
+        assert self._tap_arena is not None and 0 < numel <= n.value, (layer, which, numel, n.value)
+        return self._tap_arena[off.value:off.value + numel].view(*shape).cpu()
 
     def profile_enable(self, family):
         _check(self.lib.ssp_profile_enable(self.h, PROF[family] if isinstance(family, str) else int(family)))
