@@ -403,16 +403,13 @@ int ssp_op_bn_bwd_strided(const float* y_dev, const float* dout_dev, const float
  * DEFAULT, copied into a handle at ssp_create; takes effect at the next forward, which re-packs the weights): 1 (default) = Winograd on the fp32 matrix
  * cores, fp32 throughout: F(4x4,3x3) (4x fewer multiplies, conv_wino4_kernel) on maps of >= 60x80 pixels with >= 4 tile
  * blocks per CU, F(2x2,3x3) (2.25x fewer, software-pipelined kernel whose weight fragments come straight from L2)
- * elsewhere; results within ~2e-6 / ~3e-7 relative of the direct form, 9 = F(2x2,3x3) only (the default of rounds 1-2),
- * 10 = F(4x4,3x3) wherever legal (tests), 5 = the F(2x2,3x3) pipeline with the weights staged through LDS, 6 = its
- * two-workgroups-per-CU variant everywhere,
- * 2 = Winograd without the software pipeline (both for A/B measurements), 0 = direct implicit GEMM,
- * 3 = EXPERIMENTAL reduced precision: the Winograd kernels with bf16 matrix-core operands (fp32 storage, transforms,
- * accumulation and master weights); outputs within ~4e-3 relative RMS of fp32, gradients of the first layers up to
- * ~25 % off per step; never used for a reported fp32 number,
- * 7 = the same with split-bf16 (hi + lo) operands everywhere, 8 = MIXED (BASELINE configs[3], bench.py --dtype bf16): fp32
- * forward (algorithm 1), data / weight gradients of the 3x3 layers with one-part bf16 operands; losses equal the fp32 step's,
- * gradients within ~1e-2 per tensor, 11 = algorithm 1 with the Winograd F(3x3,4x4) weight gradient. */
+ * elsewhere; results within ~2e-6 / ~3e-7 relative of the direct form, 6 = the two-workgroups-per-CU F(2x2,3x3) pipeline
+ * everywhere, 9 = F(2x2,3x3) only (the default of rounds 1-2), 10 = F(4x4,3x3) wherever legal (tests), 11 = algorithm 1 with
+ * the Winograd F(3x3,4x4) weight gradient, 0 = direct implicit GEMM,
+ * 12 = the bf16 PATH (BASELINE configs[3], bench.py --dtype bf16): bf16 NHWC activations and activation gradients in HBM, direct
+ * bf16 matrix-core 3x3 convolutions, fp32 master weights, BatchNorm statistics, losses and Adam; the handle-less ssp_op_conv
+ * refuses a 3x3 convolution with Cin % 16 == 0 under it (-3: that case is ssp_op_conv_bf16's).
+ * 2, 3, 5, 7 and 8 (experiments of rounds 1-3) are retired: both setters refuse them (-1). */
 int ssp_set_conv_algo(int algo);
 /* the same choice for ONE handle (a new handle starts with the process-wide value of ssp_set_conv_algo, which also
  * governs the handle-less ssp_op_conv / ssp_op_conv_wgrad) */
@@ -440,7 +437,7 @@ int ssp_debug_buffer(ssp_handle* h, int slot, const char* name, float** ptr, siz
  * (S1 / S2 sums) accumulated by the data gradient above, bit 1 APPLY fused into the weight gradient, bit 2 replica reduction in
  * the weight gradient's prologue; bits 4-7 weight-gradient kernel (1 wgrad_wino_fused, 2 wgrad_wino, 3 wgrad_wino4, 4 direct,
  * 5 grouped pointwise, 6 bn_bwd_apply_l0); bits 8-11 data-gradient kernel (1 conv_wino4, 2 conv_wino_pipe, 3 conv_wino_p2,
- * 4 direct, 5 grouped pointwise, 6 other Winograd). */
+ * 4 direct, 5 grouped pointwise). */
 int ssp_debug_backward_taps(ssp_handle* h, float* arena_dev, size_t arena_floats, unsigned layer_mask);
 size_t ssp_debug_backward_tap_floats(const ssp_handle* h, unsigned layer_mask);
 int ssp_debug_backward_tap(ssp_handle* h, int slot, int layer, int which, size_t* offset, size_t* nfloats, unsigned* route);

@@ -1,15 +1,22 @@
-// Winograd F(2x2, 3x3) convolution, software-pipelined variant of conv_wino_kernel (same math, same tile / wave
-// decomposition, see conv_wino.hip.h): the K loop runs in 8-channel STAGES with double-buffered LDS images, so that
-// the staging of stage g+1 is interleaved with the MFMAs of stage g instead of stalling the matrix pipe:
+// Winograd F(2x2, 3x3) convolution on the fp32 matrix cores, software-pipelined (forward and data-gradient 3x3 convs with
+// Cin % 16 == 0; the transforms and shared constants are in conv_wino.hip.h):
+//
+//   Y(2x2) = A^T [ sum_ci (G g G^T) (.) (B^T d B) ] A        d: 4x4 input patch, g: 3x3 filter   (Lavin & Gray 2016)
+//
+// The 16 element-wise products are 16 independent GEMMs [tiles x Cin] x [Cin x Cout]: 16 multiplies per 2x2 outputs
+// instead of 36, still in fp32 arithmetic throughout (the transforms only add and halve).
+// Block = 512 threads = 8 waves (2 per SIMD), ONE block per CU: output tile 8x32 (WIDE) or 32x8 pixels = 64 Winograd
+// tiles x 64 output channels; wave w = (M-tile w >> 2 (32 tiles), N-tile (w >> 1) & 1 (32 channels), component half
+// w & 1): 8 x f32x16 accumulators.  The K loop runs in 8-channel STAGES with double-buffered LDS images, so that the
+// staging of stage g+1 is interleaved with the MFMAs of stage g instead of stalling the matrix pipe:
 //
 //   stage g, first half : 16 MFMAs / wave on sA[g&1]  ||  raw halo (g+1): registers -> sR; halo loads of stage g+2
 //   barrier
 //   stage g, second half: 16 MFMAs / wave             ||  transform sR -> sA[~g&1]
 //   barrier
 //
-// The weight (B) fragments come straight from L2 into the MFMA operand registers, one component pair ahead (template
-// parameter GB, default; GB = false stages them through sB like the input: conv algo 5).
-// LDS: 2 x (32 KB transformed input + 32 KB sB = epilogue staging / LDS-staged weights) + 10.6 KB raw halo + 8 KB
+// The weight (B) fragments come straight from L2 into the MFMA operand registers, one component pair ahead.
+// LDS: 2 x (32 KB transformed input + 32 KB sB = epilogue staging) + 10.6 KB raw halo + 8 KB
 // BatchNorm parameters = 146.6 KB, one block per CU.
 // The flat stage index runs over (tile, 8-channel chunk) pairs of the block's persistent tile list, so the pipeline
 // never drains between tiles; the tile epilogue (output transform, the two component halves meeting in ONE 64 KB
@@ -89,11 +96,11 @@ __device__ __forceinline__ void pipe_out_rows(const f32x16 (&acc)[8], int rd, in
   }
 }
 
-// GB (default; false = conv algo 5): the weight (B) fragments are loaded from global memory / L2 straight into the MFMA
-// operand registers, one component pair ahead of their use, instead of being staged through LDS (the packed weight
-// image IS the fragment layout): 32 KB less LDS writes and 64 KB less LDS reads per stage, 8 registers less; the sB
-// halves of the LDS image then only serve as the epilogue's staging tile.  +2.3 % on the pair step (1938 vs 1893).
-template <int IN_MODE, bool WIDE, bool GB = true>
+// The weight (B) fragments are loaded from global memory / L2 straight into the MFMA operand registers, one component
+// pair ahead of their use, instead of being staged through LDS (the packed weight image IS the fragment layout): 32 KB
+// less LDS writes and 64 KB less LDS reads per stage, 8 registers less than the LDS-staged form of rounds 1-3; the sB
+// halves of the LDS image only serve as the epilogue's staging tile.  +2.3 % on the pair step (1938 vs 1893).
+template <int IN_MODE, bool WIDE>
 __global__ __launch_bounds__(WINO_THREADS) void conv_wino_pipe_kernel(const ConvArgs a) {
   constexpr int TTX = WIDE ? 16 : 4;
   constexpr int TH = WIDE ? 8 : 32, TW = WIDE ? 32 : 8;
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(WINO_THREADS) void conv_wino_pipe_kernel(const Conv
   // the bank row (the former (tile >> 2) & 1 swizzle assumed contiguous lane groups and was 2-way conflicted)
   const int t_dst = ((t_row * 4) * WTILES + t_tile) * PK + ((q2 ^ ((t_tile >> 4) & 1)) << 2);
   const int pixb = a.in_cs * 4, rowb = a.W * pixb;
-  f32x4 hreg[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, wreg[4];
+  f32x4 hreg[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   f32x4 psc = {1.f, 1.f, 1.f, 1.f}, psh = {0.f, 0.f, 0.f, 0.f};
   constexpr unsigned OOB = 0x80000000u;
   unsigned hoff[2] = {OOB, OOB};
@@ -186,18 +193,14 @@ __global__ __launch_bounds__(WINO_THREADS) void conv_wino_pipe_kernel(const Conv
       hreg[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(                            \
           rsrc_in, (PIPE_ABL & 8192) ? (hoff[k] & 0xFFFFu) : hoff[k], ld_chunk * PK * 4, 0));               \
   }
-  // weights of the same (tile, chunk); advances the load cursor
-#define PIPE_ISSUE_W()                                                                                      \
+  // advances the load cursor (the weights of a stage come from L2 through PIPE_BLOAD, one component pair ahead of their use)
+#define PIPE_NEXT_CHUNK()                                                                                   \
   {                                                                                                         \
-    const int wbase_ = (cob * nst + ld_chunk) * PB_FLOATS * 4;                                              \
-    if (!GB)                                                                                                \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                           \
-      wreg[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, tid * 16, wbase_ + j * 8192, 0)); \
     if (++ld_chunk == nst) { ld_chunk = 0; ld_tile += per_cob; }                                            \
   }
-#define PIPE_ISSUE_LOADS() { PIPE_ISSUE_HALO() PIPE_ISSUE_W() }
-  // registers -> LDS for the stage whose loads are in the registers (buffer index B)
-#define PIPE_WRITE_STAGE(B)                                                                                 \
+#define PIPE_ISSUE_LOADS() { PIPE_ISSUE_HALO() PIPE_NEXT_CHUNK() }
+  // registers -> sR for the stage whose halo loads are in the registers
+#define PIPE_WRITE_STAGE()                                                                                  \
   {                                                                                                         \
     _Pragma("unroll") for (int k = 0; k < 2; ++k) {                                                         \
       if (k == 0 || r1) {                                                                                   \
@@ -206,20 +209,16 @@ __global__ __launch_bounds__(WINO_THREADS) void conv_wino_pipe_kernel(const Conv
         *reinterpret_cast<f32x4*>(sR + r_lds[k]) = v;                                                       \
       }                                                                                                     \
     }                                                                                                       \
-    f32x4* wdst = reinterpret_cast<f32x4*>(smem + (B) * (PA_FLOATS + PB_FLOATS) + PA_FLOATS);               \
-    if (!GB)                                                                                                \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) wdst[tid + WINO_THREADS * j] = wreg[j];                   \
   }
   // MFMA fragment offsets (floats, relative to the buffer base)
   const int m_tile = mt * 32 + li;
   const int a_off = (chalf * 8 * WTILES + m_tile) * PK + ((lh ^ ((m_tile >> 4) & 1)) << 2);
-  const int b_off = PA_FLOATS + ((chalf * 8 * 2 + lh) * NB + nt * 32 + li) * 4;
-  // GB: byte offset of this lane's quad inside a component's [h][64][4] weight block, two register sets of B fragments
+  // byte offset of this lane's quad inside a component's [h][64][4] weight block, two register sets of B fragments
   const int b_voff = (lh * NB + nt * 32 + li) * 16;
   f32x4 bA0 = {0.f, 0.f, 0.f, 0.f}, bA1 = bA0, bB0 = bA0, bB1 = bA0;
   const float4 abl_a = make_float4(1.f + tid * 1e-3f, 0.5f, 0.25f, 2.f);  // PIPE_ABL & 4096: constant A fragments
 #define PIPE_BLOAD(S0, S1, C, CHUNK)                                                                        \
-  if (GB && !(PIPE_ABL & 2048)) {                                                                                                 \
+  if (!(PIPE_ABL & 2048)) {                                                                                 \
     const int so_ = ((cob * nst + (CHUNK)) * PB_FLOATS + (chalf * 8 + (C)) * 2 * NB * 4) * 4;               \
     S0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, b_voff, so_, 0));          \
     S1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, b_voff, so_ + 2 * NB * 16, 0)); \
@@ -301,7 +300,7 @@ __global__ __launch_bounds__(WINO_THREADS) void conv_wino_pipe_kernel(const Conv
   }
   // ---- prologue: stage 0 into buffer 0, loads of stage 1 in flight ----
   PIPE_ISSUE_LOADS()
-  PIPE_WRITE_STAGE(0)
+  PIPE_WRITE_STAGE()
   __syncthreads();
   PIPE_TRANSFORM(0)
   PIPE_ISSUE_LOADS()
@@ -324,8 +323,8 @@ __global__ __launch_bounds__(WINO_THREADS) void conv_wino_pipe_kernel(const Conv
 #define PIPE_FRAG(C, S0, S1)                                                                                \
   const float4 a0_##C = (PIPE_ABL & 4096) ? abl_a : *reinterpret_cast<const float4*>(cA + a_off + (C) * WTILES * PK);       \
   const float4 a1_##C = (PIPE_ABL & 4096) ? abl_a : *reinterpret_cast<const float4*>(cA + a_off + ((C) + 1) * WTILES * PK); \
-  const f32x4 b0_##C = GB ? S0 : *reinterpret_cast<const f32x4*>(cA + b_off + (C) * 2 * NB * 4);            \
-  const f32x4 b1_##C = GB ? S1 : *reinterpret_cast<const f32x4*>(cA + b_off + ((C) + 1) * 2 * NB * 4);
+  const f32x4 b0_##C = S0;                                                                                  \
+  const f32x4 b1_##C = S1;
 #define PIPE_MFMA_LO(C)                                                                                     \
   if (!(PIPE_ABL & 8)) {                                                                                    \
   acc[C] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0_##C.x, b0_##C[0], acc[C], 0, 0, 0);                       \
@@ -387,8 +386,7 @@ __global__ __launch_bounds__(WINO_THREADS) void conv_wino_pipe_kernel(const Conv
     PIPE_TS(ts1)
     __syncthreads();
     PIPE_TS(ts2)
-    // ---- second half: components 4..7 || transform of stage g+1: sR -> sA, weights (g+1) -> sB of the other buffer,
-    // weight loads of stage g+2 ----
+    // ---- second half: components 4..7 || transform of stage g+1: sR -> sA of the other buffer ----
     {
       const f32x4 u0 = *reinterpret_cast<const f32x4*>(sR + t_u[0]), w0 = *reinterpret_cast<const f32x4*>(sR + t_w[0]);
       const f32x4 u1 = *reinterpret_cast<const f32x4*>(sR + t_u[1]), w1 = *reinterpret_cast<const f32x4*>(sR + t_w[1]);
@@ -415,11 +413,7 @@ __global__ __launch_bounds__(WINO_THREADS) void conv_wino_pipe_kernel(const Conv
       PIPE_FENCE();
       PIPE_MFMA_LO(6)
       PIPE_FENCE();
-      f32x4* wdst = reinterpret_cast<f32x4*>(nB + PA_FLOATS);  // weights of stage g+1 -> sB of the other buffer
-      if (!GB)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) wdst[tid + WINO_THREADS * j] = wreg[j];
-      PIPE_ISSUE_W()
+      PIPE_NEXT_CHUNK()
       PIPE_FENCE();
       PIPE_MFMA_HI(6)
     }
@@ -620,7 +614,7 @@ __global__ __launch_bounds__(WINO_THREADS) void conv_wino_pipe_kernel(const Conv
   }
 #undef PIPE_ISSUE_LOADS
 #undef PIPE_ISSUE_HALO
-#undef PIPE_ISSUE_W
+#undef PIPE_NEXT_CHUNK
 #undef PIPE_WRITE_STAGE
 #undef PIPE_TRANSFORM
 #undef PIPE_FRAG

@@ -22,12 +22,6 @@
 #include "conv_wino4.hip.h"
 #include "wgrad_wino4.hip.h"
 #include "wgrad_wino_fused.hip.h"
-#ifndef SSP_LEGACY_ALGOS
-#define SSP_LEGACY_ALGOS 0
-#endif
-#if SSP_LEGACY_ALGOS
-#include "conv_wino_bf16.hip.h"
-#endif
 #include "conv_bf16.hip.h"
 #include "conv_bf16_ws.hip.h"
 #include "wgrad_bf16.hip.h"
@@ -41,38 +35,27 @@
 
 using namespace sspk;
 
-// Convolution algorithms of rounds 1-3 that no shipped configuration selects: 2 (conv_wino_kernel, the un-pipelined F(2x2,3x3)
-// convolution), 5 (conv_wino_pipe_kernel with the weights staged through LDS) and the bf16-OPERAND experiments inside the fp32
-// Winograd kernels that the bf16 path (algorithm 12) superseded: 3 (one bf16 part), 7 (hi + lo parts), 8 (mixed: fp32 forward,
-// bf16-operand gradients) - conv_wino_bf16.hip.h.  Compiled out of the shipped library (28 kernel instances); their results are
-// profiles/PERF_LOG_rounds_1-4.md section 10 and profiles/r0[2-4]_*mixed_bf16*; -DSSP_LEGACY_ALGOS=1 (SSP_HIPCC_EXTRA) brings them back.
-#ifndef SSP_LEGACY_ALGOS
-#define SSP_LEGACY_ALGOS 0
-#endif
-
 static thread_local std::string g_err;
 static int g_dbg_ablate = 0, g_dbg_grid = 0;  // perf-debug knobs of conv_mfma_kernel (tools/archive/ablate_conv.py)
-// ssp_set_conv_algo: 0 = direct implicit GEMM, 1 = Winograd F(2x2,3x3) where eligible (software-pipelined kernel),
-// 2 = Winograd, un-pipelined kernel (conv_wino_kernel; kept for A/B measurements),
-// 3 = Winograd with bf16 matrix-core operands (conv_wino_bf16_kernel: opt-in reduced precision, BASELINE configs[3])
+// Conv algorithms (ssp_set_conv_algo, ssp_handle_set_conv_algo; check_conv_algo):
+//   0 = direct implicit GEMM everywhere;
+//   fp32 Winograd, every one of them on the software-pipelined kernels: 1 (default: F(4x4,3x3) on the large maps - conv_uses_w4 -,
+//   F(2x2,3x3) elsewhere), 6 = the second-generation F(2x2,3x3) kernel (two 4-wave workgroups per CU) everywhere, 9 = F(2x2,3x3)
+//   only (the default of rounds 1-2), 10 = F(4x4,3x3) wherever legal, 11 = algorithm 1 with the Winograd F(3x3,4x4) weight gradient
+//   (wgrad_wino4_kernel: opt-in, measured not faster);
+//   12 = the bf16 PATH (BASELINE configs[3]): bf16 NHWC activations / activation gradients in HBM, direct implicit-GEMM 3x3
+//   convolutions, data and weight gradients on v_mfma_f32_32x32x16_bf16 (conv_bf16.hip.h, wgrad_bf16.hip.h); fp32 master weights,
+//   BatchNorm statistics, losses and Adam; the pointwise heads and everything behind them stay on the fp32 kernels.
+// 2, 3, 5, 7 and 8 (rounds 1-3: the un-pipelined and the LDS-staged-weight F(2x2,3x3) kernels, bf16 operands inside the fp32
+// Winograd kernels) are retired and refused; their results are profiles/PERF_LOG_rounds_1-4.md section 10, their code commit c6c61a5.
 static int g_default_conv_algo = 1;             // process default: new handles and the handle-less ssp_op_* calls
 static thread_local int g_conv_algo = 1;        // algorithm of the call in flight (AlgoScope: the handle's, else the default)
-// 3x3 convolutions whose input channels fill whole 16-channel K-chunks run as Winograd F(2x2,3x3)
-static inline bool wino_ok(int ks, int conv_cin) { return g_conv_algo != 0 && ks == 3 && conv_cin % CK == 0; }
-// bf16 Winograd modes: number of bf16 parts per operand element.  3: one part everywhere; 7: hi + lo everywhere;
-// 8 (mixed): the FORWARD convolutions (the activations every later layer and the ReLU gates depend on) run the fp32 default
-// algorithm (FwdAlgoScope), the data-gradient and weight-gradient kernels take one part (unbiased 2^-9 noise on the gradients,
-// like any bf16 training)
-// fp32 pipelined Winograd family: 1 (default: F(4x4,3x3) on the large maps - conv_uses_w4 -, F(2x2,3x3) elsewhere), 9 = F(2x2,3x3)
-// only (the default of rounds 1-2), 10 = F(4x4,3x3) wherever legal
-// 11 = algorithm 1 with the Winograd F(3x3,4x4) weight gradient (wgrad_wino4_kernel: opt-in, measured not faster)
-static inline bool pipe_algo() { return g_conv_algo == 1 || g_conv_algo == 9 || g_conv_algo == 10 || g_conv_algo == 11; }
-static inline bool bf16_algo() { return SSP_LEGACY_ALGOS && (g_conv_algo == 3 || g_conv_algo == 7 || g_conv_algo == 8); }
-// 12 = the bf16 PATH (BASELINE configs[3]): bf16 NHWC activations / activation gradients in HBM, direct implicit-GEMM 3x3 convolutions,
-// data and weight gradients on v_mfma_f32_32x32x16_bf16 (conv_bf16.hip.h, wgrad_bf16.hip.h); fp32 master weights, BatchNorm
-// statistics, losses and Adam; the pointwise heads and everything behind them stay on the fp32 kernels
 static inline bool bf16_path() { return g_conv_algo == 12; }
-static inline int bf16_parts(bool backward) { return g_conv_algo == 7 || (g_conv_algo == 8 && !backward) ? 2 : 1; }
+// fp32 Winograd algorithms: 3x3 convolutions whose input channels fill whole 16-channel K-chunks run as Winograd
+static inline bool wino_ok(int ks, int conv_cin) {
+  const bool wino_algo = g_conv_algo == 1 || g_conv_algo == 6 || g_conv_algo == 9 || g_conv_algo == 10 || g_conv_algo == 11;
+  return wino_algo && ks == 3 && conv_cin % CK == 0;
+}
 static inline int pk_taps(int ks) { return ks == 3 ? W4C : ks * ks; }  // packed-weight capacity per (chunk, 16 ci, 64 co)
 static int fail(int code, const char* fmt, ...) {
   char buf[512];
@@ -82,6 +65,17 @@ static int fail(int code, const char* fmt, ...) {
   va_end(ap);
   g_err = buf;
   return code;
+}
+// the one validator of both conv-algorithm setters: 0 if `algo` is in the table above, else -1 and the error message
+static int check_conv_algo(int algo) {
+  if (algo == 2 || algo == 3 || algo == 5 || algo == 7 || algo == 8)
+    return fail(-1, "conv algo %d is retired: an experiment of rounds 1-3, compiled out since round 5, its code last in commit c6c61a5", algo);
+  if (algo < 0 || algo > 12 || algo == 4)
+    return fail(-1, "conv algo must be 0 (direct), 1 (Winograd, pipelined; default), 6 (Winograd, two 4-wave workgroups per CU), "
+                    "9 (Winograd F(2x2,3x3) only: algorithm 1 without F(4x4,3x3) on the large maps), 10 (F(4x4,3x3) wherever legal), "
+                    "11 (algorithm 1 with the F(3x3,4x4) weight gradient) or 12 (the bf16 path: bf16 activations in HBM, direct bf16 "
+                    "matrix-core convolutions)");
+  return 0;
 }
 #define HIPCHK(x)                                                                          \
   do {                                                                                     \
@@ -239,21 +233,12 @@ struct ssp_handle {
 // route bits of ssp_debug_backward_tap (include/ssp_hip.h)
 enum { TAP_BSUMS_FUSED = 1, TAP_APPLY_FUSED = 2, TAP_SUMS_LAZY = 4, TAP_WG_SHIFT = 4, TAP_DG_SHIFT = 8 };
 enum { TAP_WG_FUSED12 = 1, TAP_WG_WINO = 2, TAP_WG_WINO4 = 3, TAP_WG_DIRECT = 4, TAP_WG_GROUPED = 5, TAP_WG_L0 = 6 };
-enum { TAP_DG_WINO4 = 1, TAP_DG_PIPE = 2, TAP_DG_P2 = 3, TAP_DG_DIRECT = 4, TAP_DG_GROUPED = 5, TAP_DG_OTHER = 6 };
+enum { TAP_DG_WINO4 = 1, TAP_DG_PIPE = 2, TAP_DG_P2 = 3, TAP_DG_DIRECT = 4, TAP_DG_GROUPED = 5 };
 
 struct AlgoScope {  // makes the handle's conv algorithm the current one for the duration of an entry point
   int prev;
   explicit AlgoScope(const ssp_handle* h) : prev(g_conv_algo) { g_conv_algo = h ? h->conv_algo : g_default_conv_algo; }
   ~AlgoScope() { g_conv_algo = prev; }
-};
-
-// Mixed mode 8 = fp32 FORWARD (the default algorithm's kernels: F(4x4,3x3) on the large maps is faster than the split-bf16
-// F(2x2,3x3) forward this mode used to run, and exact), bf16 operands in the data-gradient and weight-gradient convolutions.
-// Forward launches and the packing of the forward images run under this scope.
-struct FwdAlgoScope {
-  int prev;
-  FwdAlgoScope() : prev(g_conv_algo) { if (prev == 8) g_conv_algo = 1; }
-  ~FwdAlgoScope() { g_conv_algo = prev; }
 };
 
 enum { L_PA = 8, L_PB = 9, L_DA = 10, L_DB = 11, L_DS = 12, L_SOUT = 13 };
@@ -513,8 +498,7 @@ struct ConvCall {
   int nprob = 1;
   const float* in2 = nullptr; float* out2 = nullptr;
   const float* in_scale2 = nullptr; const float* in_shift2 = nullptr; double* stats2 = nullptr;
-  bool wino = false;  // wpk holds pack_weights_wino_kernel's image: run conv_wino_kernel
-  bool backward = false;  // data-gradient launch (selects the operand precision of the mixed bf16 mode)
+  bool wino = false;  // (wino_ok) wpk holds a Winograd image: run one of the pipelined Winograd kernels
   // data-gradient launches: BatchNorm-backward sums of the layer below fused into the epilogue (ConvArgs::bnr_*);
   // honoured by the pipelined Winograd kernel only - can_fuse_bnr() tells the caller
   int bnr_mode = 0;
@@ -531,14 +515,13 @@ struct ConvCall {
   BnLazy lazy;           // training forward: the input layer's BatchNorm affine derived by this launch (conv_has_bn_lazy() tells the caller)
 };
 static bool can_fuse_bnr(const ConvCall& c) {
-  return c.wino && (pipe_algo() || g_conv_algo == 5 || g_conv_algo == 6 || bf16_algo()) && c.in_mode == 0 && c.cout % 4 == 0 && c.out_co % 4 == 0 &&
-         c.out_cs % 4 == 0;
+  return c.wino && c.in_mode == 0 && c.cout % 4 == 0 && c.out_co % 4 == 0 && c.out_cs % 4 == 0;
 }
 
-template <int IN_MODE, bool WIDE, bool GB = false>
+template <int IN_MODE, bool WIDE>
 static int launch_wino_pipe_t(const ConvArgs& a, int nblocks, hipStream_t st) {
   static AttrOnce attr_once;
-  auto kern = conv_wino_pipe_kernel<IN_MODE, WIDE, GB>;
+  auto kern = conv_wino_pipe_kernel<IN_MODE, WIDE>;
   if (attr_once.need()) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PIPE_LDS_BYTES));
   }
@@ -598,33 +581,6 @@ static int launch_wino4_t(const ConvArgs& a_in, int nblocks, hipStream_t st) {
   return 0;
 }
 
-#if SSP_LEGACY_ALGOS
-template <int IN_MODE, bool WIDE, int NT = 1>
-static int launch_wino_bf16_t(const ConvArgs& a, int nblocks, hipStream_t st) {
-  static AttrOnce attr_once;
-  auto kern = conv_wino_bf16_kernel<IN_MODE, WIDE, NT>;
-  constexpr int lds = NT == 1 ? BF16_LDS_BYTES : BF16X2_LDS_BYTES;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(WINO_THREADS), lds, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <int IN_MODE, bool WIDE>
-static int launch_wino_t(const ConvArgs& a, int nblocks, hipStream_t st) {
-  static AttrOnce attr_once;
-  auto kern = conv_wino_kernel<IN_MODE, WIDE>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, WINO_LDS_BYTES));
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(WINO_THREADS), WINO_LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-#endif
-
 // default algorithm (1): maps with few first-generation work items per CU (the 30x40 layers: 640 items on 256 CUs =
 // 2.5 rounds) run on the finer-grained second-generation kernel (measured 10-15 % faster there, 1-4 % slower on the
 // large maps: tools/archive/conv_probe.py)
@@ -657,16 +613,15 @@ static bool conv_uses_w4(const ssp_handle* h, const ConvCall& c) {
 static bool conv_uses_p2(const ssp_handle* h, const ConvCall& c) {
   if (!c.wino) return false;
   if (g_conv_algo == 6) return true;
-  if (!pipe_algo() || conv_uses_w4(h, c)) return false;
+  if (conv_uses_w4(h, c)) return false;
   const bool w1 = (c.W % 32) == 0;
   const long items = (long)c.nprob * c.N * cdiv(c.H, w1 ? 8 : 32) * cdiv(c.W, w1 ? 32 : 8) * c.ncob;
   return items < 4L * (h ? h->n_cu : 256);
 }
-// will this forward launch write ConvCall::pool_out (first-generation pipelined Winograd kernel, contiguous output)?
+// will this forward launch write ConvCall::pool_out (conv_wino_pipe_kernel or conv_wino4_kernel, contiguous output)?
 static bool conv_writes_pool(const ssp_handle* h, const ConvCall& c) {
-  // (first-generation pipelined kernels: fp32 algorithms 1 / 5 and the bf16-operand kernels 3 / 7 / 8, which share the tile geometry)
-  return c.wino && c.in_mode == 1 && (pipe_algo() || g_conv_algo == 5 || bf16_algo()) && !conv_uses_p2(h, c) && c.H % 2 == 0 && c.W % 2 == 0 &&
-         c.cout % 4 == 0 && c.out_co == 0 && c.out_cs == c.cout && (!conv_uses_w4(h, c) || c.cout % NB == 0);
+  return c.wino && c.in_mode == 1 && !conv_uses_p2(h, c) && c.H % 2 == 0 && c.W % 2 == 0 && c.cout % 4 == 0 && c.out_co == 0 &&
+         c.out_cs == c.cout && (!conv_uses_w4(h, c) || c.cout % NB == 0);
 }
 
 // will this launch run a kernel whose prologue can derive its input layer's BatchNorm affine from the raw statistics (BnLazy:
@@ -675,10 +630,7 @@ static bool bn_lazy_env() {
   static const int v = getenv("SSP_BN_LAZY") ? atoi(getenv("SSP_BN_LAZY")) : 1;
   return v != 0;
 }
-static bool conv_has_bn_lazy(const ssp_handle* h, const ConvCall& c) {
-  if (!bn_lazy_env() || !c.wino || c.in_mode != 1 || bf16_algo() || g_conv_algo == 5) return false;
-  return conv_uses_w4(h, c) || conv_uses_p2(h, c) || pipe_algo();
-}
+static bool conv_has_bn_lazy(const ConvCall& c) { return bn_lazy_env() && c.wino && c.in_mode == 1; }
 
 static int launch_conv(ssp_handle* h, const ConvCall& c, hipStream_t st, int prof_family = 0) {
   ConvArgs a;
@@ -688,7 +640,7 @@ static int launch_conv(ssp_handle* h, const ConvCall& c, hipStream_t st, int pro
   a.nprob = c.nprob; a.in2 = c.in2; a.out2 = c.out2; a.in_scale2 = c.in_scale2; a.in_shift2 = c.in_shift2;
   a.stats2 = c.stats2;
   if (c.lazy.mode != 0) {
-    if (!conv_has_bn_lazy(h, c)) return fail(-3, "consumer-side BatchNorm finalize needs one of the Winograd kernels of the default algorithm");
+    if (!conv_has_bn_lazy(c)) return fail(-3, "consumer-side BatchNorm finalize needs one of the Winograd kernels of the default algorithm");
     a.lazy = c.lazy;
   }
   if (c.bnr_mode != 0) {
@@ -719,7 +671,7 @@ static int launch_conv(ssp_handle* h, const ConvCall& c, hipStream_t st, int pro
   // large maps: tools/archive/conv_probe.py)
   const bool p2 = conv_uses_p2(h, c);
   const bool w4 = conv_uses_w4(h, c);
-  if (h) h->tap_dk = w4 ? TAP_DG_WINO4 : p2 ? TAP_DG_P2 : (c.wino && pipe_algo()) ? TAP_DG_PIPE : c.wino ? TAP_DG_OTHER : TAP_DG_DIRECT;
+  if (h) h->tap_dk = w4 ? TAP_DG_WINO4 : p2 ? TAP_DG_P2 : c.wino ? TAP_DG_PIPE : TAP_DG_DIRECT;
   if (c.pool_out[0] != nullptr) {
     if (!conv_writes_pool(h, c)) return fail(-3, "pooled raw output needs the first-generation pipelined Winograd kernel");
     a.pool_out[0] = c.pool_out[0]; a.pool_out[1] = c.pool_out[1]; a.pool_gamma = c.pool_gamma;
@@ -749,45 +701,20 @@ static int launch_conv(ssp_handle* h, const ConvCall& c, hipStream_t st, int pro
       c.cin == 64)
     fam = SSP_PROF_CONV_BIG_FWD;
   // multiplies executed on the matrix cores: 36 per 16 outputs x 9 taps (F(4x4,3x3)), 16 per 4 x 9 (F(2x2,3x3))
-  const int pkern = w4 ? SSP_PROF_K_CONV_WINO4 : (c.wino && bf16_algo()) ? SSP_PROF_K_OTHER : p2 ? SSP_PROF_K_CONV_WINO_P2
-                    : (c.wino && (pipe_algo() || g_conv_algo == 5)) ? SSP_PROF_K_CONV_WINO_PIPE : SSP_PROF_K_OTHER;
+  const int pkern = w4 ? SSP_PROF_K_CONV_WINO4 : p2 ? SSP_PROF_K_CONV_WINO_P2 : c.wino ? SSP_PROF_K_CONV_WINO_PIPE : SSP_PROF_K_OTHER;
   ProfScope ps(h, fam, st, flops, bytes, flops * (w4 ? 0.25 : c.wino ? 16.0 / 36.0 : 1.0), pkern);
   if (w4) {  // Winograd F(4x4,3x3), one 8-wave workgroup per CU
     if (c.in_mode == 0) return wide4 ? launch_wino4_t<0, true>(a, nblocks, st) : launch_wino4_t<0, false>(a, nblocks, st);
     return wide4 ? launch_wino4_t<1, true>(a, nblocks, st) : launch_wino4_t<1, false>(a, nblocks, st);
   }
-#if SSP_LEGACY_ALGOS
-  if (c.wino && bf16_algo()) {
-    if (bf16_parts(c.backward) == 1) {
-      a.wpk_bytes /= 2;  // one bf16 part: half the bytes of the fp32 image
-      if (c.in_mode == 0) return wide ? launch_wino_bf16_t<0, true>(a, nblocks, st) : launch_wino_bf16_t<0, false>(a, nblocks, st);
-      return wide ? launch_wino_bf16_t<1, true>(a, nblocks, st) : launch_wino_bf16_t<1, false>(a, nblocks, st);
-    }
-    // hi + lo parts (the image has the size of the fp32 one)
-    if (c.in_mode == 0) return wide ? launch_wino_bf16_t<0, true, 2>(a, nblocks, st) : launch_wino_bf16_t<0, false, 2>(a, nblocks, st);
-    return wide ? launch_wino_bf16_t<1, true, 2>(a, nblocks, st) : launch_wino_bf16_t<1, false, 2>(a, nblocks, st);
-  }
-#endif
   if (p2) {  // second-generation pipelined Winograd: two independent 4-wave workgroups per CU
     if (c.in_mode == 0) return wide ? launch_wino_p2_t<0, true>(a, nblocks, st) : launch_wino_p2_t<0, false>(a, nblocks, st);
     return wide ? launch_wino_p2_t<1, true>(a, nblocks, st) : launch_wino_p2_t<1, false>(a, nblocks, st);
   }
-  if (c.wino && pipe_algo()) {  // pipelined Winograd, weight fragments straight from L2 (default)
-    if (c.in_mode == 0) return wide ? launch_wino_pipe_t<0, true, true>(a, nblocks, st) : launch_wino_pipe_t<0, false, true>(a, nblocks, st);
-    return wide ? launch_wino_pipe_t<1, true, true>(a, nblocks, st) : launch_wino_pipe_t<1, false, true>(a, nblocks, st);
-  }
-#if SSP_LEGACY_ALGOS
-  if (c.wino && g_conv_algo == 5) {  // the same pipeline with the weights staged through LDS
+  if (c.wino) {  // first-generation pipelined Winograd, weight fragments straight from L2
     if (c.in_mode == 0) return wide ? launch_wino_pipe_t<0, true>(a, nblocks, st) : launch_wino_pipe_t<0, false>(a, nblocks, st);
     return wide ? launch_wino_pipe_t<1, true>(a, nblocks, st) : launch_wino_pipe_t<1, false>(a, nblocks, st);
   }
-  if (c.wino) {
-    if (c.in_mode == 0) return wide ? launch_wino_t<0, true>(a, nblocks, st) : launch_wino_t<0, false>(a, nblocks, st);
-    return wide ? launch_wino_t<1, true>(a, nblocks, st) : launch_wino_t<1, false>(a, nblocks, st);
-  }
-#else
-  if (c.wino) return fail(-3, "conv algorithm %d is compiled out (build with -DSSP_LEGACY_ALGOS=1)", g_conv_algo);
-#endif
 #define CONV_CASE(KS_, M_)                                                          \
   if (c.ks == KS_ && c.in_mode == M_) {                                             \
     return wide ? launch_conv_t<KS_, M_, 1, 32>(a, nblocks, st) : launch_conv_t<KS_, M_, 4, 8>(a, nblocks, st); \
@@ -997,11 +924,11 @@ static int launch_wgrad_wino_t(const WgradArgs& a, int nblocks, hipStream_t st) 
   return 0;
 }
 
-template <int IN_MODE, bool WIDE, bool POOL, bool BF16 = false>
+template <int IN_MODE, bool WIDE, bool POOL>
 static int launch_wgrad_wino_fused_t(const WgradArgs& a_in, int nblocks, hipStream_t st) {
   using GF = WgradFusedGeom<WIDE>;
   static AttrOnce attr_once;
-  auto kern = wgrad_wino_fused_kernel<IN_MODE, WIDE, POOL, BF16>;
+  auto kern = wgrad_wino_fused_kernel<IN_MODE, WIDE, POOL>;
   if (attr_once.need()) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, GF::LDS_BYTES));
   }
@@ -1051,21 +978,6 @@ static int launch_wgrad_wino4_t(const WgradArgs& a, int nblocks, hipStream_t st)
   return 0;
 }
 
-#if SSP_LEGACY_ALGOS
-template <int IN_MODE, bool WIDE, int NT = 1>
-static int launch_wgrad_wino_bf16_t(const WgradArgs& a, int nblocks, hipStream_t st) {
-  using G = WgradWinoGeom<WIDE>;
-  static AttrOnce attr_once;
-  auto kern = wgrad_wino_bf16_kernel<IN_MODE, WIDE, NT>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(512), G::LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-#endif
-
 struct WgradCall {
   const float* in; int in_cs, in_co, cin;
   const float* dout; int dout_cs, dout_co, cout;
@@ -1095,7 +1007,7 @@ struct WgradCall {
 static bool wgrad_can_fuse_apply(int ks, int in_mode, int H, int W, int cout) {
   static const int env = getenv("SSP_FUSE_APPLY") ? atoi(getenv("SSP_FUSE_APPLY")) : 1;  // (perf-debug A/B)
   static const int f4 = getenv("SSP_WGRAD_F4") ? atoi(getenv("SSP_WGRAD_F4")) : 0;        // (forces wgrad_wino4_kernel)
-  const bool algo_ok = g_conv_algo == 1 || g_conv_algo == 9 || g_conv_algo == 10 || (bf16_algo() && bf16_parts(true) == 1);
+  const bool algo_ok = g_conv_algo == 1 || g_conv_algo == 9 || g_conv_algo == 10;
   return env != 0 && f4 == 0 && algo_ok && ks == 3 && in_mode != 2 && H % 2 == 0 && W % 2 == 0 && cout % 4 == 0;
 }
 
@@ -1190,32 +1102,16 @@ static int launch_wgrad(ssp_handle* h, const WgradCall& c, float* partial, size_
     const double bytes = 4.0 * c.nprob * c.N * c.H * c.W * ((double)c.cin * (c.in_mode == 2 ? 4 : 1) +
                                                             (c.fuse_apply ? (2.0 + (c.fuse_pool ? 0.25 : 1.0)) * c.cout : (double)c.cout));
     ProfScope ps(h, c.ks == 3 ? SSP_PROF_CONV3X3_WGRAD : -1, st, flops, bytes, flops * (wino4 ? 0.25 : wino ? 16.0 / 36.0 : 1.0),
-                 wino4 ? SSP_PROF_K_WGRAD_WINO4 : wino && !bf16_algo() ? SSP_PROF_K_WGRAD_WINO : SSP_PROF_K_OTHER);
+                 wino4 ? SSP_PROF_K_WGRAD_WINO4 : wino ? SSP_PROF_K_WGRAD_WINO : SSP_PROF_K_OTHER);
     if (c.fuse_apply) {
-      const bool b16 = bf16_algo();
-      if (!wino || wino4 || (b16 && bf16_parts(true) != 1))
-        return fail(-3, "fused BatchNorm apply needs the F(3x3,2x2) weight gradient (fp32, or bf16 operands in one part)");
-#if SSP_LEGACY_ALGOS
-#define WGF_CASE(M_, P_) \
-      if (c.in_mode == M_ && c.fuse_pool == P_ && !b16) CHK((wide ? launch_wgrad_wino_fused_t<M_, true, P_>(a, nblocks, st) : launch_wgrad_wino_fused_t<M_, false, P_>(a, nblocks, st))); \
-      if (c.in_mode == M_ && c.fuse_pool == P_ && b16) CHK((wide ? launch_wgrad_wino_fused_t<M_, true, P_, true>(a, nblocks, st) : launch_wgrad_wino_fused_t<M_, false, P_, true>(a, nblocks, st)));
-#else
+      if (!wino || wino4) return fail(-3, "fused BatchNorm apply needs the fp32 F(3x3,2x2) weight gradient");
 #define WGF_CASE(M_, P_) \
       if (c.in_mode == M_ && c.fuse_pool == P_) CHK((wide ? launch_wgrad_wino_fused_t<M_, true, P_>(a, nblocks, st) : launch_wgrad_wino_fused_t<M_, false, P_>(a, nblocks, st)));
-#endif
       WGF_CASE(0, false) WGF_CASE(0, true) WGF_CASE(1, false) WGF_CASE(1, true)
 #undef WGF_CASE
     } else if (wino4) {
       if (c.in_mode == 0) CHK((wide ? launch_wgrad_wino4_t<0, true>(a, nblocks, st) : launch_wgrad_wino4_t<0, false>(a, nblocks, st)));
       else CHK((wide ? launch_wgrad_wino4_t<1, true>(a, nblocks, st) : launch_wgrad_wino4_t<1, false>(a, nblocks, st)));
-#if SSP_LEGACY_ALGOS
-    } else if (wino && bf16_algo() && bf16_parts(true) == 1) {
-      if (c.in_mode == 0) CHK((wide ? launch_wgrad_wino_bf16_t<0, true>(a, nblocks, st) : launch_wgrad_wino_bf16_t<0, false>(a, nblocks, st)));
-      else CHK((wide ? launch_wgrad_wino_bf16_t<1, true>(a, nblocks, st) : launch_wgrad_wino_bf16_t<1, false>(a, nblocks, st)));
-    } else if (wino && bf16_algo()) {
-      if (c.in_mode == 0) CHK((wide ? launch_wgrad_wino_bf16_t<0, true, 2>(a, nblocks, st) : launch_wgrad_wino_bf16_t<0, false, 2>(a, nblocks, st)));
-      else CHK((wide ? launch_wgrad_wino_bf16_t<1, true, 2>(a, nblocks, st) : launch_wgrad_wino_bf16_t<1, false, 2>(a, nblocks, st)));
-#endif
     } else if (wino) {
       if (c.in_mode == 0) CHK((wide ? launch_wgrad_wino_t<0, true>(a, nblocks, st) : launch_wgrad_wino_t<0, false>(a, nblocks, st)));
       else CHK((wide ? launch_wgrad_wino_t<1, true>(a, nblocks, st) : launch_wgrad_wino_t<1, false>(a, nblocks, st)));
@@ -1257,18 +1153,9 @@ static int launch_pack(const float* w, float* dst, int cout_w, int cin_w, int ks
     if (w4)  // F(4x4,3x3) image of conv_wino4_kernel: 8-channel chunks of 36 components
       hipLaunchKernelGGL(pack_weights_wino4_kernel, dim3(cdiv(ncob * 2 * nchunks * W4_B_FLOATS, 256)), dim3(256), 0, st, w, dst,
                          cout_w, cin_w, tf, 2 * nchunks, 0, 0, ncob, 2 * nchunks);
-#if SSP_LEGACY_ALGOS
-    else if (bf16_algo())
-      hipLaunchKernelGGL(pack_weights_wino8_bf16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w,
-                         reinterpret_cast<__bf16*>(dst), cout_w, cin_w, tf, 2 * nchunks, 0, 0, ncob, 2 * nchunks,
-                         bf16_parts(tf != 0));
-#endif
-    else if (pipe_algo() || g_conv_algo == 5 || g_conv_algo == 6)  // 8-channel stages of the pipelined kernels: twice as many chunks of half the size
+    else  // 8-channel stages of the pipelined F(2x2,3x3) kernels: twice as many chunks of half the size
       hipLaunchKernelGGL(pack_weights_wino8_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w, dst, cout_w, cin_w, tf,
                          2 * nchunks, 0, 0, ncob, 2 * nchunks);
-    else
-      hipLaunchKernelGGL(pack_weights_wino_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w, dst, cout_w, cin_w, tf,
-                         nchunks, 0, 0, ncob, nchunks);
     HIPCHK(hipGetLastError());
     return 0;
   }
@@ -1699,8 +1586,7 @@ struct BnDeferred {
 };
 
 static int pack_all(ssp_handle* h, bool with_bwd, int nprob, int N, int H, int W, hipStream_t st) {
-  // default algorithm: every Winograd image (3x3 layers forward + data gradient, concatenated heads) in one launch
-  const bool multi = pipe_algo() || g_conv_algo == 5 || g_conv_algo == 6;
+  // every Winograd image (3x3 layers forward + data gradient, concatenated heads) in one launch
   PackJobs J;
   J.n = 0;
   int nblocks = 0;
@@ -1712,8 +1598,7 @@ static int pack_all(ssp_handle* h, bool with_bwd, int nprob, int N, int H, int W
     nblocks += cdiv((long)ncob * nchunks * PK * NB, 256);  // one thread per (channel pair) cell: all components of a filter
   };
   auto pack = [&](const float* w, float* dst, int cout_w, int cin_w, int ks, int tf, bool wino, bool w4) -> int {
-    const bool multi_now = pipe_algo() || g_conv_algo == 5 || g_conv_algo == 6;  // (the forward images of mode 8 are packed as algorithm 1)
-    if (multi_now && wino && J.n < PACK_MAX_JOBS) {
+    if (wino && J.n < PACK_MAX_JOBS) {
       const int conv_cin = tf ? cout_w : cin_w, conv_cout = tf ? cin_w : cout_w;
       const int nchunks = 2 * cdiv(conv_cin, CK), ncob = cdiv(conv_cout, NB);
       add_job(w, dst, cout_w, cin_w, tf, nchunks, 0, 0, ncob, nchunks, w4);
@@ -1751,11 +1636,8 @@ static int pack_all(ssp_handle* h, bool with_bwd, int nprob, int N, int H, int W
       continue;
     }
     const bool wf = wino_ok(d.ks, d.cin), wb = wino_ok(d.ks, d.cout);
-    {
-      FwdAlgoScope fwd;
-      h->pk_w4_fwd[l] = wf && d.ks == 3 && w4_eligible(h, nprob, N, lh, lw, d.cin, d.cout);
-      CHK(pack(P(h, d.w_off), h->wpk_fwd + d.pk_fwd, d.cout, d.cin, d.ks, 0, wf, h->pk_w4_fwd[l]));
-    }
+    h->pk_w4_fwd[l] = wf && d.ks == 3 && w4_eligible(h, nprob, N, lh, lw, d.cin, d.cout);
+    CHK(pack(P(h, d.w_off), h->wpk_fwd + d.pk_fwd, d.cout, d.cin, d.ks, 0, wf, h->pk_w4_fwd[l]));
     if (with_bwd) {
       h->pk_w4_bwd[l] = wb && d.ks == 3 && w4_eligible(h, nprob, N, lh, lw, (int)align_up(d.cout, 4), d.cin);
       CHK(pack(P(h, d.w_off), h->wpk_bwd + d.pk_bwd, d.cout, d.cin, d.ks, 1, wb, h->pk_w4_bwd[l]));
@@ -1772,21 +1654,11 @@ static int pack_all(ssp_handle* h, bool with_bwd, int nprob, int N, int H, int W
     const bool wino = wino_ok(3, 256 * h->nheads);
     const int total = 2 * 16 * (wino ? WC : 9) * CK * NB;
     for (int k = 0; k < h->nheads; ++k) {
-#if SSP_LEGACY_ALGOS
-      if (wino && bf16_algo())
-        hipLaunchKernelGGL(pack_weights_wino8_bf16_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st,
-                           P(h, h->L[heads[k]].w_off), reinterpret_cast<__bf16*>(h->wpk_heads_bwd), 256, 128, 1,
-                           32 * h->nheads, 32 * k, 0, 2, 32, bf16_parts(true));
-      else
-#endif
-      if (wino && multi && J.n < PACK_MAX_JOBS)
+      if (wino && J.n < PACK_MAX_JOBS)
         add_job(P(h, h->L[heads[k]].w_off), h->wpk_heads_bwd, 256, 128, 1, 32 * h->nheads, 32 * k, 0, 2, 32);
-      else if (wino && multi)
+      else if (wino)
         hipLaunchKernelGGL(pack_weights_wino8_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st,
                            P(h, h->L[heads[k]].w_off), h->wpk_heads_bwd, 256, 128, 1, 32 * h->nheads, 32 * k, 0, 2, 32);
-      else if (wino)
-        hipLaunchKernelGGL(pack_weights_wino_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st,
-                           P(h, h->L[heads[k]].w_off), h->wpk_heads_bwd, 256, 128, 1, 16 * h->nheads, 16 * k, 0, 2, 16);
       else
         hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, P(h, h->L[heads[k]].w_off),
                            h->wpk_heads_bwd, 256, 128, 3, 1, 16 * h->nheads, 16 * k, 0, 2, 16);
@@ -1955,7 +1827,6 @@ static int conv_layer_fwd(ssp_handle* h, const SlotSet& SS, int l, int src, int 
   const LayerDesc& d = h->L[l];
   Slot& A = *SS.s[0];
   if (bf16_path()) return conv_layer_fwd_bf16(h, SS, l, src, N, H, W, in_mode, train, st, deferred);
-  FwdAlgoScope fwd_algo;
   const bool pooled = in_mode == 2;  // input = pooled output of layer src: raw pooled y (BatchNorm + ReLU on load, mode 1)
                                      // when its conv wrote it (pool_raw), else materialised maxpool(relu(bn(Y_src))) (mode 0)
   if (pooled && A.pool_raw[src]) {
@@ -1996,7 +1867,7 @@ static int conv_layer_fwd(ssp_handle* h, const SlotSet& SS, int l, int src, int 
   }
   // the input layer's statistics are still raw (fin_pending): this launch derives the affine itself where its kernel can
   if (src >= 0 && h->fin_pending[src]) {
-    if (conv_has_bn_lazy(h, c)) {
+    if (conv_has_bn_lazy(c)) {
       const LayerDesc& ds = h->L[src];
       BnLazy& z = c.lazy;
       for (int k = 0; k < SS.n; ++k) {
@@ -2016,7 +1887,7 @@ static int conv_layer_fwd(ssp_handle* h, const SlotSet& SS, int l, int src, int 
   }
   CHK(launch_conv(h, c, st, d.ks == 3 ? SSP_PROF_CONV3X3_FWD : 0));
   if (d.bn && deferred != nullptr && deferred->n < 3) deferred->layers[deferred->n++] = l;
-  else if (d.bn && train && l < 8 && bn_lazy_env() && !bf16_algo()) {   // encoder layers: the next convolution finalizes (or bn_finalize_pending)
+  else if (d.bn && train && l < 8 && bn_lazy_env()) {   // encoder layers: the next convolution finalizes (or bn_finalize_pending)
     h->fin_pending[l] = true;
     h->fin_count[l] = (double)N * H * W;
   }
@@ -2196,7 +2067,7 @@ static int bn_layer_backward(ssp_handle* h, const SlotSet& SS, int l, const floa
     h->apply_fused[l] = defer;
     // pass 1 came from the data gradient above, pass 2 goes into the weight gradient: what is left is the replica reduction, and
     // the fused weight gradient can do that in its prologue (WgradArgs::f_lazy) - no launch at all
-    if (fused && defer && bn_lazy_env() && !bf16_algo()) h->sums_lazy[l] = true;
+    if (fused && defer && bn_lazy_env()) h->sums_lazy[l] = true;
     else CHK((launch_bn_bwd<true, false>(a, SS.n, dg, db, st, fused, defer, queue)));
   }
   else if (collect != nullptr) {   // BatchNorm without ReLU (the pointwise heads): the caller launches two layers together
@@ -2279,7 +2150,7 @@ static int conv_layer_backward(ssp_handle* h, const SlotSet& SS, int l, int src,
   c.in = dy[0]; c.in_cs = dy_cs; c.in_co = dy_co; c.cin = (int)align_up(d.cout, 4);
   c.wpk = h->wpk_bwd + d.pk_bwd; c.bias = nullptr; c.wino = wino_ok(d.ks, d.cout);
   c.out = din[0]; c.out_cs = din_cs; c.out_co = din_co; c.cout = d.cin;
-  c.in_scale = nullptr; c.in_shift = nullptr; c.stats = nullptr; c.backward = true;
+  c.in_scale = nullptr; c.in_shift = nullptr; c.stats = nullptr;
   c.N = N; c.H = H; c.W = W; c.ks = d.ks; c.in_mode = 0; c.nchunks = d.nchunks_bwd; c.ncob = d.ncob_bwd;
   c.force_w4 = h->pk_w4_bwd[l] ? 1 : 0;
   if (SS.n == 2) {
@@ -2789,7 +2660,6 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
     c.allow_w4 = false;
     c.out = gP[0]; c.out_cs = 128; c.out_co = 0; c.cout = 128; c.in_scale = nullptr; c.in_shift = nullptr;
     c.stats = nullptr; c.N = N; c.H = Hc; c.W = Wc; c.ks = 3; c.in_mode = 0; c.nchunks = 16 * h->nheads; c.ncob = 2;
-    c.backward = true;
     if (SS.n == 2) { c.nprob = 2; c.in2 = gQ[1]; c.out2 = gP[1]; }
     setup_bnr(h, SS, 7, false, c);
     CHK(launch_conv(h, c, st, SSP_PROF_CONV3X3_DGRAD));
@@ -3144,9 +3014,7 @@ int ssp_adam_step_scaled(ssp_handle* h, float lr, int step, float grad_scale, vo
 
 int ssp_handle_set_conv_algo(ssp_handle* h, int algo) {
   if (!h) return fail(-1, "null handle");
-  if (algo < 0 || algo > 12 || algo == 4) return fail(-1, "conv algo must be 0..3 or 5..12 (see ssp_set_conv_algo)");
-  if (!SSP_LEGACY_ALGOS && (algo == 2 || algo == 3 || algo == 5 || algo == 7 || algo == 8))
-    return fail(-1, "conv algo %d is compiled out of the shipped library (-DSSP_LEGACY_ALGOS=1)", algo);
+  CHK(check_conv_algo(algo));
   h->conv_algo = algo;
   return 0;
 }
@@ -3258,6 +3126,9 @@ int ssp_op_conv(const float* in_dev, const float* w_oihw_dev, const float* bias_
   const int nchunks = cdiv(cin, CK), ncob = cdiv(cout, NB);
   const size_t need = (size_t)ncob * nchunks * pk_taps(ksize) * CK * NB * sizeof(float);
   if (workspace_bytes < need) return fail(-4, "ssp_op_conv workspace too small (%zu < %zu)", workspace_bytes, need);
+  // the bf16 path's convolutions are NHWC bf16 (ssp_op_conv_bf16): its fp32 Winograd-shaped case has no kernel
+  if (bf16_path() && ksize == 3 && cin % CK == 0 && in_mode != 2)
+    return fail(-3, "ssp_op_conv: conv algorithm 12 has no fp32 3x3 kernel for Cin %% 16 == 0 (use ssp_op_conv_bf16 or another algorithm)");
   hipStream_t st = (hipStream_t)stream;
   float* wpk = reinterpret_cast<float*>(workspace_dev);
   const bool w4 = wino && ksize == 3 && w4_eligible(nullptr, 1, n, hh, w, cin, cout);
@@ -3267,7 +3138,6 @@ int ssp_op_conv(const float* in_dev, const float* w_oihw_dev, const float* bias_
   c.in = in_dev; c.in_cs = cin; c.in_co = 0; c.cin = cin; c.wpk = wpk; c.bias = bias_dev; c.out = out_dev; c.out_cs = cout;
   c.out_co = 0; c.cout = cout; c.in_scale = in_scale_dev; c.in_shift = in_shift_dev; c.stats = stats_dev; c.N = n;
   c.H = hh; c.W = w; c.ks = ksize; c.in_mode = in_mode; c.nchunks = nchunks; c.ncob = ncob; c.wino = wino;
-  c.backward = transpose_flip != 0;
   return launch_conv(nullptr, c, st, 0);
 }
 
@@ -3715,20 +3585,13 @@ int ssp_op_bn_bwd_bf16(const void* y_dev, const void* dout_dev, const float* gam
 
 // perf-debug hook (tools/archive/ablate_conv.py): disable parts of conv_mfma_kernel / override its grid; 0,0 = product
 int ssp_set_conv_algo(int algo) {
-  if (algo < 0 || algo > 12 || algo == 4)
-    return fail(-1, "conv algo must be 12 (the bf16 path: bf16 activations in HBM, direct bf16 matrix-core convolutions), 0 (direct), 1 (Winograd, pipelined), 2 (Winograd, un-pipelined), 3 (Winograd, bf16 "
-                    "operands), 5 (Winograd, pipelined, weights staged through LDS), 6 (Winograd, two 4-wave workgroups per CU) "
-                    ", 7 (Winograd, split-bf16 hi + lo operands), 8 (forward split-bf16, backward bf16), 9 (Winograd "
-                    "F(2x2,3x3) only: algorithm 1 without F(4x4,3x3) on the large maps), 10 (F(4x4,3x3) wherever legal) or 11 (algorithm 1 "
-                    "with the F(3x3,4x4) weight gradient)");
-  if (!SSP_LEGACY_ALGOS && (algo == 2 || algo == 3 || algo == 5 || algo == 7 || algo == 8))
-    return fail(-1, "conv algo %d is compiled out of the shipped library (-DSSP_LEGACY_ALGOS=1)", algo);
+  CHK(check_conv_algo(algo));
   g_default_conv_algo = algo;
   return 0;
 }
 
 // test / perf-debug hook: blocks per CU the runtime admits for a kernel family (0: conv_wino_p2_kernel<1, true>,
-// 1: conv_wino_pipe_kernel<1, true, true>, 2: wgrad_wino_kernel<1, true>)
+// 1: conv_wino_pipe_kernel<1, true>, 2: wgrad_wino_kernel<1, true>)
 int ssp_debug_occupancy(int which) {
   int n = -1;
   hipError_t e = hipErrorInvalidValue;
@@ -3737,7 +3600,7 @@ int ssp_debug_occupancy(int which) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, P2_LDS_BYTES);
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, P2_THREADS, P2_LDS_BYTES);
   } else if (which == 1) {
-    auto k = conv_wino_pipe_kernel<1, true, true>;
+    auto k = conv_wino_pipe_kernel<1, true>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, PIPE_LDS_BYTES);
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, WINO_THREADS, PIPE_LDS_BYTES);
   } else if (which == 2) {

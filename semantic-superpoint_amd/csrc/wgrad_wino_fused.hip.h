@@ -20,12 +20,6 @@
 #pragma once
 #include "conv_wino.hip.h"
 #include <type_traits>
-#ifndef SSP_LEGACY_ALGOS
-#define SSP_LEGACY_ALGOS 0
-#endif
-#if SSP_LEGACY_ALGOS
-#include "conv_wino_bf16.hip.h"   // (the bf16-operand MFMA phase of the retired mixed mode 8: BF16 = true below)
-#endif
 
 #ifndef WGF_TRACE
 #define WGF_TRACE 0  // compile-time perf trace (never in the shipped library): s_memtime stamps around the phases of a tile, summed per
@@ -45,11 +39,8 @@ struct WgradFusedGeom {
   static constexpr int LDS_BYTES = (G::X_FLOATS + G::D_FLOATS + 256 + F_FLOATS + O_WORDS) * 4;
 };
 
-// BF16: the MFMA phase of wgrad_wino_bf16_kernel<.., NT = 1> (transformed operands rounded to bf16 in registers, one
-// v_mfma_f32_32x32x8_bf16 per 8 tiles; the mixed bf16 mode 8) on the same fp32 LDS tile images.
-template <int IN_MODE, bool WIDE, bool POOL, bool BF16 = false>
+template <int IN_MODE, bool WIDE, bool POOL>
 __global__ __launch_bounds__(512) void wgrad_wino_fused_kernel(const WgradArgs a) {
-  static_assert(!BF16 || SSP_LEGACY_ALGOS, "the bf16-operand form belongs to the retired conv algorithms (-DSSP_LEGACY_ALGOS=1)");
   using G = WgradWinoGeom<WIDE>;
   using GF = WgradFusedGeom<WIDE>;
   constexpr int NX = GF::NX;
@@ -282,10 +273,8 @@ __global__ __launch_bounds__(512) void wgrad_wino_fused_kernel(const WgradArgs a
     // step 0 also moves the walker and prepares the offsets: as a phase of its own between the staging barrier and the MFMA
     // phase that cost 1.0 (interior tiles) to 2.3 k cycles (border tiles) of LDS / scalar latency per tile with no MFMA in flight
     if constexpr (S == 0) {
-      if (!BF16) {
-        if (w_more) walk();  // unconditional prefetch (the last tile loads itself again)
-        WGF_PREP()
-      }
+      if (w_more) walk();  // unconditional prefetch (the last tile loads itself again)
+      WGF_PREP()
     }
     if constexpr (2 * S < NLOAD) wgf_load(std::integral_constant<int, (2 * S < NLOAD ? 2 * S : 0)>{});
     if constexpr (2 * S + 1 < NLOAD) wgf_load(std::integral_constant<int, (2 * S + 1 < NLOAD ? 2 * S + 1 : 0)>{});
@@ -317,7 +306,6 @@ __global__ __launch_bounds__(512) void wgrad_wino_fused_kernel(const WgradArgs a
       }
   }
   if (t_begin < t_end) {  // the first tile: slice 0 prepares it (w_more = false: the walker stays)
-    if (BF16) WGF_PREP()
     WGF_LOAD_ALL()
   }
 #if WGF_TRACE
@@ -420,11 +408,6 @@ __global__ __launch_bounds__(512) void wgrad_wino_fused_kernel(const WgradArgs a
       // (sliced between the MFMA steps instead - tile state behind step 0, the loads behind steps 1 - 7 - the MFMA phase grew by more
       // than this phase is long: 27.1 k instead of 25.0 k cycles per tile, profiles/r05_wgf_phase_trace.txt)
       w_more = tile + 1 < t_end;
-      if (BF16) {
-        if (w_more) walk();
-        WGF_PREP()
-        WGF_LOAD_ALL()
-      }
       __builtin_amdgcn_sched_barrier(0);
     }
     WGF_T(3)
@@ -433,69 +416,8 @@ __global__ __launch_bounds__(512) void wgrad_wino_fused_kernel(const WgradArgs a
       const float* xa0 = sX + (ra * G::WT + 2 * lh) * 64 + 2 * li;
       const float* xb0 = sX + (rb * G::WT + 2 * lh) * 64 + 2 * li;
       const float* db0 = sD + (2 * lh) * 64 + coh * 32 + li;
-      if (!BF16) wgrad_wino_steps<G>(acc, xa0, xb0, db0, f32x2{sg, sg}, f32x2{c0, c0}, f32x2{c1, c1}, wgf_load_slice);
+      wgrad_wino_steps<G>(acc, xa0, xb0, db0, f32x2{sg, sg}, f32x2{c0, c0}, f32x2{c1, c1}, wgf_load_slice);
     }
-#if SSP_LEGACY_ALGOS
-    if (BF16) {
-      // (pinned: hipcc converts each value on its own as soon as it exists and merges the halves with v_perm_b32)
-      auto cvt2 = [](float lo, float hi) -> unsigned {
-        unsigned d;
-        asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(d) : "v"(lo), "v"(hi));
-        return d;
-      };
-      typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-#pragma unroll 1
-      for (int s = 0; s < 4; ++s) {  // 8 Winograd tiles per MFMA: lane half lh supplies tiles 8 s + 4 lh .. + 3
-        // Two tiles at a time: the values of tiles (tt, tt + 1) convert PAIRWISE (one v_cvt_pk_bf16_f32 per two values, already
-        // in operand order) - converted one by one, the four values of an operand register were assembled with a v_perm_b32
-        // each; the loop is bound by its vector instructions (8 bf16 MFMAs = 128 matrix-pipe cycles beside ~150 of them)
-        unsigned Vp[4][2][2], Dp[4][2];  // [component][m-tile][tile pair]: two bf16 values each
-#pragma unroll
-        for (int tp = 0; tp < 2; ++tp) {
-          f32x2 Vt[2][4];
-          float Dt[2][4];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int t = 8 * s + 4 * lh + 2 * tp + u;
-            const int ty = t / G::TTX, tx = t - ty * G::TTX;
-            const float* xa = sX + ((2 * ty + ra) * G::WT + 2 * tx) * 64 + 2 * li;
-            const float* xb = sX + ((2 * ty + rb) * G::WT + 2 * tx) * 64 + 2 * li;
-            f32x2 T[4];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const f32x2 uu = *reinterpret_cast<const f32x2*>(xa + c * 64), w = *reinterpret_cast<const f32x2*>(xb + c * 64);
-              T[c][0] = fmaf(sg, w[0], uu[0]);
-              T[c][1] = fmaf(sg, w[1], uu[1]);
-            }
-            Vt[u][0] = T[0] - T[2]; Vt[u][1] = T[1] + T[2]; Vt[u][2] = T[2] - T[1]; Vt[u][3] = T[1] - T[3];
-            const float* db = sD + ((2 * ty) * G::TW + 2 * tx) * 64 + coh * 32 + li;
-            const float r0 = c0 * db[0] + c1 * db[G::TW * 64];
-            const float r1 = c0 * db[64] + c1 * db[G::TW * 64 + 64];
-            Dt[u][0] = r0; Dt[u][1] = r0 + r1; Dt[u][2] = r0 - r1; Dt[u][3] = -r1;
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            Vp[j][0][tp] = cvt2(Vt[0][j][0], Vt[1][j][0]);
-            Vp[j][1][tp] = cvt2(Vt[0][j][1], Vt[1][j][1]);
-            Dp[j][tp] = cvt2(Dt[0][j], Dt[1][j]);
-          }
-        }
-        // hipcc inserts no wait states between an inline-asm result and an MFMA that reads it: all operands complete, then the MFMAs
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_nop 1");
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const u32x2_t db4 = {Dp[j][0], Dp[j][1]};
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {
-            const u32x2_t vb4 = {Vp[j][e][0], Vp[j][e][1]};
-            acc[j][e] = __builtin_amdgcn_mfma_f32_32x32x8bf16_1k(__builtin_bit_cast(s16x4, vb4), __builtin_bit_cast(s16x4, db4), acc[j][e], 0, 0, 0);
-          }
-        }
-      }
-    }
-#endif
     WGF_T(4)
   }
 #if WGF_TRACE

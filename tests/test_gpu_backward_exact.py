@@ -60,7 +60,7 @@ TAU = {
 # that names a family without a tau fails with a KeyError)
 
 WG = {1: "fused12", 2: "wino", 3: "wino4", 4: "direct", 5: "grouped", 6: "l0"}
-DG = {1: "wino4", 2: "pipe", 3: "p2", 4: "direct", 5: "grouped", 6: "other"}
+DG = {1: "wino4", 2: "pipe", 3: "p2", 4: "direct", 5: "grouped"}
 L_PA, L_PB, L_DA, L_DB, L_DS, L_SOUT = 8, 9, 10, 11, 12, 13
 POOLED = (1, 3, 5)
 

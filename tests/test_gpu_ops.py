@@ -36,7 +36,7 @@ def conv_algo(request):
     F(2x2,3x3) tile-block items (conv_uses_p2), else the first-generation conv_wino_pipe_kernel; the kernel each case reaches
     is named beside it in CONV_CASES / DGRAD_CASES; 0 = direct implicit GEMM; [2 = Winograd without the software pipeline,
     5 = the pipelined kernel with LDS-staged weights and 3 / 7 / 8 = the bf16-operand experiments inside the Winograd kernels are
-    compiled out of the shipped library: SSP_LEGACY_ALGOS];
+    retired: commit c6c61a5, profiles/PERF_LOG_rounds_1-4.md section 10];
     6 = the second-generation pipelined Winograd kernel (two independent 4-wave workgroups per CU) on every 3x3 Winograd case;
     10 = Winograd F(4x4,3x3) (conv_wino4_kernel) on every 3x3 convolution it can run, F(2x2,3x3) elsewhere;
     11 = algorithm 1 with the Winograd F(3x3,4x4) weight gradient, wgrad_wino4_kernel (opt-in: correct, not faster)).
@@ -131,6 +131,36 @@ def test_conv_dgrad(N, H, W, cin, cout, ks, conv_algo):
     out = L.op_conv(dy.to(dev), w.to(dev), None, ks, 0, None, None, None, transpose_flip=True)
     torch.cuda.synchronize()
     assert _rel(out.cpu(), ref) < 2e-4
+
+
+def test_conv_algorithm_12_refuses_the_fp32_winograd_case_before_any_launch():
+    """Under process-wide conv algorithm 12 (the bf16 path) the handle-less fp32 ssp_op_conv of a 3x3 layer with Cin % 16 == 0
+    has no kernel: it returns -3 with a message and launches nothing (output and weight workspace stay as they were).  A 3x3
+    layer with another channel count still runs the direct kernel."""
+    from semantic_superpoint_amd import lib as L
+    dev = _dev()
+    lib = L.load_library()
+    rs = np.random.RandomState(12)
+    x = torch.from_numpy(rs.randn(1, 8, 16, 64).astype(np.float32)).to(dev)
+    w = torch.from_numpy(rs.randn(64, 64, 3, 3).astype(np.float32) / 24).to(dev)
+    out = torch.full((1, 8, 16, 64), 7.0, device=dev)
+    ws = torch.full((1 << 20,), 0x5A, dtype=torch.uint8, device=dev)   # >= the F(4x4,3x3) capacity of 64 -> 64 channels
+    x8 = torch.from_numpy(rs.randn(1, 8, 16, 8).astype(np.float32))
+    w8 = torch.from_numpy(rs.randn(16, 8, 3, 3).astype(np.float32) / 8)
+    L.set_conv_algo(12)
+    try:
+        rc = lib.ssp_op_conv(L._ptr(x), L._ptr(w), None, L._ptr(out), 1, 8, 16, 64, 64, 3, 0, None, None, None, 0, L._ptr(ws),
+                             ws.numel(), L._stream())
+        err = lib.ssp_last_error()
+        torch.cuda.synchronize()
+        out8 = L.op_conv(x8.to(dev), w8.to(dev), None, 3)
+        torch.cuda.synchronize()
+    finally:
+        L.set_conv_algo(1)
+    assert rc == -3 and b"conv algorithm 12" in err, (rc, err)
+    assert bool((out == 7.0).all()) and bool((ws == 0x5A).all())
+    ref8 = F.conv2d(x8.permute(0, 3, 1, 2), w8, padding=1).permute(0, 2, 3, 1)
+    assert _rel(out8.cpu(), ref8) < 2e-4
 
 
 @pytest.mark.parametrize("N,H,W,cin,cout,ks,mode", [(2, 16, 64, 64, 64, 3, 1), (2, 30, 40, 128, 128, 3, 1),
