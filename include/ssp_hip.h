@@ -387,6 +387,37 @@ int ssp_match_two_way(const float* desc1_dev, const int32_t* count1_dev, const f
                       int cap, int n_pairs, int pair_stride, float nn_thresh, void* workspace_dev, float* match_dev,
                       int32_t* n_match_dev, void* stream);
 
+/* ---- evaluation of descriptor exports (evaluation.py:86-500 with -r -homo) ---------------------------------------
+ * Points are fp64 rows (x, y, confidence) [n_pairs*pair_stride][cap][3] with int32 counts [n_pairs*pair_stride]; pair p
+ * uses entry p*pair_stride of each (pair_stride = 2 matches the interleaved image / warped image of the exporter).
+ * 1 <= cap <= SSP_MATCH_MAX_POINTS.  One workgroup per pair: a pair's result does not depend on its batch.
+ * ssp_eval_repeatability: compute_repeatability (evaluations/detector_evaluation.py:153-275) in fp64 without contraction:
+ *   the warped image's points whose hom_inv image lies in [0, width) x [0, height), the image's points warped by hom and
+ *   kept by the same rule, the keep_k (<= 2048) most confident of each (ties: the lower index), then the row / column
+ *   minima of the N1 x N2 distances.  hom_dev / hom_inv_dev: [n_pairs][9] (hom_inv = np.linalg.inv(hom), host side).
+ *   Also counts the matching score's unwarped points (evaluation.py:194-216): the warped image's (y, x) truncated to
+ *   integers, warped as (x, y) by float32(hom_inv) in float32, kept when 0 <= p <= (width - 1, height - 1).
+ *   out_dev [n_pairs][8] fp64 = N1, N2, count1, count2, sum1, sum2 (the minima <= dist_thresh and their sums),
+ *   n_unwarped, 0.  Needs no workspace.
+ * ssp_eval_ransac: a RANSAC homography of each pair's matches (match_dev [n_pairs][cap][3] = (i, j, distance) as
+ *   ssp_match_two_way writes them, n_match_dev [n_pairs]) from pts1 row i to pts2 row j: exactly 2000 hypotheses, each 4
+ *   distinct matches drawn from a counter-based stream of (seeds_dev[p], hypothesis index); a sample with 3 collinear
+ *   points in either image is invalid; normalised 4-point DLT (h33 = 1) in fp64; score = #(squared transfer error <= 9);
+ *   the highest score wins, ties to the lowest hypothesis.  H is refitted on the winner's inliers (algebraic least
+ *   squares, then up to 5 Gauss-Newton steps on the forward transfer error); mask_dev [n_pairs][cap] is the winner's
+ *   inlier set.  4 matches: one direct solve, all inliers.  Fewer than 4 matches, or no valid hypothesis: status 1
+ *   ("no model"), H = identity, empty mask, 0 inliers; otherwise status 0.  h_dev [n_pairs][9] fp64 (H[8] = 1).
+ *   ap_dev (may be NULL): sklearn's average_precision_score of the mask against max(d) - d, 0 without inliers.
+ *   workspace_dev: ssp_eval_ransac_workspace_bytes(cap, n_pairs) bytes. */
+int ssp_eval_repeatability(const double* pts1_dev, const int32_t* n1_dev, const double* pts2_dev, const int32_t* n2_dev,
+                           int cap, int n_pairs, int pair_stride, const double* hom_dev, const double* hom_inv_dev,
+                           int height, int width, int keep_k, double dist_thresh, double* out_dev, void* stream);
+size_t ssp_eval_ransac_workspace_bytes(int cap, int n_pairs);
+int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int n_pairs, int pair_stride,
+                    const float* match_dev, const int32_t* n_match_dev, const uint64_t* seeds_dev, void* workspace_dev,
+                    double* h_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev, double* ap_dev,
+                    void* stream);
+
 /* BatchNorm2d(train) (+ReLU (+MaxPool2d(2))) backward. y: raw conv output NHWC; dout: gradient wrt the activated
  * (and pooled) output; stats4 = scale|shift|mean|invstd ([4*C]); dgamma/dbeta/dbias are accumulated;
  * sums_dev: double [SSP_NREP][2*C] scratch. */

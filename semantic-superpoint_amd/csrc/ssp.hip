@@ -30,6 +30,7 @@
 #include "pair_kernels.hip.h"
 #include "export_kernels.hip.h"
 #include "describe_kernels.hip.h"
+#include "eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "backward_tail.hip.h"
 
@@ -3473,6 +3474,66 @@ int ssp_match_two_way(const float* desc1_dev, const int32_t* count1_dev, const f
                      cap, pair_stride, rowmin, colmin);
   hipLaunchKernelGGL(match_compact_kernel, dim3(n_pairs), dim3(1024), 0, st, (const uint64_t*)rowmin, (const uint64_t*)colmin,
                      count1_dev, count2_dev, cap, pair_stride, nn_thresh, match_dev, n_match_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- evaluation of descriptor exports (evaluation.py:86-500): repeatability, RANSAC homography, AP ----
+#define EVAL_KEEP_MAX 2048
+#define EVAL_LDS_MAX (120 * 1024)
+static int eval_check(const char* what, int cap, int n_pairs, int pair_stride) {
+  if (cap < 1 || cap > SSP_MATCH_MAX_POINTS || n_pairs < 1 || pair_stride < 1)
+    return fail(-1, "%s: 1 <= cap <= %d, n_pairs >= 1, pair_stride >= 1 required (cap %d)", what, SSP_MATCH_MAX_POINTS, cap);
+  return 0;
+}
+
+int ssp_eval_repeatability(const double* pts1_dev, const int32_t* n1_dev, const double* pts2_dev, const int32_t* n2_dev,
+                           int cap, int n_pairs, int pair_stride, const double* hom_dev, const double* hom_inv_dev,
+                           int height, int width, int keep_k, double dist_thresh, double* out_dev, void* stream) {
+  CHK(eval_check("eval_repeatability", cap, n_pairs, pair_stride));
+  if (!pts1_dev || !n1_dev || !pts2_dev || !n2_dev || !hom_dev || !hom_inv_dev || !out_dev)
+    return fail(-1, "eval_repeatability: null pointer");
+  if (height < 1 || width < 1 || keep_k < 1 || keep_k > EVAL_KEEP_MAX || !(dist_thresh >= 0.0))
+    return fail(-1, "eval_repeatability: height, width >= 1, 1 <= keep_k <= %d and dist_thresh >= 0 required",
+                EVAL_KEEP_MAX);
+  const int kk = std::min(keep_k, cap);
+  const size_t lds = (size_t)((cap + 1) & ~1) * sizeof(double) + (size_t)2 * kk * 2 * sizeof(double);
+  static AttrOnce attr_once;
+  if (attr_once.need())
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_repeat_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               EVAL_LDS_MAX));
+  hipLaunchKernelGGL(eval_repeat_kernel, dim3(n_pairs), dim3(EVAL_THREADS), lds, (hipStream_t)stream, pts1_dev, n1_dev,
+                     pts2_dev, n2_dev, cap, pair_stride, hom_dev, hom_inv_dev, height, width, kk, dist_thresh, out_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+size_t ssp_eval_ransac_workspace_bytes(int cap, int n_pairs) {
+  if (eval_check("eval_ransac", cap, n_pairs, 1)) return 0;
+  return align_up((size_t)n_pairs * cap * 4 * sizeof(double), 256);
+}
+
+int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int n_pairs, int pair_stride,
+                    const float* match_dev, const int32_t* n_match_dev, const uint64_t* seeds_dev, void* workspace_dev,
+                    double* h_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev, double* ap_dev,
+                    void* stream) {
+  CHK(eval_check("eval_ransac", cap, n_pairs, pair_stride));
+  if (!pts1_dev || !pts2_dev || !match_dev || !n_match_dev || !seeds_dev || !workspace_dev || !h_dev || !mask_dev ||
+      !n_inlier_dev || !status_dev)
+    return fail(-1, "eval_ransac: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  double4* xy = reinterpret_cast<double4*>(workspace_dev);
+  const size_t small = (size_t)cap * (sizeof(float) + 1);
+  const bool use_lds = (size_t)cap * sizeof(double4) + small <= EVAL_LDS_MAX;
+  static AttrOnce attr_once;
+  if (attr_once.need())
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_ransac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               EVAL_LDS_MAX));
+  hipLaunchKernelGGL(eval_gather_kernel, dim3(cdiv(cap, 256), n_pairs), dim3(256), 0, st, pts1_dev, pts2_dev, cap, pair_stride,
+                     match_dev, n_match_dev, xy);
+  hipLaunchKernelGGL(eval_ransac_kernel, dim3(n_pairs), dim3(EVAL_THREADS), use_lds ? (size_t)cap * sizeof(double4) + small : small,
+                     st, (const double4*)xy, match_dev, n_match_dev, cap, seeds_dev, (int)use_lds, h_dev, mask_dev,
+                     n_inlier_dev, status_dev, ap_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }

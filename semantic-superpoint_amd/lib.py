@@ -75,7 +75,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_op_warp_labels_full_px", "ssp_profile_read_kernel", "ssp_op_label_quantize", "ssp_profile_pause", "ssp_op_conv_bf16", "ssp_op_conv_wgrad_bf16", "ssp_op_bn_bwd_bf16", "ssp_build_id",
            "ssp_set_deterministic", "ssp_get_deterministic", "ssp_clock_probe", "ssp_op_sem_loss",
            "ssp_describe_workspace_bytes", "ssp_describe_points", "ssp_op_sample_descriptors", "ssp_match_workspace_bytes",
-           "ssp_match_two_way", "ssp_debug_backward_taps", "ssp_debug_backward_tap_floats", "ssp_debug_backward_tap"]
+           "ssp_match_two_way", "ssp_debug_backward_taps", "ssp_debug_backward_tap_floats", "ssp_debug_backward_tap",
+           "ssp_eval_repeatability", "ssp_eval_ransac_workspace_bytes", "ssp_eval_ransac"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 
@@ -208,6 +209,10 @@ def load_library(path=None):
         lib.ssp_match_workspace_bytes.argtypes = [i, i]
         lib.ssp_match_workspace_bytes.restype = C.c_size_t
         lib.ssp_match_two_way.argtypes = [vp, vp, vp, vp, i, i, i, f, vp, vp, vp, vp]
+        lib.ssp_eval_repeatability.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, i, i, i, C.c_double, vp, vp]
+        lib.ssp_eval_ransac_workspace_bytes.argtypes = [i, i]
+        lib.ssp_eval_ransac_workspace_bytes.restype = C.c_size_t
+        lib.ssp_eval_ransac.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -1164,6 +1169,84 @@ def op_match_two_way(desc1, count1, desc2, count2, nn_thresh, pair_stride=1, n_p
         _check(lib.ssp_match_two_way(_ptr(desc1), _ptr(count1), _ptr(desc2), _ptr(count2), cap, P, int(pair_stride),
                                      float(np.float32(nn_thresh)), _ptr(ws), _ptr(match), _ptr(n_match), _stream()))
     return match, n_match
+
+
+def _eval_points(pts, counts, name):
+    _need_gpu(pts, name)
+    _need_gpu(counts, name + " counts")
+    if pts.dtype != torch.float64 or pts.dim() != 3 or pts.shape[2] != 3:
+        raise ValueError("%s must be float64 [n, cap, 3] rows (x, y, confidence)" % name)
+    if counts.dtype != torch.int32 or counts.numel() != pts.shape[0]:
+        raise ValueError("%s counts must be int32 [%d]" % (name, pts.shape[0]))
+    if not 1 <= pts.shape[1] <= MATCH_MAX_POINTS:
+        raise ValueError("%s: 1 <= cap <= %d points per image (got %d)" % (name, MATCH_MAX_POINTS, pts.shape[1]))
+
+
+def op_eval_repeatability(pts1, n1, pts2, n2, hom, hom_inv, height, width, keep_k=1000, dist_thresh=3.0, pair_stride=1,
+                          n_pairs=None):
+    """compute_repeatability (evaluations/detector_evaluation.py:153-275) and the matching score's unwarped-point count
+    (evaluation.py:194-216) for P pairs on the device.  pts1, pts2: float64 [P*pair_stride, cap, 3] rows (x, y, conf),
+    n1, n2: int32 counts (pair p uses entry p*pair_stride), hom / hom_inv: float64 [P,3,3] (hom_inv from np.linalg.inv).
+    Returns float64 [P,8] = N1, N2, count1, count2, sum1, sum2, n_unwarped, 0 (device tensor)."""
+    lib = load_library()
+    _eval_points(pts1, n1, "pts1")
+    _eval_points(pts2, n2, "pts2")
+    cap = pts1.shape[1]
+    if pts2.shape[1] != cap:
+        raise ValueError("pts1 and pts2 need the same cap")
+    P = n_pairs if n_pairs is not None else pts1.shape[0] // pair_stride
+    if P < 1 or (P - 1) * pair_stride >= min(pts1.shape[0], pts2.shape[0]):
+        raise ValueError("%d pairs at stride %d do not fit the point arrays" % (P, pair_stride))
+    for t, nm in ((hom, "hom"), (hom_inv, "hom_inv")):
+        _need_gpu(t, nm)
+        if t.dtype != torch.float64 or tuple(t.shape) != (P, 3, 3):
+            raise ValueError("%s must be float64 [%d,3,3]" % (nm, P))
+    out = torch.empty(P, 8, dtype=torch.float64, device=pts1.device)
+    with torch.cuda.device(pts1.device):
+        _check(lib.ssp_eval_repeatability(_ptr(pts1), _ptr(n1), _ptr(pts2), _ptr(n2), cap, P, int(pair_stride), _ptr(hom),
+                                          _ptr(hom_inv), int(height), int(width), int(keep_k), float(dist_thresh),
+                                          _ptr(out), _stream()))
+    return out
+
+
+def op_eval_ransac(pts1, pts2, match, n_match, seeds, pair_stride=1, want_ap=False):
+    """RANSAC homography of P pairs' matches on the device (the cv2.findHomography step of the reference's evaluation,
+    restated: DESIGN.md section 13).  pts1, pts2: float64 [P*pair_stride, cap, 3] rows (x, y, conf); match: float32
+    [P, cap, 3] rows (i, j, distance) as op_match_two_way returns them, n_match: int32 [P], seeds: int64 [P].
+    Returns device tensors {"H": float64 [P,3,3], "mask": uint8 [P,cap], "n_inliers": int32 [P], "status": int32 [P]
+    (1 = no model), "ap": float64 [P] when want_ap}."""
+    lib = load_library()
+    for t, nm in ((pts1, "pts1"), (pts2, "pts2"), (match, "match"), (n_match, "n_match"), (seeds, "seeds")):
+        _need_gpu(t, nm)
+    cap = match.shape[1]
+    P = match.shape[0]
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
+    if match.dtype != torch.float32 or match.dim() != 3 or match.shape[2] != 3:
+        raise ValueError("match must be float32 [P, cap, 3]")
+    for t, nm in ((pts1, "pts1"), (pts2, "pts2")):
+        if t.dtype != torch.float64 or t.dim() != 3 or t.shape[1:] != (cap, 3) or t.shape[0] < (P - 1) * pair_stride + 1:
+            raise ValueError("%s must be float64 [P*pair_stride, %d, 3]" % (nm, cap))
+    if n_match.dtype != torch.int32 or n_match.numel() != P:
+        raise ValueError("n_match must be int32 [%d]" % P)
+    if seeds.dtype != torch.int64 or seeds.numel() != P:
+        raise ValueError("seeds must be int64 [%d]" % P)
+    wsb = lib.ssp_eval_ransac_workspace_bytes(cap, P)
+    if wsb == 0:
+        _check(-1)
+    dev = match.device
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    o = {"H": torch.empty(P, 3, 3, dtype=torch.float64, device=dev),
+         "mask": torch.empty(P, cap, dtype=torch.uint8, device=dev),
+         "n_inliers": torch.empty(P, dtype=torch.int32, device=dev),
+         "status": torch.empty(P, dtype=torch.int32, device=dev)}
+    if want_ap:
+        o["ap"] = torch.empty(P, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.ssp_eval_ransac(_ptr(pts1), _ptr(pts2), cap, P, int(pair_stride), _ptr(match), _ptr(n_match),
+                                   _ptr(seeds), _ptr(ws), _ptr(o["H"]), _ptr(o["mask"]), _ptr(o["n_inliers"]),
+                                   _ptr(o["status"]), _ptr(o.get("ap")), _stream()))
+    return o
 
 
 def points_to_numpy(pts, count, subpixel):
