@@ -458,17 +458,19 @@ int ssp_debug_occupancy(int which);
 int ssp_debug_buffer(ssp_handle* h, int slot, const char* name, float** ptr, size_t* nfloats);
 
 /* test hook: backward taps.  With a caller-owned device arena (arena_dev != NULL, at least
- * ssp_debug_backward_tap_floats(h, layer_mask) floats) the fp32 backward (ssp_pair_step eager, ssp_backward) copies, on the
+ * ssp_debug_backward_tap_floats(h, layer_mask) floats) the backward (ssp_pair_step eager, ssp_backward) copies, on the
  * step's stream, per layer l of layer_mask (bit l) and view: which = 0, dOut_l (gradient wrt the layer's (pooled) activation as it
  * enters its BatchNorm backward), which = 1, dY_l (gradient wrt its conv output after the BatchNorm backward APPLY; none for
  * layer 0).  Layer 8 stands for the three 3x3 heads: their whole [cells][256 heads] tensors; layers 9 / 11 (Pb / Db): dY only.
- * NHWC, sized for the handle's max_batch.  arena_dev == NULL: off (no extra launch).  ssp_pair_step_graph and conv
- * algorithm 12 refuse to run with taps on.  ssp_debug_backward_tap: arena offset and size of one tap (0 / 0 when not tapped) and
- * `route`, the path layer l took in the last backward pass (kept with taps off too): bit 0 pass 1 of the BatchNorm backward
- * (S1 / S2 sums) accumulated by the data gradient above, bit 1 APPLY fused into the weight gradient, bit 2 replica reduction in
- * the weight gradient's prologue; bits 4-7 weight-gradient kernel (1 wgrad_wino_fused, 2 wgrad_wino, 3 wgrad_wino4, 4 direct,
- * 5 grouped pointwise, 6 bn_bwd_apply_l0); bits 8-11 data-gradient kernel (1 conv_wino4, 2 conv_wino_pipe, 3 conv_wino_p2,
- * 4 direct, 5 grouped pointwise). */
+ * NHWC, sized for the handle's max_batch.  Conv algorithm 12 (the bf16 path): the taps of its bf16 tensors (every encoder tap,
+ * both layer-8 taps) hold bf16 elements in the first half of their slice; Pb / Db dY stay fp32.  arena_dev == NULL: off (no
+ * extra launch).  ssp_pair_step_graph refuses to run with taps on.  ssp_debug_backward_tap: arena offset and size (floats) of
+ * one tap's slice (0 / 0 when not tapped) and `route`, the path layer l took in the last backward pass (kept with taps off too):
+ * bit 0 pass 1 of the BatchNorm backward (S1 / S2 sums) accumulated by the data gradient above, bit 1 APPLY fused into the
+ * weight gradient, bit 2 replica reduction in the weight gradient's prologue, bit 3 (bf16 path) weight-gradient operand read
+ * from the activation the forward materialised; bits 4-7 weight-gradient kernel (1 wgrad_wino_fused, 2 wgrad_wino,
+ * 3 wgrad_wino4, 4 direct, 5 grouped pointwise, 6 bn_bwd_apply_l0, 7 wgrad_bf16); bits 8-11 data-gradient kernel (1 conv_wino4,
+ * 2 conv_wino_pipe, 3 conv_wino_p2, 4 direct, 5 grouped pointwise, 6 conv_bf16, 7 conv_bf16_ws). */
 int ssp_debug_backward_taps(ssp_handle* h, float* arena_dev, size_t arena_floats, unsigned layer_mask);
 size_t ssp_debug_backward_tap_floats(const ssp_handle* h, unsigned layer_mask);
 int ssp_debug_backward_tap(ssp_handle* h, int slot, int layer, int which, size_t* offset, size_t* nfloats, unsigned* route);

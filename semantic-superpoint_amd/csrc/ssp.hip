@@ -232,9 +232,9 @@ struct ssp_handle {
 };
 
 // route bits of ssp_debug_backward_tap (include/ssp_hip.h)
-enum { TAP_BSUMS_FUSED = 1, TAP_APPLY_FUSED = 2, TAP_SUMS_LAZY = 4, TAP_WG_SHIFT = 4, TAP_DG_SHIFT = 8 };
-enum { TAP_WG_FUSED12 = 1, TAP_WG_WINO = 2, TAP_WG_WINO4 = 3, TAP_WG_DIRECT = 4, TAP_WG_GROUPED = 5, TAP_WG_L0 = 6 };
-enum { TAP_DG_WINO4 = 1, TAP_DG_PIPE = 2, TAP_DG_P2 = 3, TAP_DG_DIRECT = 4, TAP_DG_GROUPED = 5 };
+enum { TAP_BSUMS_FUSED = 1, TAP_APPLY_FUSED = 2, TAP_SUMS_LAZY = 4, TAP_ACT_INPUT = 8, TAP_WG_SHIFT = 4, TAP_DG_SHIFT = 8 };
+enum { TAP_WG_FUSED12 = 1, TAP_WG_WINO = 2, TAP_WG_WINO4 = 3, TAP_WG_DIRECT = 4, TAP_WG_GROUPED = 5, TAP_WG_L0 = 6, TAP_WG_BF16 = 7 };
+enum { TAP_DG_WINO4 = 1, TAP_DG_PIPE = 2, TAP_DG_P2 = 3, TAP_DG_DIRECT = 4, TAP_DG_GROUPED = 5, TAP_DG_BF16 = 6, TAP_DG_BF16_WS = 7 };
 
 struct AlgoScope {  // makes the handle's conv algorithm the current one for the duration of an entry point
   int prev;
@@ -1726,7 +1726,7 @@ struct SlotSet {
 // ---- backward taps (test hook, ssp_debug_backward_taps): copies of per-layer gradients into a caller-owned arena ----
 // floats of tap (layer l, which: 0 = dOut, 1 = dY) at the handle's maximum batch; 0 = no such tap.  Encoder layer l: dOut = the
 // gradient wrt its (pooled) activation, dY = wrt its conv output (none for layer 0); L_PA: the whole [cells][hcs] tensors of
-// the 3x3 heads; L_PB / L_DB: dY of the pointwise heads
+// the 3x3 heads; L_PB / L_DB: dY of the pointwise heads.  (A bf16 tap of the bf16 path fills the first half of its slice.)
 static size_t tap_floats(const ssp_handle* h, int l, int which) {
   const size_t B = h->cfg.max_batch, cells = B * (h->cfg.height / 8) * (h->cfg.width / 8);
   if (l < 8) {
@@ -1751,12 +1751,15 @@ static size_t tap_offset(const ssp_handle* h, unsigned mask, int slot, int l, in
       }
   return off;
 }
-static int tap_copy(ssp_handle* h, const SlotSet& SS, int l, int which, float* const* src, size_t n, hipStream_t st) {
+// n elements of `esize` bytes (4: fp32; 2: a bf16 tensor of the bf16 path)
+static int tap_copy(ssp_handle* h, const SlotSet& SS, int l, int which, float* const* src, size_t n, hipStream_t st,
+                    size_t esize = sizeof(float)) {
   if (h->tap_arena == nullptr || !(h->tap_mask >> l & 1)) return 0;
-  if (n > tap_floats(h, l, which)) return fail(-3, "backward tap %d/%d: %zu floats exceed its arena slice", l, which, n);
+  if (n * esize > tap_floats(h, l, which) * sizeof(float))
+    return fail(-3, "backward tap %d/%d: %zu elements of %zu bytes exceed its arena slice", l, which, n, esize);
   for (int k = 0; k < SS.n; ++k) {
     float* dst = h->tap_arena + tap_offset(h, h->tap_mask, (int)(SS.s[k] - h->slot), l, which);
-    HIPCHK(hipMemcpyAsync(dst, src[k], n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(dst, src[k], n * esize, hipMemcpyDeviceToDevice, st));
   }
   return 0;
 }
@@ -2198,11 +2201,15 @@ static int conv_layer_backward(ssp_handle* h, const SlotSet& SS, int l, int src,
 static int encoder_backward_bf16(ssp_handle* h, const SlotSet& SS, int l_hi, int l_lo, hipStream_t st) {
   Slot& S0 = *SS.s[0];
   const int N = S0.N, H = S0.H, W = S0.W;
+  float *gP[2] = {nullptr, nullptr}, *gQ[2] = {nullptr, nullptr};   // (backward taps)
+  for (int k = 0; k < SS.n; ++k) { gP[k] = SS.s[k]->gP; gQ[k] = SS.s[k]->gQ; }
   for (int l = l_hi; l >= l_lo; --l) {
     const LayerDesc& d = h->L[l];
     int lh, lw; layer_res(l, H, W, lh, lw);
     const bool pool_after = (l == 1 || l == 3 || l == 5);
     const int C = d.cout;
+    // dOut of this layer (bf16): before the fused APPLY reads it and the data gradient overwrites it
+    CHK(tap_copy(h, SS, l, 0, gP, (size_t)N * (pool_after ? (lh / 2) * (lw / 2) : lh * lw) * C, st, sizeof(uint16_t)));
     BnBwdArgs a[2];
     for (int k = 0; k < SS.n; ++k) {
       Slot& S = *SS.s[k];
@@ -2218,6 +2225,7 @@ static int encoder_backward_bf16(ssp_handle* h, const SlotSet& SS, int l_hi, int
     // in its copy-out (ConvBArgs::bnr_*)
     const bool sums_fused = h->bsums_fused[l];
     h->bsums_fused[l] = false;
+    if (sums_fused) h->tap_route[l] |= TAP_BSUMS_FUSED;
     if (l == 0) {
       const BnBwdArgs &a0 = a[0], &a1 = a[SS.n - 1];
       const int nb1 = l0_resident_grid(bn_bwd_reduce_l0_kernel<uint16_t>, h, SS.n, (long)N * H, W);
@@ -2228,6 +2236,7 @@ static int encoder_backward_bf16(ssp_handle* h, const SlotSet& SS, int l_hi, int
       hipLaunchKernelGGL(bn_bwd_apply_l0_kernel<uint16_t>, dim3(nb2, SS.n), dim3(256), l0_lds_bytes(W), st, a0, a1, P(h, d.w_off), P(h, d.b_off),
                          Gd(h, d.w_off));
       HIPCHK(hipGetLastError());
+      h->tap_route[0] |= TAP_WG_L0 << TAP_WG_SHIFT;
       continue;
     }
     // pass 2 (APPLY) rides the layer's weight gradient (wgrad_bf16_kernel<.., FUSE>; SSP_BF16_FUSE_APPLY=0: the separate pass)
@@ -2267,6 +2276,7 @@ static int encoder_backward_bf16(ssp_handle* h, const SlotSet& SS, int l_hi, int
       if (src >= 5 && S0.act_valid[src] && SS.s[SS.n - 1]->act_valid[src]) {   // the forward materialised this layer's activated input
         w.in_mode = 0;
         for (int k = 0; k < SS.n; ++k) w.x[k] = SS.s[k]->act[src];
+        h->tap_route[l] |= TAP_ACT_INPUT;
       }
       if (fuse_apply) {
         w.fuse = pool_after ? 2 : 1; w.f_gamma = P(h, d.g_off); w.f_dcs = C; w.f_dco = 0;
@@ -2281,7 +2291,9 @@ static int encoder_backward_bf16(ssp_handle* h, const SlotSet& SS, int l_hi, int
       const double wbytes = 2.0 * SS.n * N * lh * lw * ((double)d.cin + (fuse_apply ? (2.0 + (pool_after ? 0.25 : 1.0)) * C : (double)C));
       ProfScope ps(h, SSP_PROF_CONV3X3_WGRAD, st, flops, wbytes, flops, SSP_PROF_K_WGRAD_BF16);
       CHK(launch_wgrad_bf16(w, h->partial, h->partial_floats, h->n_cu, st, h->rq_bf16));
+      h->tap_route[l] |= (fuse_apply ? (unsigned)TAP_APPLY_FUSED : 0u) | (unsigned)TAP_WG_BF16 << TAP_WG_SHIFT;
     }
+    CHK(tap_copy(h, SS, l, 1, gQ, (size_t)N * lh * lw * C, st, sizeof(uint16_t)));   // dY (bf16), written by the APPLY in either form
     {
       ConvBCall c;
       c.nviews = SS.n; c.N = N; c.H = lh; c.W = lw; c.ks = 3; c.in_mode = 0;
@@ -2305,6 +2317,7 @@ static int encoder_backward_bf16(ssp_handle* h, const SlotSet& SS, int l_hi, int
       ProfScope ps(h, SSP_PROF_CONV3X3_DGRAD, st, flops, 2.0 * SS.n * N * lh * lw * ((double)d.cin * (bnr ? 2.0 : 1.0) + C), flops, SSP_PROF_K_CONV_BF16);
       CHK(launch_conv_bf16(c, h->n_cu, st));
       if (bnr) h->bsums_fused[src] = true;
+      h->tap_route[l] |= (unsigned)(launch_conv_bf16_is_ws(c) ? TAP_DG_BF16_WS : TAP_DG_BF16) << TAP_DG_SHIFT;
     }
   }
   return 0;
@@ -2350,6 +2363,7 @@ static int heads_backward_bf16(ssp_handle* h, const SlotSet& SS, const float* co
     CHK(launch_wgrad_bf16(w, h->partial, h->partial_floats, h->n_cu, st, h->rq_bf16));
     CHK(launch_conv_bf16(c, h->n_cu, st));
     if (bnr) h->bsums_fused[src] = true;
+    h->tap_route[l] |= (unsigned)TAP_WG_BF16 << TAP_WG_SHIFT | (unsigned)(launch_conv_bf16_is_ws(c) ? TAP_DG_BF16_WS : TAP_DG_BF16) << TAP_DG_SHIFT;
     return 0;
   };
   // (the two fp32 BatchNorm backward passes of the pointwise heads in three launches for both, like the fp32 path)
@@ -2377,6 +2391,14 @@ static int heads_backward_bf16(ssp_handle* h, const SlotSet& SS, const float* co
     HIPCHK(hipGetLastError());
     CHK(pointwise(L_SOUT, L_DS, dsout, h->sout_cs, 512));
   }
+  // backward taps: dY of Pb / Db (fp32) before the APPLY of the 3x3 heads reuses gQ; dOut of the 3x3 heads (bf16 [cells][hcs])
+  if (has_semi) CHK(tap_copy(h, SS, L_PB, 1, gQs, ncells * 80, st));
+  if (has_desc) CHK(tap_copy(h, SS, L_DB, 1, gQd, ncells * 256, st));
+  {
+    float* gP[2] = {nullptr, nullptr};
+    for (int k = 0; k < SS.n; ++k) gP[k] = SS.s[k]->gP;
+    CHK(tap_copy(h, SS, L_PA, 0, gP, ncells * hcs, st, sizeof(uint16_t)));
+  }
   // ---- 3x3 heads ----
   const int heads[3] = {L_PA, L_DA, L_DS};
   // pass 2 (APPLY) of their BatchNorm + ReLU backward rides their weight gradients (as in encoder_backward_bf16): y, dOut and dY are
@@ -2398,6 +2420,7 @@ static int heads_backward_bf16(ssp_handle* h, const SlotSet& SS, const float* co
     }
     const bool sums_fused = h->bsums_fused[heads[hk]];
     h->bsums_fused[heads[hk]] = false;
+    if (sums_fused) h->tap_route[heads[hk]] |= TAP_BSUMS_FUSED;
     CHK((launch_bn_bwd<true, false, uint16_t>(a, SS.n, Gd(h, d.g_off), Gd(h, d.be_off), st, sums_fused, heads_fuse, &sums_queue)));
   }
   CHK(flush_bn_sums(sums_queue, SS.n, st));
@@ -2408,6 +2431,8 @@ static int heads_backward_bf16(ssp_handle* h, const SlotSet& SS, const float* co
     w.x_cs = 128; w.x_co = 0; w.cin = 128; w.dy_cs = hcs; w.dy_co = 256 * hk; w.cout = 256; w.dw = Gd(h, d.w_off);
     const bool from_act7 = S0.act_valid[7] && SS.s[SS.n - 1]->act_valid[7];   // the forward materialised the activated input
     if (from_act7) w.in_mode = 0;
+    h->tap_route[heads[hk]] |= (from_act7 ? (unsigned)TAP_ACT_INPUT : 0u) | (heads_fuse ? (unsigned)TAP_APPLY_FUSED : 0u) |
+                               (unsigned)TAP_WG_BF16 << TAP_WG_SHIFT;
     for (int k = 0; k < SS.n; ++k) {
       Slot& S = *SS.s[k];
       w.x[k] = from_act7 ? S.act[7] : S.Y[7]; w.dy[k] = S.gQ; w.x_scale[k] = S.bn[7].scale; w.x_shift[k] = S.bn[7].shift;
@@ -2424,6 +2449,11 @@ static int heads_backward_bf16(ssp_handle* h, const SlotSet& SS, const float* co
     const double flops = 2.0 * SS.n * ncells * 128.0 * 256 * 9;
     ProfScope ps(h, SSP_PROF_CONV3X3_WGRAD, st, flops, 2.0 * SS.n * ncells * (128.0 + 256.0), flops, SSP_PROF_K_WGRAD_BF16);
     CHK(launch_wgrad_bf16(w, h->partial, h->partial_floats, h->n_cu, st, h->rq_bf16));
+  }
+  {
+    float* gQ[2] = {nullptr, nullptr};
+    for (int k = 0; k < SS.n; ++k) gQ[k] = SS.s[k]->gQ;
+    CHK(tap_copy(h, SS, L_PA, 1, gQ, ncells * hcs, st, sizeof(uint16_t)));   // dY of the 3x3 heads (bf16 [cells][hcs])
   }
   ConvBCall c;
   c.nviews = SS.n; c.N = N; c.H = Hc; c.W = Wc; c.ks = 3; c.in_mode = 0;
@@ -2445,6 +2475,8 @@ static int heads_backward_bf16(ssp_handle* h, const SlotSet& SS, const float* co
   ProfScope ps(h, SSP_PROF_CONV3X3_DGRAD, st, flops, 2.0 * SS.n * ncells * (hcs + 128.0), flops, SSP_PROF_K_CONV_BF16);
   CHK(launch_conv_bf16(c, h->n_cu, st));
   if (bnr) h->bsums_fused[7] = true;
+  for (int hk = 0; hk < h->nheads; ++hk)
+    h->tap_route[heads[hk]] |= (unsigned)(launch_conv_bf16_is_ws(c) ? TAP_DG_BF16_WS : TAP_DG_BF16) << TAP_DG_SHIFT;
   return 0;
 }
 
@@ -2499,7 +2531,6 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
     }
     return flush_wgrad_reduce(h, st);  // the pending Winograd weight-gradient slabs -> OIHW gradients, one launch
   };
-  if (h->tap_arena != nullptr && bf16_path()) return fail(-3, "backward taps cover the fp32 backward only (not conv algorithm 12)");
   if (part == 2) return encoder(EARLY_SPLIT_LAYER - 1, 0);
   for (int l = 0; l < 16; ++l) h->bsums_fused[l] = h->apply_fused[l] = false;
   for (int l = 0; l < 16; ++l) h->tap_route[l] = 0;  // (a failed / aborted pass must not leave a flag behind)
@@ -2807,8 +2838,6 @@ static int pair_step_impl(ssp_handle* h, const ssp_pair_inputs* in, float* scala
   if (!in || !scalars_dev) return fail(-1, "null argument");
   if (phase < 0 || phase > 2) return fail(-1, "pair-step phase must be 0, 1 or 2");
   AlgoScope algo(h);
-  if (h->tap_arena != nullptr && bf16_path() && in->train)
-    return fail(-1, "backward taps cover the fp32 backward only: conv algorithm 12 refuses to run with them on");
   // Single-view step (`data.warped_pair.enable: false`, Train_model_heatmap_all.py:207,237-262,330-332 - the branch the shipped
   // configs/magicpoint_shapes_pair.yaml takes): warped_image_dev == NULL.  One forward, detector (+ segmentation) loss of the
   // image only, loss_det_warp = loss_sem_warp = 0; the descriptor loss needs a pair (:343 asserts).

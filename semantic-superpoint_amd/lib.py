@@ -703,14 +703,16 @@ class Engine:
         _check(self.lib.ssp_debug_backward_tap(self.h, 0, layer, 0, None, None, C.byref(r)))
         return r.value
 
-    def backward_tap(self, slot, layer, which, shape):
+    def backward_tap(self, slot, layer, which, shape, dtype=torch.float32):
         """Test hook: host copy of one backward tap (which: 0 = dOut, 1 = dY) of the last step as a tensor of `shape` (NHWC, the
-        step's batch: a prefix of the tap's max_batch slice)."""
+        step's batch: a prefix of the tap's max_batch slice).  dtype bfloat16 for the bf16 taps of the bf16 path (the slice's
+        bytes viewed as bf16, as debug_buffer does)."""
         off, n = C.c_size_t(), C.c_size_t()
         _check(self.lib.ssp_debug_backward_tap(self.h, slot, layer, which, C.byref(off), C.byref(n), None))
         numel = int(np.prod(shape))
-        assert self._tap_arena is not None and 0 < numel <= n.value, (layer, which, numel, n.value)
-        return self._tap_arena[off.value:off.value + numel].view(*shape).cpu()
+        es = 2 if dtype == torch.bfloat16 else 4
+        assert self._tap_arena is not None and 0 < numel * es <= n.value * 4, (layer, which, numel, n.value)
+        return self._tap_arena[off.value:off.value + n.value].view(dtype)[:numel].view(*shape).cpu()
 
     def profile_enable(self, family):
         _check(self.lib.ssp_profile_enable(self.h, PROF[family] if isinstance(family, str) else int(family)))

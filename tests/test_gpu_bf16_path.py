@@ -60,6 +60,11 @@ def _bf(x):
     return x.to(BF16).to(torch.float32)
 
 
+def _np(v):
+    """a state-dict entry (numpy array or tensor) as a CPU tensor"""
+    return v.detach().cpu() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v))
+
+
 class _Fp64Convs:
     """The oracle's convolutions accumulated in fp64 instead of fp32: a second CORRECT evaluation of the same bf16 network, used
     to measure how far two correct evaluations are apart (the noise floor of the end-to-end comparisons)."""
@@ -93,6 +98,34 @@ def test_bf16_forward_chain_teacher_forced(arch, H, W, B):
     e = _engine(arch, B, H, W, sd, with_grad=False)
     e.forward(x.to(_dev()), slot=0, train=True, want=())
     torch.cuda.synchronize()
+    _forward_chain(e, arch, sd, x, 0, list(range(B)))
+
+
+def test_bf16_forward_chain_teacher_forced_at_the_benchmark_size():
+    """The same layer-by-layer check at the shape bench.py --dtype bf16 measures (B = 32, 240x320, SSp, bench.py's weights and
+    inputs), both views of one pair step: the forward whose stored tensors the backward is teacher-forced from
+    (tests/test_gpu_bf16_backward_exact.py).  BatchNorm statistics over the whole stored tensors, the convolutions on the images
+    [0, 1, B/2, B-2, B-1] (bounded fp64 CPU work)."""
+    import os
+    from semantic_superpoint_amd import synth
+    from semantic_superpoint_amd.lib import layer_table
+    torch.set_num_threads(min(int(os.environ.get("OMP_NUM_THREADS", "16")), 16))
+    arch = ARCHS[1]
+    B, H, W = 32, 240, 320
+    sd = synth.default_init_state_dict(layer_table(arch), seed=0)
+    sample = synth.make_pair(B, H, W, _dev(), seed=100, semantic=True)
+    e = _engine(arch, B, H, W, sd)
+    e.zero_grad()
+    e.pair_step(sample, indices=None, seed=7, train=True)
+    torch.cuda.synchronize()
+    for v, k in enumerate(("image", "warped_img")):
+        _forward_chain(e, arch, sd, sample[k].cpu(), v, [0, 1, B // 2, B - 2, B - 1])
+
+
+def _forward_chain(e, arch, sd, x, slot, imgs):
+    """The checks of test_bf16_forward_chain_teacher_forced on view `slot` (input image x) of the engine's last forward:
+    BatchNorm statistics and pooled copies over the whole batch, the convolutions on the images `imgs`."""
+    B, _, H, W = x.shape
     t = C.layer_table(arch)
     nheads = 3 if arch.endswith("ssmall") else 2
     hcs = 256 * nheads
@@ -107,10 +140,10 @@ def test_bf16_forward_chain_teacher_forced(arch, H, W, B):
         yd = y_nchw.double()
         mean, var = yd.mean(dim=(0, 2, 3)), yd.var(dim=(0, 2, 3), unbiased=False)
         invstd = (var + 1e-5).rsqrt()
-        sc = torch.from_numpy(sd[bn + ".weight"]).double() * invstd
-        sh = torch.from_numpy(sd[bn + ".bias"]).double() - mean * sc
-        msc = e.debug_buffer(0, "scale%d" % l, (cout,)).cpu().double()
-        msh = e.debug_buffer(0, "shift%d" % l, (cout,)).cpu().double()
+        sc = _np(sd[bn + ".weight"]).double() * invstd
+        sh = _np(sd[bn + ".bias"]).double() - mean * sc
+        msc = e.debug_buffer(slot, "scale%d" % l, (cout,)).cpu().double()
+        msh = e.debug_buffer(slot, "shift%d" % l, (cout,)).cpu().double()
         assert (msc - sc).abs().max() <= 1e-5 * float(sc.abs().max()), ("scale", l)
         assert (msh - sh).abs().max() <= 1e-5 * max(1.0, float(sh.abs().max())), ("shift", l)
         return msc.float(), msh.float()
@@ -120,9 +153,9 @@ def test_bf16_forward_chain_teacher_forced(arch, H, W, B):
         return _bf(F.relu(z))
 
     # layer 0: fp32 arithmetic on the fp32 image
-    y0 = e.debug_buffer(0, "Y0", (B, H, W, 64), BF16).cpu().float().permute(0, 3, 1, 2)
-    ex = F.conv2d(x.double(), torch.from_numpy(sd[t[0][0] + ".weight"]).double(), torch.from_numpy(sd[t[0][0] + ".bias"]).double(), padding=1)
-    assert _ulp_bad(y0, ex, 1e-5 * float(ex.abs().max())) == 0, "layer 0"
+    y0 = e.debug_buffer(slot, "Y0", (B, H, W, 64), BF16).cpu().float().permute(0, 3, 1, 2)
+    ex = F.conv2d(x[imgs].double(), _np(sd[t[0][0] + ".weight"]).double(), _np(sd[t[0][0] + ".bias"]).double(), padding=1)
+    assert _ulp_bad(y0[imgs], ex, 1e-5 * float(ex.abs().max())) == 0, "layer 0"
     prev = y0
     for l in range(1, 8):
         conv, bn, cin, cout, k = t[l]
@@ -132,31 +165,31 @@ def test_bf16_forward_chain_teacher_forced(arch, H, W, B):
             a = F.max_pool2d(a, 2)
             # the engine's raw pooled copy: per-channel max / min (sign of gamma) of the stored tensor, BatchNorm + ReLU on load
             hp, wp = res(l)
-            raw = e.debug_buffer(0, "A%d" % (l - 1), (B, hp, wp, cin), BF16).cpu().float().permute(0, 3, 1, 2)
-            gam = torch.from_numpy(sd[t[l - 1][1] + ".weight"]).view(1, -1, 1, 1)
+            raw = e.debug_buffer(slot, "A%d" % (l - 1), (B, hp, wp, cin), BF16).cpu().float().permute(0, 3, 1, 2)
+            gam = _np(sd[t[l - 1][1] + ".weight"]).view(1, -1, 1, 1)
             want = torch.where(gam >= 0, F.max_pool2d(prev, 2), -F.max_pool2d(-prev, 2))
             assert torch.equal(raw, want), ("pooled copy", l - 1)
             assert torch.equal(operand(raw, sc, sh), a), ("pooled operand", l - 1)
         hl, wl = res(l)
-        y = e.debug_buffer(0, "Y%d" % l, (B, hl, wl, cout), BF16).cpu().float().permute(0, 3, 1, 2)
-        ex = F.conv2d(a.double(), _bf(torch.from_numpy(sd[conv + ".weight"])).double(), torch.from_numpy(sd[conv + ".bias"]).double(), padding=1)
-        nbad = _ulp_bad(y, ex, 1e-4 * float(ex.abs().max()))
+        y = e.debug_buffer(slot, "Y%d" % l, (B, hl, wl, cout), BF16).cpu().float().permute(0, 3, 1, 2)
+        ex = F.conv2d(a[imgs].double(), _bf(_np(sd[conv + ".weight"])).double(), _np(sd[conv + ".bias"]).double(), padding=1)
+        nbad = _ulp_bad(y[imgs], ex, 1e-4 * float(ex.abs().max()))
         assert nbad == 0, ("layer", l, nbad)
         prev = y
     sc7, sh7 = affine_check(7, prev)
     x4 = operand(prev, sc7, sh7)
-    yh = e.debug_buffer(0, "Y8", (B, Hc, Wc, hcs), BF16).cpu().float().permute(0, 3, 1, 2)   # [Pa | Da | DS] raw outputs
+    yh = e.debug_buffer(slot, "Y8", (B, Hc, Wc, hcs), BF16).cpu().float().permute(0, 3, 1, 2)   # [Pa | Da | DS] raw outputs
     for hk, (l3, l1) in enumerate(((8, 9), (10, 11), (12, 13))[:nheads]):
         conv, bn, cin, cout, k = t[l3]
-        ex = F.conv2d(x4.double(), _bf(torch.from_numpy(sd[conv + ".weight"])).double(), torch.from_numpy(sd[conv + ".bias"]).double(), padding=1)
+        ex = F.conv2d(x4[imgs].double(), _bf(_np(sd[conv + ".weight"])).double(), _np(sd[conv + ".bias"]).double(), padding=1)
         y = yh[:, 256 * hk:256 * hk + 256]
-        assert _ulp_bad(y, ex, 1e-4 * float(ex.abs().max())) == 0, ("head", conv)
+        assert _ulp_bad(y[imgs], ex, 1e-4 * float(ex.abs().max())) == 0, ("head", conv)
         sc, sh = affine_check(l3, y)
         a = operand(y, sc, sh)
         c1, b1, cin1, cout1, _ = t[l1]
         cs = {65: 80, 256: 256}.get(cout1, (cout1 + 3) // 4 * 4)
-        o = e.debug_buffer(0, "Y%d" % l1, (B, Hc, Wc, cs)).cpu().permute(0, 3, 1, 2)[:, :cout1]
-        ex = F.conv2d(a.double(), _bf(torch.from_numpy(sd[c1 + ".weight"])).double(), torch.from_numpy(sd[c1 + ".bias"]).double())
+        o = e.debug_buffer(slot, "Y%d" % l1, (B, Hc, Wc, cs)).cpu().permute(0, 3, 1, 2)[imgs, :cout1]
+        ex = F.conv2d(a[imgs].double(), _bf(_np(sd[c1 + ".weight"])).double(), _np(sd[c1 + ".bias"]).double())
         assert (o.double() - ex).abs().max() <= 2e-5 * float(ex.abs().max()), ("pointwise", c1)   # fp32 output, fp32 accumulation
 
 
