@@ -294,6 +294,42 @@ int ssp_op_label_quantize(const float* in_dev, float* out_dev, size_t n, void* s
 int ssp_op_sem_finalize(const float* sem_warped_dev, const float* valid_dev, int64_t* out_dev, size_t n, int n_classes,
                         void* stream);
 
+/* ---- photometric augmentation of the training images (utils/photometric.py) ----
+ * ssp_op_photometric_draw  : every random decision of ImgAugTransform + customizedTransform.additive_shade for b images of
+ *     h x w, from ONE seed (counter-based device RNG; the stream differs from numpy's by construction): one row of
+ *     SSP_PHOTO_DRAW_STRIDE floats per image, laid out as
+ *       [SSP_PHOTO_BRIGHTNESS]    integer delta in [-max_abs_change, +max_abs_change]          (0 when off)
+ *       [SSP_PHOTO_CONTRAST]      factor, uniform in strength_range                             (1 when off)
+ *       [SSP_PHOTO_SIGMA]         noise sigma on the 0..255 scale, uniform in stddev_range       (0 when off)
+ *       [SSP_PHOTO_IMPULSE_P]     impulse probability, uniform in prob_range                     (0 when off)
+ *       [SSP_PHOTO_BLUR_FLAG]     1 with probability 1/2, then 9 row-major 3x3 weights (sum 1) at [SSP_PHOTO_BLUR_W]
+ *       [SSP_PHOTO_ELLIPSES]      SSP_PHOTO_MAX_ELLIPSES x (cx, cy, ax, ay, angle in degrees); ax < 0 ends the list
+ *       [SSP_PHOTO_TRANSPARENCY]  shade transparency
+ *       [SSP_PHOTO_KSIZE]         odd shade kernel size                                          (0 when off)
+ *       [SSP_PHOTO_KEY]           64-bit key of the per-pixel noise as 4 floats of 16 bits each, low bits first
+ *     A neutral value switches its stage off in apply.  Enable fields are COUNTS as the reference's parser produces them
+ *     (lib.photometric_params_from_config); a count above 1 (the max_kernel_size quirk) is refused here.
+ * ssp_op_photometric_apply : pure function of the image and its row: img / out float [b,1,h,w] in [0, 1] (out may not alias
+ *     img).  Stage order, 8-bit semantics and the restated rounding choices: csrc/photo_kernels.hip.h.  Kernel sizes up to
+ *     SSP_PHOTO_MAX_KSIZE; h <= 744 (the shade keeps a full-height strip in LDS). */
+enum { SSP_PHOTO_MAX_ELLIPSES = 32, SSP_PHOTO_MAX_KSIZE = 351 };
+enum { SSP_PHOTO_BRIGHTNESS = 0, SSP_PHOTO_CONTRAST = 1, SSP_PHOTO_SIGMA = 2, SSP_PHOTO_IMPULSE_P = 3, SSP_PHOTO_BLUR_FLAG = 4,
+       SSP_PHOTO_BLUR_W = 5, SSP_PHOTO_ELLIPSES = 14, SSP_PHOTO_TRANSPARENCY = 174, SSP_PHOTO_KSIZE = 175, SSP_PHOTO_KEY = 176,
+       SSP_PHOTO_DRAW_STRIDE = 180 };
+typedef struct ssp_photometric_params {
+  uint32_t struct_size; /* sizeof(ssp_photometric_params) of the caller: an unknown size is an error */
+  int32_t random_brightness, random_contrast, additive_gaussian_noise, additive_speckle_noise, motion_blur, additive_shade;
+  int32_t brightness_max_abs_change;
+  float contrast_lo, contrast_hi;         /* random_contrast.strength_range */
+  float noise_std_lo, noise_std_hi;       /* additive_gaussian_noise.stddev_range */
+  float impulse_prob_lo, impulse_prob_hi; /* additive_speckle_noise.prob_range */
+  int32_t shade_nb_ellipses;              /* additive_shade.nb_ellipses (20), <= SSP_PHOTO_MAX_ELLIPSES */
+  float shade_transparency_lo, shade_transparency_hi;
+  int32_t shade_kernel_lo, shade_kernel_hi; /* kernel_size_range: integer in [lo, hi), made odd by adding 1 */
+} ssp_photometric_params;
+int ssp_op_photometric_draw(uint64_t seed, const ssp_photometric_params* p, int b, int h, int w, float* draws_dev, void* stream);
+int ssp_op_photometric_apply(const float* img_dev, const float* draws_dev, float* out_dev, int b, int h, int w, void* stream);
+
 /* ---- homography-adaptation export (export.py:192-352) ------------------------------
  * One image = n_views warped copies that form ONE BatchNorm batch (the reference leaves the net in train mode,
  * models/model_wrap.py:120).  ssp_export_points replaces the body of the export loop (export.py:296-309):

@@ -13,6 +13,9 @@ precision / recall scalars, the NMS maps of both views and the image overlays of
 device (`log_precision_recall`).
 Data parallel (one process per GPU, torch.distributed initialised by the launcher): the gradient all-reduce of the
 optimizer step is split in two buckets and overlapped with the tail of the backward pass (parallel.pair_step_overlapped).
+Device feed (`ssp_device_pairs: true`, with `data.warped_pair.enable`): the loader ships only the raw `image`, `labels_2D`
+and (with `data.semantic`) `semantic`; the pair - homographies, warps, masks, warped labels, and in training the photometric
+augmentation of `data.augmentation` - is built on the device by pairs.make_pairs (`_device_pair`).
 """
 import copy
 import logging
@@ -102,6 +105,9 @@ class Train_model_heatmap_all(object):
         else:
             raise KeyError("model.dense_loss.enable or model.sparse_loss.enable must be true")
         self.sampler = self.config.get("ssp_sampler", "device")  # "device" | "reference" (host RNG streams)
+        self.device_pairs = bool(self.config.get("ssp_device_pairs", False))
+        if self.device_pairs and not self.config["data"].get("warped_pair", {}).get("enable", False):
+            raise ValueError("ssp_device_pairs builds the warped pair on the device: it needs data.warped_pair.enable")
         self.n_iter = 0
         self.net = None
         self._writer = None
@@ -209,6 +215,8 @@ class Train_model_heatmap_all(object):
         B, _, H, W = img.shape
         self.batch_size = B
         eng = self._engine_for(B, H, W)
+        if self.device_pairs:
+            sample = self.sample_dev = self._device_pair(sample, n_iter, train)
         if not if_warp:  # the warped keys of a pair loader are never read (:226-251)
             sample = {k: v for k, v in sample.items() if not k.startswith(("warped_", "homographies", "inv_homographies", "cell_homographies"))}
         dev = {k: (v.to(self.device, non_blocking=True).contiguous() if torch.is_tensor(v) else v) for k, v in sample.items()}
@@ -259,6 +267,33 @@ class Train_model_heatmap_all(object):
             self.tb_hist_dict(task, self.hist_dict)   # (:568; `images_dict` stays unwritten like the reference's commented-out :567)
         self.tb_scalar_dict(self.scalar_dict, task)
         return float(s["loss"])
+
+    def _device_pair(self, sample, n_iter, train):
+        """`ssp_device_pairs`: only `image` (the loader's RAW image; float in [0, 1] or uint8), `labels_2D` and - with
+        `data.semantic` - `semantic` (uint8 / int16 / int64) are read from the loader's dict and copied to the device; every
+        other key stays untouched on the host.  The step's dict is pairs.make_pairs' with `data.warped_pair.params`,
+        `data.warped_pair.valid_border_margin` and, in training only (the reference has enable_photo_val = False,
+        datasets/Coco.py:113-117), the photometric augmentation of `data.augmentation`.  `sample["homographies"]` (and
+        `sample["inv_homographies"]`), when present, replace the sampled matrices, so a loader may keep the geometry.
+        The seed derives from ssp_seed, n_iter and the rank like the descriptor sampler's, on a stream of its own; make_pairs
+        derives the streams of the homographies and of the two photometric draws from it.
+        With `ssp_sampler: "reference"` the host sampler needs host homographies: train_val_sample fetches the [B,3,3]
+        matrices back (`.cpu()` inside sample_sparse_indices_host) - the one small copy this mode keeps."""
+        from . import pairs
+        cfg = self.config
+        wp = cfg["data"]["warped_pair"]
+
+        def up(k):
+            return sample[k].to(self.device, non_blocking=True)
+
+        aug = cfg["data"].get("augmentation") or {}
+        photo = aug if train and (aug.get("photometric") or {}).get("enable", False) else None
+        seed = ((int(cfg.get("ssp_seed", 0)) * 1000003 + n_iter) * 64 + parallel.rank()) * 4 + 1
+        return pairs.make_pairs(up("image"), up("labels_2D"), seed, warp_params=wp.get("params") or {},
+                                erosion_radius=int(wp.get("valid_border_margin", 0)),
+                                semantic=up("semantic") if cfg["data"].get("semantic", False) else None,
+                                photometric=photo, homographies=sample.get("homographies"),
+                                inv_homographies=sample.get("inv_homographies"))
 
     def log_precision_recall(self, eng, dev, B, H, W):
         """Logging branch (Train_model_heatmap_all.py:447-568): flattenDetection of both views' logits, heatmap_nms

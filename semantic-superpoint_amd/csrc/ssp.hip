@@ -28,6 +28,7 @@
 #include "loss_kernels.hip.h"
 #include "dense_loss.hip.h"
 #include "pair_kernels.hip.h"
+#include "photo_kernels.hip.h"
 #include "export_kernels.hip.h"
 #include "describe_kernels.hip.h"
 #include "eval_kernels.hip.h"
@@ -3609,6 +3610,60 @@ int ssp_op_warp_labels_full_px(const float* labels_dev, const float* hpx_dev, fl
 int ssp_op_label_quantize(const float* in_dev, float* out_dev, size_t n, void* stream) {
   if (!in_dev || !out_dev) return fail(-1, "label_quantize: null pointer");
   hipLaunchKernelGGL(label_quantize_u8_kernel, dim3(cdiv((long)n, 256)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, (long)n);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- photometric augmentation (photo_kernels.hip.h) ----
+static_assert(SSP_PHOTO_DRAW_STRIDE == PHOTO_DRAW_STRIDE && SSP_PHOTO_ELLIPSES == PHOTO_ELLIPSES && SSP_PHOTO_TRANSPARENCY == PHOTO_TRANSPARENCY &&
+                  SSP_PHOTO_KSIZE == PHOTO_KSIZE && SSP_PHOTO_KEY == PHOTO_KEY && SSP_PHOTO_BLUR_W == PHOTO_BLUR_W &&
+                  SSP_PHOTO_MAX_ELLIPSES == PHOTO_MAX_ELLIPSES && SSP_PHOTO_MAX_KSIZE == PHOTO_MAX_KSIZE,
+              "the draw row of ssp_hip.h and photo_kernels.hip.h differ");
+int ssp_op_photometric_draw(uint64_t seed, const ssp_photometric_params* p, int b, int hh, int w, float* draws_dev, void* stream) {
+  if (!p || !draws_dev || b < 1 || hh < 1 || w < 1) return fail(-1, "photometric_draw: bad argument");
+  if (p->struct_size != sizeof(ssp_photometric_params))
+    return fail(-1, "photometric_draw: ssp_photometric_params.struct_size is %u, this library knows %zu", p->struct_size,
+                sizeof(ssp_photometric_params));
+  const int32_t counts[6] = {p->random_brightness, p->random_contrast, p->additive_gaussian_noise, p->additive_speckle_noise,
+                             p->motion_blur, p->additive_shade};
+  for (int i = 0; i < 6; ++i)
+    if (counts[i] < 0 || counts[i] > 1)
+      return fail(-1, "photometric_draw: enable count %d of primitive %d: a primitive applied twice (motion_blur.max_kernel_size != 3) "
+                      "is not on the device path", counts[i], i);
+  if (p->random_brightness && (p->brightness_max_abs_change < 0 || p->brightness_max_abs_change > 255))
+    return fail(-1, "photometric_draw: max_abs_change must be in 0..255");
+  if (p->additive_shade && (p->shade_nb_ellipses < 0 || p->shade_nb_ellipses > SSP_PHOTO_MAX_ELLIPSES || p->shade_kernel_lo < 1 ||
+                            p->shade_kernel_hi <= p->shade_kernel_lo || p->shade_kernel_hi > SSP_PHOTO_MAX_KSIZE))
+    return fail(-1, "photometric_draw: additive_shade needs nb_ellipses <= %d and 1 <= kernel_size_range[0] < kernel_size_range[1] <= %d",
+                SSP_PHOTO_MAX_ELLIPSES, SSP_PHOTO_MAX_KSIZE);
+  PhotoParams q;
+  q.brightness = p->random_brightness; q.contrast = p->random_contrast; q.noise = p->additive_gaussian_noise;
+  q.impulse = p->additive_speckle_noise; q.motion_blur = p->motion_blur; q.shade = p->additive_shade;
+  q.max_abs_change = p->brightness_max_abs_change; q.nb_ellipses = p->shade_nb_ellipses;
+  q.ksize_lo = p->shade_kernel_lo; q.ksize_hi = p->shade_kernel_hi;
+  q.contrast_lo = p->contrast_lo; q.contrast_hi = p->contrast_hi; q.std_lo = p->noise_std_lo; q.std_hi = p->noise_std_hi;
+  q.p_lo = p->impulse_prob_lo; q.p_hi = p->impulse_prob_hi; q.t_lo = p->shade_transparency_lo; q.t_hi = p->shade_transparency_hi;
+  hipLaunchKernelGGL(photo_draw_kernel, dim3(cdiv(b, 64)), dim3(64), 0, (hipStream_t)stream, seed, q, b, hh, w, draws_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_op_photometric_apply(const float* img_dev, const float* draws_dev, float* out_dev, int b, int hh, int w, void* stream) {
+  if (!img_dev || !draws_dev || !out_dev || b < 1 || hh < 1 || w < 1) return fail(-1, "photometric_apply: bad argument");
+  if (img_dev == out_dev) return fail(-1, "photometric_apply: out may not alias img (the 3x3 blur reads neighbours)");
+  if (b > 65535 || (long)hh * w > (1l << 30)) return fail(-1, "photometric_apply: b <= 65535 and h * w <= 2^30 required");
+  const int tx = photo_shade_lds_bytes(hh, 32) <= 65536 ? 32 : 16;
+  const size_t lds = photo_shade_lds_bytes(hh, tx);
+  if (lds > 65536) return fail(-1, "photometric_apply: h = %d needs %zu bytes of LDS for the shade strip (64 KiB per workgroup)", hh, lds);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(photo_pixel_kernel, dim3(cdiv(hh * w, 256), b), dim3(256), 0, st, img_dev, draws_dev, out_dev, hh, w);
+  // (per call: the attribute belongs to the current device)
+  const void* kern = tx == 32 ? reinterpret_cast<const void*>(photo_shade_kernel<32>) : reinterpret_cast<const void*>(photo_shade_kernel<16>);
+  HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (tx == 32)
+    hipLaunchKernelGGL(photo_shade_kernel<32>, dim3(cdiv(w, 32), b), dim3(256), lds, st, out_dev, draws_dev, hh, w);
+  else
+    hipLaunchKernelGGL(photo_shade_kernel<16>, dim3(cdiv(w, 16), b), dim3(256), lds, st, out_dev, draws_dev, hh, w);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -55,6 +55,23 @@ class SspHomographyParams(C.Structure):
                 ("translation_overflow", C.c_float)]
 
 
+class SspPhotometricParams(C.Structure):
+    """ssp_photometric_params (include/ssp_hip.h): `struct_size` first; the enable fields are counts (see photometric_params_from_config)."""
+    _fields_ = [("struct_size", C.c_uint32), ("random_brightness", C.c_int32), ("random_contrast", C.c_int32),
+                ("additive_gaussian_noise", C.c_int32), ("additive_speckle_noise", C.c_int32), ("motion_blur", C.c_int32),
+                ("additive_shade", C.c_int32), ("brightness_max_abs_change", C.c_int32),
+                ("contrast_lo", C.c_float), ("contrast_hi", C.c_float), ("noise_std_lo", C.c_float), ("noise_std_hi", C.c_float),
+                ("impulse_prob_lo", C.c_float), ("impulse_prob_hi", C.c_float), ("shade_nb_ellipses", C.c_int32),
+                ("shade_transparency_lo", C.c_float), ("shade_transparency_hi", C.c_float),
+                ("shade_kernel_lo", C.c_int32), ("shade_kernel_hi", C.c_int32)]
+
+
+# the row of draws (SSP_PHOTO_* of include/ssp_hip.h)
+PHOTO_MAX_ELLIPSES, PHOTO_MAX_KSIZE = 32, 351
+(PHOTO_BRIGHTNESS, PHOTO_CONTRAST, PHOTO_SIGMA, PHOTO_IMPULSE_P, PHOTO_BLUR_FLAG, PHOTO_BLUR_W, PHOTO_ELLIPSES, PHOTO_TRANSPARENCY,
+ PHOTO_KSIZE, PHOTO_KEY, PHOTO_DRAW_STRIDE) = 0, 1, 2, 3, 4, 5, 14, 174, 175, 176, 180
+
+
 class SspExportParams(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("conf_thresh", C.c_float),
                 ("nms_dist", C.c_int32), ("border_remove", C.c_int32), ("top_k", C.c_int32), ("subpixel", C.c_int32)]
@@ -76,7 +93,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_set_deterministic", "ssp_get_deterministic", "ssp_clock_probe", "ssp_op_sem_loss",
            "ssp_describe_workspace_bytes", "ssp_describe_points", "ssp_op_sample_descriptors", "ssp_match_workspace_bytes",
            "ssp_match_two_way", "ssp_debug_backward_taps", "ssp_debug_backward_tap_floats", "ssp_debug_backward_tap",
-           "ssp_eval_repeatability", "ssp_eval_ransac_workspace_bytes", "ssp_eval_ransac"]
+           "ssp_eval_repeatability", "ssp_eval_ransac_workspace_bytes", "ssp_eval_ransac",
+           "ssp_op_photometric_draw", "ssp_op_photometric_apply"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 
@@ -195,6 +213,12 @@ def load_library(path=None):
     lib.ssp_op_sample_homographies.argtypes = [C.c_uint64, C.POINTER(SspHomographyParams), i, vp, vp, vp]
     lib.ssp_op_warp_labels_full.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp]
     lib.ssp_op_sem_finalize.argtypes = [vp, vp, vp, C.c_size_t, i, vp]
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_op_photometric_draw.argtypes = [C.c_uint64, C.POINTER(SspPhotometricParams), i, i, i, vp, vp]
+        lib.ssp_op_photometric_apply.argtypes = [vp, vp, vp, i, i, i, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
     try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
         lib.ssp_op_label_quantize.argtypes = [vp, vp, C.c_size_t, vp]
     except AttributeError:
@@ -1309,6 +1333,89 @@ def op_label_quantize(labels):
     out = torch.empty_like(labels)
     with torch.cuda.device(labels.device):
         _check(lib.ssp_op_label_quantize(_ptr(labels), _ptr(out), labels.numel(), _stream()))
+    return out
+
+
+# ---- photometric augmentation of the images (utils/photometric.py) ----
+def photometric_params_from_config(aug_cfg):
+    """The `data.augmentation` dict of a training yaml -> SspPhotometricParams, parsed like ImgAugTransform.__init__ and
+    customizedTransform.__call__ (utils/photometric.py:26-57, 109-112): a primitive is on when its key in
+    `photometric.params` is truthy (the `primitives` list is never read there).  The enable fields are COUNTS, because the
+    reference's parser can append one augmenter twice: with `motion_blur.max_kernel_size != 3` it assigns no augmenter and
+    appends the PREVIOUS one again (count 2, no motion blur), or raises NameError when motion blur is the only primitive of
+    the chain (:51-57).  Both outcomes are reproduced.  `GaussianBlur: {sigma}` as a photometric primitive is rejected.
+    With `photometric.enable` false every count is zero."""
+    p = SspPhotometricParams()
+    p.struct_size = C.sizeof(SspPhotometricParams)
+    p.shade_nb_ellipses, p.shade_transparency_lo, p.shade_transparency_hi, p.shade_kernel_lo, p.shade_kernel_hi = 20, -0.5, 0.8, 250, 350
+    p.contrast_lo = p.contrast_hi = 1.0
+    ph = (aug_cfg or {}).get("photometric") or {}
+    if not ph.get("enable", False):
+        return p
+    params = ph.get("params") or {}
+    last = None  # the reference's local variable `aug`
+    if params.get("random_brightness", False):
+        p.brightness_max_abs_change = int(params["random_brightness"]["max_abs_change"])
+        p.random_brightness += 1
+        last = "random_brightness"
+    if params.get("random_contrast", False):
+        p.contrast_lo, p.contrast_hi = (float(v) for v in params["random_contrast"]["strength_range"])
+        p.random_contrast += 1
+        last = "random_contrast"
+    if params.get("additive_gaussian_noise", False):
+        p.noise_std_lo, p.noise_std_hi = (float(v) for v in params["additive_gaussian_noise"]["stddev_range"])
+        p.additive_gaussian_noise += 1
+        last = "additive_gaussian_noise"
+    if params.get("additive_speckle_noise", False):
+        p.impulse_prob_lo, p.impulse_prob_hi = (float(v) for v in params["additive_speckle_noise"]["prob_range"])
+        p.additive_speckle_noise += 1
+        last = "additive_speckle_noise"
+    if params.get("motion_blur", False):
+        if int(params["motion_blur"]["max_kernel_size"]) == 3:
+            p.motion_blur += 1
+        elif last is None:
+            raise NameError("name 'aug' is not defined (motion_blur.max_kernel_size != 3 assigns no augmenter: utils/photometric.py:51-57)")
+        else:
+            setattr(p, last, getattr(p, last) + 1)
+    if params.get("GaussianBlur", False):
+        raise ValueError("photometric primitive GaussianBlur {sigma} is not on the device path (no shipped training config uses it)")
+    shade = params.get("additive_shade", False)
+    if shade:
+        shade = shade if isinstance(shade, dict) else {}
+        p.shade_nb_ellipses = int(shade.get("nb_ellipses", 20))
+        p.shade_transparency_lo, p.shade_transparency_hi = (float(v) for v in shade.get("transparency_range", (-0.5, 0.8)))
+        p.shade_kernel_lo, p.shade_kernel_hi = (int(v) for v in shade.get("kernel_size_range", (250, 350)))
+        p.additive_shade = 1
+    return p
+
+
+def op_photometric_draw(B, H, W, seed, params, device):
+    """Every random decision of the photometric chain for B images of H x W from one seed: float32 [B, PHOTO_DRAW_STRIDE]
+    (row layout: PHOTO_* above / include/ssp_hip.h).  params: SspPhotometricParams or the `data.augmentation` dict."""
+    lib = load_library()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("op_photometric_draw needs a HIP device")
+    if not isinstance(params, SspPhotometricParams):
+        params = photometric_params_from_config(params)
+    draws = torch.empty(B, PHOTO_DRAW_STRIDE, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _check(lib.ssp_op_photometric_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(params), B, H, W, _ptr(draws), _stream()))
+    return draws
+
+
+def op_photometric_apply(img, draws):
+    """ImgAugTransform + customizedTransform of img [B,1,H,W] (float32 in [0, 1]) with the rows `draws` [B, PHOTO_DRAW_STRIDE]:
+    a pure function of the two (stage order and rounding: csrc/photo_kernels.hip.h)."""
+    lib = load_library()
+    _need_gpu(img, "img")
+    _need_gpu(draws, "draws")
+    B, _, H, W = img.shape
+    if img.dtype != torch.float32 or draws.dtype != torch.float32 or tuple(draws.shape) != (B, PHOTO_DRAW_STRIDE):
+        raise ValueError("op_photometric_apply: img float32 [B,1,H,W] and draws float32 [B,%d] required" % PHOTO_DRAW_STRIDE)
+    out = torch.empty_like(img)
+    with torch.cuda.device(img.device):
+        _check(lib.ssp_op_photometric_apply(_ptr(img), _ptr(draws), _ptr(out), B, H, W, _stream()))
     return out
 
 

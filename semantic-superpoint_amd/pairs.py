@@ -13,23 +13,56 @@ datasets/Coco.py:341-392 / datasets/Coco_sem.py:395-455 for a BATCH that is alre
                     sigma-0.2 kernel: exp(-12.5) = 3.7e-6) - imgaug / cv2 are absent from the image, so that last statement is
                     restated from the kernel formula, not checked against the binaries.
 
-Not reproduced: the photometric augmentation of the IMAGES (imgaug).  The RNG streams differ from numpy / scipy, so the
-homographies are a distribution-level equivalent (like synth.py's host generator)."""
+  image, warped_img with `photometric=`: ImgAugTransform + customizedTransform (utils/photometric.py) as
+                    `ssp_op_photometric_draw` / `ssp_op_photometric_apply` in the reference's data flow
+                    (Coco.py:249, 355-361): image = photo(raw), warped_img = photo(warp(raw)) - the warp reads the RAW image
+                    and the two views draw independently.
+
+The RNG streams differ from numpy / scipy, so the homographies and the photometric draws are a distribution-level
+equivalent (like synth.py's host generator)."""
 import torch
 
 from . import lib as L
 
 
-def make_pairs(image, labels_2D, seed, warp_params=None, erosion_radius=3, semantic=None, n_classes=133):
-    """image, labels_2D: device tensors [B,1,H,W] (keypoint map: non-zero = keypoint); semantic: int64 [B,H,W] or None.
+def make_pairs(image, labels_2D, seed, warp_params=None, erosion_radius=3, semantic=None, n_classes=133, photometric=None,
+               homographies=None, photometric_draws=None, inv_homographies=None):
+    """image, labels_2D: device tensors [B,1,H,W] (keypoint map: non-zero = keypoint); semantic: integer [B,H,W] or None.
+    image may be uint8 (scaled by 1/255 here), semantic uint8 / int16 / int64: widening on the device is cheap, the point is
+    fewer bytes over PCIe.
+    photometric: the `data.augmentation` dict; when its `photometric.enable` is set, both views are augmented with
+        independent draws (seeds derived from `seed`).
+    homographies: [B,3,3] (image -> warped, normalised coordinates) used instead of sampling; inv_homographies: their
+        inverses if the caller has them (otherwise torch.inverse on the host like datasets/Coco.py:350, one small round trip).
+    photometric_draws: a pair of draw tables [B, lib.PHOTO_DRAW_STRIDE] (image, warped_img) used instead of drawing.
+    With the three at None the output is the same as without them, bit for bit.
     Returns the `sample` dict of Train_model_heatmap_all.py:212-251 (device tensors)."""
     if not image.is_cuda:
         raise RuntimeError("make_pairs needs HIP tensors: there is no CPU fallback")
     B, _, H, W = image.shape
-    image = image.contiguous().float()
+    if image.dtype == torch.uint8:
+        # k / 255 from a 256-entry table divided on the HOST: the device's division by a scalar multiplies by the reciprocal,
+        # which is not the loader's correctly rounded float32 quotient in the last bit
+        image = (torch.arange(256, dtype=torch.float32) / 255.0).to(image.device)[image.contiguous().long()]
+    else:
+        image = image.contiguous().float()
     labels_2D = labels_2D.contiguous().float()
-    hs, inv = L.op_sample_homographies(B, seed, image.device, **(warp_params or {}))
+    if semantic is not None and semantic.dtype != torch.int64:
+        semantic = semantic.long()
+    if homographies is None:
+        hs, inv = L.op_sample_homographies(B, seed, image.device, **(warp_params or {}))
+    else:
+        hs = homographies.to(image.device, torch.float32).contiguous()
+        inv = (torch.inverse(hs.cpu()) if inv_homographies is None else inv_homographies).to(image.device, torch.float32).contiguous()
     warped = L.op_warp_image(image, inv)
+    raw = image
+    if photometric_draws is None and photometric is not None and (photometric.get("photometric") or {}).get("enable", False):
+        pp = L.photometric_params_from_config(photometric)
+        photometric_draws = tuple(L.op_photometric_draw(B, H, W, (int(seed) * 2 + 1) * 0x9E3779B1 + v, pp, image.device) for v in (0, 1))
+    if photometric_draws is not None:
+        # both views in ONE call: 2 B images fill the device twice as well as B (one shade workgroup per image and 32 columns)
+        both = L.op_photometric_apply(torch.cat((raw, warped)), torch.cat([d.to(image.device) for d in photometric_draws]).contiguous())
+        image, warped = both[:B], both[B:]
     wl, wres, wbi = L.op_warp_labels_full(labels_2D, hs)
     vm = L.op_erode(L.op_warp_image(torch.ones_like(image), inv, nearest=True), erosion_radius)
     s = {"image": image, "warped_img": warped, "labels_2D": labels_2D, "warped_labels": wl, "warped_res": wres,
