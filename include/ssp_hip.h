@@ -330,6 +330,58 @@ typedef struct ssp_photometric_params {
 int ssp_op_photometric_draw(uint64_t seed, const ssp_photometric_params* p, int b, int h, int w, float* draws_dev, void* stream);
 int ssp_op_photometric_apply(const float* img_dev, const float* draws_dev, float* out_dev, int b, int h, int w, void* stream);
 
+/* ---- Synthetic Shapes on the device (datasets/synthetic_dataset.py, SyntheticDataset_gaussian.py:125-147) ----
+ * ssp_op_shapes_draw   : every random decision of generate_background + one of the nine primitives for b images from one seed:
+ *     one scene table row of SSP_SHAPES_ROW int32 words per image (float fields are stored by their bits):
+ *       [SSP_SHAPES_PRIM]    primitive 0..8 in the order of `weights`
+ *       [SSP_SHAPES_THR]     threshold of the background noise; [SSP_SHAPES_KEY], [+1] its 64-bit noise key (low, high)
+ *       [SSP_SHAPES_KSIZE]   box-kernel size of the background; [SSP_SHAPES_NBLOBS] blob count
+ *       [SSP_SHAPES_MEAN0]   int(mean) of the thresholded noise; [SSP_SHAPES_MEAN] int(mean) of noise + blobs (the
+ *                            `background_color` of every get_random_color of the primitive)
+ *       [SSP_SHAPES_NCMDS], [SSP_SHAPES_NPOINTS], [SSP_SHAPES_NVERTS], [SSP_SHAPES_NTEX]  counts
+ *       [SSP_SHAPES_BLOBS]   SSP_SHAPES_MAX_BLOBS x (x, y, radius, colour)
+ *       [SSP_SHAPES_CMDS]    SSP_SHAPES_MAX_CMDS x 12: (type, colour, bbox x0, y0, x1, y1 clipped to the image, 6 arguments), painted in order:
+ *                              1 polygon (first vertex, vertex count)        2 segment (x1, y1, x2, y2, thickness)
+ *                              3 ellipse (cx, cy, cos, sin, 1/ax^2, 1/ay^2)  4 textured polygon (first vertex, count, texture)
+ *                              5 uniform noise over the image (key low, high)
+ *       [SSP_SHAPES_VERTS]   SSP_SHAPES_MAX_VERTS x (x, y); in an ellipse image word c holds max(ax, ay) of command c instead
+ *       [SSP_SHAPES_TEX]     SSP_SHAPES_MAX_TEX x 12: (base colour, box-kernel size, key low, key high, centre x, y, radius (float),
+ *                              bbox x0, y0, x1, y1, 0): the blobs of a texture are a function of its key
+ *       [SSP_SHAPES_POINTS]  SSP_SHAPES_MAX_POINTS x (x, y) float at generation resolution
+ * ssp_op_shapes_render : pure function of the table and the parameters: uint8 image [b,1,out_h,out_w], key points scaled to
+ *     (out_h, out_w) as float [b, SSP_SHAPES_MAX_POINTS, 2] (x, y; unused slots zero) and their counts int32 [b].
+ *     workspace_dev: ssp_shapes_workspace_bytes(p, b) bytes. */
+enum { SSP_SHAPES_N_PRIMITIVES = 9, SSP_SHAPES_MAX_BLOBS = 128, SSP_SHAPES_MAX_CMDS = 64, SSP_SHAPES_MAX_VERTS = 256, SSP_SHAPES_MAX_TEX = 32,
+       SSP_SHAPES_MAX_POINTS = 256, SSP_SHAPES_MAX_BLUR = 63, SSP_SHAPES_MAX_TEX_BLOBS = 4096 };
+enum { SSP_SHAPES_PRIM = 0, SSP_SHAPES_THR = 1, SSP_SHAPES_KEY = 2, SSP_SHAPES_KSIZE = 4, SSP_SHAPES_NBLOBS = 5, SSP_SHAPES_MEAN0 = 6,
+       SSP_SHAPES_MEAN = 7, SSP_SHAPES_NCMDS = 8, SSP_SHAPES_NPOINTS = 9, SSP_SHAPES_NVERTS = 10, SSP_SHAPES_NTEX = 11, SSP_SHAPES_BLOBS = 16,
+       SSP_SHAPES_CMDS = 528, SSP_SHAPES_VERTS = 1296, SSP_SHAPES_TEX = 1808, SSP_SHAPES_POINTS = 2192, SSP_SHAPES_ROW = 2704 };
+typedef struct ssp_shapes_params {
+  uint32_t struct_size; /* sizeof(ssp_shapes_params) of the caller: an unknown size is an error */
+  int32_t gen_h, gen_w;   /* generation.image_size */
+  int32_t out_h, out_w;   /* preprocessing.resize */
+  int32_t blur_size;      /* preprocessing.blur_size: odd, <= SSP_SHAPES_MAX_BLUR (0 or 1: no blur) */
+  float weights[9];       /* truncate share of draw_lines, draw_polygon, draw_multiple_polygons, draw_ellipses, draw_star,
+                             draw_checkerboard, draw_stripes, draw_cube, gaussian_noise (0 = primitive not listed) */
+  int32_t bg_nb_blobs, bg_min_kernel, bg_max_kernel;
+  float bg_min_rad_ratio, bg_max_rad_ratio;
+  int32_t lines_nb_lines, polygon_max_sides, multi_max_sides, multi_nb_polygons, multi_nb_blobs, multi_kernel_lo, multi_kernel_hi;
+  int32_t ellipses_nb, star_nb_branches, checker_max_rows, checker_max_cols, stripes_max_nb_cols;
+  float checker_transform[2], stripes_transform[2], stripes_min_width_ratio;
+  float cube_min_size_ratio, cube_scale[2], cube_trans[2];
+  float resize_scale_y, resize_scale_x; /* float32(gen / out): the caller computes the quotient */
+  float gauss_w[63];      /* the blur_size normalised Gaussian weights (the caller computes them: lib.shapes_gaussian_weights) */
+} ssp_shapes_params;
+size_t ssp_shapes_workspace_bytes(const ssp_shapes_params* p, int b);
+int ssp_op_shapes_draw(uint64_t seed, const ssp_shapes_params* p, int b, int32_t* table_dev, void* stream);
+int ssp_op_shapes_render(const int32_t* table_dev, const ssp_shapes_params* p, int b, void* workspace_dev, uint8_t* image_dev,
+                         float* points_dev, int32_t* counts_dev, void* stream);
+/* The single-view feed (SyntheticDataset_gaussian.py:342-351, 450-472): float key points [b, stride, 2] (x, y) with counts [b] ->
+ * filter_points, warp with the pixel-space homographies hpx_dev [b,3,3] (NULL: no warp), filter_points, round half to even,
+ * clamp to (w - 1, h - 1), scatter 1 into labels_dev [b,1,h,w] (zero-filled here). */
+int ssp_op_warp_points_scatter(const float* points_dev, const int32_t* counts_dev, const float* hpx_dev, float* labels_dev, int b,
+                               int stride, int h, int w, void* stream);
+
 /* ---- homography-adaptation export (export.py:192-352) ------------------------------
  * One image = n_views warped copies that form ONE BatchNorm batch (the reference leaves the net in train mode,
  * models/model_wrap.py:120).  ssp_export_points replaces the body of the export loop (export.py:296-309):

@@ -29,6 +29,7 @@
 #include "dense_loss.hip.h"
 #include "pair_kernels.hip.h"
 #include "photo_kernels.hip.h"
+#include "shapes_kernels.hip.h"
 #include "export_kernels.hip.h"
 #include "describe_kernels.hip.h"
 #include "eval_kernels.hip.h"
@@ -3664,6 +3665,90 @@ int ssp_op_photometric_apply(const float* img_dev, const float* draws_dev, float
     hipLaunchKernelGGL(photo_shade_kernel<32>, dim3(cdiv(w, 32), b), dim3(256), lds, st, out_dev, draws_dev, hh, w);
   else
     hipLaunchKernelGGL(photo_shade_kernel<16>, dim3(cdiv(w, 16), b), dim3(256), lds, st, out_dev, draws_dev, hh, w);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- Synthetic Shapes (shapes_kernels.hip.h) ----
+static_assert(SSP_SHAPES_ROW == SH_ROW && SSP_SHAPES_CMDS == SH_CMDS && SSP_SHAPES_VERTS == SH_VERTS && SSP_SHAPES_TEX == SH_TEX &&
+                  SSP_SHAPES_POINTS == SH_POINTS && SSP_SHAPES_BLOBS == SH_BLOBS && SSP_SHAPES_MAX_BLOBS == SH_MAX_BLOBS &&
+                  SSP_SHAPES_MAX_CMDS == SH_MAX_CMDS && SSP_SHAPES_MAX_VERTS == SH_MAX_VERTS && SSP_SHAPES_MAX_TEX == SH_MAX_TEX &&
+                  SSP_SHAPES_MAX_POINTS == SH_MAX_POINTS && SSP_SHAPES_MAX_BLUR == SH_MAX_BLUR && SSP_SHAPES_MAX_TEX_BLOBS == SH_MAX_TEX_BLOBS,
+              "the scene table of ssp_hip.h and shapes_kernels.hip.h differ");
+static int shapes_check(const ssp_shapes_params* p, int b, const char* who) {
+  if (!p || b < 1 || b > 65535) return fail(-1, "%s: bad argument", who);
+  if (p->struct_size != sizeof(ssp_shapes_params))
+    return fail(-1, "%s: ssp_shapes_params.struct_size is %u, this library knows %zu", who, p->struct_size, sizeof(ssp_shapes_params));
+  if (p->gen_h < 16 || p->gen_w < 16 || p->gen_h > 8192 || p->gen_w > 8192 || p->out_h < 1 || p->out_w < 1 || p->out_h > 8192 || p->out_w > 8192)
+    return fail(-1, "%s: image_size 16..8192 and resize 1..8192 required", who);
+  if (p->blur_size < 0 || p->blur_size > SSP_SHAPES_MAX_BLUR || (p->blur_size > 1 && !(p->blur_size & 1)))
+    return fail(-1, "%s: blur_size must be odd and <= %d", who, SSP_SHAPES_MAX_BLUR);
+  float tot = 0.f;
+  for (int i = 0; i < 9; ++i) {
+    if (!(p->weights[i] >= 0.f)) return fail(-1, "%s: negative primitive weight", who);
+    tot += p->weights[i];
+  }
+  if (!(tot > 0.f)) return fail(-1, "%s: no primitive has a positive weight", who);
+  const int dim = p->gen_h > p->gen_w ? p->gen_h : p->gen_w;
+  if (p->bg_nb_blobs < 0 || p->bg_nb_blobs > SSP_SHAPES_MAX_BLOBS || p->bg_min_kernel < 1 || p->bg_max_kernel <= p->bg_min_kernel ||
+      p->bg_max_kernel > 1024 || !(p->bg_min_rad_ratio >= 0.f) || (int)(dim * (double)p->bg_max_rad_ratio) > 181)
+    return fail(-1, "%s: generate_background needs nb_blobs <= %d, 1 <= min_kernel_size < max_kernel_size <= 1024, blob radius <= 181", who,
+                SSP_SHAPES_MAX_BLOBS);
+  if (p->lines_nb_lines < 2 || p->lines_nb_lines > 33 || p->polygon_max_sides < 4 || p->polygon_max_sides > 17 || p->multi_max_sides < 4 ||
+      p->multi_max_sides > 9 || p->multi_nb_polygons < 0 || p->multi_nb_polygons > SSP_SHAPES_MAX_TEX || p->multi_nb_blobs < 0 ||
+      p->multi_nb_blobs > SSP_SHAPES_MAX_TEX_BLOBS || p->multi_kernel_lo < 1 || p->multi_kernel_hi <= p->multi_kernel_lo ||
+      p->multi_kernel_hi > 1024 || p->ellipses_nb < 0 || p->ellipses_nb > SSP_SHAPES_MAX_CMDS || p->star_nb_branches < 4 ||
+      p->star_nb_branches > 17 || p->checker_max_rows < 4 || p->checker_max_rows > 7 || p->checker_max_cols < 4 || p->checker_max_cols > 7 ||
+      p->stripes_max_nb_cols < 6 || p->stripes_max_nb_cols > 15)
+    return fail(-1, "%s: a primitive's count parameter is outside the scene table's capacity (include/ssp_hip.h)", who);
+  return 0;
+}
+size_t ssp_shapes_workspace_bytes(const ssp_shapes_params* p, int b) {
+  if (!p || b < 1) return 0;
+  const size_t px = (size_t)b * p->gen_h * p->gen_w;
+  return px * 4 + ((px + 255) & ~(size_t)255);  // window sums (uint32) + the full-resolution plane (uint8)
+}
+int ssp_op_shapes_draw(uint64_t seed, const ssp_shapes_params* p, int b, int32_t* table_dev, void* stream) {
+  if (int rc = shapes_check(p, b, "shapes_draw")) return rc;
+  if (!table_dev) return fail(-1, "shapes_draw: null table");
+  hipLaunchKernelGGL(shapes_draw_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, seed, *p, b, table_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+int ssp_op_shapes_render(const int32_t* table_dev, const ssp_shapes_params* p, int b, void* workspace_dev, uint8_t* image_dev,
+                         float* points_dev, int32_t* counts_dev, void* stream) {
+  if (int rc = shapes_check(p, b, "shapes_render")) return rc;
+  if (!table_dev || !workspace_dev || !image_dev || !points_dev || !counts_dev) return fail(-1, "shapes_render: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int H = p->gen_h, W = p->gen_w;
+  const int kmax = p->bg_max_kernel > p->multi_kernel_hi ? p->bg_max_kernel : p->multi_kernel_hi;
+  const int pre_cap = (W + kmax + 3) & ~3;
+  const int cap_bg = SSP_SHAPES_MAX_BLOBS, cap_tex = p->multi_nb_blobs > 0 ? p->multi_nb_blobs : 1;
+  const size_t lds_bg = (size_t)4 * pre_cap + (size_t)8 * cap_bg, lds_tex = (size_t)4 * pre_cap + (size_t)8 * cap_tex;
+  if (lds_tex > 60 * 1024 || lds_bg > 60 * 1024) return fail(-1, "shapes_render: image width %d with kernel %d needs %zu bytes of LDS", W, kmax, lds_tex);
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(shapes_layer_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 60 * 1024));
+  unsigned* sums = static_cast<unsigned*>(workspace_dev);
+  unsigned char* plane = static_cast<unsigned char*>(workspace_dev) + (size_t)b * H * W * 4;
+  // every image has a background; an image of draw_multiple_polygons has up to multi_nb_polygons textures (its workgroups leave at once otherwise)
+  for (int layer = -1; layer < p->multi_nb_polygons; ++layer) {
+    if (layer >= 0 && !(p->weights[2] > 0.f)) break;
+    hipLaunchKernelGGL(shapes_layer_rows_kernel, dim3(H, b), dim3(256), layer < 0 ? lds_bg : lds_tex, st, table_dev, layer, H, W,
+                       p->multi_nb_blobs, layer < 0 ? cap_bg : cap_tex, pre_cap, sums);
+    hipLaunchKernelGGL(shapes_layer_cols_kernel, dim3(cdiv(W, 256), cdiv(H, 32), b), dim3(256), 0, st, table_dev, layer, H, W, pre_cap, sums, plane);
+  }
+  hipLaunchKernelGGL(shapes_paint_kernel, dim3(cdiv(W, 64), cdiv(H, 16), b), dim3(256), 0, st, table_dev, H, W, plane);
+  hipLaunchKernelGGL(shapes_blur_resize_kernel, dim3(cdiv(p->out_w, 64), cdiv(p->out_h, 4), b), dim3(256), 0, st, plane, *p, image_dev);
+  hipLaunchKernelGGL(shapes_points_kernel, dim3(cdiv(b * SSP_SHAPES_MAX_POINTS, 256)), dim3(256), 0, st, table_dev, *p, b, points_dev, counts_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+int ssp_op_warp_points_scatter(const float* points_dev, const int32_t* counts_dev, const float* hpx_dev, float* labels_dev, int b,
+                               int stride, int hh, int w, void* stream) {
+  if (!points_dev || !counts_dev || !labels_dev || b < 1 || stride < 1 || hh < 1 || w < 1) return fail(-1, "warp_points_scatter: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(labels_dev, 0, (size_t)b * hh * w * sizeof(float), st));
+  hipLaunchKernelGGL(warp_points_scatter_kernel, dim3(cdiv(b * stride, 256)), dim3(256), 0, st, points_dev, counts_dev, hpx_dev, labels_dev,
+                     b, stride, hh, w);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -72,6 +72,30 @@ PHOTO_MAX_ELLIPSES, PHOTO_MAX_KSIZE = 32, 351
  PHOTO_KSIZE, PHOTO_KEY, PHOTO_DRAW_STRIDE) = 0, 1, 2, 3, 4, 5, 14, 174, 175, 176, 180
 
 
+class SspShapesParams(C.Structure):
+    """ssp_shapes_params (include/ssp_hip.h): `struct_size` first (see shapes_params_from_config)."""
+    _fields_ = [("struct_size", C.c_uint32), ("gen_h", C.c_int32), ("gen_w", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("blur_size", C.c_int32), ("weights", C.c_float * 9),
+                ("bg_nb_blobs", C.c_int32), ("bg_min_kernel", C.c_int32), ("bg_max_kernel", C.c_int32),
+                ("bg_min_rad_ratio", C.c_float), ("bg_max_rad_ratio", C.c_float),
+                ("lines_nb_lines", C.c_int32), ("polygon_max_sides", C.c_int32), ("multi_max_sides", C.c_int32),
+                ("multi_nb_polygons", C.c_int32), ("multi_nb_blobs", C.c_int32), ("multi_kernel_lo", C.c_int32),
+                ("multi_kernel_hi", C.c_int32), ("ellipses_nb", C.c_int32), ("star_nb_branches", C.c_int32),
+                ("checker_max_rows", C.c_int32), ("checker_max_cols", C.c_int32), ("stripes_max_nb_cols", C.c_int32),
+                ("checker_transform", C.c_float * 2), ("stripes_transform", C.c_float * 2), ("stripes_min_width_ratio", C.c_float),
+                ("cube_min_size_ratio", C.c_float), ("cube_scale", C.c_float * 2), ("cube_trans", C.c_float * 2),
+                ("resize_scale_y", C.c_float), ("resize_scale_x", C.c_float), ("gauss_w", C.c_float * 63)]
+
+
+# the scene table row (SSP_SHAPES_* of include/ssp_hip.h)
+SHAPES_PRIMITIVES = ["draw_lines", "draw_polygon", "draw_multiple_polygons", "draw_ellipses", "draw_star", "draw_checkerboard",
+                     "draw_stripes", "draw_cube", "gaussian_noise"]  # SyntheticDataset_gaussian.drawing_primitives
+SHAPES_MAX_BLOBS, SHAPES_MAX_CMDS, SHAPES_MAX_VERTS, SHAPES_MAX_TEX, SHAPES_MAX_POINTS, SHAPES_MAX_BLUR = 128, 64, 256, 32, 256, 63
+(SHAPES_PRIM, SHAPES_THR, SHAPES_KEY, SHAPES_KSIZE, SHAPES_NBLOBS, SHAPES_MEAN0, SHAPES_MEAN, SHAPES_NCMDS, SHAPES_NPOINTS, SHAPES_NVERTS,
+ SHAPES_NTEX, SHAPES_BLOBS, SHAPES_CMDS, SHAPES_VERTS, SHAPES_TEX, SHAPES_POINTS, SHAPES_ROW) = (0, 1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 16, 528, 1296,
+                                                                                              1808, 2192, 2704)
+
+
 class SspExportParams(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("conf_thresh", C.c_float),
                 ("nms_dist", C.c_int32), ("border_remove", C.c_int32), ("top_k", C.c_int32), ("subpixel", C.c_int32)]
@@ -94,7 +118,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_describe_workspace_bytes", "ssp_describe_points", "ssp_op_sample_descriptors", "ssp_match_workspace_bytes",
            "ssp_match_two_way", "ssp_debug_backward_taps", "ssp_debug_backward_tap_floats", "ssp_debug_backward_tap",
            "ssp_eval_repeatability", "ssp_eval_ransac_workspace_bytes", "ssp_eval_ransac",
-           "ssp_op_photometric_draw", "ssp_op_photometric_apply"]
+           "ssp_op_photometric_draw", "ssp_op_photometric_apply",
+           "ssp_shapes_workspace_bytes", "ssp_op_shapes_draw", "ssp_op_shapes_render", "ssp_op_warp_points_scatter"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 
@@ -216,6 +241,16 @@ def load_library(path=None):
     try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
         lib.ssp_op_photometric_draw.argtypes = [C.c_uint64, C.POINTER(SspPhotometricParams), i, i, i, vp, vp]
         lib.ssp_op_photometric_apply.argtypes = [vp, vp, vp, i, i, i, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        sp = C.POINTER(SspShapesParams)
+        lib.ssp_shapes_workspace_bytes.argtypes = [sp, i]
+        lib.ssp_shapes_workspace_bytes.restype = C.c_size_t
+        lib.ssp_op_shapes_draw.argtypes = [C.c_uint64, sp, i, vp, vp]
+        lib.ssp_op_shapes_render.argtypes = [vp, sp, i, vp, vp, vp, vp, vp]
+        lib.ssp_op_warp_points_scatter.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -1416,6 +1451,154 @@ def op_photometric_apply(img, draws):
     out = torch.empty_like(img)
     with torch.cuda.device(img.device):
         _check(lib.ssp_op_photometric_apply(_ptr(img), _ptr(draws), _ptr(out), B, H, W, _stream()))
+    return out
+
+
+# ---- Synthetic Shapes (datasets/synthetic_dataset.py, datasets/SyntheticDataset_gaussian.py) ----
+def shapes_gaussian_weights(blur_size):
+    """The normalised float32 weights of cv2.GaussianBlur(img, (b, b), 0): sigma = 0.3 ((b - 1) / 2 - 1) + 0.8, weights
+    exp(-(j - r)^2 / (2 sigma^2)) in float64, divided by their float64 sum, rounded to float32 (cv2's fixed tables for b <= 7
+    are not used).  Computed on the host so that the device and a restatement hold the same bits."""
+    b = int(blur_size)
+    if b <= 1:
+        return np.ones(1, np.float32)
+    sigma = 0.3 * ((b - 1) * 0.5 - 1.0) + 0.8
+    j = np.arange(b, dtype=np.float64) - (b - 1) // 2
+    w = np.exp(-(j * j) / (2.0 * sigma * sigma))
+    return (w / w.sum()).astype(np.float32)
+
+
+def shapes_params_from_config(data_cfg):
+    """The `data:` block of a MagicPoint yaml -> SspShapesParams: `generation` is the dataset class's default_config
+    (SyntheticDataset_gaussian.py:59-73) merged with the user's, `preprocessing` its default (:74) merged likewise; the primitive
+    weights are the `truncate` shares (a missing entry counts 1; a primitive outside `primitives` counts 0)."""
+    d = data_cfg or {}
+    gen = {"image_size": [960, 1280],
+           "params": {"generate_background": {"min_kernel_size": 150, "max_kernel_size": 500, "min_rad_ratio": 0.02, "max_rad_ratio": 0.031},
+                      "draw_stripes": {"transform_params": (0.1, 0.1)}, "draw_multiple_polygons": {"kernel_boundaries": (50, 100)}}}
+    user = d.get("generation") or {}
+    gen["image_size"] = list(user.get("image_size", gen["image_size"]))
+    for k, v in (user.get("params") or {}).items():
+        gen["params"][k] = dict(gen["params"].get(k, {}), **(v or {}))
+    pre = dict({"resize": [240, 320], "blur_size": 11}, **(d.get("preprocessing") or {}))
+    names = d.get("primitives", "all")
+    names = SHAPES_PRIMITIVES if names == "all" else ([names] if isinstance(names, str) else list(names))
+    for n in names:
+        if n not in SHAPES_PRIMITIVES:
+            raise ValueError("unknown primitive %r" % (n,))
+    trunc = d.get("truncate") or {}
+    p = SspShapesParams()
+    p.struct_size = C.sizeof(SspShapesParams)
+    p.gen_h, p.gen_w = (int(v) for v in gen["image_size"])
+    p.out_h, p.out_w = (int(v) for v in pre["resize"])
+    p.blur_size = int(pre["blur_size"])
+    for k, n in enumerate(SHAPES_PRIMITIVES):
+        p.weights[k] = float(trunc.get(n, 1.0)) if n in names else 0.0
+    g = gen["params"]
+    bg = g.get("generate_background", {})
+    p.bg_nb_blobs = int(bg.get("nb_blobs", 100))
+    p.bg_min_kernel, p.bg_max_kernel = int(bg.get("min_kernel_size", 50)), int(bg.get("max_kernel_size", 300))
+    p.bg_min_rad_ratio, p.bg_max_rad_ratio = float(bg.get("min_rad_ratio", 0.01)), float(bg.get("max_rad_ratio", 0.05))
+    p.lines_nb_lines = int(g.get("draw_lines", {}).get("nb_lines", 10))
+    p.polygon_max_sides = int(g.get("draw_polygon", {}).get("max_sides", 8))
+    mp = g.get("draw_multiple_polygons", {})
+    p.multi_max_sides, p.multi_nb_polygons, p.multi_nb_blobs = int(mp.get("max_sides", 8)), int(mp.get("nb_polygons", 30)), int(mp.get("nb_blobs", 3000))
+    p.multi_kernel_lo, p.multi_kernel_hi = (int(v) for v in mp.get("kernel_boundaries", (50, 100)))
+    p.ellipses_nb = int(g.get("draw_ellipses", {}).get("nb_ellipses", 20))
+    p.star_nb_branches = int(g.get("draw_star", {}).get("nb_branches", 6))
+    cb = g.get("draw_checkerboard", {})
+    p.checker_max_rows, p.checker_max_cols = int(cb.get("max_rows", 7)), int(cb.get("max_cols", 7))
+    p.checker_transform[0], p.checker_transform[1] = (float(v) for v in cb.get("transform_params", (0.05, 0.15)))
+    st = g.get("draw_stripes", {})
+    p.stripes_max_nb_cols, p.stripes_min_width_ratio = int(st.get("max_nb_cols", 13)), float(st.get("min_width_ratio", 0.04))
+    p.stripes_transform[0], p.stripes_transform[1] = (float(v) for v in st.get("transform_params", (0.05, 0.15)))
+    cu = g.get("draw_cube", {})
+    p.cube_min_size_ratio = float(cu.get("min_size_ratio", 0.2))
+    p.cube_scale[0], p.cube_scale[1] = (float(v) for v in cu.get("scale_interval", (0.4, 0.6)))
+    p.cube_trans[0], p.cube_trans[1] = (float(v) for v in cu.get("trans_interval", (0.5, 0.2)))
+    p.resize_scale_y = float(np.float32(p.gen_h) / np.float32(p.out_h))
+    p.resize_scale_x = float(np.float32(p.gen_w) / np.float32(p.out_w))
+    if p.blur_size > SHAPES_MAX_BLUR or (p.blur_size > 1 and p.blur_size % 2 == 0):
+        raise ValueError("preprocessing.blur_size must be odd and <= %d" % SHAPES_MAX_BLUR)
+    for k, v in enumerate(shapes_gaussian_weights(p.blur_size)):
+        p.gauss_w[k] = float(v)
+    return p
+
+
+_u8_lut = {}
+
+
+def u8_to_unit_float(img):
+    """load_as_float of a uint8 device tensor: k / 255 from a 256-entry table divided on the HOST (the device's division by a
+    scalar multiplies by the reciprocal, which is not the correctly rounded float32 quotient in the last bit); one upload per device."""
+    lut = _u8_lut.get(img.device)
+    if lut is None:
+        lut = _u8_lut[img.device] = (torch.arange(256, dtype=torch.float32) / 255.0).to(img.device)
+    return lut[img.contiguous().long()]
+
+
+def photometric_params_single_pass(aug_cfg):
+    """photometric_params_from_config with every stage applied at most once.  The reference's parser appends the previous
+    augmenter a second time when motion_blur.max_kernel_size != 3 (the shipped magicpoint yaml: 7 -> ImpulseNoise twice, no motion
+    blur); the device chain applies a stage once and ssp_op_photometric_draw refuses a count of 2, so the single-view feed
+    applies a doubled stage ONCE: a stated deviation."""
+    p = photometric_params_from_config(aug_cfg)
+    for f in ("random_brightness", "random_contrast", "additive_gaussian_noise", "additive_speckle_noise"):
+        setattr(p, f, min(getattr(p, f), 1))
+    return p
+
+
+def op_shapes_draw(B, seed, params, device):
+    """Scene tables int32 [B, SHAPES_ROW] of B Synthetic Shapes images from one seed (row layout: SHAPES_* above /
+    include/ssp_hip.h).  params: SspShapesParams or the `data:` dict."""
+    lib = load_library()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("op_shapes_draw needs a HIP device")
+    if not isinstance(params, SspShapesParams):
+        params = shapes_params_from_config(params)
+    table = torch.empty(B, SHAPES_ROW, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(lib.ssp_op_shapes_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(params), B, _ptr(table), _stream()))
+    return table
+
+
+def op_shapes_render(table, params):
+    """Scene tables -> (image uint8 [B,1,h,w], points float32 [B, SHAPES_MAX_POINTS, 2] (x, y) scaled to (h, w), counts int32 [B]):
+    a pure function of the two (rules: csrc/shapes_kernels.hip.h)."""
+    lib = load_library()
+    _need_gpu(table, "table")
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != SHAPES_ROW:
+        raise ValueError("op_shapes_render: table int32 [B,%d] required" % SHAPES_ROW)
+    if not isinstance(params, SspShapesParams):
+        params = shapes_params_from_config(params)
+    B, dev = table.shape[0], table.device
+    need = lib.ssp_shapes_workspace_bytes(C.byref(params), B)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)  # per call: torch's caching allocator orders reuse by stream
+    img = torch.empty(B, 1, params.out_h, params.out_w, dtype=torch.uint8, device=dev)
+    pts = torch.empty(B, SHAPES_MAX_POINTS, 2, dtype=torch.float32, device=dev)
+    cnt = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.ssp_op_shapes_render(_ptr(table), C.byref(params), B, _ptr(ws), _ptr(img), _ptr(pts), _ptr(cnt), _stream()))
+    return img, pts, cnt
+
+
+def op_warp_points_scatter(points, counts, H, W, hpx=None):
+    """Float key points [B,N,2] (x, y) with counts [B] -> label map [B,1,H,W]: filter_points, warp with the pixel-space
+    homographies hpx [B,3,3] (None: no warp), filter_points, round, clamp to (W - 1, H - 1), scatter
+    (SyntheticDataset_gaussian.py:342-351, 376, 450-472)."""
+    lib = load_library()
+    _need_gpu(points, "points")
+    _need_gpu(counts, "counts")
+    B, N = points.shape[0], points.shape[1]
+    if points.dtype != torch.float32 or counts.dtype != torch.int32 or tuple(points.shape) != (B, N, 2) or tuple(counts.shape) != (B,):
+        raise ValueError("op_warp_points_scatter: points float32 [B,N,2] and counts int32 [B] required")
+    if hpx is not None:
+        hpx = hpx.to(points.device, torch.float32).contiguous()
+        assert tuple(hpx.shape) == (B, 3, 3)
+    out = torch.empty(B, 1, H, W, dtype=torch.float32, device=points.device)
+    with torch.cuda.device(points.device):
+        _check(lib.ssp_op_warp_points_scatter(_ptr(points), _ptr(counts), _ptr(hpx), _ptr(out), B, N, int(H), int(W), _stream()))
     return out
 
 

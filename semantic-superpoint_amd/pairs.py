@@ -76,3 +76,58 @@ def make_pairs(image, labels_2D, seed, warp_params=None, erosion_radius=3, seman
         s["semantic"] = semantic
         s["warped_sem"] = L.op_sem_finalize(sw.view(B, H, W), vm.view(B, H, W), n_classes)
     return s
+
+
+def make_single_view(image, points, counts, seed, homographic=None, photometric=None, homographies=None, photometric_draws=None):
+    """The single-view branch of the loaders (datasets/SyntheticDataset_gaussian.py:381-480, datasets/Coco.py:307-339) for a
+    batch that is resident in HBM: the `sample` dict of the single-view step (`image`, `labels_2D`, `valid_mask`,
+    `labels_2D_gaussian`), built in the reference's order:
+
+      1 photometric augmentation of the UNWARPED image (:385-394)
+      2 a homography from `augmentation.homographic.params`, inverted (:429-440)
+      3 bilinear warp of the image (:442-446)
+      4 the key points warped with the pixel-scaled homography (:450)
+      5 filter_points, round, clamp to (W - 1, H - 1), scatter (:342-351, 451, 472)
+      6 valid mask = nearest warp of ones, eroded by `valid_border_margin` (:463-470)
+
+    image: [B,1,H,W] uint8 or float32; points: float32 [B,N,2] (x, y) at the image's resolution; counts: int32 [B].
+    homographic: the `augmentation.homographic` dict (`params`, `valid_border_margin`) or None: labels are the rounded, clamped
+        points, the mask is all ones and the image is only augmented photometrically.
+    photometric: the `data.augmentation` dict (on when its `photometric.enable` is set) or None; a stage that the reference's
+        parser doubles (motion_blur.max_kernel_size != 3) is applied once (lib.photometric_params_single_pass).
+    Host work per batch: sampled homographies cost one small D2H copy, the reference's own fp32 `T^-1 H T` per matrix on the host
+        (lib.scaled_homographies: bit-identical rounded indices) and one H2D copy - a synchronisation point, as in make_pairs;
+        supplied homographies are also inverted on the host.  No image or label map ever leaves the device.
+    homographies: [B,3,3] used instead of sampling (the matrix that warps the points; the image is warped with its inverse);
+    photometric_draws: one draw table [B, lib.PHOTO_DRAW_STRIDE] used instead of drawing.
+    `labels_res` is NOT produced: the heat-map trainer never reads it with `subpixel` off (Train_model_heatmap_all.py).
+    `labels_2D_gaussian` is op_label_quantize(labels_2D) as in make_pairs.  The RNG streams differ from numpy's: a
+    distribution-level equivalent."""
+    if not image.is_cuda:
+        raise RuntimeError("make_single_view needs HIP tensors: there is no CPU fallback")
+    B, _, H, W = image.shape
+    dev = image.device
+    if image.dtype == torch.uint8:  # load_as_float: k / 255 from the host's correctly rounded table (see make_pairs)
+        image = L.u8_to_unit_float(image)
+    else:
+        image = image.contiguous().float()
+    points = points.contiguous().float()
+    counts = counts.contiguous().to(torch.int32)
+    if photometric_draws is None and photometric is not None and (photometric.get("photometric") or {}).get("enable", False):
+        pp = L.photometric_params_single_pass(photometric)
+        photometric_draws = L.op_photometric_draw(B, H, W, (int(seed) * 2 + 1) * 0x9E3779B1, pp, dev)
+    if photometric_draws is not None:
+        image = L.op_photometric_apply(image, photometric_draws.to(dev).contiguous())
+    if homographic is None and homographies is None:
+        labels = L.op_warp_points_scatter(points, counts, H, W)
+        mask = torch.ones_like(image)
+    else:
+        if homographies is None:
+            hs, inv = L.op_sample_homographies(B, int(seed) ^ 0x53564945, dev, **((homographic or {}).get("params") or {}))
+        else:
+            hs = homographies.to(dev, torch.float32).contiguous()
+            inv = torch.inverse(hs.cpu()).to(dev).contiguous()
+        image = L.op_warp_image(image, inv)
+        labels = L.op_warp_points_scatter(points, counts, H, W, L.scaled_homographies(hs, H, W).to(dev))
+        mask = L.op_erode(L.op_warp_image(torch.ones_like(image), inv, nearest=True), int((homographic or {}).get("valid_border_margin", 0)))
+    return {"image": image, "labels_2D": labels, "valid_mask": mask, "labels_2D_gaussian": L.op_label_quantize(labels)}
