@@ -257,6 +257,17 @@ int ssp_op_detector_loss(const float* semi_nhwc_dev, int cs, const float* labels
 int ssp_op_sem_loss(const float* sout_nhwc_dev, int cs, const int64_t* labels_dev, int b, int h, int w, int n_classes, int algo,
                     void* scratch_dev, size_t scratch_bytes, float* loss_dev, float* dsout_nhwc_dev, void* stream);
 
+/* Segmentation head read-out: class map and confusion matrix from convSout NHWC [b][h/8*w/8][cs] (n_classes
+ * logits, channel stride cs >= n_classes, 1 <= n_classes <= 256) without the [b,n_classes,h,w] logits: bilinear upsample x8
+ * (align_corners=False, models/SuperPointNet_gauss2_ssmall.py:87-91) + argmax over the classes (ties: the lowest class index).
+ * pred_dev (nullable): uint8 [b,h,w].  confusion_dev (nullable; needs labels_dev): int64 [n_classes][n_classes], row = label,
+ * column = prediction, ACCUMULATED (+=; the caller zeroes it) - labels int64 [b,h,w], values outside [0, n_classes) are ignored
+ * (ssp_op_sem_loss).  h and w must be multiples of 8.
+ * ssp_sem_predict: the same from the logits the last forward / pair step left in `slot` (like ssp_detector_heatmap). */
+int ssp_op_sem_predict(const float* sout_nhwc_dev, int cs, const int64_t* labels_dev, int b, int h, int w, int n_classes,
+                       uint8_t* pred_dev, int64_t* confusion_dev, void* stream);
+int ssp_sem_predict(ssp_handle* h, int slot, const int64_t* labels_dev, uint8_t* pred_dev, int64_t* confusion_dev, void* stream);
+
 /* ---- pair construction on the device (dataset side of the reference, datasets/Coco.py:341-392) ----
  * ssp_op_warp_image : inv_warp_image_batch (utils/utils.py:347-385): out[p] = sample(img, inv_h * p), p on the
  *                     linspace(-1,1) grid, zeros padding, align_corners=True; nearest != 0 selects mode="nearest".

@@ -16,6 +16,9 @@ optimizer step is split in two buckets and overlapped with the tail of the backw
 Device feed (`ssp_device_pairs: true`, with `data.warped_pair.enable`): the loader ships only the raw `image`, `labels_2D`
 and (with `data.semantic`) `semantic`; the pair - homographies, warps, masks, warped labels, and in training the photometric
 augmentation of `data.augmentation` - is built on the device by pairs.make_pairs (`_device_pair`).
+Segmentation metrics (`ssp_sem_metrics: true`, with `data.semantic` and a model with a segmentation head; off by default): on
+the steps of the logging branch, pixel accuracy and mIoU of both views and their class maps (`log_sem_metrics`); validation
+steps also sum one confusion matrix on the device, which train() reports per validation round.
 """
 import copy
 import logging
@@ -30,6 +33,7 @@ from . import parallel
 from .models import SuperPointNet_gauss2, SuperPointNet_gauss2_ssmall
 
 _MODELS = {"SuperPointNet_gauss2": SuperPointNet_gauss2, "SuperPointNet_gauss2_ssmall": SuperPointNet_gauss2_ssmall}
+_SEM_MODELS = ("SuperPointNet_gauss2_ssmall",)  # models with a segmentation head
 
 
 def dict_update(d, u):
@@ -87,6 +91,11 @@ class Train_model_heatmap_all(object):
         self.r = m["real_batch_size"] // m["batch_size"]
         for k in ("train_iter", "validation_interval", "tensorboard_interval", "save_interval"):
             self.config[k] *= self.r
+        self.sem_metrics = bool(self.config.get("ssp_sem_metrics", False))
+        if self.sem_metrics and not (self.config["data"].get("semantic", False) and m.get("name") in _SEM_MODELS):
+            raise ValueError("ssp_sem_metrics reads the segmentation head: it needs data.semantic and a model with that head (%s), "
+                             "got data.semantic=%r and model %r" % (", ".join(_SEM_MODELS), self.config["data"].get("semantic", False), m.get("name")))
+        self.sem_confusion_val = None  # int64 [C,C] on the device: both views of the validation steps since reset_sem_confusion()
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("Train_model_heatmap_all (MI355X build) needs a HIP device, got %s" % device)
@@ -264,6 +273,8 @@ class Train_model_heatmap_all(object):
             self.scalar_dict["eta_sem"] = eta[2]
         if n_iter % cfg["tensorboard_interval"] == 0 or task == "val":
             self.log_precision_recall(eng, dev, B, H, W)
+            if self.sem_metrics:
+                self.log_sem_metrics(eng, dev, B, H, W, task == "val")
             self.tb_hist_dict(task, self.hist_dict)   # (:568; `images_dict` stays unwritten like the reference's commented-out :567)
         self.tb_scalar_dict(self.scalar_dict, task)
         return float(s["loss"])
@@ -316,6 +327,35 @@ class Train_model_heatmap_all(object):
             # sample 0; the heat-map overlays (:481-487) cover the whole batch
             self.images_dict[name + "_nms_overlap"] = self.img_overlap(lab[:1], nm[:1].unsqueeze(1), img[:1]).cpu().numpy()
             self.images_dict[name + "_heatmap_nms_overlap"] = self.img_overlap(lab, hm.view(B, 1, H, W), img).cpu().numpy()
+
+    def log_sem_metrics(self, eng, dev, B, H, W, val):
+        """`ssp_sem_metrics`: what the segmentation head predicts on this step.  Engine.sem_predict reads the logits the pair step
+        left in the engine (fused upsample + argmax + confusion matrix; the [B,133,H,W] logits of the reference's
+        images_dict["sem_pred"], Train_model_heatmap_all.py:442-443, are never materialised):
+          scalar_dict  sem_pixel_acc, sem_miou (view 0 against `semantic`), sem_pixel_acc_warp, sem_miou_warp (view 1 against
+                       `warped_sem`; pairs only) - lib.sem_metrics of the step's confusion matrix, ignore label excluded;
+          images_dict  sem_class, warp_sem_class: uint8 [B,1,H,W] class maps.  (Not `sem_pred`: tb_images_dict takes an argmax over
+                       axis 1 of anything with that name, which would turn a class map into zeros.)
+        Validation steps add both views into `sem_confusion_val`.  The step itself is untouched."""
+        views = [(0, "semantic", "", "sem_class")]
+        if "warped_img" in dev:
+            views.append((1, "warped_sem", "_warp", "warp_sem_class"))
+        for slot, key, suffix, img_key in views:
+            conf = torch.zeros(eng.n_classes, eng.n_classes, dtype=torch.int64, device=self.device)
+            pred, conf = eng.sem_predict(slot, B, H, W, labels=dev[key], confusion=conf)
+            met = L.sem_metrics(conf)
+            self.scalar_dict["sem_pixel_acc" + suffix] = met["pixel_acc"]
+            self.scalar_dict["sem_miou" + suffix] = met["miou"]
+            self.images_dict[img_key] = pred.unsqueeze(1).cpu().numpy()
+            if val:
+                if self.sem_confusion_val is None or self.sem_confusion_val.shape != conf.shape:
+                    self.sem_confusion_val = torch.zeros_like(conf)
+                self.sem_confusion_val += conf
+
+    def reset_sem_confusion(self):
+        """Zero the validation confusion matrix (train() calls it in front of a validation round)."""
+        if self.sem_confusion_val is not None:
+            self.sem_confusion_val.zero_()
 
     @staticmethod
     def img_overlap(img_r, img_g, img_gray):
@@ -372,10 +412,15 @@ class Train_model_heatmap_all(object):
                 self.train_val_sample(sample_train, self.n_iter, True)
                 self.n_iter += 1
                 if self._eval and self.n_iter % self.config["validation_interval"] == 0:
+                    if self.sem_metrics:
+                        self.reset_sem_confusion()
                     for j, sample_val in enumerate(self.val_loader):
                         self.train_val_sample(sample_val, self.n_iter + j, False)
                         if j > self.config.get("validation_size", 3):
                             break
+                    if self.sem_metrics and self.sem_confusion_val is not None:  # one matrix read per round
+                        met = L.sem_metrics(self.sem_confusion_val)
+                        self.tb_scalar_dict({"sem_miou_round": met["miou"], "sem_pixel_acc_round": met["pixel_acc"]}, "val")
                 if self.n_iter % self.config["save_interval"] == 0:
                     self.saveModel()
                 if self.n_iter > self.max_iter:

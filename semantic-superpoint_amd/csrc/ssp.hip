@@ -34,6 +34,7 @@
 #include "describe_kernels.hip.h"
 #include "eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
+#include "sem_eval_kernels.hip.h"
 #include "backward_tail.hip.h"
 
 using namespace sspk;
@@ -4015,6 +4016,38 @@ int ssp_op_sem_loss(const float* sout_nhwc_dev, int cs, const int64_t* labels_de
   hipLaunchKernelGGL(sem_op_finish_kernel, dim3(1), dim3(64), 0, st, acc, loss_dev);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+int ssp_op_sem_predict(const float* sout_nhwc_dev, int cs, const int64_t* labels_dev, int b, int hh, int w, int n_classes,
+                       uint8_t* pred_dev, int64_t* confusion_dev, void* stream) {
+  if (!sout_nhwc_dev || b < 1 || hh < 8 || w < 8) return fail(-1, "sem_predict: bad argument");
+  if (hh % 8 || w % 8) return fail(-1, "sem_predict: H and W must be multiples of 8 (got %dx%d)", hh, w);
+  if (n_classes < 1 || n_classes > SEMP_MAX_C || cs < n_classes)
+    return fail(-1, "sem_predict: 1 <= n_classes <= %d and channel stride >= n_classes required (got %d, stride %d)", SEMP_MAX_C, n_classes, cs);
+  if (!pred_dev && !confusion_dev) return fail(-1, "sem_predict: neither a class map nor a confusion matrix requested");
+  if (confusion_dev && !labels_dev) return fail(-1, "sem_predict: a confusion matrix needs labels");
+  const int hc = hh / 8, wc = w / 8;
+  const long ntile = (long)b * (hc + 1) * (wc + 1);
+  if (ntile > (1L << 30) || (size_t)b * hc * wc * cs > ((size_t)1 << 40)) return fail(-1, "sem_predict: shape too large");
+  const int tpw = std::max(SEMP_MIN_TILES, cdiv((int)ntile, SEMP_WAVES));
+  const dim3 grid(cdiv(cdiv((int)ntile, tpw), 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* conf = reinterpret_cast<unsigned long long*>(confusion_dev);
+  if (cs % 4 == 0 && (reinterpret_cast<size_t>(sout_nhwc_dev) & 15) == 0)
+    hipLaunchKernelGGL(sem_predict_kernel<true>, grid, block, 0, st, sout_nhwc_dev, labels_dev, pred_dev, conf, b, hc, wc, n_classes, cs, tpw);
+  else
+    hipLaunchKernelGGL(sem_predict_kernel<false>, grid, block, 0, st, sout_nhwc_dev, labels_dev, pred_dev, conf, b, hc, wc, n_classes, cs, tpw);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_sem_predict(ssp_handle* h, int slot, const int64_t* labels_dev, uint8_t* pred_dev, int64_t* confusion_dev, void* stream) {
+  if (!h || !h->bound) return fail(-1, "handle not bound");
+  if (h->nheads != 3) return fail(-1, "sem_predict: the model has no segmentation head");
+  if (slot < 0 || slot > 1) return fail(-1, "sem_predict: slot must be 0 or 1");
+  Slot& S = h->slot[slot];
+  if (S.N <= 0) return fail(-1, "sem_predict: slot %d holds no forward", slot);
+  return ssp_op_sem_predict(S.Y[L_SOUT], h->sout_cs, labels_dev, S.N, S.H, S.W, h->cfg.n_classes, pred_dev, confusion_dev, stream);
 }
 
 int ssp_op_labels(const float* labels2d_dev, const float* mask2d_dev, float* target_dev, float* cellmask_dev, int b,

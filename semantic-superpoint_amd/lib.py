@@ -119,7 +119,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_match_two_way", "ssp_debug_backward_taps", "ssp_debug_backward_tap_floats", "ssp_debug_backward_tap",
            "ssp_eval_repeatability", "ssp_eval_ransac_workspace_bytes", "ssp_eval_ransac",
            "ssp_op_photometric_draw", "ssp_op_photometric_apply",
-           "ssp_shapes_workspace_bytes", "ssp_op_shapes_draw", "ssp_op_shapes_render", "ssp_op_warp_points_scatter"]
+           "ssp_shapes_workspace_bytes", "ssp_op_shapes_draw", "ssp_op_shapes_render", "ssp_op_warp_points_scatter",
+           "ssp_op_sem_predict", "ssp_sem_predict"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 
@@ -260,6 +261,12 @@ def load_library(path=None):
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
     lib.ssp_op_dense_loss.argtypes = [vp, vp, vp, vp, i, i, i, f, f, i, f, vp, C.c_size_t, vp, vp, vp, vp]
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_op_sem_predict.argtypes = [vp, i, vp, i, i, i, i, vp, vp, vp]
+        lib.ssp_sem_predict.argtypes = [vp, i, vp, vp, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
     try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
         lib.ssp_describe_workspace_bytes.argtypes = [ep, i]
         lib.ssp_describe_workspace_bytes.restype = C.c_size_t
@@ -730,6 +737,14 @@ class Engine:
             _check(self.lib.ssp_detector_heatmap(self.h, slot, _ptr(out), _stream()))
         return out
 
+    def sem_predict(self, slot, n, hh, ww, labels=None, want_pred=True, confusion=None):
+        """Class map and / or confusion matrix of the segmentation logits left in `slot` by the last forward / pair step (fused
+        upsample + argmax + counting, ssp_sem_predict; see op_sem_predict) -> (pred uint8 [n,hh,ww] | None, confusion | None)."""
+        labels, pred, confusion = _sem_predict_buffers(n, hh, ww, self.n_classes, self.device, labels, want_pred, confusion)
+        with torch.cuda.device(self.device):
+            _check(self.lib.ssp_sem_predict(self.h, int(slot), _ptr(labels), _ptr(pred), _ptr(confusion), _stream()))
+        return pred, confusion
+
     def debug_buffer(self, slot, name, shape, dtype=torch.float32):
         """Test hook: copy of an internal NHWC buffer as a torch tensor of `shape` (dtype bfloat16 for the activation /
         gradient tensors of the bf16 path)."""
@@ -948,6 +963,78 @@ def op_sem_loss(sout_nchw, labels, grad=True, algo=0, cs=None):
         _check(lib.ssp_op_sem_loss(_ptr(x), cs, _ptr(lab), B, Hc * 8, Wc * 8, c, algo, _ptr(scratch), scratch.numel(), _ptr(out), _ptr(d),
                                    _stream()))
     return float(out.item()), (d[..., :c].permute(0, 3, 1, 2).contiguous() if grad else None)
+
+
+def _sem_predict_buffers(n, hh, ww, n_classes, dev, labels, want_pred, confusion):
+    """Checked arguments of the two sem_predict entry points: (labels | None, pred | None, confusion | None)."""
+    if confusion is True:
+        confusion = torch.zeros(n_classes, n_classes, dtype=torch.int64, device=dev)
+    if confusion is not None:
+        _need_gpu(confusion, "confusion")
+        if confusion.dtype != torch.int64 or tuple(confusion.shape) != (n_classes, n_classes):
+            raise ValueError("confusion must be int64 [%d,%d], got %s %s" % (n_classes, n_classes, confusion.dtype, tuple(confusion.shape)))
+        if labels is None:
+            raise ValueError("a confusion matrix needs labels")
+    if not want_pred and confusion is None:
+        raise ValueError("sem_predict: neither a class map nor a confusion matrix requested")
+    if hh % 8 or ww % 8:
+        raise ValueError("sem_predict: H and W must be multiples of 8, got %dx%d" % (hh, ww))
+    if labels is not None:
+        _need_gpu(labels, "semantic labels")
+        if labels.dtype != torch.int64 or tuple(labels.shape) != (n, hh, ww):
+            raise ValueError("semantic labels must be int64 [B,H,W] = %s, got %s %s" % ((n, hh, ww), labels.dtype, tuple(labels.shape)))
+    pred = torch.empty(n, hh, ww, dtype=torch.uint8, device=dev) if want_pred else None
+    return labels, pred, confusion
+
+
+def op_sem_predict(sout_nchw, labels=None, want_pred=True, confusion=None, cs=None, n_classes=None):
+    """Class map and confusion matrix of public NCHW logits [B,C,Hc,Wc] at 1/8 resolution, as the segmentation head is read during
+    training: bilinear upsample x8 (align_corners=False) + argmax over the classes in one kernel, without the [B,C,8Hc,8Wc] logits.
+    Ties go to the lowest class index.  labels: int64 [B,8Hc,8Wc] on the device; values outside [0, C) are ignored (op_sem_loss).
+    confusion: an int64 [C,C] device matrix to ACCUMULATE into (row = label, column = prediction), True for a fresh one, None for
+    none.  cs: channel stride of the NHWC copy the kernel reads (default: C rounded up to 8; the padding is zero).  n_classes <
+    C: only the first n_classes channels are classes, the others play the padding of a stride-C map AS GIVEN (test hook).
+    Returns (pred uint8 [B,8Hc,8Wc] | None, confusion | None)."""
+    lib = load_library()
+    _need_gpu(sout_nchw, "sout")
+    B, c, Hc, Wc = sout_nchw.shape
+    dev = sout_nchw.device
+    if n_classes is None:
+        n_classes = c
+        cs = cs or (c + 7) // 8 * 8
+        x = torch.zeros(B, Hc, Wc, cs, dtype=torch.float32, device=dev)
+        x[..., :c] = sout_nchw.permute(0, 2, 3, 1)
+    else:
+        cs = c
+        x = sout_nchw.permute(0, 2, 3, 1).contiguous().float()
+    labels, pred, confusion = _sem_predict_buffers(B, Hc * 8, Wc * 8, n_classes, dev, labels, want_pred, confusion)
+    with torch.cuda.device(dev):
+        _check(lib.ssp_op_sem_predict(_ptr(x), cs, _ptr(labels), B, Hc * 8, Wc * 8, n_classes, _ptr(pred), _ptr(confusion), _stream()))
+    return pred, confusion
+
+
+def sem_metrics(confusion):
+    """Pixel accuracy and mean intersection over union of a confusion matrix [C,C] (row = label, column = prediction; torch tensor on
+    any device or numpy array; one device-to-host copy).  With tp = diag, row = sums over the predictions, col = sums over the labels:
+      n_pixels = confusion.sum();  pixel_acc = tp.sum() / n_pixels (nan without pixels);
+      iou[c] = tp[c] / (row[c] + col[c] - tp[c]) (nan where that union is 0: the class occurs in neither labels nor predictions);
+      miou = mean of the non-nan iou (nan when there is none);  classes_present = their number.
+    This is the standard definition.  The reference's only mIoU is the smoothed soft-IoU of the non-functional `_ang` trainer
+    (Train_model_heatmap_all_ang.py:181-190, under "TODO: mIoU with ignore index"): one (intersection + 0.01) / (union + 0.01) over
+    all classes and pixels of soft predictions at once, without an ignore label; it is deliberately not reproduced."""
+    m = confusion.detach().cpu().numpy() if torch.is_tensor(confusion) else np.asarray(confusion)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("confusion must be a square matrix, got shape %s" % (tuple(m.shape),))
+    m = m.astype(np.float64)
+    tp, row, col = np.diag(m), m.sum(1), m.sum(0)
+    n_pixels = m.sum()
+    union = row + col - tp
+    present = union > 0
+    iou = np.full(m.shape[0], np.nan)
+    iou[present] = tp[present] / union[present]
+    return {"n_pixels": int(n_pixels), "pixel_acc": float(tp.sum() / n_pixels) if n_pixels > 0 else float("nan"),
+            "iou": iou, "miou": float(iou[present].mean()) if present.any() else float("nan"),
+            "classes_present": int(present.sum())}
 
 
 def op_detector_loss(semi_nchw, labels2d, mask2d, grad=True):
