@@ -517,6 +517,39 @@ int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int
                     double* h_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev, double* ap_dev,
                     void* stream);
 
+/* ---- point tracks over a frame sequence (PointTracker.update / get_tracks, models/model_wrap.py:521-615) ----------
+ * The track table of max_length = L frames lives in caller-owned arrays of row_cap rows: ids [row_cap][L] int32 (point id
+ * of retained frame 0 .. L-1, oldest first, -1 = none), tid [row_cap] int32 (track id), score [row_cap] fp64 (running mean
+ * of the match distances, 9999 = no match yet) and a state vector int32 [2 + L] = n_rows, track_count, point count of each
+ * retained frame.  An empty tracker is a zeroed state vector.  2 <= L <= SSP_TRACK_MAX_LENGTH, 1 <= point_cap <=
+ * SSP_MATCH_MAX_POINTS points per frame, row_cap >= L * point_cap (every point of the retained frames may own a row).
+ * The rules are DESIGN.md section 17; results are bit-identical from run to run.
+ * ssp_op_track_update: one PointTracker.update from the *_in arrays into the *_out arrays (never in place): n_points_dev [1]
+ *   points in the new frame, match_dev [point_cap][3] float rows (i, j, distance) with n_match_dev [1] rows as
+ *   ssp_match_two_way writes them (i indexes the previous frame = the last frame of state_in, j the new one);
+ *   match_score64_dev (may be NULL): fp64 distances [point_cap] that replace column 2 (a host matcher's float64 scores).
+ *   The mean is updated in fp64 as (1 - 1/len) * old + (1/len) * d without contraction.
+ * ssp_op_track_select: get_tracks(min_length): the rows with at least min_length ids != -1 and a last id != -1, in table
+ *   order, as the reference's fp64 matrix tracks_dev [row_cap][2 + L] = (track id, score, ids), n_tracks_dev [1].
+ *   min_length == 0 returns every row (the reference's `tracker.tracks`).
+ * ssp_op_track_points: the coordinates a tracks matrix names (the index arithmetic of draw_tracks): tracks_dev
+ *   [track_cap][2 + L] fp64 with n_tracks_dev [1] rows, pts_dev [L][point_cap][2] fp64 (x, y) used as a ring: retained frame c
+ *   lives in slot (first_slot + c) % L; state_dev gives the frame counts.  xy_dev [track_cap][L][2] fp64, NaN where the id
+ *   is -1 (rows >= n_tracks are not written).
+ * workspace_dev: ssp_track_workspace_bytes(L, point_cap, row_cap) bytes serve update and select (0 = bad arguments). */
+#define SSP_TRACK_MAX_LENGTH 16
+size_t ssp_track_workspace_bytes(int max_length, int point_cap, int row_cap);
+int ssp_op_track_update(const int32_t* ids_in_dev, const int32_t* tid_in_dev, const double* score_in_dev,
+                        const int32_t* state_in_dev, const float* match_dev, const double* match_score64_dev,
+                        const int32_t* n_match_dev, const int32_t* n_points_dev, int max_length, int point_cap, int row_cap,
+                        void* workspace_dev, int32_t* ids_out_dev, int32_t* tid_out_dev, double* score_out_dev,
+                        int32_t* state_out_dev, void* stream);
+int ssp_op_track_select(const int32_t* ids_dev, const int32_t* tid_dev, const double* score_dev, const int32_t* state_dev,
+                        int max_length, int row_cap, int min_length, void* workspace_dev, double* tracks_dev,
+                        int32_t* n_tracks_dev, void* stream);
+int ssp_op_track_points(const double* tracks_dev, const int32_t* n_tracks_dev, const double* pts_dev, const int32_t* state_dev,
+                        int max_length, int point_cap, int track_cap, int first_slot, double* xy_dev, void* stream);
+
 /* BatchNorm2d(train) (+ReLU (+MaxPool2d(2))) backward. y: raw conv output NHWC; dout: gradient wrt the activated
  * (and pooled) output; stats4 = scale|shift|mean|invstd ([4*C]); dgamma/dbeta/dbias are accumulated;
  * sums_dev: double [SSP_NREP][2*C] scratch. */

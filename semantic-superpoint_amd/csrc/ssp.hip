@@ -32,6 +32,7 @@
 #include "shapes_kernels.hip.h"
 #include "export_kernels.hip.h"
 #include "describe_kernels.hip.h"
+#include "track_kernels.hip.h"
 #include "eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
@@ -3506,6 +3507,107 @@ int ssp_match_two_way(const float* desc1_dev, const int32_t* count1_dev, const f
                      cap, pair_stride, rowmin, colmin);
   hipLaunchKernelGGL(match_compact_kernel, dim3(n_pairs), dim3(1024), 0, st, (const uint64_t*)rowmin, (const uint64_t*)colmin,
                      count1_dev, count2_dev, cap, pair_stride, nn_thresh, match_dev, n_match_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- point tracks over a frame sequence (PointTracker.update / get_tracks) ----
+struct TrackWs {
+  int32_t* ids_tmp;       // [row_cap][L]
+  double* score_tmp;      // [row_cap]
+  int32_t* row_of_point;  // [point_cap]
+  int32_t* matched;       // [point_cap]
+  int32_t* block_sums;    // [cdiv(row_cap, TRACK_BLOCK) + cdiv(point_cap, TRACK_BLOCK)]
+  size_t bytes;
+};
+static TrackWs track_carve(int L, int point_cap, int row_cap, void* base) {
+  Carver c{reinterpret_cast<char*>(base), 0};
+  TrackWs w;
+  w.ids_tmp = c.take<int32_t>((size_t)row_cap * L);
+  w.score_tmp = c.take<double>((size_t)row_cap);
+  w.row_of_point = c.take<int32_t>((size_t)point_cap);
+  w.matched = c.take<int32_t>((size_t)point_cap);
+  w.block_sums = c.take<int32_t>((size_t)cdiv(row_cap, TRACK_BLOCK) + cdiv(point_cap, TRACK_BLOCK));
+  w.bytes = align_up(c.off, 256);
+  return w;
+}
+
+static int track_check(const char* what, int L, int point_cap, int row_cap) {
+  if (L < 2 || L > SSP_TRACK_MAX_LENGTH)
+    return fail(-1, "%s: 2 <= max_length <= %d required (got %d)", what, SSP_TRACK_MAX_LENGTH, L);
+  if (point_cap < 1 || point_cap > SSP_MATCH_MAX_POINTS)
+    return fail(-1, "%s: 1 <= point_cap <= %d points per frame required (got %d)", what, SSP_MATCH_MAX_POINTS, point_cap);
+  if (row_cap < 1 || row_cap > SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS)
+    return fail(-1, "%s: 1 <= row_cap <= %d rows required (got %d)", what, SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS, row_cap);
+  return 0;
+}
+
+size_t ssp_track_workspace_bytes(int max_length, int point_cap, int row_cap) {
+  if (track_check("track_workspace_bytes", max_length, point_cap, row_cap)) return 0;
+  return track_carve(max_length, point_cap, row_cap, nullptr).bytes;
+}
+
+int ssp_op_track_update(const int32_t* ids_in_dev, const int32_t* tid_in_dev, const double* score_in_dev,
+                        const int32_t* state_in_dev, const float* match_dev, const double* match_score64_dev,
+                        const int32_t* n_match_dev, const int32_t* n_points_dev, int max_length, int point_cap, int row_cap,
+                        void* workspace_dev, int32_t* ids_out_dev, int32_t* tid_out_dev, double* score_out_dev,
+                        int32_t* state_out_dev, void* stream) {
+  CHK(track_check("track_update", max_length, point_cap, row_cap));
+  if (row_cap < max_length * point_cap)
+    return fail(-1, "track_update: row_cap %d is below max_length * point_cap = %d (every point of the retained frames may own a row)",
+                row_cap, max_length * point_cap);
+  if (!ids_in_dev || !tid_in_dev || !score_in_dev || !state_in_dev || !match_dev || !n_match_dev || !n_points_dev ||
+      !workspace_dev || !ids_out_dev || !tid_out_dev || !score_out_dev || !state_out_dev)
+    return fail(-1, "track_update: null pointer");
+  if (ids_in_dev == ids_out_dev || tid_in_dev == tid_out_dev || score_in_dev == score_out_dev || state_in_dev == state_out_dev)
+    return fail(-1, "track_update: the table is not updated in place (pass a second set of arrays)");
+  hipStream_t st = (hipStream_t)stream;
+  const int L = max_length;
+  const TrackWs w = track_carve(L, point_cap, row_cap, workspace_dev);
+  const int nb_old = cdiv(row_cap, TRACK_BLOCK), nb = nb_old + cdiv(point_cap, TRACK_BLOCK);
+  HIPCHK(hipMemsetAsync(w.row_of_point, 0xFF, (size_t)point_cap * sizeof(int32_t), st));
+  HIPCHK(hipMemsetAsync(w.matched, 0, (size_t)point_cap * sizeof(int32_t), st));
+  hipLaunchKernelGGL(track_shift_kernel, dim3(cdiv(row_cap, 256)), dim3(256), 0, st, ids_in_dev, score_in_dev, state_in_dev, L,
+                     point_cap, row_cap, w.ids_tmp, w.score_tmp, w.row_of_point);
+  hipLaunchKernelGGL(track_match_kernel, dim3(cdiv(point_cap, 256)), dim3(256), 0, st, match_dev, match_score64_dev, n_match_dev,
+                     n_points_dev, state_in_dev, L, point_cap, row_cap, (const int32_t*)w.row_of_point, w.ids_tmp, w.score_tmp,
+                     w.matched);
+  hipLaunchKernelGGL(track_count_kernel, dim3(nb), dim3(TRACK_BLOCK), 0, st, (const int32_t*)w.ids_tmp, (const int32_t*)w.matched,
+                     state_in_dev, n_points_dev, L, point_cap, row_cap, nb_old, w.block_sums);
+  hipLaunchKernelGGL(track_scatter_kernel, dim3(nb), dim3(TRACK_BLOCK), 0, st, (const int32_t*)w.ids_tmp,
+                     (const double*)w.score_tmp, tid_in_dev, (const int32_t*)w.matched, state_in_dev, n_points_dev,
+                     (const int32_t*)w.block_sums, L, point_cap, row_cap, nb_old, ids_out_dev, tid_out_dev, score_out_dev,
+                     state_out_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_op_track_select(const int32_t* ids_dev, const int32_t* tid_dev, const double* score_dev, const int32_t* state_dev,
+                        int max_length, int row_cap, int min_length, void* workspace_dev, double* tracks_dev,
+                        int32_t* n_tracks_dev, void* stream) {
+  CHK(track_check("track_select", max_length, 1, row_cap));
+  if (min_length < 0) return fail(-1, "track_select: min_length >= 0 required (0 = every row; got %d)", min_length);
+  if (!ids_dev || !tid_dev || !score_dev || !state_dev || !workspace_dev || !tracks_dev || !n_tracks_dev)
+    return fail(-1, "track_select: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const TrackWs w = track_carve(max_length, 1, row_cap, workspace_dev);
+  const int nb = cdiv(row_cap, TRACK_BLOCK);
+  hipLaunchKernelGGL(track_select_count_kernel, dim3(nb), dim3(TRACK_BLOCK), 0, st, ids_dev, state_dev, max_length, row_cap,
+                     min_length, w.block_sums);
+  hipLaunchKernelGGL(track_select_scatter_kernel, dim3(nb), dim3(TRACK_BLOCK), 0, st, ids_dev, tid_dev, score_dev, state_dev,
+                     (const int32_t*)w.block_sums, max_length, row_cap, min_length, tracks_dev, n_tracks_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_op_track_points(const double* tracks_dev, const int32_t* n_tracks_dev, const double* pts_dev, const int32_t* state_dev,
+                        int max_length, int point_cap, int track_cap, int first_slot, double* xy_dev, void* stream) {
+  CHK(track_check("track_points", max_length, point_cap, track_cap));
+  if (first_slot < 0 || first_slot >= max_length)
+    return fail(-1, "track_points: 0 <= first_slot < max_length required (got %d)", first_slot);
+  if (!tracks_dev || !n_tracks_dev || !pts_dev || !state_dev || !xy_dev) return fail(-1, "track_points: null pointer");
+  hipLaunchKernelGGL(track_points_kernel, dim3(cdiv((long)track_cap * max_length, 256)), dim3(256), 0, (hipStream_t)stream,
+                     tracks_dev, n_tracks_dev, pts_dev, state_dev, max_length, point_cap, track_cap, first_slot, xy_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -10,8 +10,9 @@ plus `HomoAdaptExporter`, the fused MI355X path the loop uses: one ssp_export_po
 accumulation, greedy NMS, soft-argmax refinement, top-k) with no host round trip before the final point list.
 
 The descriptor export (keypoints, sparse descriptors and two-way matches of image pairs):
-  PointTracker(max_length=2, nn_thresh).nn_match_two_way / update / get_matches / get_mscores / clear_desc
-                                                                     models/model_wrap.py:451-597
+  PointTracker(max_length, nn_thresh).nn_match_two_way / update / get_matches / get_mscores / clear_desc / get_tracks /
+  get_offsets (2 <= max_length <= 16; plus update_device / track_points)          models/model_wrap.py:426-615
+  SequenceTracker: forward -> points / descriptors -> match -> track update per frame, all on the device
   export_descriptor(config, output_dir, args)                        export.py:66-190
 with `Val_model_heatmap` (Val_model_heatmap.py) as the per-image front end and `DescriptorExporter`, the fused path the
 loop uses: ONE eval forward over the 2P images of P pairs, keypoints + sparse descriptors (ssp_describe_points) and the
@@ -228,26 +229,97 @@ def export_detector_homoAdapt_gpu(config, output_dir, args):
 
 
 class PointTracker(object):
-    """models/model_wrap.py:416-597 for two-frame tracks (max_length=2, as export_descriptor uses it): the two-way
-    nearest-neighbour matcher runs on the device (ssp_match_two_way).  Track bookkeeping beyond the last pair of frames
-    (get_tracks / draw_tracks) is not provided."""
+    """models/model_wrap.py:416-615 on the device for 2 <= max_length <= lib.TRACK_MAX_LENGTH: the two-way nearest-neighbour
+    matcher (ssp_match_two_way) and the track bookkeeping (ssp_op_track_update / _select / _points).
+    The table, the running track count, the last max_length point sets and the previous frame's descriptors stay in HBM;
+    `update` uploads one frame and reads the matches back (get_matches is a numpy contract), `update_device` takes device
+    tensors and synchronises with the host only to allocate.  Descriptors are 256-dimensional.  draw_tracks is not provided
+    (no drawing here): `track_points` returns the coordinates it would connect."""
 
     def __init__(self, max_length, nn_thresh, device=None):
         if max_length < 2:
             raise ValueError("max_length must be greater than or equal to 2.")
-        if max_length != 2:
-            raise NotImplementedError("PointTracker keeps the last two frames only (max_length=2)")
-        self.maxl = max_length
+        if max_length > L.TRACK_MAX_LENGTH:
+            raise ValueError("max_length must be at most %d (SSP_TRACK_MAX_LENGTH)." % L.TRACK_MAX_LENGTH)
+        self.maxl = int(max_length)
         self.nn_thresh = nn_thresh
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.all_pts = [np.zeros((2, 0)) for _ in range(self.maxl)]
         self.last_desc = None
-        self.track_count = 0
         self.max_score = 9999
         self.matches = None
         self.last_pts = None
         self.mscores = None
+        self._host_pts = [np.zeros((2, 0)) for _ in range(self.maxl)]  # None = only on the device (update_device)
+        self._frames = 0          # updates so far: frame f lives in ring slot f % maxl
+        self._cap = 0             # points per frame the device buffers hold
+        self._table = self._spare = None
+        self._pts = None          # float64 [maxl, cap, 2] ring of (x, y)
+        self._desc = None         # float32 [2, cap, 256]: the descriptors of frame f in slot f % 2
+        self._counts = None       # int32 [2]: their counts; a cleared / missing previous frame reads _zero instead
+        self._zero = None
+        self._prev_ok = False     # the previous frame's descriptors take part in the next match
+        self._pending = None      # device (match, n_match, had_prev) whose numpy form get_matches() has not been asked for yet
 
+    # ---- device buffers -------------------------------------------------------------------------------------------
+    def _ensure(self, n):
+        """Buffers for frames of at least n points (grown by copying: the table's rows keep their places)."""
+        if n <= self._cap:
+            return
+        if n > L.MATCH_MAX_POINTS:
+            raise ValueError("at most %d points per frame (got %d)" % (L.MATCH_MAX_POINTS, n))
+        cap = min(L.MATCH_MAX_POINTS, max(n, 2 * self._cap, 1024))
+        dev = self.device
+        table, spare = L.track_table(self.maxl, cap, dev), L.track_table(self.maxl, cap, dev)
+        pts = torch.zeros(self.maxl, cap, 2, dtype=torch.float64, device=dev)
+        desc = torch.zeros(2, cap, 256, dtype=torch.float32, device=dev)
+        counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        if self._cap:
+            rows = self._table["row_cap"]
+            for k in ("ids", "tid", "score"):
+                table[k][:rows] = self._table[k]
+            table["state"].copy_(self._table["state"])
+            pts[:, :self._cap] = self._pts
+            desc[:, :self._cap] = self._desc
+            counts.copy_(self._counts)
+        self._table, self._spare, self._pts, self._desc, self._counts, self._cap = table, spare, pts, desc, counts, cap
+        self._zero = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _slots(self):
+        """(ring slot of the newest frame, desc slot of the newest frame)."""
+        return (self._frames - 1) % self.maxl, (self._frames - 1) % 2
+
+    def _advance(self, xy, count, desc):
+        """The device half of an update: xy float64 [n, 2], count int32 [1], desc float32 [n, 256] device tensors (rows past
+        the count are ignored).  Returns the device (match, n_match) of the new frame against the previous one and whether
+        the previous frame's descriptors took part."""
+        n = xy.shape[0]
+        if n > L.MATCH_MAX_POINTS:  # a capacity, not a count: the matcher takes the first MATCH_MAX_POINTS rows at most
+            n = L.MATCH_MAX_POINTS
+            xy, desc, count = xy[:n], desc[:n], count.clamp(max=n)
+        self._ensure(max(n, 1))
+        self._frames += 1
+        slot, dslot = self._slots()
+        self._pts[slot, :n] = xy
+        self._desc[dslot, :n] = desc
+        self._counts[dslot:dslot + 1] = count
+        m, nm = self._match_device()
+        self._track_device(m, nm)
+        had_prev, self._prev_ok = self._prev_ok, True
+        return m, nm, had_prev
+
+    def _match_device(self):
+        _, dslot = self._slots()
+        prev = self._counts[1 - dslot:2 - dslot] if self._prev_ok else self._zero
+        m, nm = L.op_match_two_way(self._desc[1 - dslot:2 - dslot], prev, self._desc[dslot:dslot + 1],
+                                   self._counts[dslot:dslot + 1], self.nn_thresh)
+        return m[0], nm
+
+    def _track_device(self, m, nm):
+        _, dslot = self._slots()
+        out = L.op_track_update(self._table, m, nm, self._counts[dslot:dslot + 1], out=self._spare)
+        self._table, self._spare = out, self._table
+
+    # ---- the reference's interface --------------------------------------------------------------------------------
     def nn_match_two_way(self, desc1, desc2, nn_thresh):
         """desc1 [D,N1], desc2 [D,N2] unit columns -> float64 [3,L] (index in desc1, index in desc2, distance), rows of
         desc1 ascending.  Same checks and order as models/model_wrap.py:451-497 (an empty side returns before the
@@ -275,40 +347,182 @@ class PointTracker(object):
         self.mscores = matches
         return matches
 
+    @property
+    def all_pts(self):
+        """The last max_length point sets, oldest first (numpy; a frame given to update_device is read back as [2,N])."""
+        if any(p is None for p in self._host_pts):
+            counts = self._table["state"][2:].cpu().numpy()
+            first = self._frames % self.maxl  # ring slot of the oldest retained frame
+            for c, p in enumerate(self._host_pts):
+                if p is None:
+                    self._host_pts[c] = self._pts[(first + c) % self.maxl, :int(counts[c])].cpu().numpy().T.copy()
+        return self._host_pts
+
+    @property
+    def table(self):
+        """The device track table (the dict of lib.track_table; None before the first frame).  Read it, e.g. with
+        lib.op_track_select or as the input of lib.op_track_update with another `out`; the tracker owns its arrays."""
+        return self._table
+
+    @property
+    def track_count(self):
+        return int(self._table["state"][1].item()) if self._table is not None else 0
+
+    @property
+    def tracks(self):
+        """The whole table as the reference keeps it: float64 [M, 2 + max_length] (track id, mean score, point ids)."""
+        if self._table is None:
+            return np.zeros((0, self.maxl + 2))
+        return L.tracks_to_numpy(*L.op_track_select(self._table, 0))
+
+    def get_offsets(self):
+        """models/model_wrap.py:496-510: the id of point 0 of every retained frame."""
+        return np.cumsum(np.array([0] + [p.shape[1] for p in self.all_pts[:-1]]))
+
+    def _materialize(self):
+        if self._pending is None:
+            return
+        (m, nm, had_prev), self._pending = self._pending, None
+        matches = _matches_to_numpy(m, int(nm.item()))
+        pts = self.all_pts
+        if had_prev and pts[-2].shape[1] and pts[-1].shape[1]:
+            self.mscores = matches   # (an empty side returns before the reference stores them)
+        self.matches = matches
+        if self._frames > 1:
+            self.matches = np.concatenate((pts[-2][:2, matches[0].astype(int)], pts[-1][:2, matches[1].astype(int)]), axis=0)
+
     def get_matches(self):
+        self._materialize()
         return self.matches
 
     def get_mscores(self):
+        self._materialize()
         return self.mscores
 
     def clear_desc(self):
         self.last_desc = None
+        self._prev_ok = False
 
     def update(self, pts, desc):
-        """pts [3,N] points, desc [D,N] descriptors of the next frame.  After it, get_matches() is [4,L]
-        (x0, y0, x1, y1) of the mutual matches with the previous frame (models/model_wrap.py:521-597)."""
+        """pts [3,N] points, desc [256,N] descriptors of the next frame (numpy).  After it, get_matches() is [4,K]
+        (x0, y0, x1, y1) of the mutual matches with the previous frame and get_tracks() follows them over the last
+        max_length frames (models/model_wrap.py:521-597)."""
         if pts is None or desc is None:
             print("PointTracker: Warning, no points were added to tracker.")
             return
         assert pts.shape[1] == desc.shape[1]
-        if self.last_desc is None:
-            self.last_desc = np.zeros((desc.shape[0], 0))
-        self.all_pts.pop(0)
-        self.all_pts.append(pts)
-        matches = self.nn_match_two_way(self.last_desc, desc, self.nn_thresh)
-        self.matches = matches
-        if self.last_pts is not None:
-            id1 = self.last_pts[:, matches[0, :].astype(int)]
-            id2 = pts[:2, :][:, matches[1, :].astype(int)]
-            self.matches = np.concatenate((id1, id2), axis=0)
+        n = pts.shape[1]
+        if self.nn_thresh < 0.0 and n and self._prev_ok and self.all_pts[-1].shape[1]:
+            raise ValueError("'nn_thresh' should be non-negative")
+        if n and desc.shape[0] != 256:
+            raise ValueError("the device matcher takes 256-dimensional descriptors")
+        if n > L.MATCH_MAX_POINTS:
+            raise ValueError("at most %d descriptors per side (got %d)" % (L.MATCH_MAX_POINTS, n))
+        self._materialize()
+        dev = self.device
+        xy = torch.from_numpy(np.ascontiguousarray(pts[:2].T, dtype=np.float64)).to(dev)
+        d = torch.from_numpy(np.ascontiguousarray(desc.T, dtype=np.float32)).to(dev).reshape(n, 256)
+        self._host_pts = self.all_pts[1:] + [pts]
+        self._pending = self._advance(xy, torch.tensor([n], dtype=torch.int32, device=dev), d)
+        self._materialize()
         self.last_desc = desc.copy()
         self.last_pts = pts[:2, :].copy()
 
+    def update_device(self, pts, count, desc):
+        """The same update from device tensors, e.g. one image's slice of Engine.describe_points: pts [cap, >= 2] rows
+        starting (x, y), count int32 [1] (or 0-d), desc float32 [cap, 256] unit rows.  Matching and the track update are
+        queued on the current stream; nothing is copied to the host and the host is not synchronised (the first call, and a
+        call with a larger cap than any before, allocate).  A cap above lib.MATCH_MAX_POINTS is cut to that many rows (and the
+        count with it).  get_matches / get_mscores / all_pts read back on demand and describe the NEWEST frame: matches of
+        earlier frames that were never asked for are dropped, so get_mscores() is the last non-empty match set among the
+        frames it was asked about, not among all frames as after `update`."""
+        for t, nm in ((pts, "pts"), (count, "count"), (desc, "desc")):
+            if not t.is_cuda:
+                raise RuntimeError("%s must live on a HIP device: the MI355X path has no CPU fallback" % nm)
+        if pts.dim() != 2 or pts.shape[1] < 2 or desc.shape != (pts.shape[0], 256) or count.dtype != torch.int32:
+            raise ValueError("pts [cap, >= 2], desc [cap, 256] and an int32 count are required")
+        if self.nn_thresh < 0.0:
+            raise ValueError("'nn_thresh' should be non-negative")
+        self._pending = None  # the previous frame's matches were not asked for: they are dropped, not read back
+        self._host_pts = self._host_pts[1:] + [None]
+        self._pending = self._advance(pts[:, :2].to(torch.float64), count.reshape(1), desc)
+        self.last_desc = self.last_pts = None  # (host copies exist for frames given to update only)
+
+    def get_tracks_device(self, min_length):
+        """get_tracks on the device: (tracks float64 [row_cap, 2 + max_length], n_tracks int32 [1]); no synchronisation."""
+        if min_length < 1:
+            raise ValueError("'min_length' too small.")
+        if self._table is None:
+            raise RuntimeError("no frame yet")
+        return L.op_track_select(self._table, int(min_length))
+
     def get_tracks(self, min_length):
-        raise NotImplementedError("PointTracker keeps no tracks here: use get_matches() after the second update")
+        """models/model_wrap.py:599-615: float64 [M, 2 + max_length] rows (track id, mean score, point ids) of the tracks
+        with at least min_length points and a point in the newest frame."""
+        if min_length < 1:
+            raise ValueError("'min_length' too small.")
+        if self._table is None:
+            return np.zeros((0, self.maxl + 2))
+        return L.tracks_to_numpy(*L.op_track_select(self._table, int(min_length)))
+
+    def track_points_device(self, tracks, n_tracks):
+        """Device (tracks, n_tracks) as get_tracks_device returns them -> float64 [row_cap, max_length, 2] coordinates in
+        the retained frames (NaN where a track has no point); no synchronisation."""
+        return L.op_track_points(tracks, n_tracks, self._pts, self._table["state"], self._frames % self.maxl)
+
+    def track_points(self, tracks):
+        """The coordinates a tracks matrix (get_tracks) names: float64 [M, max_length, 2], NaN where the id is -1.  This is
+        the read-out draw_tracks would connect with lines (models/model_wrap.py:617-648)."""
+        tracks = np.ascontiguousarray(tracks, dtype=np.float64)
+        if tracks.shape[0] == 0 or self._table is None:
+            return np.zeros((tracks.shape[0], self.maxl, 2))
+        t = torch.from_numpy(tracks).to(self.device)
+        n = torch.tensor([tracks.shape[0]], dtype=torch.int32, device=self.device)
+        return self.track_points_device(t, n).cpu().numpy()
 
     def draw_tracks(self, out, tracks):
-        raise NotImplementedError("PointTracker keeps no tracks here: use get_matches() after the second update")
+        raise NotImplementedError("PointTracker draws nothing here: track_points(tracks) returns the [M, max_length, 2] "
+                                  "coordinates of the tracks (NaN where a track has no point) for the caller's own drawing")
+
+
+class SequenceTracker:
+    """Point tracks over an image sequence on one GPU: per frame one eval forward, keypoints + sparse descriptors
+    (ssp_describe_points), the two-way matcher against the previous frame and the track update, all on the device with no
+    host copy of points, descriptors or matches.  `net` is one of this package's model drop-ins; the vocabulary is
+    DescriptorExporter's.  Read the result with get_tracks / track_points (or `tracker`, the PointTracker)."""
+
+    def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4):
+        if nn_thresh < 0.0:
+            raise ValueError("'nn_thresh' should be non-negative")
+        self.net, self.device = net, torch.device(device)
+        self.conf_thresh, self.nms_dist, self.subpixel = conf_thresh, nms_dist, bool(subpixel)
+        self.border_remove = border_remove
+        self.tracker = PointTracker(max_length, nn_thresh, self.device)
+
+    def describe(self, image):
+        """image [H,W] / [1,H,W] / [1,1,H,W] -> the device tensors of Engine.describe_points for this one image."""
+        x = _image_2d(image).to(self.device, torch.float32)[None, None].contiguous()
+        eng = self.net.engine(1, x.shape[2], x.shape[3], self.device)
+        with torch.no_grad():
+            eng.forward(x, slot=0, train=False, want=())
+        return eng.describe_points(0, 1, conf_thresh=self.conf_thresh, nms_dist=self.nms_dist, subpixel=self.subpixel,
+                                   border_remove=self.border_remove)
+
+    def step(self, image):
+        """The next frame: forward -> points / descriptors -> PointTracker.update_device.  Returns describe()'s tensors."""
+        o = self.describe(image)
+        pts = o["pts"][0]
+        xy = pts[:, :2].to(torch.float64)
+        if self.subpixel:  # the same float64 sum as lib.points_to_numpy
+            xy = xy + pts[:, 3:5].to(torch.float64) - 2
+        self.tracker.update_device(xy, o["count"][0:1], o["desc"][0])
+        return o
+
+    def get_tracks(self, min_length):
+        return self.tracker.get_tracks(min_length)
+
+    def track_points(self, tracks):
+        return self.tracker.track_points(tracks)
 
 
 def _matches_to_numpy(m, n):

@@ -120,9 +120,12 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_eval_repeatability", "ssp_eval_ransac_workspace_bytes", "ssp_eval_ransac",
            "ssp_op_photometric_draw", "ssp_op_photometric_apply",
            "ssp_shapes_workspace_bytes", "ssp_op_shapes_draw", "ssp_op_shapes_render", "ssp_op_warp_points_scatter",
-           "ssp_op_sem_predict", "ssp_sem_predict"]
+           "ssp_op_sem_predict", "ssp_sem_predict",
+           "ssp_track_workspace_bytes", "ssp_op_track_update", "ssp_op_track_select", "ssp_op_track_points"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
+TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
+TRACK_NO_SCORE = 9999.0  # score of a track that has no match yet (PointTracker.max_score)
 
 
 def load_library(path=None):
@@ -279,6 +282,15 @@ def load_library(path=None):
         lib.ssp_eval_ransac_workspace_bytes.argtypes = [i, i]
         lib.ssp_eval_ransac_workspace_bytes.restype = C.c_size_t
         lib.ssp_eval_ransac.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_track_workspace_bytes.argtypes = [i, i, i]
+        lib.ssp_track_workspace_bytes.restype = C.c_size_t
+        lib.ssp_op_track_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp]
+        lib.ssp_op_track_select.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]
+        lib.ssp_op_track_points.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -1317,6 +1329,109 @@ def op_match_two_way(desc1, count1, desc2, count2, nn_thresh, pair_stride=1, n_p
         _check(lib.ssp_match_two_way(_ptr(desc1), _ptr(count1), _ptr(desc2), _ptr(count2), cap, P, int(pair_stride),
                                      float(np.float32(nn_thresh)), _ptr(ws), _ptr(match), _ptr(n_match), _stream()))
     return match, n_match
+
+
+# ---- point tracks over a frame sequence (PointTracker.update / get_tracks) ----
+def track_table(max_length, point_cap, device):
+    """An empty device track table for frames of at most point_cap points: {"ids": int32 [row_cap,L], "tid": int32 [row_cap],
+    "score": float64 [row_cap], "state": int32 [2+L] = n_rows, track_count, point counts of the L retained frames} plus the
+    host-known sizes "L", "point_cap", "row_cap" = L * point_cap and a "ws" workspace shared by the table's successors."""
+    lib = load_library()
+    L, point_cap = int(max_length), int(point_cap)
+    if not 2 <= L <= TRACK_MAX_LENGTH:
+        raise ValueError("2 <= max_length <= %d required (got %d)" % (TRACK_MAX_LENGTH, L))
+    if not 1 <= point_cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= point_cap <= %d points per frame (got %d)" % (MATCH_MAX_POINTS, point_cap))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("track_table needs a HIP device: the MI355X path has no CPU fallback")
+    row_cap = L * point_cap
+    wsb = lib.ssp_track_workspace_bytes(L, point_cap, row_cap)
+    if wsb == 0:
+        _check(-1)
+    t = _track_arrays(L, row_cap, device)
+    t["state"].zero_()
+    t.update(L=L, point_cap=point_cap, row_cap=row_cap, ws=torch.empty(wsb, dtype=torch.uint8, device=device))
+    return t
+
+
+def _track_arrays(L, row_cap, device):
+    return {"ids": torch.empty(row_cap, L, dtype=torch.int32, device=device),
+            "tid": torch.empty(row_cap, dtype=torch.int32, device=device),
+            "score": torch.empty(row_cap, dtype=torch.float64, device=device),
+            "state": torch.empty(2 + L, dtype=torch.int32, device=device)}
+
+
+def op_track_update(table, match, n_match, n_points, match_score64=None, out=None):
+    """One PointTracker.update on the device (ssp_op_track_update).  table: a track_table() or the result of an earlier call;
+    match: float32 [>= point_cap rows, 3] (i, j, distance) with n_match int32 [1] rows, as op_match_two_way returns them for
+    (previous frame, new frame); n_points: int32 [1] points of the new frame; match_score64: optional float64 [point_cap]
+    distances used instead of column 2.  Returns the updated table in `out` (another table of the same sizes, default: new
+    arrays); the input table is left as it was.  No host synchronisation."""
+    lib = load_library()
+    L, point_cap, row_cap = table["L"], table["point_cap"], table["row_cap"]
+    for t, nm in ((match, "match"), (n_match, "n_match"), (n_points, "n_points")):
+        _need_gpu(t, nm)
+    if match.dtype != torch.float32 or match.dim() != 2 or match.shape[1] != 3 or match.shape[0] < point_cap:
+        raise ValueError("match must be float32 [>= %d, 3] rows (i, j, distance)" % point_cap)
+    if n_match.dtype != torch.int32 or n_points.dtype != torch.int32:
+        raise ValueError("n_match and n_points must be int32 device scalars")
+    if match_score64 is not None:
+        _need_gpu(match_score64, "match_score64")
+        if match_score64.dtype != torch.float64 or match_score64.numel() < point_cap:
+            raise ValueError("match_score64 must be float64 [>= %d]" % point_cap)
+    dev = table["ids"].device
+    if out is None:
+        out = _track_arrays(L, row_cap, dev)
+    elif out["ids"].shape != table["ids"].shape or out["ids"].data_ptr() == table["ids"].data_ptr():
+        raise ValueError("out must be another table of the same sizes")
+    out.update(L=L, point_cap=point_cap, row_cap=row_cap, ws=table["ws"])
+    with torch.cuda.device(dev):
+        _check(lib.ssp_op_track_update(_ptr(table["ids"]), _ptr(table["tid"]), _ptr(table["score"]), _ptr(table["state"]),
+                                       _ptr(match), _ptr(match_score64), _ptr(n_match), _ptr(n_points), L, point_cap, row_cap,
+                                       _ptr(table["ws"]), _ptr(out["ids"]), _ptr(out["tid"]), _ptr(out["score"]),
+                                       _ptr(out["state"]), _stream()))
+    return out
+
+
+def op_track_select(table, min_length):
+    """get_tracks(min_length) on the device (ssp_op_track_select): (tracks float64 [row_cap, 2+L] rows (track id, score, ids),
+    n_tracks int32 [1]) as device tensors; min_length = 0 returns every row of the table."""
+    lib = load_library()
+    L, row_cap = table["L"], table["row_cap"]
+    dev = table["ids"].device
+    tracks = torch.empty(row_cap, 2 + L, dtype=torch.float64, device=dev)
+    n = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.ssp_op_track_select(_ptr(table["ids"]), _ptr(table["tid"]), _ptr(table["score"]), _ptr(table["state"]), L,
+                                       row_cap, int(min_length), _ptr(table["ws"]), _ptr(tracks), _ptr(n), _stream()))
+    return tracks, n
+
+
+def tracks_to_numpy(tracks, n_tracks):
+    """Device (tracks, n_tracks) of op_track_select -> the reference's float64 [M, 2+L] matrix (one host synchronisation)."""
+    return tracks[:int(n_tracks.item())].cpu().numpy()
+
+
+def op_track_points(tracks, n_tracks, pts, state, first_slot=0):
+    """Coordinates of the points a tracks matrix names (ssp_op_track_points).  tracks: float64 [track_cap, 2+L] with n_tracks
+    int32 [1] rows; pts: float64 [L, point_cap, 2] (x, y), retained frame c in slot (first_slot + c) % L; state: the table's
+    state vector.  Returns float64 [track_cap, L, 2], NaN where the id is -1 (rows >= n_tracks are undefined)."""
+    lib = load_library()
+    for t, nm in ((tracks, "tracks"), (n_tracks, "n_tracks"), (pts, "pts"), (state, "state")):
+        _need_gpu(t, nm)
+    L = tracks.shape[1] - 2
+    if tracks.dtype != torch.float64 or pts.dtype != torch.float64 or pts.dim() != 3 or pts.shape[0] != L or pts.shape[2] != 2:
+        raise ValueError("tracks must be float64 [M, 2+L] and pts float64 [L, point_cap, 2]")
+    if state.dtype != torch.int32 or state.numel() != 2 + L or n_tracks.dtype != torch.int32:
+        raise ValueError("state must be int32 [2+L] and n_tracks an int32 device scalar")
+    xy = torch.empty(tracks.shape[0], L, 2, dtype=torch.float64, device=tracks.device)
+    if tracks.shape[0] == 0:
+        return xy
+    with torch.cuda.device(tracks.device):
+        _check(lib.ssp_op_track_points(_ptr(tracks), _ptr(n_tracks), _ptr(pts), _ptr(state), L, pts.shape[1], tracks.shape[0],
+                                       int(first_slot), _ptr(xy), _stream()))
+    return xy
 
 
 def _eval_points(pts, counts, name):
