@@ -486,6 +486,44 @@ int ssp_match_two_way(const float* desc1_dev, const int32_t* count1_dev, const f
                       int cap, int n_pairs, int pair_stride, float nn_thresh, void* workspace_dev, float* match_dev,
                       int32_t* n_match_dev, void* stream);
 
+/* ---- semantic keypoints: classes at points, class filter, class-aware matching -------------
+ * ssp_op_point_classes: the class of each keypoint without the class map.  sout_nhwc_dev, cs, b, h, w, n_classes: the map
+ *   of ssp_op_sem_predict under the same contract (cs >= n_classes, the padding channels are never read), with
+ *   1 <= n_classes <= 255 here.  pts_dev [b][cap][pts_stride] float rows whose first two floats are the integer pixel
+ *   (x, y), as ssp_describe_points writes them (pts_stride 5); count_dev [b] (clamped to cap).  cls_dev [b][cap] uint8:
+ *   row r < count gets exactly the class ssp_op_sem_predict gives pixel (y, x) of its image (the x8 align_corners=False
+ *   upsample, the same fp32 operations in the same order, the lowest class on ties); rows >= count get SSP_CLASS_NONE.
+ *   A point outside [0, w) x [0, h) is a caller error and is clamped into the image.
+ * ssp_point_classes: the same on the logits the last forward / pair step left in `slot`, for its first n images (like
+ *   ssp_sem_predict).  Returns -1 without a segmentation head or without a forward that computed it.
+ * ssp_op_filter_points: stable per-image compaction of a point set by class.  pts_dev [n][cap][5], count_dev [n],
+ *   desc_dev [n][cap][256] (16-byte aligned), cls_dev [n][cap]; keep_mask: 256 bits on the HOST, bit c of word c / 32 set =
+ *   rows of class c are kept.  The rows r < count whose class is kept go, in their order (so the descending confidence of
+ *   ssp_describe_points survives), to pts_out_dev / desc_out_dev / cls_out_dev, their number to count_out_dev [n].
+ *   cls_out rows past the new count are SSP_CLASS_NONE, the other rows past it are unspecified.  Never in place.  The
+ *   result is a prefix scan, not an atomic ticket: bit-identical from run to run in every mode.
+ *   workspace_dev: ssp_filter_workspace_bytes(n, cap) bytes (0 = bad arguments).
+ * ssp_match_two_way_classes: ssp_match_two_way with classes cls1_dev, cls2_dev [n_pairs*pair_stride][cap] beside the
+ *   descriptors.  A pair (i, j) with cls1[i] != cls2[j] is no candidate: it takes part in neither the row nor the column
+ *   arg-min, and a row or column without a candidate has no match.  Distances, the nn_thresh test, the mutual test, the
+ *   tie rule, the order of the output, the limits and the workspace are those of ssp_match_two_way; with all classes equal
+ *   the output is bit-identical to it.
+ * All of them check their arguments before anything is launched (-1, ssp_last_error), take the caller's stream, can be
+ * captured into a graph and never synchronise with the host. */
+#define SSP_CLASS_NONE 255
+int ssp_op_point_classes(const float* sout_nhwc_dev, int cs, int b, int h, int w, int n_classes, const float* pts_dev,
+                         int pts_stride, const int32_t* count_dev, int cap, uint8_t* cls_dev, void* stream);
+int ssp_point_classes(ssp_handle* h, int slot, int n, const float* pts_dev, int pts_stride, const int32_t* count_dev, int cap,
+                      uint8_t* cls_dev, void* stream);
+size_t ssp_filter_workspace_bytes(int n, int cap);
+int ssp_op_filter_points(const float* pts_dev, const int32_t* count_dev, const float* desc_dev, const uint8_t* cls_dev,
+                         const uint32_t keep_mask[8], int n, int cap, float* pts_out_dev, int32_t* count_out_dev,
+                         float* desc_out_dev, uint8_t* cls_out_dev, void* workspace_dev, void* stream);
+int ssp_match_two_way_classes(const float* desc1_dev, const int32_t* count1_dev, const float* desc2_dev,
+                              const int32_t* count2_dev, const uint8_t* cls1_dev, const uint8_t* cls2_dev, int cap, int n_pairs,
+                              int pair_stride, float nn_thresh, void* workspace_dev, float* match_dev, int32_t* n_match_dev,
+                              void* stream);
+
 /* ---- evaluation of descriptor exports (evaluation.py:86-500 with -r -homo) ---------------------------------------
  * Points are fp64 rows (x, y, confidence) [n_pairs*pair_stride][cap][3] with int32 counts [n_pairs*pair_stride]; pair p
  * uses entry p*pair_stride of each (pair_stride = 2 matches the interleaved image / warped image of the exporter).

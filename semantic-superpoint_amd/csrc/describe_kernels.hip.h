@@ -73,11 +73,15 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int o) {
 // Pair p: descriptors d1[p*pair_stride][cap][256] (n1 = count1[p*pair_stride] rows), d2 likewise.  rowmin: [P][cap] keys
 // of each d1 row's nearest d2 column, colmin: [P][cap] the reverse; both start at ~0.
 // MFMA operands: lane (r = l & 31, h = l >> 5) loads 4 consecutive k of row r at 8s + 4h and feeds component c as k-pair
-// (8s + c, 8s + 4 + c) -- the same permutation of K on both sides, so each dot product still runs over all 256 channels.
+// CLASSES (ssp_match_two_way_classes): cls1, cls2 [.][cap] uint8 beside the descriptors; a pair (i, j)
+// with cls1[i] != cls2[j] is no candidate of either arg-min.  A row or column without a candidate keeps its ~0 key, which
+// match_compact_kernel never keeps (its distance bits are a NaN, its index is >= n2).  CLASSES = false reads neither pointer.
+template <bool CLASSES>
 __global__ __launch_bounds__(256) void match_dist_kernel(const float* __restrict__ d1, const int32_t* __restrict__ count1,
                                                          const float* __restrict__ d2, const int32_t* __restrict__ count2,
                                                          int cap, int pair_stride, uint64_t* __restrict__ rowmin,
-                                                         uint64_t* __restrict__ colmin) {
+                                                         uint64_t* __restrict__ colmin, const uint8_t* __restrict__ cls1,
+                                                         const uint8_t* __restrict__ cls2) {
   const int p = blockIdx.z, ps = p * pair_stride;
   const int n1 = min(count1[ps], cap), n2 = min(count2[ps], cap);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
@@ -85,6 +89,12 @@ __global__ __launch_bounds__(256) void match_dist_kernel(const float* __restrict
   if (wi >= n1 || wj >= n2) return;  // (whole waves; no block barrier below)
   const float4* A = reinterpret_cast<const float4*>(d1 + ((size_t)ps * cap + min(wi + r, n1 - 1)) * 256) + h;
   const float4* B = reinterpret_cast<const float4*>(d2 + ((size_t)ps * cap + min(wj + r, n2 - 1)) * 256) + h;
+  // the classes of the wave's 32 rows (lane l: row wi + (l & 31)) and of this lane's column, loaded ahead of the MFMA loop
+  int ci_rows = 0, cj = 0;
+  if (CLASSES) {
+    ci_rows = cls1[(size_t)ps * cap + min(wi + r, n1 - 1)];
+    cj = cls2[(size_t)ps * cap + min(wj + r, n2 - 1)];
+  }
   typedef float floatx16 __attribute__((ext_vector_type(16)));
   floatx16 acc;
 #pragma unroll
@@ -103,7 +113,12 @@ __global__ __launch_bounds__(256) void match_dist_kernel(const float* __restrict
 #pragma unroll
   for (int t = 0; t < 16; ++t) {
     const int i = wi + (t & 3) + 8 * (t >> 2) + 4 * h;
-    const bool ok = i < n1 && j < n2;
+    bool ok = i < n1 && j < n2;
+    if (CLASSES) {  // row (t & 3) + 8 (t >> 2) + 4h of the wave: two wave-uniform lane reads, chosen by h
+      const int c0 = __builtin_amdgcn_readlane(ci_rows, (t & 3) + 8 * (t >> 2));
+      const int c1 = __builtin_amdgcn_readlane(ci_rows, (t & 3) + 8 * (t >> 2) + 4);
+      ok = ok && (h ? c1 : c0) == cj;
+    }
     // np.sqrt(2 - 2 * np.clip(dmat, -1, 1)) in fp32: 2 * clip is exact, one rounding for the difference, one for sqrt
     const float dd = __fsqrt_rn(2.f - 2.f * fminf(fmaxf(acc[t], -1.f), 1.f));
     const uint64_t hi = (uint64_t)__float_as_uint(dd) << 32;

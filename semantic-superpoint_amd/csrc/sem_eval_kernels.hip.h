@@ -29,6 +29,12 @@ constexpr int SEMP_MIN_TILES = 4;     // tiles per wave at least: the pending li
 //   * a wave walks tiles_per_wave consecutive tiles and keeps up to 64 pending (key, count) pairs, one per lane; a key that is
 //     already pending only adds to its lane's count.  The pairs go out as ONE atomic instruction at the end of the walk.  A tile key
 //     that finds the list full goes out at once from its leading lane (uniformly random labels: still exact, only slower).
+// The value of one class at one pixel: four products of exact weights and three sums on the raw fp32 logits, innermost first
+// (shared with point_class_kernel, point_class_kernels.hip.h: both must give a pixel the same bits).
+__device__ __forceinline__ float semp_interp(float w00, float w01, float w10, float w11, float a, float b, float c, float d) {
+  return fmaf(w00, a, fmaf(w01, b, fmaf(w10, c, w11 * d)));
+}
+
 // VEC4: cs % 4 == 0 and a 16-byte aligned map - four classes per wave-uniform 16-byte load.
 template <bool VEC4>
 __global__ __launch_bounds__(256) void sem_predict_kernel(const float* __restrict__ sout, const int64_t* __restrict__ labels,
@@ -56,7 +62,7 @@ __global__ __launch_bounds__(256) void sem_predict_kernel(const float* __restric
     int idx = 0;
 #define SEMP_CLASS(CI, A, B_, C_, D)                                      \
     {                                                                     \
-      const float l = fmaf(w00, A, fmaf(w01, B_, fmaf(w10, C_, w11 * D))); \
+      const float l = semp_interp(w00, w01, w10, w11, A, B_, C_, D);       \
       if (l > best) { best = l; idx = (CI); }                             \
     }
     int c = 0;

@@ -36,6 +36,7 @@
 #include "eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
+#include "point_class_kernels.hip.h"
 #include "backward_tail.hip.h"
 
 using namespace sspk;
@@ -3491,22 +3492,109 @@ size_t ssp_match_workspace_bytes(int cap, int n_pairs) {
   return align_up((size_t)2 * n_pairs * cap * sizeof(uint64_t), 256);
 }
 
-int ssp_match_two_way(const float* desc1_dev, const int32_t* count1_dev, const float* desc2_dev, const int32_t* count2_dev,
-                      int cap, int n_pairs, int pair_stride, float nn_thresh, void* workspace_dev, float* match_dev,
-                      int32_t* n_match_dev, void* stream) {
+// cls1_dev == NULL: the plain matcher (match_dist_kernel<false>)
+static int match_two_way_impl(const char* what, const float* desc1_dev, const int32_t* count1_dev, const float* desc2_dev,
+                              const int32_t* count2_dev, const uint8_t* cls1_dev, const uint8_t* cls2_dev, int cap, int n_pairs,
+                              int pair_stride, float nn_thresh, void* workspace_dev, float* match_dev, int32_t* n_match_dev,
+                              void* stream) {
   CHK(match_check(cap, n_pairs, pair_stride));
-  if (!(nn_thresh >= 0.f)) return fail(-1, "match_two_way: nn_thresh must be non-negative");
+  if (!(nn_thresh >= 0.f)) return fail(-1, "%s: nn_thresh must be non-negative", what);
   if (!desc1_dev || !count1_dev || !desc2_dev || !count2_dev || !workspace_dev || !match_dev || !n_match_dev)
-    return fail(-1, "match_two_way: null pointer");
+    return fail(-1, "%s: null pointer", what);
   hipStream_t st = (hipStream_t)stream;
   uint64_t* rowmin = reinterpret_cast<uint64_t*>(workspace_dev);
   uint64_t* colmin = rowmin + (size_t)n_pairs * cap;
   HIPCHK(hipMemsetAsync(rowmin, 0xFF, (size_t)2 * n_pairs * cap * sizeof(uint64_t), st));
   const int t = cdiv(cap, MATCH_TILE);
-  hipLaunchKernelGGL(match_dist_kernel, dim3(t, t, n_pairs), dim3(256), 0, st, desc1_dev, count1_dev, desc2_dev, count2_dev,
-                     cap, pair_stride, rowmin, colmin);
+  if (cls1_dev != nullptr)
+    hipLaunchKernelGGL(match_dist_kernel<true>, dim3(t, t, n_pairs), dim3(256), 0, st, desc1_dev, count1_dev, desc2_dev,
+                       count2_dev, cap, pair_stride, rowmin, colmin, cls1_dev, cls2_dev);
+  else
+    hipLaunchKernelGGL(match_dist_kernel<false>, dim3(t, t, n_pairs), dim3(256), 0, st, desc1_dev, count1_dev, desc2_dev,
+                       count2_dev, cap, pair_stride, rowmin, colmin, (const uint8_t*)nullptr, (const uint8_t*)nullptr);
   hipLaunchKernelGGL(match_compact_kernel, dim3(n_pairs), dim3(1024), 0, st, (const uint64_t*)rowmin, (const uint64_t*)colmin,
                      count1_dev, count2_dev, cap, pair_stride, nn_thresh, match_dev, n_match_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_match_two_way(const float* desc1_dev, const int32_t* count1_dev, const float* desc2_dev, const int32_t* count2_dev,
+                      int cap, int n_pairs, int pair_stride, float nn_thresh, void* workspace_dev, float* match_dev,
+                      int32_t* n_match_dev, void* stream) {
+  return match_two_way_impl("match_two_way", desc1_dev, count1_dev, desc2_dev, count2_dev, nullptr, nullptr, cap, n_pairs,
+                            pair_stride, nn_thresh, workspace_dev, match_dev, n_match_dev, stream);
+}
+
+int ssp_match_two_way_classes(const float* desc1_dev, const int32_t* count1_dev, const float* desc2_dev,
+                              const int32_t* count2_dev, const uint8_t* cls1_dev, const uint8_t* cls2_dev, int cap, int n_pairs,
+                              int pair_stride, float nn_thresh, void* workspace_dev, float* match_dev, int32_t* n_match_dev,
+                              void* stream) {
+  if (!cls1_dev || !cls2_dev) return fail(-1, "match_two_way_classes: null class pointer");
+  return match_two_way_impl("match_two_way_classes", desc1_dev, count1_dev, desc2_dev, count2_dev, cls1_dev, cls2_dev, cap,
+                            n_pairs, pair_stride, nn_thresh, workspace_dev, match_dev, n_match_dev, stream);
+}
+
+// ---- semantic keypoints: classes at points, class filter ----
+int ssp_op_point_classes(const float* sout_nhwc_dev, int cs, int b, int hh, int w, int n_classes, const float* pts_dev,
+                         int pts_stride, const int32_t* count_dev, int cap, uint8_t* cls_dev, void* stream) {
+  if (!sout_nhwc_dev || !pts_dev || !count_dev || !cls_dev) return fail(-1, "point_classes: null pointer");
+  if (b < 1 || b > 65535 || hh < 8 || w < 8 || hh % 8 || w % 8)
+    return fail(-1, "point_classes: 1 <= b <= 65535 and H, W multiples of 8 required (got %d of %dx%d)", b, hh, w);
+  if (n_classes < 1 || n_classes > SSP_CLASS_NONE || cs < n_classes)
+    return fail(-1, "point_classes: 1 <= n_classes <= %d and channel stride >= n_classes required (got %d, stride %d)",
+                SSP_CLASS_NONE, n_classes, cs);
+  if (cap < 1 || cap > (1 << 24) || pts_stride < 2)
+    return fail(-1, "point_classes: 1 <= cap <= 2^24 rows of at least 2 floats required (cap %d, stride %d)", cap, pts_stride);
+  if ((size_t)b * (hh / 8) * (w / 8) * cs > ((size_t)1 << 40)) return fail(-1, "point_classes: shape too large");
+  hipLaunchKernelGGL(point_class_kernel, dim3(cdiv(cap, 4), b), dim3(256), 0, (hipStream_t)stream, sout_nhwc_dev, pts_dev,
+                     count_dev, cls_dev, hh / 8, w / 8, n_classes, cs, cap, pts_stride);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_point_classes(ssp_handle* h, int slot, int n, const float* pts_dev, int pts_stride, const int32_t* count_dev, int cap,
+                      uint8_t* cls_dev, void* stream) {
+  if (!h || !h->bound) return fail(-1, "handle not bound");
+  if (h->nheads != 3) return fail(-1, "point_classes: the model has no segmentation head");
+  if (slot < 0 || slot > 1) return fail(-1, "point_classes: slot must be 0 or 1");
+  Slot& S = h->slot[slot];
+  if (S.N <= 0 || !S.has_desc) return fail(-1, "point_classes: slot %d holds no forward with segmentation logits", slot);
+  if (n < 1 || n > S.N) return fail(-1, "point_classes: %d images asked of a forward over %d", n, S.N);
+  return ssp_op_point_classes(S.Y[L_SOUT], h->sout_cs, n, S.H, S.W, h->cfg.n_classes, pts_dev, pts_stride, count_dev, cap,
+                              cls_dev, stream);
+}
+
+static int filter_check(int n, int cap) {
+  if (n < 1 || n > 65535 || cap < 1 || cap > (1 << 24))
+    return fail(-1, "filter_points: 1 <= n <= 65535 images of 1 <= cap <= 2^24 rows required (got %d of %d)", n, cap);
+  return 0;
+}
+
+size_t ssp_filter_workspace_bytes(int n, int cap) {
+  if (filter_check(n, cap)) return 0;
+  return align_up((size_t)n * cdiv(cap, TRACK_BLOCK) * sizeof(int32_t), 256);
+}
+
+int ssp_op_filter_points(const float* pts_dev, const int32_t* count_dev, const float* desc_dev, const uint8_t* cls_dev,
+                         const uint32_t keep_mask[8], int n, int cap, float* pts_out_dev, int32_t* count_out_dev,
+                         float* desc_out_dev, uint8_t* cls_out_dev, void* workspace_dev, void* stream) {
+  CHK(filter_check(n, cap));
+  if (!pts_dev || !count_dev || !desc_dev || !cls_dev || !keep_mask || !pts_out_dev || !count_out_dev || !desc_out_dev ||
+      !cls_out_dev || !workspace_dev)
+    return fail(-1, "filter_points: null pointer");
+  if (pts_dev == pts_out_dev || count_dev == count_out_dev || desc_dev == desc_out_dev || cls_dev == cls_out_dev)
+    return fail(-1, "filter_points: the point set is not filtered in place (pass a second set of arrays)");
+  if ((reinterpret_cast<size_t>(desc_dev) | reinterpret_cast<size_t>(desc_out_dev)) & 15)
+    return fail(-1, "filter_points: the descriptor arrays must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  ClassMask m;
+  for (int k = 0; k < 8; ++k) m.w[k] = keep_mask[k];
+  int32_t* block_sums = reinterpret_cast<int32_t*>(workspace_dev);
+  const dim3 grid(cdiv(cap, TRACK_BLOCK), n);
+  HIPCHK(hipMemsetAsync(cls_out_dev, POINT_CLASS_NONE, (size_t)n * cap, st));
+  hipLaunchKernelGGL(filter_count_kernel, grid, dim3(TRACK_BLOCK), 0, st, count_dev, cls_dev, m, cap, block_sums);
+  hipLaunchKernelGGL(filter_scatter_kernel, grid, dim3(TRACK_BLOCK), 0, st, pts_dev, count_dev, desc_dev, cls_dev, m, cap,
+                     (const int32_t*)block_sums, pts_out_dev, count_out_dev, desc_out_dev, cls_out_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }

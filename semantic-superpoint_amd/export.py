@@ -234,9 +234,12 @@ class PointTracker(object):
     The table, the running track count, the last max_length point sets and the previous frame's descriptors stay in HBM;
     `update` uploads one frame and reads the matches back (get_matches is a numpy contract), `update_device` takes device
     tensors and synchronises with the host only to allocate.  Descriptors are 256-dimensional.  draw_tracks is not provided
-    (no drawing here): `track_points` returns the coordinates it would connect."""
+    (no drawing here): `track_points` returns the coordinates it would connect.
+    class_consistent=True: every frame comes with the class of each point (`cls`); the previous
+    frame's classes are kept beside its descriptors and only points of equal class are matched
+    (ssp_match_two_way_classes).  The track table logic is the same."""
 
-    def __init__(self, max_length, nn_thresh, device=None):
+    def __init__(self, max_length, nn_thresh, device=None, class_consistent=False):
         if max_length < 2:
             raise ValueError("max_length must be greater than or equal to 2.")
         if max_length > L.TRACK_MAX_LENGTH:
@@ -259,6 +262,8 @@ class PointTracker(object):
         self._zero = None
         self._prev_ok = False     # the previous frame's descriptors take part in the next match
         self._pending = None      # device (match, n_match, had_prev) whose numpy form get_matches() has not been asked for yet
+        self.class_consistent = bool(class_consistent)
+        self._cls = None          # uint8 [2, cap] beside _desc (class_consistent only)
 
     # ---- device buffers -------------------------------------------------------------------------------------------
     def _ensure(self, n):
@@ -281,6 +286,11 @@ class PointTracker(object):
             pts[:, :self._cap] = self._pts
             desc[:, :self._cap] = self._desc
             counts.copy_(self._counts)
+        if self.class_consistent:
+            cls = torch.full((2, cap), L.CLASS_NONE, dtype=torch.uint8, device=dev)
+            if self._cap:
+                cls[:, :self._cap] = self._cls
+            self._cls = cls
         self._table, self._spare, self._pts, self._desc, self._counts, self._cap = table, spare, pts, desc, counts, cap
         self._zero = torch.zeros(1, dtype=torch.int32, device=dev)
 
@@ -288,20 +298,23 @@ class PointTracker(object):
         """(ring slot of the newest frame, desc slot of the newest frame)."""
         return (self._frames - 1) % self.maxl, (self._frames - 1) % 2
 
-    def _advance(self, xy, count, desc):
+    def _advance(self, xy, count, desc, cls=None):
         """The device half of an update: xy float64 [n, 2], count int32 [1], desc float32 [n, 256] device tensors (rows past
-        the count are ignored).  Returns the device (match, n_match) of the new frame against the previous one and whether
-        the previous frame's descriptors took part."""
+        the count are ignored), cls uint8 [n] with class_consistent.  Returns the device (match, n_match) of the new frame
+        against the previous one and whether the previous frame's descriptors took part."""
         n = xy.shape[0]
         if n > L.MATCH_MAX_POINTS:  # a capacity, not a count: the matcher takes the first MATCH_MAX_POINTS rows at most
             n = L.MATCH_MAX_POINTS
             xy, desc, count = xy[:n], desc[:n], count.clamp(max=n)
+            cls = cls[:n] if cls is not None else None
         self._ensure(max(n, 1))
         self._frames += 1
         slot, dslot = self._slots()
         self._pts[slot, :n] = xy
         self._desc[dslot, :n] = desc
         self._counts[dslot:dslot + 1] = count
+        if self.class_consistent:
+            self._cls[dslot, :n] = cls
         m, nm = self._match_device()
         self._track_device(m, nm)
         had_prev, self._prev_ok = self._prev_ok, True
@@ -310,6 +323,11 @@ class PointTracker(object):
     def _match_device(self):
         _, dslot = self._slots()
         prev = self._counts[1 - dslot:2 - dslot] if self._prev_ok else self._zero
+        if self.class_consistent:
+            m, nm = L.op_match_two_way(self._desc[1 - dslot:2 - dslot], prev, self._desc[dslot:dslot + 1],
+                                       self._counts[dslot:dslot + 1], self.nn_thresh, cls1=self._cls[1 - dslot:2 - dslot],
+                                       cls2=self._cls[dslot:dslot + 1])
+            return m[0], nm
         m, nm = L.op_match_two_way(self._desc[1 - dslot:2 - dslot], prev, self._desc[dslot:dslot + 1],
                                    self._counts[dslot:dslot + 1], self.nn_thresh)
         return m[0], nm
@@ -410,6 +428,8 @@ class PointTracker(object):
         if pts is None or desc is None:
             print("PointTracker: Warning, no points were added to tracker.")
             return
+        if self.class_consistent:
+            raise ValueError("a class-consistent tracker takes its frames, with their classes, through update_device")
         assert pts.shape[1] == desc.shape[1]
         n = pts.shape[1]
         if self.nn_thresh < 0.0 and n and self._prev_ok and self.all_pts[-1].shape[1]:
@@ -428,14 +448,25 @@ class PointTracker(object):
         self.last_desc = desc.copy()
         self.last_pts = pts[:2, :].copy()
 
-    def update_device(self, pts, count, desc):
+    def update_device(self, pts, count, desc, cls=None):
         """The same update from device tensors, e.g. one image's slice of Engine.describe_points: pts [cap, >= 2] rows
         starting (x, y), count int32 [1] (or 0-d), desc float32 [cap, 256] unit rows.  Matching and the track update are
         queued on the current stream; nothing is copied to the host and the host is not synchronised (the first call, and a
         call with a larger cap than any before, allocate).  A cap above lib.MATCH_MAX_POINTS is cut to that many rows (and the
         count with it).  get_matches / get_mscores / all_pts read back on demand and describe the NEWEST frame: matches of
         earlier frames that were never asked for are dropped, so get_mscores() is the last non-empty match set among the
-        frames it was asked about, not among all frames as after `update`."""
+        frames it was asked about, not among all frames as after `update`.
+        cls: uint8 [cap] classes of the rows (Engine.describe_points(classes=True)); required by a class-consistent tracker,
+        ignored by a plain one."""
+        if self.class_consistent:
+            if cls is None:
+                raise ValueError("a class-consistent tracker needs the classes of every frame (cls)")
+            if not cls.is_cuda:
+                raise RuntimeError("cls must live on a HIP device: the MI355X path has no CPU fallback")
+            if cls.dtype != torch.uint8 or tuple(cls.shape) != (pts.shape[0],):
+                raise ValueError("cls must be uint8 [cap] beside pts")
+        else:
+            cls = None
         for t, nm in ((pts, "pts"), (count, "count"), (desc, "desc")):
             if not t.is_cuda:
                 raise RuntimeError("%s must live on a HIP device: the MI355X path has no CPU fallback" % nm)
@@ -445,7 +476,7 @@ class PointTracker(object):
             raise ValueError("'nn_thresh' should be non-negative")
         self._pending = None  # the previous frame's matches were not asked for: they are dropped, not read back
         self._host_pts = self._host_pts[1:] + [None]
-        self._pending = self._advance(pts[:, :2].to(torch.float64), count.reshape(1), desc)
+        self._pending = self._advance(pts[:, :2].to(torch.float64), count.reshape(1), desc, cls)
         self.last_desc = self.last_pts = None  # (host copies exist for frames given to update only)
 
     def get_tracks_device(self, min_length):
@@ -489,33 +520,50 @@ class SequenceTracker:
     """Point tracks over an image sequence on one GPU: per frame one eval forward, keypoints + sparse descriptors
     (ssp_describe_points), the two-way matcher against the previous frame and the track update, all on the device with no
     host copy of points, descriptors or matches.  `net` is one of this package's model drop-ins; the vocabulary is
-    DescriptorExporter's.  Read the result with get_tracks / track_points (or `tracker`, the PointTracker)."""
+    DescriptorExporter's.  Read the result with get_tracks / track_points (or `tracker`, the PointTracker).
+    Semantic keypoints (the model needs a segmentation head): keep_classes / drop_classes (one of them)
+    remove the keypoints of unwanted classes on the device before they enter the track table; class_consistent matches only
+    points of equal class.  Neither adds a host copy or a synchronisation."""
 
-    def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4):
+    def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4,
+                 keep_classes=None, drop_classes=None, class_consistent=False):
         if nn_thresh < 0.0:
             raise ValueError("'nn_thresh' should be non-negative")
+        self.class_consistent = bool(class_consistent)
+        self._mask = None
+        if keep_classes is not None or drop_classes is not None or self.class_consistent:
+            if not hasattr(net, "convSout"):
+                raise ValueError("keep_classes / drop_classes / class_consistent need a model with a segmentation head")
+            if keep_classes is not None or drop_classes is not None:
+                self._mask = L.class_mask(keep=keep_classes, drop=drop_classes, n_classes=net.n_classes)
         self.net, self.device = net, torch.device(device)
         self.conf_thresh, self.nms_dist, self.subpixel = conf_thresh, nms_dist, bool(subpixel)
         self.border_remove = border_remove
-        self.tracker = PointTracker(max_length, nn_thresh, self.device)
+        self.tracker = PointTracker(max_length, nn_thresh, self.device, class_consistent=self.class_consistent)
 
     def describe(self, image):
-        """image [H,W] / [1,H,W] / [1,1,H,W] -> the device tensors of Engine.describe_points for this one image."""
+        """image [H,W] / [1,H,W] / [1,1,H,W] -> the device tensors of Engine.describe_points for this one image (with "cls",
+        and already filtered, when the tracker was built with class arguments)."""
         x = _image_2d(image).to(self.device, torch.float32)[None, None].contiguous()
         eng = self.net.engine(1, x.shape[2], x.shape[3], self.device)
         with torch.no_grad():
             eng.forward(x, slot=0, train=False, want=())
-        return eng.describe_points(0, 1, conf_thresh=self.conf_thresh, nms_dist=self.nms_dist, subpixel=self.subpixel,
-                                   border_remove=self.border_remove)
+        if self._mask is None and not self.class_consistent:
+            return eng.describe_points(0, 1, conf_thresh=self.conf_thresh, nms_dist=self.nms_dist, subpixel=self.subpixel,
+                                       border_remove=self.border_remove)
+        o = eng.describe_points(0, 1, conf_thresh=self.conf_thresh, nms_dist=self.nms_dist, subpixel=self.subpixel,
+                                border_remove=self.border_remove, classes=True)
+        return o if self._mask is None else L.op_filter_points(o["pts"], o["count"], o["desc"], o["cls"], self._mask)
 
     def step(self, image):
-        """The next frame: forward -> points / descriptors -> PointTracker.update_device.  Returns describe()'s tensors."""
+        """The next frame: forward -> points / descriptors (-> classes -> class filter) -> PointTracker.update_device.
+        Returns describe()'s tensors."""
         o = self.describe(image)
         pts = o["pts"][0]
         xy = pts[:, :2].to(torch.float64)
         if self.subpixel:  # the same float64 sum as lib.points_to_numpy
             xy = xy + pts[:, 3:5].to(torch.float64) - 2
-        self.tracker.update_device(xy, o["count"][0:1], o["desc"][0])
+        self.tracker.update_device(xy, o["count"][0:1], o["desc"][0], o["cls"][0] if self.class_consistent else None)
         return o
 
     def get_tracks(self, min_length):
@@ -546,9 +594,12 @@ class DescriptorExporter:
     at the threshold), so the forward always runs over 2 x batch_pairs images, zero-padded: a pair's result does not
     depend on how many pairs share its call."""
 
-    def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, border_remove=4, batch_pairs=16):
+    def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, border_remove=4, batch_pairs=16, classes=False):
         if nn_thresh < 0.0:
             raise ValueError("'nn_thresh' should be non-negative")
+        if classes and not hasattr(net, "convSout"):
+            raise ValueError("classes=True needs a model with a segmentation head")
+        self.classes = bool(classes)  # run_device adds "cls": uint8 [2P,cap], the class at each keypoint
         self.net, self.device = net, torch.device(device)
         self.conf_thresh, self.nms_dist, self.subpixel = conf_thresh, nms_dist, bool(subpixel)
         self.nn_thresh, self.border_remove = nn_thresh, border_remove
@@ -571,7 +622,7 @@ class DescriptorExporter:
         with torch.no_grad():
             eng.forward(x, slot=0, train=False, want=())
         o = eng.describe_points(0, n, conf_thresh=self.conf_thresh, nms_dist=self.nms_dist, subpixel=self.subpixel,
-                                border_remove=self.border_remove)
+                                border_remove=self.border_remove, classes=self.classes)
         o["match"], o["n_match"] = L.op_match_two_way(o["desc"], o["count"], o["desc"][1:], o["count"][1:],
                                                       self.nn_thresh, pair_stride=2, n_pairs=len(pairs))
         return o

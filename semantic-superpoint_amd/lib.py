@@ -121,11 +121,14 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_op_photometric_draw", "ssp_op_photometric_apply",
            "ssp_shapes_workspace_bytes", "ssp_op_shapes_draw", "ssp_op_shapes_render", "ssp_op_warp_points_scatter",
            "ssp_op_sem_predict", "ssp_sem_predict",
-           "ssp_track_workspace_bytes", "ssp_op_track_update", "ssp_op_track_select", "ssp_op_track_points"]
+           "ssp_track_workspace_bytes", "ssp_op_track_update", "ssp_op_track_select", "ssp_op_track_points",
+           "ssp_op_point_classes", "ssp_point_classes", "ssp_filter_workspace_bytes", "ssp_op_filter_points",
+           "ssp_match_two_way_classes"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
 TRACK_NO_SCORE = 9999.0  # score of a track that has no match yet (PointTracker.max_score)
+CLASS_NONE = 255  # SSP_CLASS_NONE (include/ssp_hip.h): the class of a row past its image's point count
 
 
 def load_library(path=None):
@@ -291,6 +294,16 @@ def load_library(path=None):
         lib.ssp_op_track_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp]
         lib.ssp_op_track_select.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]
         lib.ssp_op_track_points.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_op_point_classes.argtypes = [vp, i, i, i, i, i, vp, i, vp, i, vp, vp]
+        lib.ssp_point_classes.argtypes = [vp, i, i, vp, i, vp, i, vp, vp]
+        lib.ssp_filter_workspace_bytes.argtypes = [i, i]
+        lib.ssp_filter_workspace_bytes.restype = C.c_size_t
+        lib.ssp_op_filter_points.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_uint32), i, i, vp, vp, vp, vp, vp, vp]
+        lib.ssp_match_two_way_classes.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, f, vp, vp, vp, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -717,10 +730,11 @@ class Engine:
                                               arr(self._export_ws[:k]), arr(hm), arr(pts), arr(cnt), _stream()))
         return [{"pts": pts[j], "count": cnt[j], "heatmap": hm[j]} for j in range(k)]
 
-    def describe_points(self, slot, n, conf_thresh=0.015, nms_dist=4, subpixel=True, top_k=0, border_remove=4):
+    def describe_points(self, slot, n, conf_thresh=0.015, nms_dist=4, subpixel=True, top_k=0, border_remove=4, classes=False):
         """Keypoints + sparse descriptors of the first n images of the last EVAL forward in `slot` (Val_model_heatmap's
         run / heatmap_to_pts / soft_argmax_points / desc_to_sparseDesc, export.py:126-142).  Returns device tensors
-        {"pts": [n,cap,5] rows (x, y, conf, sx, sy), "count": [n] int32, "desc": [n,cap,256]}; no host synchronisation."""
+        {"pts": [n,cap,5] rows (x, y, conf, sx, sy), "count": [n] int32, "desc": [n,cap,256]}; no host synchronisation.
+        classes=True adds "cls": uint8 [n,cap], the segmentation head's class at each keypoint (point_classes)."""
         hh, ww = self.height, self.width
         x = getattr(self, "_x", [None, None])[slot]
         if x is not None:
@@ -740,7 +754,22 @@ class Engine:
         with torch.cuda.device(self.device):
             _check(self.lib.ssp_describe_points(self.h, int(slot), C.byref(p), int(n), _ptr(self._describe_ws), _ptr(pts),
                                                 _ptr(cnt), _ptr(desc), _stream()))
+        if classes:
+            return {"pts": pts, "count": cnt, "desc": desc, "cls": self.point_classes(slot, pts, cnt)}
         return {"pts": pts, "count": cnt, "desc": desc}
+
+    def point_classes(self, slot, pts, count):
+        """The class the segmentation head gives each keypoint, from the logits the last forward / pair step left in `slot`
+        (ssp_point_classes; see op_point_classes): pts float32 [n,cap,>=2] rows starting with the integer pixel (x, y), count
+        int32 [n] -> uint8 [n,cap], CLASS_NONE in the rows past each count.  No host synchronisation."""
+        pts, count = _point_class_args(pts, count)
+        n, cap, stride = pts.shape
+        cls = torch.empty(n, cap, dtype=torch.uint8, device=self.device)
+        if cap == 0:
+            return cls
+        with torch.cuda.device(self.device):
+            _check(self.lib.ssp_point_classes(self.h, int(slot), n, _ptr(pts), stride, _ptr(count), cap, _ptr(cls), _stream()))
+        return cls
 
     def detector_heatmap(self, slot, n, hh, ww):
         """flattenDetection of the detector logits left in `slot` by the last forward / pair step -> [n,1,hh,ww]."""
@@ -1025,6 +1054,100 @@ def op_sem_predict(sout_nchw, labels=None, want_pred=True, confusion=None, cs=No
     return pred, confusion
 
 
+def _point_class_args(pts, count):
+    _need_gpu(pts, "pts")
+    _need_gpu(count, "count")
+    if pts.dtype != torch.float32 or pts.dim() != 3 or pts.shape[2] < 2:
+        raise ValueError("pts must be float32 [n, cap, >= 2] rows starting (x, y), got %s %s" % (pts.dtype, tuple(pts.shape)))
+    if count.dtype != torch.int32 or count.numel() != pts.shape[0]:
+        raise ValueError("count must be int32 [%d]" % pts.shape[0])
+    return pts, count
+
+
+def op_point_classes(sout_nchw, pts, count, n_classes=None):
+    """The class of each keypoint on public NCHW logits [B,C,Hc,Wc] at 1/8 resolution, without the class map: row r < count[b]
+    of pts [B,cap,>=2] (float32 rows starting with the integer pixel (x, y), e.g. Engine.describe_points' "pts") gets exactly
+    op_sem_predict(sout_nchw)[0][b, y, x]; rows past the count get CLASS_NONE.  n_classes < C: only the first n_classes channels
+    are classes, the others play the padding of a stride-C map AS GIVEN (test hook, as in op_sem_predict).  At most 255 classes.
+    Returns uint8 [B,cap] on the device; no host synchronisation."""
+    lib = load_library()
+    _need_gpu(sout_nchw, "sout")
+    pts, count = _point_class_args(pts, count)
+    B, c, Hc, Wc = sout_nchw.shape
+    if pts.shape[0] != B:
+        raise ValueError("pts holds %d images, the logits %d" % (pts.shape[0], B))
+    dev = sout_nchw.device
+    if n_classes is None:
+        n_classes, cs = c, (c + 7) // 8 * 8
+        x = torch.zeros(B, Hc, Wc, cs, dtype=torch.float32, device=dev)
+        x[..., :c] = sout_nchw.permute(0, 2, 3, 1)
+    else:
+        cs = c
+        x = sout_nchw.permute(0, 2, 3, 1).contiguous().float()
+    cap, stride = pts.shape[1], pts.shape[2]
+    cls = torch.empty(B, cap, dtype=torch.uint8, device=dev)
+    if cap == 0:
+        return cls
+    with torch.cuda.device(dev):
+        _check(lib.ssp_op_point_classes(_ptr(x), cs, B, Hc * 8, Wc * 8, int(n_classes), _ptr(pts), stride, _ptr(count), cap,
+                                        _ptr(cls), _stream()))
+    return cls
+
+
+def class_mask(keep=None, drop=None, n_classes=133):
+    """The 256-bit keep mask of op_filter_points as eight 32-bit words (bit c of word c // 32 = class c is kept): exactly one of
+    `keep` (the classes to keep) and `drop` (the classes to remove among 0 .. n_classes-1) is given.  Ids outside [0, n_classes)
+    raise ValueError."""
+    if (keep is None) == (drop is None):
+        raise ValueError("class_mask: exactly one of keep and drop must be given")
+    n_classes = int(n_classes)
+    if not 1 <= n_classes <= CLASS_NONE:
+        raise ValueError("class_mask: 1 <= n_classes <= %d required (got %d)" % (CLASS_NONE, n_classes))
+    ids = [int(c) for c in (keep if keep is not None else drop)]
+    for c in ids:
+        if not 0 <= c < n_classes:
+            raise ValueError("class_mask: class id %d outside [0, %d)" % (c, n_classes))
+    kept = set(ids) if keep is not None else set(range(n_classes)) - set(ids)
+    words = [0] * 8
+    for c in kept:
+        words[c >> 5] |= 1 << (c & 31)
+    return tuple(words)
+
+
+def op_filter_points(pts, count, desc, cls, mask):
+    """Stable per-image compaction of a point set by class (ssp_op_filter_points): pts float32 [n,cap,5], count int32 [n], desc
+    float32 [n,cap,256], cls uint8 [n,cap] as Engine.describe_points(classes=True) returns them, mask = class_mask(...).  The rows
+    below the count whose class bit is set keep their order.  Returns new device tensors {"pts", "count", "desc", "cls"}: rows
+    past the new count are CLASS_NONE in "cls" and unspecified elsewhere.  No host synchronisation."""
+    lib = load_library()
+    for t, nm in ((pts, "pts"), (count, "count"), (desc, "desc"), (cls, "cls")):
+        _need_gpu(t, nm)
+    mask = [int(w) for w in mask]
+    if len(mask) != 8 or any(not 0 <= w < 1 << 32 for w in mask):
+        raise ValueError("mask must be eight 32-bit words (class_mask)")
+    if pts.dtype != torch.float32 or pts.dim() != 3 or pts.shape[2] != 5:
+        raise ValueError("pts must be float32 [n, cap, 5], got %s %s" % (pts.dtype, tuple(pts.shape)))
+    n, cap = pts.shape[0], pts.shape[1]
+    if desc.dtype != torch.float32 or tuple(desc.shape) != (n, cap, 256):
+        raise ValueError("desc must be float32 [%d, %d, 256]" % (n, cap))
+    if cls.dtype != torch.uint8 or tuple(cls.shape) != (n, cap) or count.dtype != torch.int32 or count.numel() != n:
+        raise ValueError("cls must be uint8 [%d, %d] and count int32 [%d]" % (n, cap, n))
+    dev = pts.device
+    out = {"pts": torch.empty_like(pts), "count": torch.zeros(n, dtype=torch.int32, device=dev),
+           "desc": torch.empty_like(desc), "cls": torch.empty_like(cls)}
+    if n == 0 or cap == 0:
+        return out
+    wsb = lib.ssp_filter_workspace_bytes(n, cap)
+    if wsb == 0:
+        _check(-1)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.ssp_op_filter_points(_ptr(pts), _ptr(count), _ptr(desc), _ptr(cls), (C.c_uint32 * 8)(*mask), n, cap,
+                                        _ptr(out["pts"]), _ptr(out["count"]), _ptr(out["desc"]), _ptr(out["cls"]), _ptr(ws),
+                                        _stream()))
+    return out
+
+
 def sem_metrics(confusion):
     """Pixel accuracy and mean intersection over union of a confusion matrix [C,C] (row = label, column = prediction; torch tensor on
     any device or numpy array; one device-to-host copy).  With tp = diag, row = sums over the predictions, col = sums over the labels:
@@ -1305,13 +1428,17 @@ def op_sample_descriptors(desc, xy, counts=None):
     return out
 
 
-def op_match_two_way(desc1, count1, desc2, count2, nn_thresh, pair_stride=1, n_pairs=None):
+def op_match_two_way(desc1, count1, desc2, count2, nn_thresh, pair_stride=1, n_pairs=None, cls1=None, cls2=None):
     """PointTracker.nn_match_two_way (models/model_wrap.py:451-497) for P pairs on the device.  desc1, desc2:
     [P*pair_stride, cap, 256] unit rows, count1, count2: [P*pair_stride] int32 (pair p uses entry p*pair_stride).
+    cls1, cls2 (both or neither): uint8 [P*pair_stride, cap] classes beside the descriptors; rows of different classes are
+    never matched (ssp_match_two_way_classes).
     Returns (match [P,cap,3] rows (i, j, score) in ascending i, n_match [P] int32) as device tensors."""
     lib = load_library()
     if nn_thresh < 0.0:
         raise ValueError("'nn_thresh' should be non-negative")
+    if (cls1 is None) != (cls2 is None):
+        raise ValueError("cls1 and cls2: both or neither")
     for t, nm in ((desc1, "desc1"), (desc2, "desc2"), (count1, "count1"), (count2, "count2")):
         _need_gpu(t, nm)
     cap = desc1.shape[1]
@@ -1325,9 +1452,19 @@ def op_match_two_way(desc1, count1, desc2, count2, nn_thresh, pair_stride=1, n_p
     ws = torch.empty(wsb, dtype=torch.uint8, device=desc1.device)
     match = torch.empty(P, cap, 3, dtype=torch.float32, device=desc1.device)
     n_match = torch.empty(P, dtype=torch.int32, device=desc1.device)
+    if cls1 is not None:
+        for t, d, nm in ((cls1, desc1, "cls1"), (cls2, desc2, "cls2")):
+            _need_gpu(t, nm)
+            if t.dtype != torch.uint8 or tuple(t.shape) != (d.shape[0], cap):
+                raise ValueError("%s must be uint8 %s beside its descriptors" % (nm, (d.shape[0], cap)))
     with torch.cuda.device(desc1.device):
-        _check(lib.ssp_match_two_way(_ptr(desc1), _ptr(count1), _ptr(desc2), _ptr(count2), cap, P, int(pair_stride),
-                                     float(np.float32(nn_thresh)), _ptr(ws), _ptr(match), _ptr(n_match), _stream()))
+        if cls1 is not None:
+            _check(lib.ssp_match_two_way_classes(_ptr(desc1), _ptr(count1), _ptr(desc2), _ptr(count2), _ptr(cls1), _ptr(cls2),
+                                                 cap, P, int(pair_stride), float(np.float32(nn_thresh)), _ptr(ws), _ptr(match),
+                                                 _ptr(n_match), _stream()))
+        else:
+            _check(lib.ssp_match_two_way(_ptr(desc1), _ptr(count1), _ptr(desc2), _ptr(count2), cap, P, int(pair_stride),
+                                         float(np.float32(nn_thresh)), _ptr(ws), _ptr(match), _ptr(n_match), _stream()))
     return match, n_match
 
 
