@@ -555,6 +555,57 @@ int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int
                     double* h_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev, double* ap_dev,
                     void* stream);
 
+/* ---- detector evaluation against ground-truth corners (evaluations/detector_evaluation.py:15-136) --
+ * compute_tp_fp / compute_pr / compute_mAP / compute_loc_error for a validation set that is fed batch by batch and never
+ * leaves the device.  The caller owns a key buffer int64 [capacity] and a state block int64 [SSP_DET_EVAL_STATE_WORDS]
+ * (zeroed = empty): word 0 records fed so far (counts past capacity too), word 1 n_gt, word 2 != 0 after an overflow,
+ * word 3 point-list rows that were skipped because they lie outside the image (a mis-scaled list shows here),
+ * words 8 .. 8 + SSP_DET_EVAL_MAX_R2: number of predictions above prob_thresh whose nearest ground-truth point is at squared
+ * distance d2 (compute_loc_error = sum(count[d2] * sqrt(d2)) / sum(count), formed in fp64 by the caller).
+ * Labels are [b][height][width], fp32 (labels_u8 == 0) or uint8, nonzero = ground truth.  r2 is the largest integer d2 with
+ * sqrt((double)d2) <= distance_thresh, computed by the caller: the kernels compare integers only.
+ * ssp_op_det_tp_fp: candidates are the pixels of prob_dev [b][height][width] with prob > remove_zero (fp32 compare), in
+ *   image order, then row-major.  A candidate is assigned to the FIRST label pixel, in row-major order, within r2 (np.argmax of
+ *   the reference's match row: not the nearest) and is a true positive iff it has the largest (probability, position) among
+ *   the candidates assigned to that pixel.  simplified != 0 (the reference's flag): tp = any label pixel within r2, and n_gt
+ *   counts the label pixels within r2 of some candidate.  Candidate k of the call becomes record (word 0) + k and writes
+ *   keys_dev[record] = prob bits << 32 | record << 1 | tp; every key is unique, so a descending sort of the keys is the order
+ *   "descending probability, among equals the later record first" whatever sort produces it.  Record positions come from a
+ *   prefix scan, not an atomic ticket: the keys are bit-identical from run to run and for any split of a set into calls.
+ *   A record >= capacity sets word 2 and is not written.
+ * ssp_op_det_tp_fp_points: the same for point lists pts_dev [b][cap][5] rows (x, y, confidence, ..) with count_dev [b] (clamped
+ *   to cap) as ssp_op_heatmap_points / ssp_describe_points write them: the candidates are the rows < count with confidence >
+ *   remove_zero at the integer pixel (x, y), in list order (rows outside the image are skipped).
+ * ssp_op_det_pr_curve: compute_pr + compute_mAP over n_records keys sorted in DESCENDING order (as signed or unsigned 64-bit
+ *   integers: bit 63 is never set): prob_dev [n] fp32, tp_dev [n] uint8, precision_dev / recall_dev [n + 2] fp64 with the
+ *   reference's padding (recall 0 .. 1, precision 0 .. 0), the running maximum of precision from the right, recall by div0's
+ *   rule when n_gt == 0 (1 where tp_cum == 0, else 0), and map_dev [1] = sum(precision[1:] * (recall[1:] - recall[:-1])).
+ *   fp64 without contraction; every element equals numpy's except map_dev, whose summation order differs.
+ *   n_records == 0 gives precision [0, 0], recall [0, 1], mAP 0.
+ * Bad arguments (r2 > SSP_DET_EVAL_MAX_R2, remove_zero < 0, prob_thresh < remove_zero, capacity or batch x pixels >= 2^31,
+ * ..) return -1 with ssp_last_error before anything is launched.  No call synchronises with the host.  workspace_dev: ssp_det_eval_workspace_bytes(p, b, cap) bytes (cap = 0 for
+ * the dense form) / ssp_det_pr_curve_workspace_bytes(n_records) bytes; 0 = bad arguments. */
+#define SSP_DET_EVAL_MAX_R2 64
+#define SSP_DET_EVAL_STATE_WORDS 80
+#define SSP_DET_EVAL_CURVE_TILE 1024 /* records per workgroup of the curve kernels (tests place record counts around it) */
+typedef struct ssp_det_eval_params {
+  int32_t height, width;
+  float remove_zero;  /* compute_tp_fp's remove_zero (1e-4), >= 0 */
+  int32_t r2;         /* squared match radius, 0 .. SSP_DET_EVAL_MAX_R2 */
+  float prob_thresh;  /* compute_loc_error's prob_thresh (0.5), >= remove_zero: only candidates are measured */
+  int32_t simplified; /* compute_tp_fp's simplified */
+} ssp_det_eval_params;
+size_t ssp_det_eval_workspace_bytes(const ssp_det_eval_params* p, int b, int cap);
+int ssp_op_det_tp_fp(const float* prob_dev, const void* labels_dev, int labels_u8, const ssp_det_eval_params* p, int b,
+                     void* workspace_dev, int64_t* keys_dev, int64_t capacity, int64_t* state_dev, void* stream);
+int ssp_op_det_tp_fp_points(const float* pts_dev, const int32_t* count_dev, int cap, const void* labels_dev, int labels_u8,
+                            const ssp_det_eval_params* p, int b, void* workspace_dev, int64_t* keys_dev, int64_t capacity,
+                            int64_t* state_dev, void* stream);
+size_t ssp_det_pr_curve_workspace_bytes(int64_t n_records);
+int ssp_op_det_pr_curve(const int64_t* sorted_keys_dev, int64_t n_records, const int64_t* state_dev, void* workspace_dev,
+                        float* prob_dev, uint8_t* tp_dev, double* precision_dev, double* recall_dev, double* map_dev,
+                        void* stream);
+
 /* ---- point tracks over a frame sequence (PointTracker.update / get_tracks, models/model_wrap.py:521-615) ----------
  * The track table of max_length = L frames lives in caller-owned arrays of row_cap rows: ids [row_cap][L] int32 (point id
  * of retained frame 0 .. L-1, oldest first, -1 = none), tid [row_cap] int32 (track id), score [row_cap] fp64 (running mean

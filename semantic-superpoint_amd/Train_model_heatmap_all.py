@@ -19,6 +19,9 @@ augmentation of `data.augmentation` - is built on the device by pairs.make_pairs
 Segmentation metrics (`ssp_sem_metrics: true`, with `data.semantic` and a model with a segmentation head; off by default): on
 the steps of the logging branch, pixel accuracy and mIoU of both views and their class maps (`log_sem_metrics`); validation
 steps also sum one confusion matrix on the device, which train() reports per validation round.
+Detector mAP (`ssp_detector_map: true`; off by default): the validation steps feed the heat maps and label maps of their views
+into one detector_evaluation.DetectorEvaluator per round, and train() reports `detector_mAP_round` and
+`detector_loc_err_round` after it (the reference's evaluations/detector_evaluation.py numbers).
 """
 import copy
 import logging
@@ -96,6 +99,13 @@ class Train_model_heatmap_all(object):
             raise ValueError("ssp_sem_metrics reads the segmentation head: it needs data.semantic and a model with that head (%s), "
                              "got data.semantic=%r and model %r" % (", ".join(_SEM_MODELS), self.config["data"].get("semantic", False), m.get("name")))
         self.sem_confusion_val = None  # int64 [C,C] on the device: both views of the validation steps since reset_sem_confusion()
+        self.detector_map = bool(self.config.get("ssp_detector_map", False))
+        self.detector_eval_val = None  # DetectorEvaluator of the validation steps since reset_detector_eval()
+        self._detector_fed = 0         # pixels fed into it since then: an upper bound of its records, kept on the host
+        resize = (self.config["data"].get("preprocessing") or {}).get("resize")
+        if self.detector_map and resize:  # a round that cannot fit is refused here, not at the first validation step
+            views = 2 if self.config["data"].get("warped_pair", {}).get("enable", False) else 1
+            self._detector_capacity(views, int(m.get("eval_batch_size", m["batch_size"])), int(resize[0]), int(resize[1]))
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("Train_model_heatmap_all (MI355X build) needs a HIP device, got %s" % device)
@@ -275,6 +285,8 @@ class Train_model_heatmap_all(object):
             self.log_precision_recall(eng, dev, B, H, W)
             if self.sem_metrics:
                 self.log_sem_metrics(eng, dev, B, H, W, task == "val")
+            if self.detector_map and task == "val":
+                self.log_detector_map(eng, dev, B, H, W)
             self.tb_hist_dict(task, self.hist_dict)   # (:568; `images_dict` stays unwritten like the reference's commented-out :567)
         self.tb_scalar_dict(self.scalar_dict, task)
         return float(s["loss"])
@@ -352,6 +364,39 @@ class Train_model_heatmap_all(object):
                     self.sem_confusion_val = torch.zeros_like(conf)
                 self.sem_confusion_val += conf
 
+    def _detector_capacity(self, views, B, H, W, fed=0):
+        """Records a validation round of `ssp_detector_map` can hold: one per pixel of validation_size + 2 steps (the most
+        train() runs), on top of `fed` pixels already in the round.  The record index has 31 bits."""
+        steps = int(self.config.get("validation_size", 3)) + 2
+        n = fed + steps * views * B * H * W
+        if n >= 2 ** 31:
+            raise ValueError("ssp_detector_map keeps one record per pixel of a validation round: (validation_size + 2) x views x "
+                             "batch x height x width = %d x %d x %d x %d x %d reaches 2^31: lower validation_size (or the "
+                             "evaluation batch or the resolution), or switch ssp_detector_map off" % (steps, views, B, H, W))
+        return n
+
+    def log_detector_map(self, eng, dev, B, H, W):
+        """`ssp_detector_map`: the heat map of each view of this validation step against its label map goes into the round's
+        DetectorEvaluator (made at the first step for validation_size + 2 steps, the most train() runs; no host copy here).
+        A step that would not fit (a larger batch than the first one's) grows the evaluator first."""
+        from .detector_evaluation import DetectorEvaluator
+        views = [(0, "labels_2D")] + ([(1, "warped_labels")] if "warped_img" in dev else [])
+        ev = self.detector_eval_val
+        if ev is None or (ev.height, ev.width) != (H, W):
+            ev = self.detector_eval_val = DetectorEvaluator(H, W, self.device, self._detector_capacity(len(views), B, H, W))
+            self._detector_fed = 0
+        self._detector_fed += len(views) * B * H * W
+        if self._detector_fed > ev.capacity:
+            ev.reserve(self._detector_capacity(len(views), B, H, W, fed=self._detector_fed))
+        for slot, key in views:
+            ev.update(prob=eng.detector_heatmap(slot, B, H, W), labels=dev[key].float().contiguous())
+
+    def reset_detector_eval(self):
+        """Empty the validation evaluator (train() calls it in front of a validation round)."""
+        if self.detector_eval_val is not None:
+            self.detector_eval_val.reset()
+        self._detector_fed = 0
+
     def reset_sem_confusion(self):
         """Zero the validation confusion matrix (train() calls it in front of a validation round)."""
         if self.sem_confusion_val is not None:
@@ -414,6 +459,8 @@ class Train_model_heatmap_all(object):
                 if self._eval and self.n_iter % self.config["validation_interval"] == 0:
                     if self.sem_metrics:
                         self.reset_sem_confusion()
+                    if self.detector_map:
+                        self.reset_detector_eval()
                     for j, sample_val in enumerate(self.val_loader):
                         self.train_val_sample(sample_val, self.n_iter + j, False)
                         if j > self.config.get("validation_size", 3):
@@ -421,6 +468,9 @@ class Train_model_heatmap_all(object):
                     if self.sem_metrics and self.sem_confusion_val is not None:  # one matrix read per round
                         met = L.sem_metrics(self.sem_confusion_val)
                         self.tb_scalar_dict({"sem_miou_round": met["miou"], "sem_pixel_acc_round": met["pixel_acc"]}, "val")
+                    if self.detector_map and self.detector_eval_val is not None:  # one state read per round
+                        res = self.detector_eval_val.result()
+                        self.tb_scalar_dict({"detector_mAP_round": res["mAP"], "detector_loc_err_round": res["loc_error"]}, "val")
                 if self.n_iter % self.config["save_interval"] == 0:
                     self.saveModel()
                 if self.n_iter > self.max_iter:

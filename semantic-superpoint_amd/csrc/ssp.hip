@@ -34,6 +34,7 @@
 #include "describe_kernels.hip.h"
 #include "track_kernels.hip.h"
 #include "eval_kernels.hip.h"
+#include "detector_eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
 #include "point_class_kernels.hip.h"
@@ -3756,6 +3757,151 @@ int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int
   hipLaunchKernelGGL(eval_ransac_kernel, dim3(n_pairs), dim3(EVAL_THREADS), use_lds ? (size_t)cap * sizeof(double4) + small : small,
                      st, (const double4*)xy, match_dev, n_match_dev, cap, seeds_dev, (int)use_lds, h_dev, mask_dev,
                      n_inlier_dev, status_dev, ap_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- detector evaluation against ground-truth corners (evaluations/detector_evaluation.py:15-136) ----
+static_assert(DET_MAX_R2 == SSP_DET_EVAL_MAX_R2 && DET_STATE_WORDS == SSP_DET_EVAL_STATE_WORDS && DET_CURVE_TILE == SSP_DET_EVAL_CURVE_TILE,
+              "include/ssp_hip.h and detector_eval_kernels.hip.h disagree");
+struct DetWs {
+  unsigned long long* best;  // [b][H*W]
+  int32_t* gidx;             // [b][items]
+  int32_t* block_sums;       // [nb]
+  int32_t* block_offs;       // [nb + 1]
+  size_t bytes;
+};
+static long det_items(const ssp_det_eval_params* p, int b, int cap) { return (long)b * (cap > 0 ? (long)cap : (long)p->height * p->width); }
+static DetWs det_carve(const ssp_det_eval_params* p, int b, int cap, void* base) {
+  Carver c{reinterpret_cast<char*>(base), 0};
+  const long items = det_items(p, b, cap);
+  const size_t nb = (size_t)cdiv(items, DET_BLOCK);
+  DetWs w;
+  w.best = c.take<unsigned long long>((size_t)b * p->height * p->width);
+  w.gidx = c.take<int32_t>((size_t)items);
+  w.block_sums = c.take<int32_t>(nb);
+  w.block_offs = c.take<int32_t>(nb + 1);
+  w.bytes = align_up(c.off, 256);
+  return w;
+}
+static int det_check(const char* what, const ssp_det_eval_params* p, int b, int cap) {
+  if (!p || p->height < 1 || p->width < 1 || b < 1 || cap < 0)
+    return fail(-1, "%s: height, width, batch >= 1 and cap >= 0 required", what);
+  if (p->r2 < 0 || p->r2 > SSP_DET_EVAL_MAX_R2)
+    return fail(-1, "%s: 0 <= r2 <= %d required (got %d): the squared match radius in pixels", what, SSP_DET_EVAL_MAX_R2, p->r2);
+  if (!(p->remove_zero >= 0.f) || !(p->prob_thresh >= 0.f))
+    return fail(-1, "%s: remove_zero >= 0 and prob_thresh >= 0 required (candidates are positive probabilities)", what);
+  if ((double)b * p->height * p->width >= 2147483648.0 || (double)b * cap >= 2147483648.0)
+    return fail(-1, "%s: batch x height x width (or batch x cap) exceeds 2^31: lower the batch", what);
+  if (p->prob_thresh < p->remove_zero)
+    return fail(-1, "%s: prob_thresh >= remove_zero required (only candidates, prob > remove_zero, reach the localisation histogram)", what);
+  return 0;
+}
+
+size_t ssp_det_eval_workspace_bytes(const ssp_det_eval_params* p, int b, int cap) {
+  if (det_check("det_eval_workspace_bytes", p, b, cap)) return 0;
+  return det_carve(p, b, cap, nullptr).bytes;
+}
+
+static int det_tp_fp(bool points, const float* src, const int32_t* count, int cap, const void* labels, int labels_u8, const ssp_det_eval_params* p,
+                     int b, void* workspace, int64_t* keys, int64_t capacity, int64_t* state, hipStream_t st) {
+  const DetWs w = det_carve(p, b, cap, workspace);
+  DetParams P;
+  P.H = p->height; P.W = p->width; P.r2 = p->r2; P.simplified = p->simplified ? 1 : 0; P.labels_u8 = labels_u8 ? 1 : 0;
+  P.remove_zero = p->remove_zero; P.prob_thresh = p->prob_thresh;
+  P.r = 0;
+  while ((P.r + 1) * (P.r + 1) <= P.r2) ++P.r;
+  const long items = det_items(p, b, cap), n_pix = (long)b * p->height * p->width;
+  const int n_items = (int)(items / b), nb = cdiv(items, DET_BLOCK);
+  unsigned long long* ust = reinterpret_cast<unsigned long long*>(state);
+  HIPCHK(hipMemsetAsync(w.best, 0, (size_t)n_pix * sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(points ? det_match_kernel<true> : det_match_kernel<false>, dim3(nb), dim3(DET_BLOCK), 0, st, src, count, labels,
+                     P, n_items, items, w.best, w.gidx, w.block_sums, ust);
+  hipLaunchKernelGGL(det_offsets_kernel, dim3(1), dim3(DET_BLOCK), 0, st, (const int32_t*)w.block_sums, nb, w.block_offs);
+  hipLaunchKernelGGL(points ? det_emit_kernel<true> : det_emit_kernel<false>, dim3(nb), dim3(DET_BLOCK), 0, st, src, count, P, n_items, items,
+                     (const unsigned long long*)w.best, (const int32_t*)w.gidx, (const int32_t*)w.block_offs,
+                     reinterpret_cast<unsigned long long*>(keys), (long long)capacity, ust);
+  hipLaunchKernelGGL(det_finish_kernel, dim3(cdiv(n_pix, DET_BLOCK)), dim3(DET_BLOCK), 0, st, labels, P, n_pix,
+                     (const unsigned long long*)w.best, (const int32_t*)w.block_offs, nb, ust);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+static int det_buffers_check(const char* what, const void* labels, const void* workspace, const int64_t* keys, int64_t capacity,
+                             const int64_t* state) {
+  if (!labels || !workspace || !keys || !state) return fail(-1, "%s: null pointer", what);
+  if (capacity < 1 || capacity > 2147483647LL)
+    return fail(-1, "%s: 1 <= capacity < 2^31 records required (the record index is 31 bits of the key)", what);
+  return 0;
+}
+
+int ssp_op_det_tp_fp(const float* prob_dev, const void* labels_dev, int labels_u8, const ssp_det_eval_params* p, int b,
+                     void* workspace_dev, int64_t* keys_dev, int64_t capacity, int64_t* state_dev, void* stream) {
+  CHK(det_check("det_tp_fp", p, b, 0));
+  if (!prob_dev) return fail(-1, "det_tp_fp: null pointer");
+  CHK(det_buffers_check("det_tp_fp", labels_dev, workspace_dev, keys_dev, capacity, state_dev));
+  return det_tp_fp(false, prob_dev, nullptr, 0, labels_dev, labels_u8, p, b, workspace_dev, keys_dev, capacity, state_dev,
+                          (hipStream_t)stream);
+}
+
+int ssp_op_det_tp_fp_points(const float* pts_dev, const int32_t* count_dev, int cap, const void* labels_dev, int labels_u8,
+                            const ssp_det_eval_params* p, int b, void* workspace_dev, int64_t* keys_dev, int64_t capacity,
+                            int64_t* state_dev, void* stream) {
+  CHK(det_check("det_tp_fp_points", p, b, cap));
+  if (cap < 1) return fail(-1, "det_tp_fp_points: cap >= 1 rows per image required");
+  if (!pts_dev || !count_dev) return fail(-1, "det_tp_fp_points: null pointer");
+  CHK(det_buffers_check("det_tp_fp_points", labels_dev, workspace_dev, keys_dev, capacity, state_dev));
+  return det_tp_fp(true, pts_dev, count_dev, cap, labels_dev, labels_u8, p, b, workspace_dev, keys_dev, capacity, state_dev,
+                         (hipStream_t)stream);
+}
+
+struct DetCurveWs {
+  int32_t *block_sums, *block_offs;
+  double *block_max, *suffix, *partial;
+  size_t bytes;
+};
+static DetCurveWs det_curve_carve(int64_t n, void* base) {
+  Carver c{reinterpret_cast<char*>(base), 0};
+  const size_t nb = (size_t)std::max<int64_t>(cdiv(n, (int64_t)DET_CURVE_TILE), 1);
+  DetCurveWs w;
+  w.block_max = c.take<double>(nb);
+  w.suffix = c.take<double>(nb);
+  w.partial = c.take<double>(nb);
+  w.block_sums = c.take<int32_t>(nb);
+  w.block_offs = c.take<int32_t>(nb + 1);
+  w.bytes = align_up(c.off, 256);
+  return w;
+}
+
+size_t ssp_det_pr_curve_workspace_bytes(int64_t n_records) {
+  if (n_records < 0 || n_records > 2147483647LL) {
+    fail(-1, "det_pr_curve_workspace_bytes: 0 <= n_records < 2^31 required");
+    return 0;
+  }
+  return det_curve_carve(n_records, nullptr).bytes;
+}
+
+int ssp_op_det_pr_curve(const int64_t* sorted_keys_dev, int64_t n_records, const int64_t* state_dev, void* workspace_dev,
+                        float* prob_dev, uint8_t* tp_dev, double* precision_dev, double* recall_dev, double* map_dev,
+                        void* stream) {
+  if (n_records < 0 || n_records > 2147483647LL) return fail(-1, "det_pr_curve: 0 <= n_records < 2^31 required");
+  if (!state_dev || !workspace_dev || !precision_dev || !recall_dev || !map_dev ||
+      (n_records > 0 && (!sorted_keys_dev || !prob_dev || !tp_dev)))
+    return fail(-1, "det_pr_curve: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const DetCurveWs w = det_curve_carve(n_records, workspace_dev);
+  const long long n = n_records;
+  const int nb = (int)std::max<int64_t>(cdiv(n_records, (int64_t)DET_CURVE_TILE), 1);
+  const unsigned long long* keys = reinterpret_cast<const unsigned long long*>(sorted_keys_dev);
+  const unsigned long long* ust = reinterpret_cast<const unsigned long long*>(state_dev);
+  hipLaunchKernelGGL(det_curve_count_kernel, dim3(nb), dim3(DET_BLOCK), 0, st, keys, n, w.block_sums);
+  hipLaunchKernelGGL(det_offsets_kernel, dim3(1), dim3(DET_BLOCK), 0, st, (const int32_t*)w.block_sums, nb, w.block_offs);
+  hipLaunchKernelGGL(det_curve_pr_kernel, dim3(nb), dim3(DET_BLOCK), 0, st, keys, n, ust, (const int32_t*)w.block_offs, prob_dev,
+                     tp_dev, precision_dev, recall_dev, w.block_max);
+  hipLaunchKernelGGL(det_suffix_blocks_kernel, dim3(1), dim3(DET_BLOCK), 0, st, (const double*)w.block_max, nb, w.suffix);
+  hipLaunchKernelGGL(det_curve_final_kernel, dim3(nb), dim3(DET_BLOCK), 0, st, n, (const double*)w.suffix,
+                     (const double*)recall_dev, precision_dev, w.partial);
+  hipLaunchKernelGGL(det_sum_kernel, dim3(1), dim3(DET_BLOCK), 0, st, (const double*)w.partial, nb, map_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -96,6 +96,11 @@ SHAPES_MAX_BLOBS, SHAPES_MAX_CMDS, SHAPES_MAX_VERTS, SHAPES_MAX_TEX, SHAPES_MAX_
                                                                                               1808, 2192, 2704)
 
 
+class SspDetEvalParams(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("remove_zero", C.c_float), ("r2", C.c_int32),
+                ("prob_thresh", C.c_float), ("simplified", C.c_int32)]
+
+
 class SspExportParams(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("conf_thresh", C.c_float),
                 ("nms_dist", C.c_int32), ("border_remove", C.c_int32), ("top_k", C.c_int32), ("subpixel", C.c_int32)]
@@ -123,12 +128,19 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_op_sem_predict", "ssp_sem_predict",
            "ssp_track_workspace_bytes", "ssp_op_track_update", "ssp_op_track_select", "ssp_op_track_points",
            "ssp_op_point_classes", "ssp_point_classes", "ssp_filter_workspace_bytes", "ssp_op_filter_points",
-           "ssp_match_two_way_classes"]
+           "ssp_match_two_way_classes",
+           "ssp_det_eval_workspace_bytes", "ssp_op_det_tp_fp", "ssp_op_det_tp_fp_points", "ssp_det_pr_curve_workspace_bytes",
+           "ssp_op_det_pr_curve"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
 TRACK_NO_SCORE = 9999.0  # score of a track that has no match yet (PointTracker.max_score)
 CLASS_NONE = 255  # SSP_CLASS_NONE (include/ssp_hip.h): the class of a row past its image's point count
+DET_EVAL_MAX_R2 = 64  # SSP_DET_EVAL_MAX_R2 (include/ssp_hip.h): largest squared match radius of the detector evaluation
+DET_EVAL_STATE_WORDS = 80  # SSP_DET_EVAL_STATE_WORDS: int64 words of an evaluation state block
+DET_EVAL_OUTSIDE = 3  # state word: point-list rows skipped because they lie outside the image (DET_STATE_OUTSIDE)
+DET_EVAL_HIST = 8  # first word of the d2 histogram in a state block (DET_STATE_HIST, csrc/detector_eval_kernels.hip.h)
+DET_CURVE_TILE = 1024  # DET_CURVE_TILE (csrc/detector_eval_kernels.hip.h): records per workgroup of the curve kernels
 
 
 def load_library(path=None):
@@ -304,6 +316,18 @@ def load_library(path=None):
         lib.ssp_filter_workspace_bytes.restype = C.c_size_t
         lib.ssp_op_filter_points.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_uint32), i, i, vp, vp, vp, vp, vp, vp]
         lib.ssp_match_two_way_classes.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, f, vp, vp, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        dp = C.POINTER(SspDetEvalParams)
+        lib.ssp_det_eval_workspace_bytes.argtypes = [dp, i, i]
+        lib.ssp_det_eval_workspace_bytes.restype = C.c_size_t
+        lib.ssp_op_det_tp_fp.argtypes = [vp, vp, i, dp, i, vp, vp, C.c_int64, vp, vp]
+        lib.ssp_op_det_tp_fp_points.argtypes = [vp, vp, i, vp, i, dp, i, vp, vp, C.c_int64, vp, vp]
+        lib.ssp_det_pr_curve_workspace_bytes.argtypes = [C.c_int64]
+        lib.ssp_det_pr_curve_workspace_bytes.restype = C.c_size_t
+        lib.ssp_op_det_pr_curve.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -1569,6 +1593,121 @@ def op_track_points(tracks, n_tracks, pts, state, first_slot=0):
         _check(lib.ssp_op_track_points(_ptr(tracks), _ptr(n_tracks), _ptr(pts), _ptr(state), L, pts.shape[1], tracks.shape[0],
                                        int(first_slot), _ptr(xy), _stream()))
     return xy
+
+
+# ---- detector evaluation against ground-truth corners (evaluations/detector_evaluation.py:15-136) ----
+def detector_eval_r2(distance_thresh):
+    """The largest integer d2 with np.sqrt(np.float64(d2)) <= distance_thresh: the reference's `dist <= distance_thresh` on
+    integer pixel offsets as an integer compare (-1: nothing matches)."""
+    d = float(distance_thresh)
+    if not d >= 0.0:
+        return -1
+    r2 = int(min(d, 1e4) ** 2) + 1
+    while r2 >= 0 and not np.sqrt(np.float64(r2)) <= np.float64(d):
+        r2 -= 1
+    return r2
+
+
+def detector_eval_state(device):
+    """An empty evaluation state block: int64 [DET_EVAL_STATE_WORDS] (records, n_gt, overflow flag, rows outside the image, d2
+    histogram)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("detector_eval_state needs a HIP device: the MI355X path has no CPU fallback")
+    return torch.zeros(DET_EVAL_STATE_WORDS, dtype=torch.int64, device=device)
+
+
+def _det_eval_args(labels, keys, state, remove_zero, r2, prob_thresh, simplified):
+    for t, nm in ((labels, "labels"), (keys, "keys"), (state, "state")):
+        _need_gpu(t, nm)
+    if labels.dtype not in (torch.float32, torch.uint8):
+        raise ValueError("labels must be float32 or uint8 (nonzero = ground truth)")
+    if labels.dim() == 4 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    if labels.dim() != 3:
+        raise ValueError("labels must be [B,H,W] (or [B,1,H,W])")
+    if keys.dtype != torch.int64 or keys.dim() != 1 or keys.numel() < 1:
+        raise ValueError("keys must be a non-empty int64 vector (its length is the record capacity)")
+    if state.dtype != torch.int64 or state.numel() != DET_EVAL_STATE_WORDS:
+        raise ValueError("state must be int64 [%d] (detector_eval_state)" % DET_EVAL_STATE_WORDS)
+    B, H, W = labels.shape
+    p = SspDetEvalParams(H, W, float(np.float32(remove_zero)), int(r2), float(np.float32(prob_thresh)), int(bool(simplified)))
+    return labels, p
+
+
+def _det_eval_ws(lib, p, B, cap, ws, device):
+    wsb = lib.ssp_det_eval_workspace_bytes(C.byref(p), int(B), int(cap))
+    if wsb == 0:
+        _check(-1)
+    if ws is None or ws.numel() < wsb:
+        ws = torch.empty(wsb, dtype=torch.uint8, device=device)
+    return ws
+
+
+def op_detector_tp_fp(prob, labels, keys, state, remove_zero=1e-4, r2=4, prob_thresh=0.5, simplified=False, ws=None):
+    """compute_tp_fp for one batch on the device (ssp_op_det_tp_fp).  prob: float32 [B,H,W] (or [B,1,H,W]), labels: float32 or
+    uint8 of the same shape; the pixels with prob > remove_zero are appended to `keys` (int64 [capacity]) as records
+    prob bits << 32 | record << 1 | tp, and `state` (detector_eval_state) is advanced: records, n_gt, overflow flag and the
+    d2 histogram of compute_loc_error.  r2: detector_eval_r2(distance_thresh).  Returns the workspace (pass it back as `ws`
+    to reuse it).  No host synchronisation."""
+    lib = load_library()
+    _need_gpu(prob, "prob")
+    labels, p = _det_eval_args(labels, keys, state, remove_zero, r2, prob_thresh, simplified)
+    B, H, W = labels.shape
+    if prob.dtype != torch.float32 or prob.numel() != labels.numel() or tuple(prob.shape[-2:]) != (H, W):
+        raise ValueError("prob must be float32 with the labels' shape [%d,%d,%d]" % (B, H, W))
+    ws = _det_eval_ws(lib, p, B, 0, ws, prob.device)
+    with torch.cuda.device(prob.device):
+        _check(lib.ssp_op_det_tp_fp(_ptr(prob), _ptr(labels), int(labels.dtype == torch.uint8), C.byref(p), B, _ptr(ws),
+                                    _ptr(keys), keys.numel(), _ptr(state), _stream()))
+    return ws
+
+
+def op_detector_tp_fp_points(pts, count, labels, keys, state, remove_zero=1e-4, r2=4, prob_thresh=0.5, simplified=False, ws=None):
+    """op_detector_tp_fp for point lists (ssp_op_det_tp_fp_points): pts float32 [B,cap,5] rows (x, y, confidence, ..) with count
+    int32 [B], as Engine.describe_points / op_heatmap_points produce them.  The rows < count with confidence > remove_zero are
+    the candidates, in list order; rows outside the image are skipped and counted in state word DET_EVAL_OUTSIDE."""
+    lib = load_library()
+    _need_gpu(pts, "pts")
+    _need_gpu(count, "count")
+    labels, p = _det_eval_args(labels, keys, state, remove_zero, r2, prob_thresh, simplified)
+    B = labels.shape[0]
+    if pts.dtype != torch.float32 or pts.dim() != 3 or pts.shape[0] != B or pts.shape[2] != 5 or pts.shape[1] < 1:
+        raise ValueError("pts must be float32 [%d, cap >= 1, 5] rows (x, y, confidence, sx, sy)" % B)
+    if count.dtype != torch.int32 or count.numel() != B:
+        raise ValueError("count must be int32 [%d]" % B)
+    cap = pts.shape[1]
+    ws = _det_eval_ws(lib, p, B, cap, ws, pts.device)
+    with torch.cuda.device(pts.device):
+        _check(lib.ssp_op_det_tp_fp_points(_ptr(pts), _ptr(count), cap, _ptr(labels), int(labels.dtype == torch.uint8),
+                                           C.byref(p), B, _ptr(ws), _ptr(keys), keys.numel(), _ptr(state), _stream()))
+    return ws
+
+
+def op_detector_pr_curve(sorted_keys, state):
+    """compute_pr + compute_mAP over keys sorted in descending order (ssp_op_det_pr_curve; torch.sort(keys[:n], descending=True)
+    is the sort: the keys are unique).  Returns device tensors {"prob": float32 [n], "tp": uint8 [n], "precision", "recall":
+    float64 [n+2], "mAP": float64 [1]}."""
+    lib = load_library()
+    _need_gpu(sorted_keys, "sorted_keys")
+    _need_gpu(state, "state")
+    if sorted_keys.dtype != torch.int64 or sorted_keys.dim() != 1:
+        raise ValueError("sorted_keys must be an int64 vector")
+    if state.dtype != torch.int64 or state.numel() != DET_EVAL_STATE_WORDS:
+        raise ValueError("state must be int64 [%d] (detector_eval_state)" % DET_EVAL_STATE_WORDS)
+    n, dev = sorted_keys.numel(), sorted_keys.device
+    wsb = lib.ssp_det_pr_curve_workspace_bytes(n)
+    if wsb == 0:
+        _check(-1)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = {"prob": torch.empty(n, dtype=torch.float32, device=dev), "tp": torch.empty(n, dtype=torch.uint8, device=dev),
+           "precision": torch.empty(n + 2, dtype=torch.float64, device=dev),
+           "recall": torch.empty(n + 2, dtype=torch.float64, device=dev), "mAP": torch.empty(1, dtype=torch.float64, device=dev)}
+    with torch.cuda.device(dev):
+        _check(lib.ssp_op_det_pr_curve(_ptr(sorted_keys) if n else None, n, _ptr(state), _ptr(ws), _ptr(out["prob"]) if n else None,
+                                       _ptr(out["tp"]) if n else None, _ptr(out["precision"]), _ptr(out["recall"]),
+                                       _ptr(out["mAP"]), _stream()))
+    return out
 
 
 def _eval_points(pts, counts, name):
