@@ -904,8 +904,10 @@ __global__ __launch_bounds__(256) void desc_normalize_bwd_kernel(const float* __
 }
 
 // Adam (torch.optim.Adam defaults: betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad)
+// step_size = lr / (1 - 0.9^t) and bc2_sqrt = sqrt(1 - 0.999^t) come from the host (adam_scalars() of ssp.hip: evaluated in double,
+// rounded to fp32 once each)
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long n, float lr, float bc1, float bc2_sqrt) {
+                            float* __restrict__ v, long n, float step_size, float bc2_sqrt) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float gi = g[i];
@@ -914,12 +916,12 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   m[i] = mi;
   v[i] = vi;
   const float denom = sqrtf(vi) / bc2_sqrt + 1e-8f;
-  p[i] -= (lr / bc1) * (mi / denom);
+  p[i] -= step_size * (mi / denom);
 }
 
 // the same step on g * gscale (data parallel: gscale = 1 / world after the all-reduce SUM), leaving g untouched
 __global__ void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                   float* __restrict__ v, long n, float lr, float bc1, float bc2_sqrt, float gscale) {
+                                   float* __restrict__ v, long n, float step_size, float bc2_sqrt, float gscale) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float gi = g[i] * gscale;
@@ -928,7 +930,7 @@ __global__ void adam_scaled_kernel(float* __restrict__ p, const float* __restric
   m[i] = mi;
   v[i] = vi;
   const float denom = sqrtf(vi) / bc2_sqrt + 1e-8f;
-  p[i] -= (lr / bc1) * (mi / denom);
+  p[i] -= step_size * (mi / denom);
 }
 
 }  // namespace sspk

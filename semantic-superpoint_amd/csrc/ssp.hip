@@ -1543,6 +1543,18 @@ int ssp_profile_read_executed(ssp_handle* h, double* executed_flops) {
 // forward / backward of one activation slot
 // ------------------------------------------------------------------------------------------------
 static const float* P(const ssp_handle* h, size_t off) { return h->buf.params_dev + off; }
+
+// The per-step scalars of Adam, shared by ssp_adam_step and ssp_adam_step_scaled.  The bias corrections 1 - beta^t are evaluated in
+// double like torch.optim.Adam does and each quantity is rounded to fp32 once: in fp32, 1 - 0.999f loses ~1.3e-5 to cancellation,
+// which put the step size sqrt(bc2) / bc1 off by up to 1e-5 (170 units of 2^-24) in every early step.
+struct AdamScalars {
+  float step_size;  // lr / (1 - 0.9^t)
+  float bc2_sqrt;   // sqrt(1 - 0.999^t)
+};
+static AdamScalars adam_scalars(float lr, int step) {
+  const double bc1 = 1.0 - pow(0.9, (double)step), bc2 = 1.0 - pow(0.999, (double)step);
+  return {(float)((double)lr / bc1), (float)sqrt(bc2)};
+}
 static float* Gd(const ssp_handle* h, size_t off) { return h->buf.grads_dev + off; }
 
 // BatchNorm statistics -> affine of layer l for every view of the set, ONE launch (view 0 then view 1 in the same thread)
@@ -2788,10 +2800,9 @@ int ssp_adam_step(ssp_handle* h, float lr, int step, void* stream) {
     return fail(-1, "handle not bound with gradient and Adam state buffers");
   if (step < 1) return fail(-1, "Adam step index starts at 1");
   const long n = (long)h->n_params + 3;
-  const float bc1 = 1.f - powf(0.9f, (float)step);
-  const float bc2 = 1.f - powf(0.999f, (float)step);
+  const AdamScalars a = adam_scalars(lr, step);
   hipLaunchKernelGGL(adam_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, h->buf.params_dev,
-                     h->buf.grads_dev, h->buf.adam_m_dev, h->buf.adam_v_dev, n, lr, bc1, sqrtf(bc2));
+                     h->buf.grads_dev, h->buf.adam_m_dev, h->buf.adam_v_dev, n, a.step_size, a.bc2_sqrt);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3040,10 +3051,9 @@ int ssp_adam_step_scaled(ssp_handle* h, float lr, int step, float grad_scale, vo
     return fail(-1, "handle not bound with gradient and Adam state buffers");
   if (step < 1) return fail(-1, "Adam step index starts at 1");
   const long n = (long)h->n_params + 3;
-  const float bc1 = 1.f - powf(0.9f, (float)step);
-  const float bc2 = 1.f - powf(0.999f, (float)step);
+  const AdamScalars a = adam_scalars(lr, step);
   hipLaunchKernelGGL(adam_scaled_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, h->buf.params_dev,
-                     h->buf.grads_dev, h->buf.adam_m_dev, h->buf.adam_v_dev, n, lr, bc1, sqrtf(bc2), grad_scale);
+                     h->buf.grads_dev, h->buf.adam_m_dev, h->buf.adam_v_dev, n, a.step_size, a.bc2_sqrt, grad_scale);
   HIPCHK(hipGetLastError());
   return 0;
 }
