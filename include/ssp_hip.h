@@ -704,6 +704,16 @@ int ssp_op_sparse_loss(const float* desc_a_nhwc_dev, const float* desc_b_nhwc_de
                        const int32_t* match_b_dev, const int32_t* nonmatch_b_dev, int b, int hc, int wc, int n_match,
                        int n_non, int method, int dist, float coef_pos, float coef_neg, float* dd_a_nhwc_dev, float* dd_b_nhwc_dev,
                        float* out2_dev, void* stream);
+/* The same with the path of the match term's gradient chosen by the caller.  gather: 1 = per-cell gather over corner lists (two
+ * gradient rows per match, no atomics for the match term: a fixed summation order), 0 = atomic scatter, -1 = the process default
+ * (SSP_DESC_GATHER, default 1).  csr_*_dev (all three or none; gather path with gradients only) receive the corner lists: for
+ * list = image * 2 + side, csr_off [b * 2][hc * wc + 1] offsets per cell, csr_match / csr_weight [b * 2][4 * n_match] the match
+ * index and bilinear weight of every corner with a non-zero weight, sorted by cell and, within a cell, by match index. */
+int ssp_op_sparse_loss_path(const float* desc_a_nhwc_dev, const float* desc_b_nhwc_dev, const int32_t* match_a_dev,
+                            const int32_t* match_b_dev, const int32_t* nonmatch_b_dev, int b, int hc, int wc, int n_match,
+                            int n_non, int method, int dist, float coef_pos, float coef_neg, float* dd_a_nhwc_dev, float* dd_b_nhwc_dev,
+                            float* out2_dev, int gather, int32_t* csr_off_dev, int32_t* csr_match_dev, float* csr_weight_dev,
+                            void* stream);
 
 /* Dense descriptor loss as an operator (utils/utils.py:779-893) on NHWC descriptor maps [B][hc*wc][256]:
  * out3_dev = {loss_desc, pos_sum, neg_sum}; with dda_dev / ddb_dev (both or none) also the gradients of

@@ -879,13 +879,70 @@ __global__ __launch_bounds__(256) void desc_normalize_kernel(const float* __rest
   if (lane == 0) inv_norm[wave] = inv;
 }
 
+// Match term of the sparse descriptor loss as a GATHER (desc_csr_kernel / desc_match_kernel<.., GATHER> of loss_kernels.hip.h): per
+// (image, side) a list of (match, corner weight) sorted by corner cell, and per match two sample-space gradient rows
+// rows[(image * n_match + match) * 2 + side][256].  off == nullptr: no gather.
+struct DescGather {
+  const int32_t* off;     // [B * 2][cells + 1] list (image * 2 + side): entries off[c] .. off[c + 1] - 1 land in cell c
+  const int32_t* match;   // [B * 2][4 * n_match] match index, ascending within a cell
+  const float* weight;    // [B * 2][4 * n_match] bilinear weight of the corner
+  const float* rows;
+  int cells, n_match;     // cells per image
+};
+// one wave per cell: g += sum over the cell's list, in list order (one fixed summation order); lane l holds channels 4 l .. 4 l + 3,
+// every row load of the wave is 1 KB contiguous
+__device__ __forceinline__ float4 desc_gather_cell(const DescGather& G, int cell, int side, int lane, float4 g) {
+  const int img = cell / G.cells, c = cell - img * G.cells;
+  const int list = img * 2 + side;
+  const int32_t* off = G.off + (size_t)list * (G.cells + 1);
+  const int e0 = off[c], e1 = off[c + 1];   // wave-uniform
+  const int32_t* em = G.match + (size_t)list * 4 * G.n_match;
+  const float* ew = G.weight + (size_t)list * 4 * G.n_match;
+  const float* rows = G.rows + ((size_t)img * G.n_match * 2 + side) * 256 + lane * 4;
+  for (int b0 = e0; b0 < e1; b0 += 64) {
+    // the lanes fetch up to 64 entries with one load each; the rows then go four at a time, their loads independent of each
+    // other (a loop over em[e] -> row would chain two L2 latencies per entry).  Slots past the list repeat its last entry with
+    // weight 0: a valid, cached row that adds nothing.
+    const int n = min(64, e1 - b0);
+    const int le = b0 + min(lane, n - 1);
+    const int ml = em[le];
+    const int wl = lane < n ? __float_as_int(ew[le]) : 0;
+    for (int i = 0; i < n; i += 4) {
+      float4 r[4];
+      float w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int s = min(i + u, 63);   // wave-uniform
+        w[u] = __int_as_float(__builtin_amdgcn_readlane(wl, s));
+        r[u] = *reinterpret_cast<const float4*>(rows + (size_t)__builtin_amdgcn_readlane(ml, s) * 512);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        g.x = fmaf(w[u], r[u].x, g.x); g.y = fmaf(w[u], r[u].y, g.y); g.z = fmaf(w[u], r[u].z, g.z); g.w = fmaf(w[u], r[u].w, g.w);
+      }
+    }
+  }
+  return g;
+}
+// the gather alone (ssp_op_sparse_loss: gradients with respect to the normalised descriptors); blockIdx.y = side
+__global__ __launch_bounds__(256) void desc_gather_kernel(float* __restrict__ d0, float* __restrict__ d1, int ncells, DescGather G) {
+  float* __restrict__ d = blockIdx.y != 0 ? d1 : d0;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (wave >= ncells) return;
+  float4* p = reinterpret_cast<float4*>(d + (size_t)wave * 256 + lane * 4);
+  *p = desc_gather_cell(G, wave, (int)blockIdx.y, lane, *p);
+}
+
 // backward of the L2 normalisation: d_raw = (d - desc * <desc, d>) * inv_norm   (in place on d)
+// G.off != nullptr: d first receives the match term of the sparse descriptor loss (desc_gather_cell; view = side)
 __global__ __launch_bounds__(256) void desc_normalize_bwd_kernel(const float* __restrict__ desc0,
                                                                  const float* __restrict__ inv_norm0,
                                                                  float* __restrict__ d0, int ncells,
                                                                  const float* __restrict__ desc1 = nullptr,
                                                                  const float* __restrict__ inv_norm1 = nullptr,
-                                                                 float* __restrict__ d1 = nullptr) {   // (blockIdx.y = view)
+                                                                 float* __restrict__ d1 = nullptr,   // (blockIdx.y = view)
+                                                                 DescGather G = DescGather{nullptr, nullptr, nullptr, nullptr, 0, 0}) {
   const bool v1 = blockIdx.y != 0;
   const float* __restrict__ desc = v1 ? desc1 : desc0;
   const float* __restrict__ inv_norm = v1 ? inv_norm1 : inv_norm0;
@@ -895,6 +952,7 @@ __global__ __launch_bounds__(256) void desc_normalize_bwd_kernel(const float* __
   if (wave >= ncells) return;
   const float4 n = *reinterpret_cast<const float4*>(desc + (size_t)wave * 256 + lane * 4);
   float4 g = *reinterpret_cast<const float4*>(d + (size_t)wave * 256 + lane * 4);
+  if (G.off != nullptr) g = desc_gather_cell(G, wave, v1 ? 1 : 0, lane, g);
   float s = n.x * g.x + n.y * g.y + n.z * g.z + n.w * g.w;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);

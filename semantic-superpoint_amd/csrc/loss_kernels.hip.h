@@ -265,13 +265,17 @@ __device__ __forceinline__ int desc_wave_of_block(int B, int n_match, int& img) 
 // Channel mapping: lane l holds channels l, l+64, l+128, l+192, so every load AND every atomic instruction of a wave
 // covers 256 contiguous bytes (with 4 consecutive channels per lane the scatter hit each cache line 4 times).
 // EUC (compile time: the shipped form keeps its instruction stream): dist "euclidean"; flags & DESC_METHOD_1D (run time): method "1d"
-template <bool BWD, bool EUC = false>
+// GATHER (with BWD): no scatter.  The kernel stores the two sample-space gradient rows of its match, d term / d (sampled a) and
+// d term / d (sampled b), to g_rows[(image * n_match + match) * 2 + side][256] with plain 256-byte stores (zeros where the hinge is
+// inactive); the corner weights are applied by the per-cell gather over the lists of desc_csr_kernel (desc_gather_cell, bn_kernels.hip.h).
+template <bool BWD, bool EUC = false, bool GATHER = false>
 __global__ __launch_bounds__(256) void desc_match_kernel(const float* __restrict__ desc_a, const float* __restrict__ desc_b,
                                                          const int32_t* __restrict__ match_a,
                                                          const int32_t* __restrict__ match_b, float* __restrict__ dd_a,
                                                          float* __restrict__ dd_b, StepAccum* __restrict__ acc, int B,
-                                                         int Hc, int Wc, int n_match, int flags) {
-  const DetTarget t_a = det_resolve(dd_a), t_b = det_resolve(dd_b);   // (deterministic mode: fixed-point shadows)
+                                                         int Hc, int Wc, int n_match, int flags, float* __restrict__ g_rows = nullptr) {
+  const DetTarget t_a = GATHER ? DetTarget{nullptr, nullptr} : det_resolve(dd_a);   // (deterministic mode: fixed-point shadows)
+  const DetTarget t_b = GATHER ? DetTarget{nullptr, nullptr} : det_resolve(dd_b);
   int img;
   const int w = desc_wave_of_block(B, n_match, img);  // one wave per match, images pinned to XCDs
   const int lane = threadIdx.x & 63;
@@ -313,7 +317,16 @@ __global__ __launch_bounds__(256) void desc_match_kernel(const float* __restrict
   // (the gradient of the match term does not depend on any sum over the batch - coef_pos is set by step_begin_kernel - so a training
   // step runs the BWD instantiation alone: loss sum and scatter from one gather of the eight corner rows)
   if (lane == 0) acc_add_loss(&acc->pos_sum[img * 16 + ((w >> 2) & 15)], (double)term);  // 16 replicas / image
-  if (BWD && (euc || term > 0.f)) {
+  if (BWD && GATHER) {
+    const bool on = euc || term > 0.f;
+    const float c = on ? acc->coef_pos / ((float)n_match * (float)B) * (euc ? 2.f : -1.f) : 0.f;
+    float* ga = g_rows + (size_t)w * 512 + lane;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ga[64 * j] = on ? c * (euc ? va[j] - vb[j] : vb[j]) : 0.f;
+      ga[256 + 64 * j] = on ? c * (euc ? vb[j] - va[j] : va[j]) : 0.f;
+    }
+  } else if (BWD && (euc || term > 0.f)) {
     const float c = acc->coef_pos / ((float)n_match * (float)B) * (euc ? 2.f : -1.f);  // d total / d <a, b>  resp.  d total / d (a - b) / (a - b)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {   // (method "1d": the weights of corners 1 - 3 are 0)
@@ -326,6 +339,100 @@ __global__ __launch_bounds__(256) void desc_match_kernel(const float* __restrict
         for (int j = 0; j < 4; ++j) facc_add(t_b, dd_b + base + (size_t)ib[k] * 256 + 64 * j, wb[k] * c * (euc ? vb[j] - va[j] : va[j]));
       }
     }
+  }
+}
+
+// Per-cell corner lists of the match term (CSR), from the index arrays alone: for every (image, side) the corners of the image's
+// matches with a non-zero weight - the ones desc_match_kernel scatters to - sorted by the cell they land in and, within a cell,
+// by ascending match index (one fixed summation order for the gather).  Corner cells and weights come from bilin_setup /
+// bilin_cell as in desc_match_kernel.  A match reaches a cell through at most one corner: two corners share a cell only where one of
+// them is clamped at the border, and that one has weight 0.
+// grid (B, 2 sides), one workgroup per list; dynamic LDS: (2 cells + 1 + 8 n_match) words (desc_csr_lds_bytes).
+//   count -> exclusive scan -> fill in arrival order (LDS) -> rank within the cell -> global
+static inline size_t desc_csr_lds_bytes(int cells, int n_match) { return ((size_t)2 * cells + 1 + (size_t)8 * n_match) * 4; }
+constexpr int DESC_CSR_THREADS = 1024;
+// (an index array with a cell outside the grid must not reach past the LDS counters; valid cells pass unchanged)
+__device__ __forceinline__ int csr_cell(int c, int cells) { return min(max(c, 0), cells - 1); }
+__global__ __launch_bounds__(DESC_CSR_THREADS) void desc_csr_kernel(const int32_t* __restrict__ match_a, const int32_t* __restrict__ match_b,
+                                                                    int32_t* __restrict__ off_out, int32_t* __restrict__ match_out,
+                                                                    float* __restrict__ weight_out, int Hc, int Wc, int n_match,
+                                                                    int flags) {
+  extern __shared__ __align__(16) int csr_lds[];
+  __shared__ int part[DESC_CSR_THREADS];
+  const int cells = Hc * Wc;
+  int* off = csr_lds;                 // [cells + 1]
+  int* cur = off + cells + 1;         // [cells]
+  int* tm = cur + cells;              // [4 n_match] entries in arrival order
+  float* tw = reinterpret_cast<float*>(tm + 4 * n_match);
+  const int img = blockIdx.x, side = blockIdx.y, list = img * 2 + side;
+  const int32_t* __restrict__ mt = (side ? match_b : match_a) + (size_t)img * n_match;
+  const bool m1d = (flags & DESC_METHOD_1D) != 0;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int c = tid; c <= cells; c += nt) off[c] = 0;
+  __syncthreads();
+  // count (off[c + 1] = entries of cell c)
+  for (int k = tid; k < n_match; k += nt) {
+    const Bilin b = m1d ? bilin_cell(mt[k]) : bilin_setup(mt[k], Hc, Wc);
+    const int ci[4] = {csr_cell(b.i00, cells), csr_cell(b.i01, cells), csr_cell(b.i10, cells), csr_cell(b.i11, cells)};
+    const float cw[4] = {b.w00, b.w01, b.w10, b.w11};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (cw[q] != 0.f) atomicAdd(&off[ci[q] + 1], 1);
+  }
+  __syncthreads();
+  // inclusive scan of off[1 .. cells] (off[0] = 0): a contiguous chunk per thread, Hillis-Steele over the chunk sums
+  const int per = (cells + nt - 1) / nt;
+  const int c0 = min(tid * per, cells), c1 = min(c0 + per, cells);
+  int sum = 0;
+  for (int c = c0; c < c1; ++c) sum += off[c + 1];
+  part[tid] = sum;
+  __syncthreads();
+  for (int o = 1; o < nt; o <<= 1) {
+    const int v = tid >= o ? part[tid - o] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  int run = part[tid] - sum;   // entries in front of this thread's chunk
+  for (int c = c0; c < c1; ++c) {
+    cur[c] = run;
+    run += off[c + 1];
+    off[c + 1] = run;
+  }
+  __syncthreads();
+  int32_t* __restrict__ go = off_out + (size_t)list * (cells + 1);
+  for (int c = tid; c <= cells; c += nt) go[c] = off[c];
+  // fill, in whatever order the LDS atomics arrive
+  for (int k = tid; k < n_match; k += nt) {
+    const Bilin b = m1d ? bilin_cell(mt[k]) : bilin_setup(mt[k], Hc, Wc);
+    const int ci[4] = {csr_cell(b.i00, cells), csr_cell(b.i01, cells), csr_cell(b.i10, cells), csr_cell(b.i11, cells)};
+    const float cw[4] = {b.w00, b.w01, b.w10, b.w11};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (cw[q] != 0.f) {
+        const int p = atomicAdd(&cur[ci[q]], 1);
+        tm[p] = k;
+        tw[p] = cw[q];
+      }
+  }
+  __syncthreads();
+  // order fix: an entry's place within its cell is the number of entries of the cell with a smaller match index.  Every thread
+  // takes entries, not cells, so a cell that holds every match costs 4 n_match compares per thread at the most.
+  int32_t* __restrict__ gm = match_out + (size_t)list * 4 * n_match;
+  float* __restrict__ gw = weight_out + (size_t)list * 4 * n_match;
+  const int total = off[cells];
+  for (int p = tid; p < total; p += nt) {
+    // the cell of entry p: the last c with off[c] <= p (binary search over the non-decreasing offsets)
+    int lo = 0, hi = cells - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (off[mid] <= p) lo = mid; else hi = mid - 1;
+    }
+    const int b0 = off[lo], b1 = off[lo + 1], mk = tm[p];
+    int rank = 0;
+    for (int q = b0; q < b1; ++q) rank += tm[q] < mk ? 1 : 0;
+    gm[b0 + rank] = mk;
+    gw[b0 + rank] = tw[p];
   }
 }
 

@@ -191,6 +191,12 @@ struct ssp_handle {
                                 // (bf16_fuse_apply_env: tests switch it between two steps of one process) and part of the graph key
   StepAccum* accum;
   float* dots;       // [B * n_match * n_non] non-match dot products of the current step
+  // match term of the sparse descriptor loss as a gather (desc_csr_kernel, desc_match_kernel<.., GATHER>, desc_gather_cell).
+  // SSP_DESC_GATHER=0 (read ONCE, at ssp_create; part of the graph key): the atomic scatter of desc_match_kernel instead.
+  bool desc_gather = true;
+  int32_t *csr_off = nullptr, *csr_match = nullptr;   // [B * 2][cells + 1], [B * 2][4 n_match]
+  float* csr_weight = nullptr;                        // [B * 2][4 n_match]
+  float* g_rows = nullptr;                            // [B * n_match * 2][256] sample-space gradient rows of the current step
   float* dense_coef; // [B * cells * cells] d total / d dot of the dense descriptor loss (cfg.dense_loss), else nullptr
   int sout_cs;
   int conv_algo;     // ssp_handle_set_conv_algo (initialised from the process default of ssp_set_conv_algo)
@@ -404,6 +410,12 @@ static size_t carve(ssp_handle* h, void* base) {
   h->accum = c.take<StepAccum>(1);
   h->graph_seed = c.take<uint64_t>(1);
   h->dots = c.take<float>((size_t)B * h->cfg.n_match * h->cfg.n_non);
+  if (h->desc_gather) {
+    h->csr_off = c.take<int32_t>((size_t)B * 2 * ((size_t)(H / 8) * (W / 8) + 1));
+    h->csr_match = c.take<int32_t>((size_t)B * 2 * 4 * h->cfg.n_match);
+    h->csr_weight = c.take<float>((size_t)B * 2 * 4 * h->cfg.n_match);
+    h->g_rows = c.take_skewed<float>((size_t)B * h->cfg.n_match * 2 * 256);
+  }
   {
     const size_t pc = (size_t)(H / 8) * (W / 8);
     h->dense_coef = h->cfg.dense_loss ? c.take_skewed<float>((size_t)std::min(B, 64) * pc * pc) : nullptr;
@@ -1243,6 +1255,7 @@ static int l0_resident_grid(K kern, const ssp_handle* h, int nviews, long rows, 
 static int flush_wgrad_reduce_bf16(ssp_handle* h, hipStream_t st) { return h->rq_bf16 != nullptr ? h->rq_bf16->flush(st) : 0; }
 
 static int ensure_aux_stream(ssp_handle* h);
+static bool desc_gather_env();
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -1398,6 +1411,7 @@ int ssp_create(const ssp_config* cfg, ssp_handle** out) {
   if (h->cfg.n_match <= 0) h->cfg.n_match = 1000;
   if (h->cfg.n_non <= 0) h->cfg.n_non = 100;
   h->conv_algo = g_default_conv_algo;
+  h->desc_gather = desc_gather_env();
   h->rq_bf16 = new WredBQueue();
   AlgoScope algo(h);
   build_layers(h);
@@ -2814,6 +2828,11 @@ int ssp_adam_step(ssp_handle* h, float lr, int step, void* stream) {
 // Segmentation loss of one view.  algo 0: the step's choice - the (x, class) lane form (sem_ce_xc_kernel) when the label map is exactly
 // 8x the logit map and the classes fit its 9 x 16 slots, the pixels-then-classes form (sem_ce_kernel) otherwise; SSP_SEM_XC=0 keeps
 // the latter everywhere (same-box A/B).  1 / 2 force a form (2 fails on shapes it does not cover).
+// SSP_DESC_GATHER=0 (same-box A/B, fallback): the match term of the sparse descriptor loss scatters with atomics
+static bool desc_gather_env() {
+  static const int v = getenv("SSP_DESC_GATHER") ? atoi(getenv("SSP_DESC_GATHER")) : 1;
+  return v != 0;
+}
 static int sem_xc_env() {
   static const int v = [] { const char* e = getenv("SSP_SEM_XC"); return e ? atoi(e) : 1; }();
   return v;
@@ -2846,6 +2865,20 @@ static int launch_sem_ce(int algo, bool train, const float* sout, const int64_t*
       else hipLaunchKernelGGL((sem_ce_kernel<1>), dim3(grid), dim3(256), 0, st, so, la, ds, acc, view + v, B, Hc, Wc, H, W, C, cs);
     }
   }
+  return 0;
+}
+
+// per-cell corner lists of the match term for both sides of every pair (desc_csr_kernel): one launch, index arrays only
+static int launch_desc_csr(const int32_t* match_a, const int32_t* match_b, int32_t* off, int32_t* em, float* ew, int B, int Hc, int Wc,
+                           int n_match, int dflags, hipStream_t st) {
+  const size_t lds = desc_csr_lds_bytes(Hc * Wc, n_match);
+  constexpr size_t lds_max = 128 * 1024;
+  if (lds > lds_max) return fail(-1, "desc_csr: %d cells x %d matches need %zu B of LDS (> %zu)", Hc * Wc, n_match, lds, lds_max);
+  static AttrOnce attr_once;
+  if (attr_once.need())
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(desc_csr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+  hipLaunchKernelGGL(desc_csr_kernel, dim3(B, 2), dim3(DESC_CSR_THREADS), lds, st, match_a, match_b, off, em, ew, Hc, Wc, n_match, dflags);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 
@@ -2896,7 +2929,12 @@ static int pair_step_impl(ssp_handle* h, const ssp_pair_inputs* in, float* scala
   const float* masks[2] = {in->valid_mask_dev, in->warped_valid_mask_dev};
   const int64_t* sems[2] = {in->semantic_dev, in->warped_semantic_dev};
   const bool zero_dsout = semantic && in->train;
+  // the corner lists of the match term need the index arrays only: beside the forward pass as well
+  const bool gather = h->desc_gather && in->train && use_desc && !dense;
+  const int dflags = (in->sparse_method != 0 ? DESC_METHOD_1D : 0) | (in->sparse_dist != 0 ? DESC_EUCLIDEAN : 0);
   auto label_kernels = [&](hipStream_t se) -> int {
+    if (gather)
+      CHK(launch_desc_csr(in->match_a_dev, in->match_b_dev, h->csr_off, h->csr_match, h->csr_weight, B, Hc, Wc, h->cfg.n_match, dflags, se));
     hipLaunchKernelGGL(cell_mask_kernel, dim3(std::min(cdiv(ncells, 4), 512), nv), dim3(256), 0, se, masks[0], h->slot[0].cellmask,
                        &h->accum->mask_cnt[0], B, H, W, masks[nv - 1], h->slot[nv - 1].cellmask, &h->accum->mask_cnt[nv - 1]);
     if (semantic)
@@ -2952,7 +2990,6 @@ static int pair_step_impl(ssp_handle* h, const ssp_pair_inputs* in, float* scala
     HIPCHK(hipGetLastError());
   } else if (use_desc) {
     Slot &A = h->slot[0], &Bs = h->slot[1];
-    const int dflags = (in->sparse_method != 0 ? DESC_METHOD_1D : 0) | (in->sparse_dist != 0 ? DESC_EUCLIDEAN : 0);
     const bool euc = (dflags & DESC_EUCLIDEAN) != 0;
     const dim3 dgrid(desc_grid(B, h->cfg.n_match));
 #define SSP_DESC(KERNEL, ...)                                                                 \
@@ -2971,19 +3008,27 @@ static int pair_step_impl(ssp_handle* h, const ssp_pair_inputs* in, float* scala
     SSP_DESC(desc_nonmatch_fwd_kernel, A.desc, Bs.desc, in->match_a_dev, in->nonmatch_b_dev, in->train ? h->dots : (float*)nullptr, h->accum,
              B, Hc, Wc, h->cfg.n_match, h->cfg.n_non, dflags)
     if (in->train) {
-      if (!early) {
+      if (!early) {   // (early: zeroed by the descriptor normalisation of the forward pass; the non-match atomics need a zeroed target either way)
         CHK(dev_zero(A.ddesc, (size_t)ncells * 256 * sizeof(float), sd));
         CHK(dev_zero(Bs.ddesc, (size_t)ncells * 256 * sizeof(float), sd));
       }
-      SSP_DESC_MATCH(true, A.desc, Bs.desc, in->match_a_dev, in->match_b_dev, A.ddesc, Bs.ddesc, h->accum, B, Hc, Wc, h->cfg.n_match, dflags)
+      if (gather) {   // two gradient rows per match instead of the scatter; desc_normalize_bwd_kernel below gathers them per cell
+        if (euc) hipLaunchKernelGGL((desc_match_kernel<true, true, true>), dgrid, dim3(256), 0, sd, A.desc, Bs.desc, in->match_a_dev, in->match_b_dev,
+                                    (float*)nullptr, (float*)nullptr, h->accum, B, Hc, Wc, h->cfg.n_match, dflags, h->g_rows);
+        else hipLaunchKernelGGL((desc_match_kernel<true, false, true>), dgrid, dim3(256), 0, sd, A.desc, Bs.desc, in->match_a_dev, in->match_b_dev,
+                                (float*)nullptr, (float*)nullptr, h->accum, B, Hc, Wc, h->cfg.n_match, dflags, h->g_rows);
+      } else
+        SSP_DESC_MATCH(true, A.desc, Bs.desc, in->match_a_dev, in->match_b_dev, A.ddesc, Bs.ddesc, h->accum, B, Hc, Wc, h->cfg.n_match, dflags)
       SSP_DESC(desc_nonmatch_bwd_kernel, A.desc, Bs.desc, in->match_a_dev, in->nonmatch_b_dev, h->dots, A.ddesc, Bs.ddesc, h->accum, B, Hc, Wc,
                h->cfg.n_match, h->cfg.n_non, dflags)
 #undef SSP_DESC
 #undef SSP_DESC_MATCH
       CHK(det_fold(A.ddesc, sd));   // (deterministic mode) the scattered gradients: fixed-point shadow -> tensor
       CHK(det_fold(Bs.ddesc, sd));
+      // (the gather adds to the folded tensor in list order: the match term needs no fixed-point shadow in deterministic mode)
+      const DescGather dg = {gather ? h->csr_off : nullptr, h->csr_match, h->csr_weight, h->g_rows, Hc * Wc, h->cfg.n_match};
       hipLaunchKernelGGL(desc_normalize_bwd_kernel, dim3(cdiv(ncells, 4), 2), dim3(256), 0, sd, A.desc, A.inv_norm, A.ddesc, ncells,
-                         Bs.desc, Bs.inv_norm, Bs.ddesc);
+                         Bs.desc, Bs.inv_norm, Bs.ddesc, dg);
     }
     HIPCHK(hipGetLastError());
   }
@@ -3086,14 +3131,15 @@ int ssp_pair_step_graph(ssp_handle* h, const ssp_pair_inputs* in, float* scalars
   if (st == nullptr) return fail(-1, "ssp_pair_step_graph needs a non-default stream (stream capture)");
   if (h->tap_arena != nullptr) return fail(-1, "ssp_pair_step_graph: backward taps are on (ssp_debug_backward_taps); they need the eager step");
   // key = everything a captured launch depends on except the seed (kept in device memory)
-  std::vector<unsigned char> key(sizeof(ssp_pair_inputs) + sizeof(void*) + 4 * sizeof(int));
+  std::vector<unsigned char> key(sizeof(ssp_pair_inputs) + sizeof(void*) + 5 * sizeof(int));
   {
     ssp_pair_inputs k;
     memcpy(&k, in, sizeof(k));  // bytewise (padding included: the caller's struct is the key)
     k.seed = 0;
     memcpy(key.data(), &k, sizeof(k));
     memcpy(key.data() + sizeof(k), &scalars_dev, sizeof(void*));
-    const int extra[4] = {phase, sample_indices, h->conv_algo, bf16_fuse_apply_env() ? 1 : 0};   // (a captured backward freezes the switch)
+    const int extra[5] = {phase, sample_indices, h->conv_algo, bf16_fuse_apply_env() ? 1 : 0,   // (a captured backward freezes the switch)
+                          h->desc_gather ? 1 : 0};
     memcpy(key.data() + sizeof(k) + sizeof(void*), extra, sizeof(extra));
   }
   hipGraphExec_t exec = nullptr;
@@ -4280,6 +4326,15 @@ int ssp_op_sparse_loss(const float* desc_a_nhwc_dev, const float* desc_b_nhwc_de
                        const int32_t* match_b_dev, const int32_t* nonmatch_b_dev, int b, int hc, int wc, int n_match,
                        int n_non, int method, int dist, float coef_pos, float coef_neg, float* dd_a_nhwc_dev, float* dd_b_nhwc_dev,
                        float* out2_dev, void* stream) {
+  return ssp_op_sparse_loss_path(desc_a_nhwc_dev, desc_b_nhwc_dev, match_a_dev, match_b_dev, nonmatch_b_dev, b, hc, wc, n_match, n_non, method,
+                                 dist, coef_pos, coef_neg, dd_a_nhwc_dev, dd_b_nhwc_dev, out2_dev, -1, nullptr, nullptr, nullptr, stream);
+}
+
+int ssp_op_sparse_loss_path(const float* desc_a_nhwc_dev, const float* desc_b_nhwc_dev, const int32_t* match_a_dev,
+                            const int32_t* match_b_dev, const int32_t* nonmatch_b_dev, int b, int hc, int wc, int n_match,
+                            int n_non, int method, int dist, float coef_pos, float coef_neg, float* dd_a_nhwc_dev, float* dd_b_nhwc_dev,
+                            float* out2_dev, int gather, int32_t* csr_off_dev, int32_t* csr_match_dev, float* csr_weight_dev,
+                            void* stream) {
   if (b < 1 || b > SSP_MAX_PAIRS) return fail(-1, "batch out of range (1..%d)", SSP_MAX_PAIRS);
   if ((dd_a_nhwc_dev == nullptr) != (dd_b_nhwc_dev == nullptr)) return fail(-1, "sparse_loss: both gradient pointers or none");
   hipStream_t st = (hipStream_t)stream;
@@ -4293,17 +4348,36 @@ int ssp_op_sparse_loss(const float* desc_a_nhwc_dev, const float* desc_b_nhwc_de
   const size_t ncell_floats = (size_t)b * hc * wc * 256;
   const bool euc = (dflags & DESC_EUCLIDEAN) != 0;
   const dim3 dgrid(desc_grid(b, n_match));
+  const bool use_gather = grad && (gather < 0 ? desc_gather_env() : gather != 0);
+  const bool own_csr = csr_off_dev == nullptr || csr_match_dev == nullptr || csr_weight_dev == nullptr;
+  if (!own_csr && !use_gather) return fail(-1, "sparse_loss: the corner lists exist on the gather path with gradients only");
+  int32_t *csr_off = csr_off_dev, *csr_match = csr_match_dev;
+  float *csr_weight = csr_weight_dev, *g_rows = nullptr;
   if (grad) {
     HIPCHK(hipMallocAsync((void**)&dots, (size_t)b * n_match * n_non * sizeof(float), st));
     CHK(dev_zero(dd_a_nhwc_dev, ncell_floats * sizeof(float), st));
     CHK(dev_zero(dd_b_nhwc_dev, ncell_floats * sizeof(float), st));
+  }
+  if (use_gather) {
+    if (own_csr) {
+      HIPCHK(hipMallocAsync((void**)&csr_off, (size_t)b * 2 * ((size_t)hc * wc + 1) * sizeof(int32_t), st));
+      HIPCHK(hipMallocAsync((void**)&csr_match, (size_t)b * 2 * 4 * n_match * sizeof(int32_t), st));
+      HIPCHK(hipMallocAsync((void**)&csr_weight, (size_t)b * 2 * 4 * n_match * sizeof(float), st));
+    }
+    HIPCHK(hipMallocAsync((void**)&g_rows, (size_t)b * n_match * 2 * 256 * sizeof(float), st));
+    CHK(launch_desc_csr(match_a_dev, match_b_dev, csr_off, csr_match, csr_weight, b, hc, wc, n_match, dflags, st));
   }
 #define SSP_OPD(KERNEL, ...)                                                                  \
   {                                                                                           \
     if (euc) hipLaunchKernelGGL((KERNEL<true>), dgrid, dim3(256), 0, st, __VA_ARGS__);        \
     else hipLaunchKernelGGL((KERNEL<false>), dgrid, dim3(256), 0, st, __VA_ARGS__);           \
   }
-  if (grad) {
+  if (use_gather) {
+    if (euc) hipLaunchKernelGGL((desc_match_kernel<true, true, true>), dgrid, dim3(256), 0, st, desc_a_nhwc_dev, desc_b_nhwc_dev, match_a_dev,
+                                match_b_dev, (float*)nullptr, (float*)nullptr, acc, b, hc, wc, n_match, dflags, g_rows);
+    else hipLaunchKernelGGL((desc_match_kernel<true, false, true>), dgrid, dim3(256), 0, st, desc_a_nhwc_dev, desc_b_nhwc_dev, match_a_dev,
+                            match_b_dev, (float*)nullptr, (float*)nullptr, acc, b, hc, wc, n_match, dflags, g_rows);
+  } else if (grad) {
     if (euc) hipLaunchKernelGGL((desc_match_kernel<true, true>), dgrid, dim3(256), 0, st, desc_a_nhwc_dev, desc_b_nhwc_dev, match_a_dev,
                                 match_b_dev, dd_a_nhwc_dev, dd_b_nhwc_dev, acc, b, hc, wc, n_match, dflags);
     else hipLaunchKernelGGL((desc_match_kernel<true, false>), dgrid, dim3(256), 0, st, desc_a_nhwc_dev, desc_b_nhwc_dev, match_a_dev,
@@ -4319,9 +4393,19 @@ int ssp_op_sparse_loss(const float* desc_a_nhwc_dev, const float* desc_b_nhwc_de
     SSP_OPD(desc_nonmatch_bwd_kernel, desc_a_nhwc_dev, desc_b_nhwc_dev, match_a_dev, nonmatch_b_dev, dots, dd_a_nhwc_dev, dd_b_nhwc_dev, acc, b,
             hc, wc, n_match, n_non, dflags)
 #undef SSP_OPD
+  if (use_gather) {   // behind the non-match atomics, as in the pair step (there inside desc_normalize_bwd_kernel)
+    const DescGather dg = {csr_off, csr_match, csr_weight, g_rows, hc * wc, n_match};
+    hipLaunchKernelGGL(desc_gather_kernel, dim3(cdiv((long)b * hc * wc, 4), 2), dim3(256), 0, st, dd_a_nhwc_dev, dd_b_nhwc_dev, b * hc * wc, dg);
+  }
   hipLaunchKernelGGL(sparse_loss_means_kernel, dim3(1), dim3(1), 0, st, acc, out2_dev, b, n_match);
   HIPCHK(hipGetLastError());
   if (dots != nullptr) HIPCHK(hipFreeAsync(dots, st));
+  if (g_rows != nullptr) HIPCHK(hipFreeAsync(g_rows, st));
+  if (use_gather && own_csr) {
+    HIPCHK(hipFreeAsync(csr_off, st));
+    HIPCHK(hipFreeAsync(csr_match, st));
+    HIPCHK(hipFreeAsync(csr_weight, st));
+  }
   HIPCHK(hipFreeAsync(acc, st));
   return 0;
 }

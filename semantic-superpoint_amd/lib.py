@@ -130,7 +130,7 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_op_point_classes", "ssp_point_classes", "ssp_filter_workspace_bytes", "ssp_op_filter_points",
            "ssp_match_two_way_classes",
            "ssp_det_eval_workspace_bytes", "ssp_op_det_tp_fp", "ssp_op_det_tp_fp_points", "ssp_det_pr_curve_workspace_bytes",
-           "ssp_op_det_pr_curve"]
+           "ssp_op_det_pr_curve", "ssp_op_sparse_loss_path"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -242,6 +242,11 @@ def load_library(path=None):
     lib.ssp_op_bn_bwd_strided.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
     lib.ssp_op_labels.argtypes = [vp, vp, vp, vp, i, i, i, vp]
     lib.ssp_op_sparse_loss.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, C.c_float, C.c_float, vp, vp, vp, vp]
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_op_sparse_loss_path.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, C.c_float, C.c_float, vp, vp, vp, i, vp, vp, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
     ep = C.POINTER(SspExportParams)
     lib.ssp_export_workspace_bytes.argtypes = [ep]
     lib.ssp_export_workspace_bytes.restype = C.c_size_t
@@ -1214,10 +1219,13 @@ def op_detector_loss(semi_nchw, labels2d, mask2d, grad=True):
     return float(out.item()), (d[..., :65].permute(0, 3, 1, 2).contiguous() if grad else None)
 
 
-def op_sparse_loss(desc_a_nchw, desc_b_nchw, match_a, match_b, nonmatch_b, method="2d", dist="cos", grad=None):
+def op_sparse_loss(desc_a_nchw, desc_b_nchw, match_a, match_b, nonmatch_b, method="2d", dist="cos", grad=None, gather=None, csr=False):
     """(positive_dist, negative_dist) of the sparse descriptor loss for NCHW descriptor maps and explicit indices; with
     grad = (coef_pos, coef_neg) also the gradients of coef_pos * positive_dist + coef_neg * negative_dist wrt both maps (NCHW).
-    method / dist: sparse_loss.params ("2d" / "cos" in every shipped config; see Engine.pair_step)."""
+    method / dist: sparse_loss.params ("2d" / "cos" in every shipped config; see Engine.pair_step).
+    gather: path of the match term's gradient - True = per-cell gather over corner lists, False = atomic scatter, None = the process
+    default (SSP_DESC_GATHER).  csr (gather path with grad): also return the corner lists (offsets [B, 2, Hc*Wc + 1] int32,
+    match [B, 2, 4 n_match] int32, weight [B, 2, 4 n_match] float32; only the first offsets[..., -1] entries of a list are defined)."""
     lib = load_library()
     _need_gpu(desc_a_nchw, "desc")
     B, D, Hc, Wc = desc_a_nchw.shape
@@ -1227,14 +1235,28 @@ def op_sparse_loss(desc_a_nchw, desc_b_nchw, match_a, match_b, nonmatch_b, metho
     da = torch.full_like(a, float("nan")) if grad is not None else None   # (the operator overwrites them)
     db = torch.full_like(b, float("nan")) if grad is not None else None
     cp, cn = grad if grad is not None else (0.0, 0.0)
+    n_match = match_a.shape[1]
+    lists = None
+    if csr:
+        lists = (torch.zeros(B, 2, Hc * Wc + 1, dtype=torch.int32, device=a.device),
+                 torch.full((B, 2, 4 * n_match), -1, dtype=torch.int32, device=a.device),
+                 torch.full((B, 2, 4 * n_match), float("nan"), dtype=torch.float32, device=a.device))
     with torch.cuda.device(a.device):
-        _check(lib.ssp_op_sparse_loss(_ptr(a), _ptr(b), _ptr(match_a), _ptr(match_b), _ptr(nonmatch_b), B, Hc, Wc,
-                                      match_a.shape[1], nonmatch_b.shape[1] // match_a.shape[1], int(method != "2d"), int(dist != "cos"),
-                                      float(cp), float(cn), _ptr(da), _ptr(db), _ptr(out), _stream()))
+        if gather is None and not csr:
+            _check(lib.ssp_op_sparse_loss(_ptr(a), _ptr(b), _ptr(match_a), _ptr(match_b), _ptr(nonmatch_b), B, Hc, Wc,
+                                          n_match, nonmatch_b.shape[1] // n_match, int(method != "2d"), int(dist != "cos"),
+                                          float(cp), float(cn), _ptr(da), _ptr(db), _ptr(out), _stream()))
+        else:
+            _check(lib.ssp_op_sparse_loss_path(_ptr(a), _ptr(b), _ptr(match_a), _ptr(match_b), _ptr(nonmatch_b), B, Hc, Wc,
+                                               n_match, nonmatch_b.shape[1] // n_match, int(method != "2d"), int(dist != "cos"),
+                                               float(cp), float(cn), _ptr(da), _ptr(db), _ptr(out),
+                                               -1 if gather is None else int(bool(gather)), _ptr(lists[0]) if csr else None,
+                                               _ptr(lists[1]) if csr else None, _ptr(lists[2]) if csr else None, _stream()))
     torch.cuda.synchronize()
     if grad is None:
         return float(out[0]), float(out[1])
-    return float(out[0]), float(out[1]), da.permute(0, 3, 1, 2).contiguous(), db.permute(0, 3, 1, 2).contiguous()
+    res = (float(out[0]), float(out[1]), da.permute(0, 3, 1, 2).contiguous(), db.permute(0, 3, 1, 2).contiguous())
+    return res + (lists,) if csr else res
 
 
 def op_dense_loss(desc_a_nchw, desc_b_nchw, homographies, mask_valid, lamda_d=250.0, descriptor_dist=4.0, grad=None):

@@ -22,5 +22,10 @@ i0 = max(i for i, e in enumerate(step) if "desc_normalize_kernel" in e[2])
 i1 = min(i for i, e in enumerate(step) if i > i0 and ("bn_bwd" in e[2] or "colsum" in e[2]))
 t0 = step[i0][0]
 print("loss phase: %.1f us from the start of the last forward kernel to the start of the first backward kernel" % ((step[i1][0] - t0) / 1e3))
+# the index- / label-only kernels that run beside the forward pass (relative to the same origin: negative = before the loss phase)
+for s, e, n, q in step[:i0]:
+    if any(k in n for k in ("desc_csr_kernel", "cell_mask_kernel", "sem_count_kernel")):
+        print("%8.1f %8.1f  %6.1f us  stream %-4s %s   (beside the forward pass, step begins at %.1f)"
+              % ((s - t0) / 1e3, (e - t0) / 1e3, (e - s) / 1e3, q, n.split("(")[0][:70], (step[0][0] - t0) / 1e3))
 for s, e, n, q in step[i0:i1 + 1]:
     print("%8.1f %8.1f  %6.1f us  stream %-4s %s" % ((s - t0) / 1e3, (e - t0) / 1e3, (e - s) / 1e3, q, n.split("(")[0][:70]))
