@@ -211,10 +211,15 @@ struct Bilin {
 __device__ __forceinline__ Bilin bilin_setup(int cell, int Hc, int Wc) {
   const float u = (float)(cell % Wc), v = (float)(cell / Wc);
   const float gx = u / (float)Wc * 2.f - 1.f, gy = v / (float)Hc * 2.f - 1.f;
-  const float ix = ((gx + 1.f) / 2.f) * (float)(Wc - 1), iy = ((gy + 1.f) / 2.f) * (float)(Hc - 1);
+  const float tx = (gx + 1.f) / 2.f, ty = (gy + 1.f) / 2.f;
+  const float ix = tx * (float)(Wc - 1), iy = ty * (float)(Hc - 1);
   const float fx = floorf(ix), fy = floorf(iy);
   const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-  const float ax = ix - fx, ay = iy - fy;
+  // The fractions as ONE explicit fused multiply-add each.  Written `ix - fx`, the compiler contracts the product into the
+  // subtraction in some inlined copies of this function and not in others (desc_match_kernel<.., GATHER> rounded ix first for its
+  // a side only): the forward sample then used corner weights up to 1e-5 (relative) away from the ones desc_csr_kernel hands the
+  // gather of the gradient.  Every copy now takes the same instruction.
+  const float ax = fmaf(tx, (float)(Wc - 1), -fx), ay = fmaf(ty, (float)(Hc - 1), -fy);
   Bilin b;
   // zeros padding: out-of-range corners contribute nothing (weight 0, index clamped)
   const bool vx0 = x0 >= 0 && x0 < Wc, vx1 = x1 >= 0 && x1 < Wc, vy0 = y0 >= 0 && y0 < Hc, vy1 = y1 >= 0 && y1 < Hc;

@@ -21,7 +21,8 @@ that has it:
   * Data gradient: the dOut tap of the layer below = conv2d_input(W, dY) (the 3x3 heads: one sum over the concatenated
     [Pa | Da | DS] channels), bound tau * conv2d_input(|W|, |dY|), on the images [0, 1, B/2, B-2, B-1] at B = 32.
   * Heads: Pb / Db (BatchNorm without ReLU) from the dsemi / ddesc roots, the grouped pointwise weight and data gradients,
-    Sout's bias = the column sums of dsout.  The roots themselves are pinned by the loss tests.
+    Sout's bias = the column sums of dsout.  The roots themselves are pinned element by element by
+    tests/test_gpu_loss_exact.py.
 
 Every case asserts the per-layer route record of the backward (ssp_debug_backward_tap) against a mirror of the dispatch
 predicates, and that taps on / off give bit-identical results under set_deterministic(True)."""

@@ -2,8 +2,9 @@
 
 After one eager pair step with the backward taps on (Engine.debug_backward_taps; dOut = the gradient wrt a layer's (pooled)
 activation as it enters its BatchNorm backward, dY = the gradient wrt its conv output after the APPLY pass, bf16 tensors on this
-path except Pb / Db dY), every stage is recomputed in fp64 from the step's OWN stored tensors.  The semantics are those of
-oracle/cpu_ref.py with operand_dtype=torch.bfloat16:
+path except Pb / Db dY), every stage is recomputed in fp64 from the step's OWN stored tensors.  The roots dsemi / ddesc / dsout
+are taken as given: tests/test_gpu_loss_exact.py pins them element by element, under this algorithm too.  The semantics are those
+of oracle/cpu_ref.py with operand_dtype=torch.bfloat16:
 
   * Operands.  The forward operand of layer l is bf16(relu(fma_fp32(Y_{l-1}, scale, shift))) from the stored bf16 Y_{l-1} and
     the engine's own affine, 2x2 max-pooled after layers 1, 3, 5 (the materialised act[] and the raw pooled copies hold the same
