@@ -555,6 +555,44 @@ int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int
                     double* h_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev, double* ap_dev,
                     void* stream);
 
+/* ---- streamed descriptor metrics ----------------------------------------------------------
+ * The per-pair metrics of evaluation.py -r -homo for a set that is fed batch by batch and never leaves the device, on
+ * top of ssp_eval_repeatability, ssp_match_two_way and ssp_eval_ransac.  fp64 without contraction.  No call
+ * synchronises with the host.
+ * ssp_eval_pixel_homographies: hn_dev float32 [n_pairs][9], the trainer's normalised image-to-warped homographies
+ *   (sample["homographies"]), widened to fp64 -> hom_dev = Tinv @ (Hn @ T) with T = [[2/W,0,-1],[0,2/H,-1],[0,0,1]]
+ *   (2/W, 2/H correctly rounded) and Tinv = [[W/2,0,W/2],[0,H/2,H/2],[0,0,1]] (utils/utils.py:291-294
+ *   homography_scaling in closed form; no division by h33); every element ((a0*b0 + a1*b1) + a2*b2), each product and
+ *   each sum rounded.  hom_inv_dev = adj(M) / det(M): each cofactor a rounded p*q - r*s,
+ *   det = ((m00*A00 + m01*A10) + m02*A20), nine divisions.  This is NOT np.linalg.inv (an LU solve): the two agree to
+ *   about 5e-16 relative, not bit for bit.  Both outputs fp64 [n_pairs][9].
+ * ssp_eval_accumulate: one workgroup, 1 <= n_pairs <= SSP_EVAL_ACC_MAX_PAIRS.  rep_dev: the [n_pairs][8] rows of
+ *   ssp_eval_repeatability, or NULL (repeatability off; n_unwarped counts as 0).  h_dev / n_inlier_dev / status_dev: the
+ *   crossCheck call of ssp_eval_ransac; ap_dev: the nn call's; n1_dev: the image-side point counts (pair p reads entry
+ *   p * pair_stride); hom_dev: the true pixel homographies [n_pairs][9]; these six come together, or all NULL (homography
+ *   metrics off).  The slots of a group that is off stay 0.  thresholds: 6 doubles (host).  Pair p has the number
+ *   first_pair + p and writes the row of that number in rows_dev [capacity][SSP_EVAL_ROW_WORDS] (skipped, and counted in
+ *   the state, when the number >= capacity):
+ *     0 rep = c / (N1 + N2), c = count1 + count2 (0 when c = 0)   1 loc_err = 0 + sum1 / c + sum2 / c (-1 when c = 0)
+ *     2..7 mean corner distance <= threshold k, as 0 / 1 (all 0 with status 1)
+ *     8 mscore = 2 n_inliers / (n1 + n_unwarped) (0 for a zero denominator)   9 mAP = ap if ap > 0 else 0
+ *     10 status   11 n_inliers   12 n1   13 n_unwarped   14 the mean corner distance (inf without a model)   15 pair number
+ *   A corner is ((x*h0 + y*h1) + h2, (x*h3 + y*h4) + h5) / ((x*h6 + y*h7) + h8) for (0, 0), (0, ch - 1), (cw - 1, 0),
+ *   (cw - 1, ch - 1); the distance sqrt(dx*dx + dy*dy); the mean (((d0 + d1) + d2) + d3) / 4.
+ *   state_dev [SSP_EVAL_STATE_WORDS] fp64, caller-owned, zeroed = empty; one lane adds the rows in pair order, so the state
+ *   of a set does not depend on how it was split into calls:
+ *     0 pairs   1 sum rep   2 sum loc_err over loc_err > 0   3 their count   4..9 correct counts   10 sum mscore   11 sum mAP
+ *     12 pairs without a model   13 rows dropped (pair number >= capacity)   14, 15: 0. */
+#define SSP_EVAL_ACC_MAX_PAIRS 128
+#define SSP_EVAL_ROW_WORDS 16
+#define SSP_EVAL_STATE_WORDS 16
+int ssp_eval_pixel_homographies(const float* hn_dev, int n_pairs, int height, int width, double* hom_dev, double* hom_inv_dev,
+                                void* stream);
+int ssp_eval_accumulate(const double* rep_dev, const double* h_dev, const int32_t* n_inlier_dev, const int32_t* status_dev,
+                        const double* ap_dev, const int32_t* n1_dev, int pair_stride, const double* hom_dev, int n_pairs,
+                        int corner_h, int corner_w, const double* thresholds, int64_t first_pair, double* rows_dev,
+                        int64_t capacity, double* state_dev, void* stream);
+
 /* ---- detector evaluation against ground-truth corners (evaluations/detector_evaluation.py:15-136) --
  * compute_tp_fp / compute_pr / compute_mAP / compute_loc_error for a validation set that is fed batch by batch and never
  * leaves the device.  The caller owns a key buffer int64 [capacity] and a state block int64 [SSP_DET_EVAL_STATE_WORDS]

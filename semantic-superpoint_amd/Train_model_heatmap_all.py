@@ -22,6 +22,10 @@ steps also sum one confusion matrix on the device, which train() reports per val
 Detector mAP (`ssp_detector_map: true`; off by default): the validation steps feed the heat maps and label maps of their views
 into one detector_evaluation.DetectorEvaluator per round, and train() reports `detector_mAP_round` and
 `detector_loc_err_round` after it (the reference's evaluations/detector_evaluation.py numbers).
+Descriptor metrics (`ssp_descriptor_metrics: true`, with `data.warped_pair.enable`; off by default): the validation steps turn
+what the step left in the engine into keypoints and sparse descriptors of both views and feed one
+evaluation.StreamingEvaluator per round; train() reports repeatability, localisation error, homography correctness, matching
+score and nn-mAP of the round after one read (the reference's `evaluation.py -r -homo` numbers).
 """
 import copy
 import logging
@@ -106,6 +110,10 @@ class Train_model_heatmap_all(object):
         if self.detector_map and resize:  # a round that cannot fit is refused here, not at the first validation step
             views = 2 if self.config["data"].get("warped_pair", {}).get("enable", False) else 1
             self._detector_capacity(views, int(m.get("eval_batch_size", m["batch_size"])), int(resize[0]), int(resize[1]))
+        self.descriptor_metrics = bool(self.config.get("ssp_descriptor_metrics", False))
+        if self.descriptor_metrics and not self.config["data"].get("warped_pair", {}).get("enable", False):
+            raise ValueError("ssp_descriptor_metrics evaluates the two views of a pair: it needs data.warped_pair.enable")
+        self.descriptor_eval_val = None  # StreamingEvaluator of the validation steps since reset_descriptor_eval()
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("Train_model_heatmap_all (MI355X build) needs a HIP device, got %s" % device)
@@ -288,6 +296,8 @@ class Train_model_heatmap_all(object):
             if self.detector_map and task == "val":
                 self.log_detector_map(eng, dev, B, H, W)
             self.tb_hist_dict(task, self.hist_dict)   # (:568; `images_dict` stays unwritten like the reference's commented-out :567)
+        if self.descriptor_metrics and task == "val":
+            self.log_descriptor_metrics(eng, dev, B, H, W)
         self.tb_scalar_dict(self.scalar_dict, task)
         return float(s["loss"])
 
@@ -391,6 +401,40 @@ class Train_model_heatmap_all(object):
         for slot, key in views:
             ev.update(prob=eng.detector_heatmap(slot, B, H, W), labels=dev[key].float().contiguous())
 
+    def log_descriptor_metrics(self, eng, dev, B, H, W):
+        """`ssp_descriptor_metrics`: keypoints and sparse descriptors of both views from what this validation step left in the
+        engine's slots (Engine.describe_points with model.detection_threshold, model.nms, model.subpixel.enable and
+        border_remove 4; the detector logits and the normalised descriptors are the step's own, BatchNorm in train mode as the
+        step runs it), then StreamingEvaluator.update_views with the step's normalised homographies: repeatability, the two
+        matchers, the two RANSACs and the accumulation are queued on the device, nothing is read back.  The evaluator is made
+        at the first step for (validation_size + 2) * B pairs, the most train() runs, and measures correctness on the corners
+        of the images' own (H, W).  The step itself is untouched."""
+        from .evaluation import StreamingEvaluator
+        m = self.config["model"]
+        ev = self.descriptor_eval_val
+        cap = (int(self.config.get("validation_size", 3)) + 2) * B
+        if ev is None or (ev.height, ev.width) != (H, W) or ev.capacity < cap:
+            ev = self.descriptor_eval_val = StreamingEvaluator(H, W, self.device, cap, corner_shape=(H, W))
+        subpixel = bool(m["subpixel"]["enable"])
+        kw = dict(conf_thresh=m.get("detection_threshold", 0.015), nms_dist=m.get("nms", 4), subpixel=subpixel, border_remove=4)
+        d0, d1 = eng.describe_points(0, B, **kw), eng.describe_points(1, B, **kw)
+        ev.update_views(d0, d1, dev["homographies"].to(torch.float32).contiguous(), subpixel=subpixel)
+
+    def reset_descriptor_eval(self):
+        """Empty the validation evaluator (train() calls it in front of a validation round)."""
+        if self.descriptor_eval_val is not None:
+            self.descriptor_eval_val.reset()
+
+    def descriptor_round_scalars(self):
+        """The round's descriptor metrics under the names train() reports (one host read)."""
+        res = self.descriptor_eval_val.result()
+        out = {"repeatability_round": float(res["repeatability"]), "localization_err_round": float(res["localization_err"])}
+        for t, c in zip(res["homography_thresh"], res["correctness"]):
+            out["homography_correctness_%d_round" % t] = float(c)
+        out["matching_score_round"] = float(res["mscore"])
+        out["nn_mAP_round"] = float(res["mAP"])
+        return out
+
     def reset_detector_eval(self):
         """Empty the validation evaluator (train() calls it in front of a validation round)."""
         if self.detector_eval_val is not None:
@@ -461,6 +505,8 @@ class Train_model_heatmap_all(object):
                         self.reset_sem_confusion()
                     if self.detector_map:
                         self.reset_detector_eval()
+                    if self.descriptor_metrics:
+                        self.reset_descriptor_eval()
                     for j, sample_val in enumerate(self.val_loader):
                         self.train_val_sample(sample_val, self.n_iter + j, False)
                         if j > self.config.get("validation_size", 3):
@@ -471,6 +517,8 @@ class Train_model_heatmap_all(object):
                     if self.detector_map and self.detector_eval_val is not None:  # one state read per round
                         res = self.detector_eval_val.result()
                         self.tb_scalar_dict({"detector_mAP_round": res["mAP"], "detector_loc_err_round": res["loc_error"]}, "val")
+                    if self.descriptor_metrics and self.descriptor_eval_val is not None:  # one state + rows read per round
+                        self.tb_scalar_dict(self.descriptor_round_scalars(), "val")
                 if self.n_iter % self.config["save_interval"] == 0:
                     self.saveModel()
                 if self.n_iter > self.max_iter:

@@ -578,4 +578,155 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_ransac_kernel(const double4
   }
 }
 
+// ---- streamed descriptor metrics ----
+#define EVAL_ACC_MAX_PAIRS 128
+#define EVAL_ROW_WORDS 16
+#define EVAL_STATE_WORDS 16
+
+// c = a @ b for 3x3 row-major matrices: every element ((a0*b0 + a1*b1) + a2*b2), each product and each sum rounded.
+__device__ __forceinline__ void eval_mat3(const double (&a)[9], const double (&b)[9], double (&c)[9]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[3 * r + k] = (a[3 * r] * b[k] + a[3 * r + 1] * b[3 + k]) + a[3 * r + 2] * b[6 + k];
+}
+
+// One lane per pair: the trainer's normalised homography hn (float32, image -> warped image in [-1, 1]^2) to pixels,
+// M = Tinv @ (Hn @ T) (utils/utils.py:291-294 homography_scaling in closed form, no division by h33), and its inverse
+// adj(M) / det(M).  The inverse is the adjugate, NOT np.linalg.inv's LU solve: the two differ in the last places.
+__global__ __launch_bounds__(64) void eval_pixel_hom_kernel(const float* __restrict__ hn, int n_pairs, int height, int width,
+                                                            double* __restrict__ hom, double* __restrict__ hom_inv) {
+#pragma clang fp contract(off)
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= n_pairs) return;
+  const double W = (double)width, Hh = (double)height;
+  const double T[9] = {2.0 / W, 0.0, -1.0, 0.0, 2.0 / Hh, -1.0, 0.0, 0.0, 1.0};
+  const double Ti[9] = {W * 0.5, 0.0, W * 0.5, 0.0, Hh * 0.5, Hh * 0.5, 0.0, 0.0, 1.0};
+  double h[9], b[9], m[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) h[k] = (double)hn[(size_t)p * 9 + k];
+  eval_mat3(h, T, b);
+  eval_mat3(Ti, b, m);
+  double a[9];
+  a[0] = m[4] * m[8] - m[5] * m[7];
+  a[1] = m[2] * m[7] - m[1] * m[8];
+  a[2] = m[1] * m[5] - m[2] * m[4];
+  a[3] = m[5] * m[6] - m[3] * m[8];
+  a[4] = m[0] * m[8] - m[2] * m[6];
+  a[5] = m[2] * m[3] - m[0] * m[5];
+  a[6] = m[3] * m[7] - m[4] * m[6];
+  a[7] = m[1] * m[6] - m[0] * m[7];
+  a[8] = m[0] * m[4] - m[1] * m[3];
+  const double det = (m[0] * a[0] + m[1] * a[3]) + m[2] * a[6];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    hom[(size_t)p * 9 + k] = m[k];
+    hom_inv[(size_t)p * 9 + k] = a[k] / det;
+  }
+}
+
+struct EvalThresholds {
+  double t[6];
+};
+
+// Mean distance of the four corners of (corner_h, corner_w) under H and under G (compute_homography,
+// descriptor_evaluation.py:127-149): corners (0, 0), (0, h - 1), (w - 1, 0), (w - 1, h - 1) as (x, y).
+__device__ __forceinline__ double eval_corner_dist(const double* H, const double* G, int corner_h, int corner_w) {
+#pragma clang fp contract(off)
+  const double xs[2] = {0.0, (double)(corner_w - 1)}, ys[2] = {0.0, (double)(corner_h - 1)};
+  double d[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double x = xs[k >> 1], y = ys[k & 1];
+    double eu, ev, gu, gv;
+    eval_warp(H, x, y, eu, ev);
+    eval_warp(G, x, y, gu, gv);
+    const double dx = gu - eu, dy = gv - ev;
+    d[k] = sqrt(dx * dx + dy * dy);
+  }
+  return (((d[0] + d[1]) + d[2]) + d[3]) / 4.0;
+}
+
+// One workgroup of EVAL_ACC_MAX_PAIRS lanes; lane p forms the row of pair p (evaluation.rep_from_counts, correctness_of
+// and the mscore / mAP lines of Evaluator.run_points), then lane 0 adds the rows into the state in pair order, so the state
+// is the same sequence of fp64 additions however a set is split into calls.  rep == nullptr: repeatability off (and
+// n_unwarped = 0); h_est == nullptr: the homography metrics are off; the slots of a group that is off stay 0.
+__global__ __launch_bounds__(EVAL_ACC_MAX_PAIRS) void eval_accumulate_kernel(
+    const double* __restrict__ rep, const double* __restrict__ h_est, const int32_t* __restrict__ n_inl,
+    const int32_t* __restrict__ status, const double* __restrict__ ap, const int32_t* __restrict__ n1, int pair_stride,
+    const double* __restrict__ hom, int n_pairs, int corner_h, int corner_w, EvalThresholds thr, long long first_pair,
+    double* __restrict__ rows, long long capacity, double* __restrict__ state) {
+#pragma clang fp contract(off)
+  __shared__ double s_row[EVAL_ACC_MAX_PAIRS][EVAL_ROW_WORDS + 1];
+  const int p = threadIdx.x;
+  if (p < n_pairs) {
+    double r[EVAL_ROW_WORDS];
+#pragma unroll
+    for (int k = 0; k < EVAL_ROW_WORDS; ++k) r[k] = 0.0;
+    double n_unw = 0.0;
+    if (rep != nullptr) {
+      const double* q = rep + (size_t)p * 8;
+      const long long c = (long long)q[2] + (long long)q[3];
+      if (c == 0) {
+        r[1] = -1.0;
+      } else {
+        const double cd = (double)c;
+        r[0] = cd / (double)((long long)q[0] + (long long)q[1]);
+        r[1] = (0.0 + q[4] / cd) + q[5] / cd;
+      }
+      n_unw = q[6];
+    }
+    if (h_est != nullptr) {
+      const int st = status[p], inl = n_inl[p], np1 = n1[(size_t)p * pair_stride];
+      double mean = INFINITY;
+      if (st == 0) {
+        mean = eval_corner_dist(h_est + (size_t)p * 9, hom + (size_t)p * 9, corner_h, corner_w);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) r[2 + k] = mean <= thr.t[k] ? 1.0 : 0.0;
+      }
+      const double den = (double)((long long)np1 + (long long)n_unw);
+      r[8] = den > 0.0 ? (double)(2 * (long long)inl) / den : 0.0;
+      const double a = ap[p];
+      r[9] = a > 0.0 ? a : 0.0;
+      r[10] = (double)st;
+      r[11] = (double)inl;
+      r[12] = (double)np1;
+      r[13] = n_unw;
+      r[14] = mean;
+    }
+    r[15] = (double)(first_pair + p);
+#pragma unroll
+    for (int k = 0; k < EVAL_ROW_WORDS; ++k) s_row[p][k] = r[k];
+    if (first_pair + p < capacity) {
+      double* o = rows + (size_t)(first_pair + p) * EVAL_ROW_WORDS;
+#pragma unroll
+      for (int k = 0; k < EVAL_ROW_WORDS; ++k) o[k] = r[k];
+    }
+  }
+  __syncthreads();
+  if (p == 0) {
+    double s[EVAL_STATE_WORDS];
+#pragma unroll
+    for (int k = 0; k < EVAL_STATE_WORDS; ++k) s[k] = state[k];
+    for (int i = 0; i < n_pairs; ++i) {
+      const double* r = s_row[i];
+      s[0] = s[0] + 1.0;
+      s[1] = s[1] + r[0];
+      if (r[1] > 0.0) {
+        s[2] = s[2] + r[1];
+        s[3] = s[3] + 1.0;
+      }
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s[4 + k] = s[4 + k] + r[2 + k];
+      s[10] = s[10] + r[8];
+      s[11] = s[11] + r[9];
+      if (r[10] != 0.0) s[12] = s[12] + 1.0;
+      if (first_pair + i >= capacity) s[13] = s[13] + 1.0;
+    }
+#pragma unroll
+    for (int k = 0; k < EVAL_STATE_WORDS; ++k) state[k] = s[k];
+  }
+}
+
 }  // namespace sspk

@@ -3817,6 +3817,43 @@ int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int
   return 0;
 }
 
+// ---- streamed descriptor metrics: pixel homographies of the trainer's pairs, per-pair rows and running sums ----
+static_assert(EVAL_ACC_MAX_PAIRS == SSP_EVAL_ACC_MAX_PAIRS && EVAL_ROW_WORDS == SSP_EVAL_ROW_WORDS && EVAL_STATE_WORDS == SSP_EVAL_STATE_WORDS,
+              "include/ssp_hip.h and eval_kernels.hip.h disagree");
+int ssp_eval_pixel_homographies(const float* hn_dev, int n_pairs, int height, int width, double* hom_dev, double* hom_inv_dev,
+                                void* stream) {
+  if (!hn_dev || !hom_dev || !hom_inv_dev) return fail(-1, "eval_pixel_homographies: null pointer");
+  if (n_pairs < 1 || height < 1 || width < 1) return fail(-1, "eval_pixel_homographies: n_pairs, height, width >= 1 required");
+  hipLaunchKernelGGL(eval_pixel_hom_kernel, dim3(cdiv(n_pairs, 64)), dim3(64), 0, (hipStream_t)stream, hn_dev, n_pairs, height,
+                     width, hom_dev, hom_inv_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_eval_accumulate(const double* rep_dev, const double* h_dev, const int32_t* n_inlier_dev, const int32_t* status_dev,
+                        const double* ap_dev, const int32_t* n1_dev, int pair_stride, const double* hom_dev, int n_pairs,
+                        int corner_h, int corner_w, const double* thresholds, int64_t first_pair, double* rows_dev,
+                        int64_t capacity, double* state_dev, void* stream) {
+  if (n_pairs < 1 || n_pairs > EVAL_ACC_MAX_PAIRS)
+    return fail(-1, "eval_accumulate: 1 <= n_pairs <= %d per call (got %d)", EVAL_ACC_MAX_PAIRS, n_pairs);
+  if (!rows_dev || !state_dev || !thresholds) return fail(-1, "eval_accumulate: null pointer");
+  if (capacity < 1 || first_pair < 0) return fail(-1, "eval_accumulate: capacity >= 1 and first_pair >= 0 required");
+  const int n_ransac = (h_dev != nullptr) + (n_inlier_dev != nullptr) + (status_dev != nullptr) + (ap_dev != nullptr) +
+                       (n1_dev != nullptr) + (hom_dev != nullptr);
+  if (n_ransac != 0 && n_ransac != 6)
+    return fail(-1, "eval_accumulate: H, n_inliers, status, ap, n1 and the true homographies come together or not at all");
+  if (!rep_dev && n_ransac == 0) return fail(-1, "eval_accumulate: neither the repeatability rows nor the RANSAC results");
+  if (n_ransac && (pair_stride < 1 || corner_h < 1 || corner_w < 1))
+    return fail(-1, "eval_accumulate: pair_stride, corner_h, corner_w >= 1 required");
+  EvalThresholds thr;
+  for (int k = 0; k < 6; ++k) thr.t[k] = thresholds[k];
+  hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(EVAL_ACC_MAX_PAIRS), 0, (hipStream_t)stream, rep_dev, h_dev,
+                     n_inlier_dev, status_dev, ap_dev, n1_dev, pair_stride, hom_dev, n_pairs, corner_h, corner_w, thr,
+                     (long long)first_pair, rows_dev, (long long)capacity, state_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // ---- detector evaluation against ground-truth corners (evaluations/detector_evaluation.py:15-136) ----
 static_assert(DET_MAX_R2 == SSP_DET_EVAL_MAX_R2 && DET_STATE_WORDS == SSP_DET_EVAL_STATE_WORDS && DET_CURVE_TILE == SSP_DET_EVAL_CURVE_TILE,
               "include/ssp_hip.h and detector_eval_kernels.hip.h disagree");

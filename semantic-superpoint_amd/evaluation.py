@@ -5,7 +5,8 @@
 
 reads the exporter's `<int>.npz` files in numeric order, evaluates them in batches of pairs on one GPU and appends the
 reference's summary to `<dir>/result.txt` and writes `<dir>/result.npz`.  Evaluator.run_device evaluates the device
-tensors of DescriptorExporter.run_device without a host copy of points or descriptors.  The RANSAC step restates
+tensors of DescriptorExporter.run_device without a host copy of points or descriptors.  StreamingEvaluator keeps the
+per-pair metrics and their sums on the device as well and reads them once per set (a validation round, an export).  The RANSAC step restates
 cv2.findHomography; there is no CPU fallback.
 """
 import argparse
@@ -125,6 +126,179 @@ class Evaluator:
         if subpixel:
             pts[:, :, :2] = pts[:, :, :2] + pts5[:, :, 3:5].double() - 2
         return self.run_points(pts.contiguous(), o["count"], o["desc"], homographies, seeds)
+
+
+class StreamingEvaluator:
+    """The -r -homo metrics of a set of pairs that is fed batch by batch and never leaves the device (DESIGN.md section
+    21): every update queues op_eval_repeatability, the two matchers, the two RANSACs and op_eval_accumulate on the
+    current stream and reads nothing back; result() makes the one read of the state block and the per-pair rows.
+    height / width: the images' shape; capacity: pairs whose rows are kept (pairs past it still count in the sums and
+    in `rows_dropped`); corner_shape: the (height, width) whose corners measure homography correctness -
+    compute_homography's default (240, 320) as `evaluate` uses it, or the images' own shape.  Pairs are numbered in
+    feeding order from 0 and pair f draws its RANSAC seeds from pair_seeds(f), like the file numbers of `evaluate`.
+    With repeatability off and homography on, the repeatability rows are still computed (the matching score needs their
+    unwarped-point count) and result() leaves the repeatability keys out."""
+
+    def __init__(self, height, width, device, capacity, repeatability=True, homography=True, keep_k=TOP_K, rep_thd=REP_THD,
+                 nn_thresh=NN_THRESH, corner_shape=CORNER_SHAPE):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("StreamingEvaluator needs a HIP device (got %s): no CPU fallback exists" % self.device)
+        self.height, self.width, self.capacity = int(height), int(width), int(capacity)
+        if self.capacity < 1:
+            raise ValueError("capacity >= 1 pairs required (got %d)" % self.capacity)
+        self.repeatability, self.homography = bool(repeatability), bool(homography)
+        if not (self.repeatability or self.homography):
+            raise ValueError("repeatability or homography (or both) must be on")
+        self.keep_k, self.rep_thd, self.nn_thresh = int(keep_k), float(rep_thd), float(nn_thresh)
+        self.corner_shape = (int(corner_shape[0]), int(corner_shape[1]))
+        self.rows, self.state = L.eval_metrics_state(self.capacity, self.device)
+        self.pairs = 0  # pairs fed since reset(): the next pair's number (host side; nothing is read back for it)
+
+    def reset(self):
+        self.rows.zero_()
+        self.state.zero_()
+        self.pairs = 0
+
+    def _pixel(self, t, name, P):
+        if torch.is_tensor(t) and t.is_cuda:
+            if t.dtype != torch.float64 or tuple(t.shape) != (P, 3, 3):
+                raise ValueError("%s on the device must be float64 [%d,3,3] (got %s %s)" % (name, P, t.dtype, tuple(t.shape)))
+            return t.contiguous()
+        a = t.detach().numpy() if torch.is_tensor(t) else np.asarray(t)
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(P, 3, 3)).to(self.device)
+
+    def update_points(self, pts, count, desc, homographies=None, pair_stride=2, pts2=None, count2=None, desc2=None,
+                      hom_inv=None, normalised=None):
+        """The next P pairs.  pts float64 [P*pair_stride,cap,3] rows (x, y, conf), count int32, desc float32
+        [..,cap,256] unit rows: pair p's image is entry p * pair_stride; its warped image is that entry of pts2 / count2 /
+        desc2, or entry p * pair_stride + 1 of the same arrays when they are None (the exporter's interleaved layout).
+        homographies: the true pixel matrices [P,3,3], host (any array) or device float64, with hom_inv beside them
+        (default for host matrices: np.linalg.inv, as Evaluator; device matrices need it) - or normalised=hn, the
+        trainer's device float32 [P,3,3] (sample["homographies"]), converted by op_eval_pixel_homographies.
+        No host read."""
+        for t, nm in ((pts, "pts"), (count, "count"), (desc, "desc")):
+            L._need_gpu(t, nm)
+        if pts.dim() != 3 or pts.shape[1] > L.MATCH_MAX_POINTS:
+            raise ValueError("at most %d points per image (the arrays hold %s)" % (L.MATCH_MAX_POINTS, tuple(pts.shape)))
+        if (homographies is None) == (normalised is None):
+            raise ValueError("update_points(homographies=pixel matrices) or update_points(normalised=hn)")
+        if (pts2 is None) != (count2 is None) or (pts2 is None) != (desc2 is None):
+            raise ValueError("pts2, count2 and desc2 come together")
+        pair_stride = int(pair_stride)
+        if normalised is not None:
+            if not torch.is_tensor(normalised) or normalised.dtype != torch.float32 or normalised.dim() != 3 \
+                    or tuple(normalised.shape[1:]) != (3, 3):
+                raise ValueError("normalised must be a device float32 [P,3,3] tensor")
+            if hom_inv is not None:
+                raise ValueError("hom_inv belongs to pixel homographies, not to normalised ones")
+            P = normalised.shape[0]
+        else:
+            P = (homographies.numel() if torch.is_tensor(homographies) else np.asarray(homographies).size) // 9
+        if pts2 is None:
+            if pair_stride < 2:
+                raise ValueError("interleaved pairs need pair_stride >= 2")
+            pts2, count2, desc2 = pts[1:], count[1:], desc[1:]
+            n2 = pts.shape[0] - 1
+        else:
+            n2 = pts2.shape[0]
+            if pts2.shape[1:] != pts.shape[1:]:
+                raise ValueError("pts2 must have the cap of pts")
+        if P < 1 or pts.shape[0] != P * pair_stride or count.numel() != pts.shape[0] or desc.shape[:2] != pts.shape[:2] \
+                or n2 < (P - 1) * pair_stride + 1:
+            raise ValueError("%d homographies do not match point arrays of %d entries at stride %d"
+                             % (P, pts.shape[0], pair_stride))
+        if normalised is not None:
+            Hd, Hi = L.op_eval_pixel_homographies(normalised, self.height, self.width)
+        else:
+            if hom_inv is None:
+                if torch.is_tensor(homographies) and homographies.is_cuda:
+                    raise ValueError("device homographies need hom_inv (or pass normalised=hn)")
+                Hs = np.asarray(homographies, dtype=np.float64).reshape(P, 3, 3)
+                hom_inv = np.stack([np.linalg.inv(h) for h in Hs])
+            Hd, Hi = self._pixel(homographies, "homographies", P), self._pixel(hom_inv, "hom_inv", P)
+        f0 = self.pairs
+        rep = L.op_eval_repeatability(pts, count, pts2, count2, Hd, Hi, self.height, self.width, self.keep_k, self.rep_thd,
+                                      pair_stride=pair_stride, n_pairs=P)
+        cc = nn = None
+        if self.homography:
+            s_cc, s_nn = pair_seeds(np.arange(f0, f0 + P))
+            m, nm = L.op_match_two_way(desc, count, desc2, count2, float("inf"), pair_stride=pair_stride, n_pairs=P)
+            cc = L.op_eval_ransac(pts, pts2, m, nm, torch.from_numpy(s_cc).to(self.device), pair_stride=pair_stride)
+            m, nm = L.op_match_two_way(desc, count, desc2, count2, self.nn_thresh, pair_stride=pair_stride, n_pairs=P)
+            nn = L.op_eval_ransac(pts, pts2, m, nm, torch.from_numpy(s_nn).to(self.device), pair_stride=pair_stride,
+                                  want_ap=True)
+        for a in range(0, P, L.EVAL_ACC_MAX_PAIRS):
+            b = min(P, a + L.EVAL_ACC_MAX_PAIRS)
+            kw = {}
+            if self.homography:
+                kw = dict(ransac={k: cc[k][a:b] for k in ("H", "n_inliers", "status")}, ap=nn["ap"][a:b],
+                          n1=count[a * pair_stride:], pair_stride=pair_stride, hom=Hd[a:b])
+            L.op_eval_accumulate(self.rows, self.state, f0 + a, rep=rep[a:b], corner_shape=self.corner_shape,
+                                 thresholds=HOMOGRAPHY_THRESH, **kw)
+        self.pairs = f0 + P
+
+    @staticmethod
+    def _points64(pts5, subpixel):
+        pts = pts5[:, :, :3].double()
+        if subpixel:  # prob = x + sx - 2 in float64, as export.py stores it (Evaluator.run_device)
+            pts[:, :, :2] = pts[:, :, :2] + pts5[:, :, 3:5].double() - 2
+        return pts.contiguous()
+
+    def update_device(self, o, homographies, subpixel=True, hom_inv=None):
+        """The dict of DescriptorExporter.run_device (interleaved pts [2P,cap,5], count [2P], desc [2P,cap,256]) with the
+        pairs' true pixel homographies; subpixel: the exporter's setting."""
+        self.update_points(self._points64(o["pts"], subpixel), o["count"], o["desc"], homographies, hom_inv=hom_inv)
+
+    def update_views(self, d0, d1, hn, subpixel=True):
+        """Two Engine.describe_points dicts over the B images of a training pair's two views (image b of d0 against image
+        b of d1) and the step's normalised homographies hn (device float32 [B,3,3])."""
+        self.update_points(self._points64(d0["pts"], subpixel), d0["count"], d0["desc"], pair_stride=1,
+                           pts2=self._points64(d1["pts"], subpixel), count2=d1["count"], desc2=d1["desc"], normalised=hn)
+
+    def result(self):
+        """The one host read (state block and rows, in one copy) -> the summary: summarize's keys as means over the pairs
+        fed (sum / count, formed here in fp64), plus `pairs`, `no_model`, `rows_dropped` and `rows`, the float64
+        [min(pairs, capacity), 16] per-pair rows (include/ssp_hip.h).  repeatability is 0 and localization_err NaN when
+        no pair counts towards them."""
+        n = min(self.pairs, self.capacity)
+        host = torch.cat([self.state, self.rows[:n].reshape(-1)]).cpu().numpy()
+        st, rows = host[:L.EVAL_STATE_WORDS], host[L.EVAL_STATE_WORDS:].reshape(n, L.EVAL_ROW_WORDS)
+        pairs = st[0]
+        out = {"pairs": int(pairs), "rows_dropped": int(st[13]), "rows": rows}
+        if self.repeatability:
+            out["repeatability"] = st[1] / pairs if pairs > 0 else np.float64(0.0)
+            out["localization_err"] = st[2] / st[3] if st[3] > 0 else np.float64("nan")
+        if self.homography:
+            nan = np.float64("nan")
+            out["correctness"] = st[4:10] / pairs if pairs > 0 else np.full(6, nan)
+            out["homography_thresh"] = HOMOGRAPHY_THRESH
+            out["mscore"] = st[10] / pairs if pairs > 0 else nan
+            out["mAP"] = st[11] / pairs if pairs > 0 else nan
+            out["no_model"] = int(st[12])
+        return out
+
+    def per_file(self, rows=None):
+        """The rows as the per-pair dicts of Evaluator.run_points (without the estimated homography)."""
+        rows = self.result()["rows"] if rows is None else rows
+        res = []
+        for r in rows:
+            d = {}
+            if self.repeatability:
+                d["rep"], d["loc_err"] = (0, -1) if r[1] == -1 else (r[0], r[1])
+            if self.homography:
+                d["correctness"] = r[2:8] != 0
+                d["mscore"] = r[8]
+                d["mAP"] = r[9] if r[9] > 0 else 0
+            res.append(d)
+        return res
+
+    def write(self, path, files):
+        """result.txt / result.npz of `evaluate` for the pairs fed (named `files`, in feeding order) -> summarize's dict."""
+        per_file = self.per_file()
+        if len(files) != len(per_file):
+            raise ValueError("%d names for %d kept rows" % (len(files), len(per_file)))
+        return summarize(path, list(files), per_file, self.repeatability, self.homography, output_img=False)
 
 
 def _upload(datas, dev):

@@ -17,6 +17,7 @@ The descriptor export (keypoints, sparse descriptors and two-way matches of imag
 with `Val_model_heatmap` (Val_model_heatmap.py) as the per-image front end and `DescriptorExporter`, the fused path the
 loop uses: ONE eval forward over the 2P images of P pairs, keypoints + sparse descriptors (ssp_describe_points) and the
 matcher (ssp_match_two_way) on the device, then one read of the counts and sized copies.
+  evaluate_descriptor(config, args): the same loop feeding evaluation.StreamingEvaluator: the metrics, no files.
 
 Every arithmetic step runs in libssp_hip.so; tensors must live on a HIP device (no CPU fallback).  The dense-descriptor
 branch of SuperPointFrontend_torch.run (`onlyHeatmap=False`) is not provided and raises.
@@ -714,6 +715,64 @@ def export_descriptor(config, output_dir, args, test_loader=None, pairs_per_flus
     flush()
     logging.info("output pairs: %d", count)
     return count
+
+
+def evaluate_descriptor(config, args, test_loader=None, pairs_per_flush=16):
+    """export_descriptor's loop feeding an evaluation.StreamingEvaluator instead of writing `.npz` files: the -r -homo
+    metrics of the reference's `evaluation.py` over the loader's pairs with no export on disk and one host read at the
+    end.  Same config and loader as export_descriptor.  args: `repeatibility` / `homography` as evaluation.evaluate
+    reads them (both on when args is None or lacks them).  Returns StreamingEvaluator.result(); under torch.distributed
+    each rank evaluates the pairs i with i % world == rank and returns the summary of that shard (its pairs are
+    numbered in the shard's own order)."""
+    from .Val_model_heatmap import Val_model_heatmap
+    from .evaluation import StreamingEvaluator
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("evaluate_descriptor needs a HIP device: there is no CPU fallback")
+    rank, world = 0, 1
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+    mcfg = config["model"]
+    subpixel = bool(mcfg.get("subpixel", {}).get("enable", False))
+    if subpixel and mcfg.get("subpixel", {}).get("patch_size", 5) != 5:
+        raise ValueError("the device soft-argmax implements the 5x5 patch of the reference configs")
+    if test_loader is None:
+        from utils.loader import dataLoader_test as dataLoader  # the reference's own loader (export.py:100-104)
+        test_loader = dataLoader(config, dataset=config["data"]["dataset"])["test_loader"]
+    if not hasattr(test_loader, "__len__"):
+        test_loader = list(test_loader)
+    agent = Val_model_heatmap(mcfg, device=device)
+    agent.loadModel()
+    exporter = DescriptorExporter(agent.net, device, agent.conf_thresh, agent.nms_dist, subpixel, agent.nn_thresh,
+                                  agent.border_remove, batch_pairs=pairs_per_flush)
+    rep_on, homo_on = bool(getattr(args, "repeatibility", True)), bool(getattr(args, "homography", True))
+    capacity = max(1, (len(test_loader) + world - 1 - rank) // world)
+    ev, pending = None, []
+
+    def flush():
+        nonlocal ev
+        if not pending:
+            return
+        if ev is None:
+            h, w = _image_2d(pending[0]["image"]).shape
+            ev = StreamingEvaluator(h, w, device, capacity, repeatability=rep_on, homography=homo_on)
+        o = exporter.run_device([(s["image"], s["warped_image"]) for s in pending])
+        ev.update_device(o, np.stack([_squeeze_np(s["homography"]) for s in pending]), subpixel=subpixel)
+        pending.clear()
+
+    for i, sample in enumerate(test_loader):
+        if i % world != rank:
+            continue
+        pending.append(sample)
+        if len(pending) == pairs_per_flush:
+            flush()
+    flush()
+    if ev is None:
+        raise ValueError("the loader gave this rank no pair")
+    res = ev.result()
+    logging.info("evaluated pairs: %d", res["pairs"])
+    return res
 
 
 def _squeeze_np(t):

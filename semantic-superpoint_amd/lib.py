@@ -130,7 +130,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_op_point_classes", "ssp_point_classes", "ssp_filter_workspace_bytes", "ssp_op_filter_points",
            "ssp_match_two_way_classes",
            "ssp_det_eval_workspace_bytes", "ssp_op_det_tp_fp", "ssp_op_det_tp_fp_points", "ssp_det_pr_curve_workspace_bytes",
-           "ssp_op_det_pr_curve", "ssp_op_sparse_loss_path"]
+           "ssp_op_det_pr_curve", "ssp_op_sparse_loss_path",
+           "ssp_eval_pixel_homographies", "ssp_eval_accumulate"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -141,6 +142,9 @@ DET_EVAL_STATE_WORDS = 80  # SSP_DET_EVAL_STATE_WORDS: int64 words of an evaluat
 DET_EVAL_OUTSIDE = 3  # state word: point-list rows skipped because they lie outside the image (DET_STATE_OUTSIDE)
 DET_EVAL_HIST = 8  # first word of the d2 histogram in a state block (DET_STATE_HIST, csrc/detector_eval_kernels.hip.h)
 DET_CURVE_TILE = 1024  # DET_CURVE_TILE (csrc/detector_eval_kernels.hip.h): records per workgroup of the curve kernels
+EVAL_ACC_MAX_PAIRS = 128  # SSP_EVAL_ACC_MAX_PAIRS (include/ssp_hip.h): pairs per ssp_eval_accumulate call
+EVAL_ROW_WORDS = 16  # SSP_EVAL_ROW_WORDS: fp64 words of a pair's row of the streamed descriptor metrics
+EVAL_STATE_WORDS = 16  # SSP_EVAL_STATE_WORDS: fp64 words of their state block
 
 
 def load_library(path=None):
@@ -333,6 +337,13 @@ def load_library(path=None):
         lib.ssp_det_pr_curve_workspace_bytes.argtypes = [C.c_int64]
         lib.ssp_det_pr_curve_workspace_bytes.restype = C.c_size_t
         lib.ssp_op_det_pr_curve.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_eval_pixel_homographies.argtypes = [vp, i, i, i, vp, vp, vp]
+        lib.ssp_eval_accumulate.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, i, i, C.POINTER(C.c_double), C.c_int64, vp,
+                                            C.c_int64, vp, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -1808,6 +1819,86 @@ def op_eval_ransac(pts1, pts2, match, n_match, seeds, pair_stride=1, want_ap=Fal
                                    _ptr(seeds), _ptr(ws), _ptr(o["H"]), _ptr(o["mask"]), _ptr(o["n_inliers"]),
                                    _ptr(o["status"]), _ptr(o.get("ap")), _stream()))
     return o
+
+
+def op_eval_pixel_homographies(hn, height, width):
+    """The trainer's normalised homographies (sample["homographies"]: float32 [P,3,3] on the device) as pixel matrices of a
+    height x width image: (hom, hom_inv), float64 [P,3,3] device tensors.  hom = Tinv @ (Hn @ T) (homography_scaling,
+    utils/utils.py:291-294, in closed form); hom_inv = adj(hom) / det(hom), which is not np.linalg.inv bit for bit
+    (DESIGN.md section 21).  No host synchronisation."""
+    lib = load_library()
+    _need_gpu(hn, "hn")
+    if hn.dtype != torch.float32 or hn.dim() != 3 or tuple(hn.shape[1:]) != (3, 3) or hn.shape[0] < 1:
+        raise ValueError("hn must be float32 [P,3,3] (got %s %s)" % (hn.dtype, tuple(hn.shape)))
+    hn = hn.contiguous()
+    P = hn.shape[0]
+    hom = torch.empty(P, 3, 3, dtype=torch.float64, device=hn.device)
+    inv = torch.empty(P, 3, 3, dtype=torch.float64, device=hn.device)
+    with torch.cuda.device(hn.device):
+        _check(lib.ssp_eval_pixel_homographies(_ptr(hn), P, int(height), int(width), _ptr(hom), _ptr(inv), _stream()))
+    return hom, inv
+
+
+def eval_metrics_state(capacity, device):
+    """(rows float64 [capacity, EVAL_ROW_WORDS], state float64 [EVAL_STATE_WORDS]) of op_eval_accumulate, zeroed = empty."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("eval_metrics_state needs a HIP device: the MI355X path has no CPU fallback")
+    if int(capacity) < 1:
+        raise ValueError("capacity >= 1 pairs required (got %d)" % capacity)
+    return (torch.zeros(int(capacity), EVAL_ROW_WORDS, dtype=torch.float64, device=device),
+            torch.zeros(EVAL_STATE_WORDS, dtype=torch.float64, device=device))
+
+
+def op_eval_accumulate(rows, state, first_pair, rep=None, ransac=None, ap=None, n1=None, pair_stride=1, hom=None,
+                       corner_shape=(240, 320), thresholds=(1, 3, 5, 10, 20, 50)):
+    """Per-pair rows and running sums of the descriptor metrics (ssp_eval_accumulate, include/ssp_hip.h) for the P <=
+    EVAL_ACC_MAX_PAIRS pairs of a call, numbered first_pair, first_pair + 1, ...  rows / state: eval_metrics_state.
+    rep: float64 [P,8] of op_eval_repeatability, or None (repeatability off).  ransac: the dict of the crossCheck
+    op_eval_ransac with ap (float64 [P], the nn call's), n1 (int32 image-side counts, pair p at p * pair_stride) and hom
+    (float64 [P,3,3], the true pixel homographies), or None for all four (homography metrics off).  corner_shape: the
+    (height, width) whose corners measure correctness.  Updates rows and state in place; no host synchronisation."""
+    lib = load_library()
+    _need_gpu(rows, "rows")
+    _need_gpu(state, "state")
+    if rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[1] != EVAL_ROW_WORDS or rows.shape[0] < 1 or not rows.is_contiguous():
+        raise ValueError("rows must be contiguous float64 [capacity, %d] (eval_metrics_state)" % EVAL_ROW_WORDS)
+    if state.dtype != torch.float64 or tuple(state.shape) != (EVAL_STATE_WORDS,) or not state.is_contiguous():
+        raise ValueError("state must be float64 [%d] (eval_metrics_state)" % EVAL_STATE_WORDS)
+    group = (ransac, ap, n1, hom)
+    if any(g is None for g in group) and not all(g is None for g in group):
+        raise ValueError("ransac, ap, n1 and hom come together or not at all")
+    if rep is None and ransac is None:
+        raise ValueError("neither repeatability rows nor RANSAC results to accumulate")
+    P = rep.shape[0] if rep is not None else ap.numel()
+    if not 1 <= P <= EVAL_ACC_MAX_PAIRS:
+        raise ValueError("1 <= P <= %d pairs per call (got %d)" % (EVAL_ACC_MAX_PAIRS, P))
+    if int(first_pair) < 0:
+        raise ValueError("first_pair >= 0 required")
+    if len(thresholds) != 6 or len(corner_shape) != 2:
+        raise ValueError("six thresholds and a (height, width) corner shape are required")
+    if rep is not None:
+        _need_gpu(rep, "rep")
+        if rep.dtype != torch.float64 or tuple(rep.shape) != (P, 8) or not rep.is_contiguous():
+            raise ValueError("rep must be contiguous float64 [%d,8]" % P)
+    H = ninl = status = None
+    if ransac is not None:
+        H, ninl, status = ransac["H"], ransac["n_inliers"], ransac["status"]
+        for t, nm, dt, shp in ((H, "H", torch.float64, (P, 3, 3)), (ninl, "n_inliers", torch.int32, (P,)),
+                               (status, "status", torch.int32, (P,)), (ap, "ap", torch.float64, (P,)),
+                               (hom, "hom", torch.float64, (P, 3, 3))):
+            _need_gpu(t, nm)
+            if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
+                raise ValueError("%s must be contiguous %s %s" % (nm, dt, list(shp)))
+        _need_gpu(n1, "n1")
+        if n1.dtype != torch.int32 or n1.dim() != 1 or int(pair_stride) < 1 or n1.numel() < (P - 1) * int(pair_stride) + 1 \
+                or not n1.is_contiguous():
+            raise ValueError("n1 must be contiguous int32 with an entry at p * pair_stride for each of the %d pairs" % P)
+    thr = (C.c_double * 6)(*[float(t) for t in thresholds])
+    with torch.cuda.device(rows.device):
+        _check(lib.ssp_eval_accumulate(_ptr(rep), _ptr(H), _ptr(ninl), _ptr(status), _ptr(ap), _ptr(n1), int(pair_stride),
+                                       _ptr(hom), P, int(corner_shape[0]), int(corner_shape[1]), thr, int(first_pair),
+                                       _ptr(rows), rows.shape[0], _ptr(state), _stream()))
 
 
 def points_to_numpy(pts, count, subpixel):
