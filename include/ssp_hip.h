@@ -555,6 +555,37 @@ int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int
                     double* h_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev, double* ap_dev,
                     void* stream);
 
+/* ---- epipolar check of matches -------------------------------------------------------------
+ * A fundamental-matrix RANSAC for scenes that are not a plane (b^T F a = 0 for a = pts1 row i, b = pts2 row j of a match),
+ * and the compaction of the match rows by its mask.  fp64 without contraction; the rules are DESIGN.md section 22 and are
+ * restated in numpy by tests/epipolar_ref.py.  No call synchronises with the host or allocates.
+ * ssp_epi_ransac: pts1_dev / pts2_dev: fp64 rows starting (x, y), pt_stride >= 2 doubles per row, cap rows per entry; pair
+ *   p reads entry p * pair_stride of each.  match_dev [n_pairs][cap][3] = (i, j, distance) as ssp_match_two_way writes them,
+ *   n_match_dev [n_pairs]; seeds_dev [n_pairs].  Exactly 2000 hypotheses: 8 distinct matches from the counter-based stream
+ *   of ssp_eval_ransac (the same redraw rule), both images normalised over the 8 points, the null vector of the 8x9
+ *   system by Gaussian elimination with complete pivoting (pivot <= 1e-12: invalid), no rank-2 step per hypothesis;
+ *   score = #(squared Sampson distance <= thresh^2); the highest score wins, ties to the lowest hypothesis; a winner needs
+ *   a score of at least 8.  8 matches: one direct solve.  mask_dev [n_pairs][cap] is the winner's inlier set.  F is
+ *   refitted on the inliers (8x8 normal equations with the winner's largest entry held at 1), made rank 2 (Jacobi on
+ *   F^T F, F - (F v) v^T), scaled to unit Frobenius norm with its largest |entry| positive.  f_dev [n_pairs][9].
+ *   Fewer than 8 matches or no winner: status 1 ("no model"), F = 0, empty mask, 0 inliers, winner -1; otherwise 0.
+ *   winner_dev (may be NULL): the winning hypothesis; err_dev (may be NULL): RMS Sampson distance of the inliers under F.
+ *   groups: workgroups that share the hypotheses of one pair (1 .. 64; 0 = the library's choice: 32 while 32 * n_pairs
+ *   workgroups fit the 256 CUs at one each, else 16).  A pair's result does
+ *   not depend on groups, on its batch or on the order the workgroups run in.
+ *   workspace_dev: ssp_epi_ransac_workspace_bytes(cap, n_pairs) bytes.
+ * ssp_op_filter_matches: match_out_dev [n_pairs][cap][3] = the rows of match_dev whose mask byte is set, in order, zero
+ *   rows behind them; n_match_out_dev [n_pairs] their count.  A pair with status != 0 or n_inlier < min_inliers passes
+ *   through unchanged (decided on the device).  Never in place. */
+size_t ssp_epi_ransac_workspace_bytes(int cap, int n_pairs);
+int ssp_epi_ransac(const double* pts1_dev, const double* pts2_dev, int pt_stride, int cap, int n_pairs, int pair_stride,
+                   const float* match_dev, const int32_t* n_match_dev, const uint64_t* seeds_dev, double thresh, int groups,
+                   void* workspace_dev, double* f_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev,
+                   int32_t* winner_dev, double* err_dev, void* stream);
+int ssp_op_filter_matches(const float* match_dev, const int32_t* n_match_dev, const uint8_t* mask_dev, const int32_t* status_dev,
+                          const int32_t* n_inlier_dev, int min_inliers, int cap, int n_pairs, float* match_out_dev,
+                          int32_t* n_match_out_dev, void* stream);
+
 /* ---- streamed descriptor metrics ----------------------------------------------------------
  * The per-pair metrics of evaluation.py -r -homo for a set that is fed batch by batch and never leaves the device, on
  * top of ssp_eval_repeatability, ssp_match_two_way and ssp_eval_ransac.  fp64 without contraction.  No call

@@ -34,6 +34,7 @@
 #include "describe_kernels.hip.h"
 #include "track_kernels.hip.h"
 #include "eval_kernels.hip.h"
+#include "epipolar_kernels.hip.h"
 #include "detector_eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
@@ -3813,6 +3814,72 @@ int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int
   hipLaunchKernelGGL(eval_ransac_kernel, dim3(n_pairs), dim3(EVAL_THREADS), use_lds ? (size_t)cap * sizeof(double4) + small : small,
                      st, (const double4*)xy, match_dev, n_match_dev, cap, seeds_dev, (int)use_lds, h_dev, mask_dev,
                      n_inlier_dev, status_dev, ap_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- epipolar check of matches: fundamental-matrix RANSAC over several workgroups per pair ----
+// groups = 0: the measured choice (PERF_LOG.md, "Epipolar check").  One pair is fastest with 32 workgroups (120.7 / 208.5 us at
+// 500 / 1200 matches against 121.3 / 210.4 with 16 and 121.5 / 213.6 with 8); 16 pairs are fastest with 16 (124.0 / 213.7 us against
+// 194.6 / 365.2 with 32: 512 workgroups of more than 256 registers per lane run in two rounds on 256 CUs).  So 32 while
+// 32 x n_pairs workgroups fit the CUs at one each, else 16.  The result does not depend on the choice.
+#define EPI_GROUPS_FEW_PAIRS 32
+#define EPI_GROUPS_MANY_PAIRS 16
+#define EPI_CU_COUNT 256
+#define EPI_LDS_MAX ((size_t)SSP_MATCH_MAX_POINTS * (sizeof(double4) + 1))
+static int epi_check(const char* what, int cap, int n_pairs, int pair_stride, int pt_stride) {
+  if (cap < 1 || cap > SSP_MATCH_MAX_POINTS || n_pairs < 1 || n_pairs > 65535 || pair_stride < 1 || pt_stride < 2)
+    return fail(-1, "%s: 1 <= cap <= %d, 1 <= n_pairs <= 65535, pair_stride >= 1, pt_stride >= 2 required (cap %d, n_pairs %d)",
+                what, SSP_MATCH_MAX_POINTS, cap, n_pairs);
+  return 0;
+}
+
+size_t ssp_epi_ransac_workspace_bytes(int cap, int n_pairs) {
+  if (epi_check("epi_ransac", cap, n_pairs, 1, 2)) return 0;
+  return align_up((size_t)n_pairs * EPI_MAX_GROUPS * sizeof(uint64_t), 256);
+}
+
+int ssp_epi_ransac(const double* pts1_dev, const double* pts2_dev, int pt_stride, int cap, int n_pairs, int pair_stride,
+                   const float* match_dev, const int32_t* n_match_dev, const uint64_t* seeds_dev, double thresh, int groups,
+                   void* workspace_dev, double* f_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev,
+                   int32_t* winner_dev, double* err_dev, void* stream) {
+  CHK(epi_check("epi_ransac", cap, n_pairs, pair_stride, pt_stride));
+  if (!pts1_dev || !pts2_dev || !match_dev || !n_match_dev || !seeds_dev || !workspace_dev || !f_dev || !mask_dev ||
+      !n_inlier_dev || !status_dev)
+    return fail(-1, "epi_ransac: null pointer");
+  if (!(thresh >= 0.0) || !std::isfinite(thresh)) return fail(-1, "epi_ransac: a finite thresh >= 0 is required");
+  if (groups < 0 || groups > EPI_MAX_GROUPS)
+    return fail(-1, "epi_ransac: 0 (the library's choice) <= groups <= %d required (got %d)", EPI_MAX_GROUPS, groups);
+  if (groups == 0) groups = n_pairs * EPI_GROUPS_FEW_PAIRS <= EPI_CU_COUNT ? EPI_GROUPS_FEW_PAIRS : EPI_GROUPS_MANY_PAIRS;
+  hipStream_t st = (hipStream_t)stream;
+  uint64_t* keys = reinterpret_cast<uint64_t*>(workspace_dev);
+  static AttrOnce attr_once;
+  if (attr_once.need()) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(epi_hypotheses_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)EPI_LDS_MAX));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(epi_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)EPI_LDS_MAX));
+  }
+  hipLaunchKernelGGL(epi_hypotheses_kernel, dim3(groups, n_pairs), dim3(EPI_THREADS), (size_t)cap * sizeof(double4), st, pts1_dev,
+                     pts2_dev, pt_stride, cap, pair_stride, match_dev, n_match_dev, seeds_dev, thresh, keys);
+  hipLaunchKernelGGL(epi_finish_kernel, dim3(n_pairs), dim3(EPI_THREADS), (size_t)cap * (sizeof(double4) + 1), st, pts1_dev,
+                     pts2_dev, pt_stride, cap, pair_stride, match_dev, n_match_dev, seeds_dev, thresh, groups,
+                     (const uint64_t*)keys, f_dev, mask_dev, n_inlier_dev, status_dev, winner_dev, err_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_op_filter_matches(const float* match_dev, const int32_t* n_match_dev, const uint8_t* mask_dev, const int32_t* status_dev,
+                          const int32_t* n_inlier_dev, int min_inliers, int cap, int n_pairs, float* match_out_dev,
+                          int32_t* n_match_out_dev, void* stream) {
+  if (cap < 1 || cap > SSP_MATCH_MAX_POINTS || n_pairs < 1)
+    return fail(-1, "filter_matches: 1 <= cap <= %d and n_pairs >= 1 required (cap %d)", SSP_MATCH_MAX_POINTS, cap);
+  if (!match_dev || !n_match_dev || !mask_dev || !status_dev || !n_inlier_dev || !match_out_dev || !n_match_out_dev)
+    return fail(-1, "filter_matches: null pointer");
+  if (match_dev == match_out_dev || n_match_dev == n_match_out_dev)
+    return fail(-1, "filter_matches: the matches are not filtered in place (pass a second set of arrays)");
+  hipLaunchKernelGGL(match_filter_kernel, dim3(n_pairs), dim3(TRACK_BLOCK), 0, (hipStream_t)stream, match_dev, n_match_dev, mask_dev,
+                     status_dev, n_inlier_dev, min_inliers, cap, match_out_dev, n_match_out_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -238,9 +238,20 @@ class PointTracker(object):
     (no drawing here): `track_points` returns the coordinates it would connect.
     class_consistent=True: every frame comes with the class of each point (`cls`); the previous
     frame's classes are kept beside its descriptors and only points of equal class are matched
-    (ssp_match_two_way_classes).  The track table logic is the same."""
+    (ssp_match_two_way_classes).  The track table logic is the same.
+    geometric_check: None accepts every mutual match below nn_thresh (the reference).  "fundamental"
+    fits a fundamental matrix to the frame's matches (lib.op_epipolar_ransac, inliers within check_thresh pixels of Sampson
+    distance) and "homography" a homography (lib.op_eval_ransac with its own 3 px rule); only the inliers continue tracks and
+    are reported by get_matches / get_mscores.  A frame with no model or fewer than min_inliers inliers keeps all its
+    matches; that is decided on the device.  Frame f (0-based) uses seed check_seed + f.  last_geometry() is the newest
+    frame's result."""
 
-    def __init__(self, max_length, nn_thresh, device=None, class_consistent=False):
+    def __init__(self, max_length, nn_thresh, device=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
+                 min_inliers=16, check_seed=0):
+        if geometric_check not in (None, "fundamental", "homography"):
+            raise ValueError("geometric_check must be None, 'fundamental' or 'homography' (got %r)" % (geometric_check,))
+        if geometric_check is not None and not (check_thresh >= 0.0 and min_inliers >= 0):
+            raise ValueError("check_thresh and min_inliers must be non-negative")
         if max_length < 2:
             raise ValueError("max_length must be greater than or equal to 2.")
         if max_length > L.TRACK_MAX_LENGTH:
@@ -265,6 +276,10 @@ class PointTracker(object):
         self._pending = None      # device (match, n_match, had_prev) whose numpy form get_matches() has not been asked for yet
         self.class_consistent = bool(class_consistent)
         self._cls = None          # uint8 [2, cap] beside _desc (class_consistent only)
+        self.geometric_check = geometric_check
+        self.check_thresh, self.min_inliers, self.check_seed = float(check_thresh), int(min_inliers), int(check_seed)
+        self._seed = None         # int64 [1] on the device: the seed of the next frame's check
+        self._geometry = None
 
     # ---- device buffers -------------------------------------------------------------------------------------------
     def _ensure(self, n):
@@ -317,6 +332,8 @@ class PointTracker(object):
         if self.class_consistent:
             self._cls[dslot, :n] = cls
         m, nm = self._match_device()
+        if self.geometric_check is not None:
+            m, nm = self._check_device(m, nm)
         self._track_device(m, nm)
         had_prev, self._prev_ok = self._prev_ok, True
         return m, nm, had_prev
@@ -332,6 +349,28 @@ class PointTracker(object):
         m, nm = L.op_match_two_way(self._desc[1 - dslot:2 - dslot], prev, self._desc[dslot:dslot + 1],
                                    self._counts[dslot:dslot + 1], self.nn_thresh)
         return m[0], nm
+
+    def _check_device(self, m, nm):
+        """The geometric check of the newest frame's matches against the previous frame: (match, n_match) of the inliers."""
+        if self._seed is None:
+            self._seed = torch.full((1,), self.check_seed + self._frames - 1, dtype=torch.int64, device=self.device)
+        slot, _ = self._slots()
+        pslot = (slot - 1) % self.maxl
+        p1, p2 = self._pts[pslot:pslot + 1], self._pts[slot:slot + 1]
+        if self.geometric_check == "fundamental":
+            g = L.op_epipolar_ransac(p1, p2, m[None], nm, self._seed, thresh=self.check_thresh)
+        else:
+            pad = torch.zeros(2, self._cap, 1, dtype=torch.float64, device=self.device)
+            p12 = torch.cat([torch.cat([p1, p2]), pad], dim=2)
+            g = L.op_eval_ransac(p12[0:1], p12[1:2], m[None], nm, self._seed)
+        self._seed = self._seed + 1
+        self._geometry = g
+        return L.op_filter_matches(m, nm, g["mask"], g["status"], g["n_inliers"], self.min_inliers)
+
+    def last_geometry(self):
+        """The device dict of the newest frame's geometric check (lib.op_epipolar_ransac or lib.op_eval_ransac), None before
+        the first checked frame or without a check.  Its mask indexes the UNFILTERED matches of that frame."""
+        return self._geometry
 
     def _track_device(self, m, nm):
         _, dslot = self._slots()
@@ -524,10 +563,13 @@ class SequenceTracker:
     DescriptorExporter's.  Read the result with get_tracks / track_points (or `tracker`, the PointTracker).
     Semantic keypoints (the model needs a segmentation head): keep_classes / drop_classes (one of them)
     remove the keypoints of unwanted classes on the device before they enter the track table; class_consistent matches only
-    points of equal class.  Neither adds a host copy or a synchronisation."""
+    points of equal class.  Neither adds a host copy or a synchronisation.
+    geometric_check / check_thresh / min_inliers / check_seed: PointTracker's epipolar or homography check of every frame's
+    matches, also without a host copy or a synchronisation."""
 
     def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4,
-                 keep_classes=None, drop_classes=None, class_consistent=False):
+                 keep_classes=None, drop_classes=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
+                 min_inliers=16, check_seed=0):
         if nn_thresh < 0.0:
             raise ValueError("'nn_thresh' should be non-negative")
         self.class_consistent = bool(class_consistent)
@@ -540,7 +582,9 @@ class SequenceTracker:
         self.net, self.device = net, torch.device(device)
         self.conf_thresh, self.nms_dist, self.subpixel = conf_thresh, nms_dist, bool(subpixel)
         self.border_remove = border_remove
-        self.tracker = PointTracker(max_length, nn_thresh, self.device, class_consistent=self.class_consistent)
+        self.tracker = PointTracker(max_length, nn_thresh, self.device, class_consistent=self.class_consistent,
+                                    geometric_check=geometric_check, check_thresh=check_thresh, min_inliers=min_inliers,
+                                    check_seed=check_seed)
 
     def describe(self, image):
         """image [H,W] / [1,H,W] / [1,1,H,W] -> the device tensors of Engine.describe_points for this one image (with "cls",

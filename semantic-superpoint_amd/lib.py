@@ -131,7 +131,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_match_two_way_classes",
            "ssp_det_eval_workspace_bytes", "ssp_op_det_tp_fp", "ssp_op_det_tp_fp_points", "ssp_det_pr_curve_workspace_bytes",
            "ssp_op_det_pr_curve", "ssp_op_sparse_loss_path",
-           "ssp_eval_pixel_homographies", "ssp_eval_accumulate"]
+           "ssp_eval_pixel_homographies", "ssp_eval_accumulate",
+           "ssp_epi_ransac_workspace_bytes", "ssp_epi_ransac", "ssp_op_filter_matches"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -337,6 +338,14 @@ def load_library(path=None):
         lib.ssp_det_pr_curve_workspace_bytes.argtypes = [C.c_int64]
         lib.ssp_det_pr_curve_workspace_bytes.restype = C.c_size_t
         lib.ssp_op_det_pr_curve.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_epi_ransac_workspace_bytes.argtypes = [i, i]
+        lib.ssp_epi_ransac_workspace_bytes.restype = C.c_size_t
+        lib.ssp_epi_ransac.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, C.c_double, i, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.ssp_op_filter_matches.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -1819,6 +1828,79 @@ def op_eval_ransac(pts1, pts2, match, n_match, seeds, pair_stride=1, want_ap=Fal
                                    _ptr(seeds), _ptr(ws), _ptr(o["H"]), _ptr(o["mask"]), _ptr(o["n_inliers"]),
                                    _ptr(o["status"]), _ptr(o.get("ap")), _stream()))
     return o
+
+
+def op_epipolar_ransac(pts1, pts2, match, n_match, seeds, thresh=1.0, pair_stride=1, groups=0):
+    """Fundamental-matrix RANSAC of P pairs' matches on the device (ssp_epi_ransac): b^T F a = 0 for
+    a = pts1 row i, b = pts2 row j of a match.  pts1, pts2: float64 [>= (P-1)*pair_stride+1, cap, pt_stride >= 2] rows starting
+    (x, y) (the evaluator's [.,cap,3] arrays or the tracker's [.,cap,2] ring); match: float32 [P, cap, 3] rows (i, j, distance)
+    as op_match_two_way returns them, n_match: int32 [P], seeds: int64 [P]; thresh: the Sampson distance of an inlier in
+    pixels; groups: workgroups per pair (0 = the library's choice; the result does not depend on it).
+    Returns device tensors {"F": float64 [P,3,3] (unit Frobenius norm, rank 2), "mask": uint8 [P,cap], "n_inliers": int32 [P],
+    "status": int32 [P] (1 = no model), "winner": int32 [P] (the hypothesis, -1), "err": float64 [P] (RMS Sampson distance
+    of the inliers)}.  No host synchronisation."""
+    lib = load_library()
+    for t, nm in ((pts1, "pts1"), (pts2, "pts2"), (match, "match"), (n_match, "n_match"), (seeds, "seeds")):
+        _need_gpu(t, nm)
+    if match.dtype != torch.float32 or match.dim() != 3 or match.shape[2] != 3 or not match.is_contiguous():
+        raise ValueError("match must be contiguous float32 [P, cap, 3]")
+    P, cap = match.shape[0], match.shape[1]
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
+    if pts1.dim() != 3 or pts1.shape[2] < 2 or pts2.shape[2] != pts1.shape[2]:
+        raise ValueError("pts1 and pts2 must be float64 [., cap, pt_stride >= 2] with one pt_stride")
+    for t, nm in ((pts1, "pts1"), (pts2, "pts2")):
+        if t.dtype != torch.float64 or t.shape[1] != cap or t.shape[0] < (P - 1) * pair_stride + 1 or not t.is_contiguous():
+            raise ValueError("%s must be contiguous float64 [P*pair_stride, %d, pt_stride]" % (nm, cap))
+    if n_match.dtype != torch.int32 or n_match.numel() != P:
+        raise ValueError("n_match must be int32 [%d]" % P)
+    if seeds.dtype != torch.int64 or seeds.numel() != P:
+        raise ValueError("seeds must be int64 [%d]" % P)
+    wsb = lib.ssp_epi_ransac_workspace_bytes(cap, P)
+    if wsb == 0:
+        _check(-1)
+    dev = match.device
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    o = {"F": torch.empty(P, 3, 3, dtype=torch.float64, device=dev),
+         "mask": torch.empty(P, cap, dtype=torch.uint8, device=dev),
+         "n_inliers": torch.empty(P, dtype=torch.int32, device=dev),
+         "status": torch.empty(P, dtype=torch.int32, device=dev),
+         "winner": torch.empty(P, dtype=torch.int32, device=dev),
+         "err": torch.empty(P, dtype=torch.float64, device=dev)}
+    with torch.cuda.device(dev):
+        _check(lib.ssp_epi_ransac(_ptr(pts1), _ptr(pts2), int(pts1.shape[2]), cap, P, int(pair_stride), _ptr(match),
+                                  _ptr(n_match), _ptr(seeds), float(thresh), int(groups), _ptr(ws), _ptr(o["F"]),
+                                  _ptr(o["mask"]), _ptr(o["n_inliers"]), _ptr(o["status"]), _ptr(o["winner"]), _ptr(o["err"]),
+                                  _stream()))
+    return o
+
+
+def op_filter_matches(match, n_match, mask, status, n_inliers, min_inliers):
+    """The match rows a geometric check kept (ssp_op_filter_matches): match float32 [P, cap, 3] (or [cap, 3] for one pair),
+    n_match int32 [P], and the mask uint8 [P, cap], status int32 [P], n_inliers int32 [P] of op_epipolar_ransac or
+    op_eval_ransac.  Returns (match_out, n_match_out): the rows whose mask byte is set, in order (zero rows behind them); a
+    pair with status != 0 or fewer than min_inliers inliers passes through unchanged.  That decision is taken on the device:
+    no host synchronisation."""
+    lib = load_library()
+    for t, nm in ((match, "match"), (n_match, "n_match"), (mask, "mask"), (status, "status"), (n_inliers, "n_inliers")):
+        _need_gpu(t, nm)
+    m3 = match if match.dim() == 3 else match[None]
+    if m3.dtype != torch.float32 or m3.dim() != 3 or m3.shape[2] != 3 or not m3.is_contiguous():
+        raise ValueError("match must be contiguous float32 [P, cap, 3] or [cap, 3]")
+    P, cap = m3.shape[0], m3.shape[1]
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
+    if mask.dtype != torch.uint8 or mask.numel() != P * cap or not mask.is_contiguous():
+        raise ValueError("mask must be contiguous uint8 [%d, %d]" % (P, cap))
+    for t, nm in ((n_match, "n_match"), (status, "status"), (n_inliers, "n_inliers")):
+        if t.dtype != torch.int32 or t.numel() != P:
+            raise ValueError("%s must be int32 [%d]" % (nm, P))
+    out = torch.empty_like(m3)
+    n_out = torch.empty(P, dtype=torch.int32, device=m3.device)
+    with torch.cuda.device(m3.device):
+        _check(lib.ssp_op_filter_matches(_ptr(m3), _ptr(n_match), _ptr(mask), _ptr(status), _ptr(n_inliers), int(min_inliers),
+                                         cap, P, _ptr(out), _ptr(n_out), _stream()))
+    return (out if match.dim() == 3 else out[0]), n_out
 
 
 def op_eval_pixel_homographies(hn, height, width):
