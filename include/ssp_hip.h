@@ -286,7 +286,11 @@ int ssp_op_warp_labels_px(const float* labels_dev, const float* hpx_dev, float* 
  *     equivalent of the numpy / scipy streams); h_dev = `homographies` (image -> warped), inv_h_dev = `inv_homographies`.
  * ssp_op_warp_labels_full : warpLabels(..., bilinear=True) (datasets/data_tools.py:37-63) on a keypoint map:
  *     labels [b,1,h,w], res [b,2,h,w] (warped - round(warped) at the rounded position), labels_bi [b,1,h,w]
- *     (get_labels_bi :26-34); any output may be NULL; last-write-wins scatters like torch.
+ *     (get_labels_bi :26-34); any output may be NULL.  Where several key points claim one pixel the winner does not depend on
+ *     thread order: points count in row-major order of the map (torch.nonzero); labels / res keep the LAST point that rounds to
+ *     the pixel; labels_bi keeps the later of the four neighbour lists (x,y), (x,y+1), (x+1,y), (x+1,y+1) that the reference
+ *     concatenates before its single scatter, and within a list the later point.  Two passes (integer atomicMax of a priority
+ *     key into the zero-filled maps, then the winner's value in place): no extra memory; h * w < 2^29 or the call is refused.
  * ssp_op_sem_finalize     : datasets/Coco_sem.py:447-448: float class map -> int64, invalid pixels -> n_classes. */
 typedef struct ssp_homography_params {
   int32_t perspective, scaling, rotation, translation, allow_artifacts;

@@ -1007,8 +1007,9 @@ def descriptor_loss_dense(desc, desc_w, homographies, mask_valid=None, cell_size
 def warp_labels_full(pnts_xy, H, W, homography):
     """warpLabels(pnts, H, W, homography, bilinear=True): returns (labels [1,H,W], res [2,H,W] = warped point minus its
     rounded position, written at the rounded position, labels_bi [1,H,W] = the 4-neighbour bilinear splat of
-    get_labels_bi, :26-34).  Scatters are last-write-wins (torch index_put), so results are only defined when no two
-    points land on the same pixel."""
+    get_labels_bi, :26-34).  The scatters are torch's indexed assignment, whose winner among repeated indices is not
+    specified by torch: this function is used where no two points land on one pixel; the order-defined winners (the last write
+    of the reference's own list) are restated with explicit loops in tests/pairs_ref.py::warp_labels_full."""
     Hpix = scale_homography(homography.float(), (H, W))
     wp_all = warp_points(pnts_xy.long().float(), Hpix)
     # get_labels_bi works on ALL warped points, filtering the 4 extrapolated neighbours afterwards

@@ -136,14 +136,20 @@ __global__ void warp_labels_kernel(const float* __restrict__ labels, const float
 //   out_res [B,2,H,W]  (x, y) residual warped - round(warped), written at the rounded position
 //   out_bi  [B,1,H,W]  get_labels_bi (:26-34): the 4 neighbours of the TRUNCATED warped point (all points, the
 //                      neighbours are range-filtered individually) receive their bilinear weight
-// All three must be zero-filled; scatters are last-write-wins like torch's index_put.
-__global__ void warp_labels_full_kernel(const float* __restrict__ labels, const float* __restrict__ hn,
-                                        const float* __restrict__ hpx, float* __restrict__ out_lab,
-                                        float* __restrict__ out_res, float* __restrict__ out_bi, int B, int H, int W) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)B * H * W) return;
-  if (labels[idx] == 0.f) return;
-  const int x = (int)(idx % W), y = (int)((idx / W) % H), n = (int)(idx / ((long)W * H));
+// When several points claim one pixel the winner is the one the reference's single index_put of the point list in
+// row-major order of the map (torch.nonzero) leaves behind: for labels / res the LAST point in that order; for labels_bi
+// the reference concatenates the four neighbour lists (x,y), (x,y+1), (x+1,y), (x+1,y+1) of all points, so the later list
+// wins and within a list the later point.  Two passes make this independent of thread order without extra memory:
+//   pass 1 (one thread per source pixel) atomicMax-es an integer priority key into the zero-filled float maps themselves:
+//          bi: list << 29 | (source index + 1); res channel 0: source index + 1; labels: plain store of 1 (all writers agree)
+//   pass 2 (one thread per output pixel) recomputes the winner's weight / residual from its key and overwrites the key.
+// Key 0 = no claimant = 0.0f, the value the reference leaves there.  H * W < 2^29 (checked by the host wrapper).
+#define SSP_WLF_IDX_BITS 29
+struct WarpedPoint {
+  float wx, wy;
+};
+__device__ __forceinline__ WarpedPoint wlf_warp(const float* __restrict__ hn, const float* __restrict__ hpx, int n, int x, int y,
+                                                int H, int W) {
   float P[9];
   if (hpx != nullptr) {
 #pragma unroll
@@ -151,25 +157,65 @@ __global__ void warp_labels_full_kernel(const float* __restrict__ labels, const 
   } else {
     pixel_homography_analytic(hn + n * 9, H, W, P);
   }
-  float wx, wy;
-  warp_point_exact(P, (float)x, (float)y, wx, wy);
+  WarpedPoint p;
+  warp_point_exact(P, (float)x, (float)y, p.wx, p.wy);
+  return p;
+}
+__device__ __forceinline__ bool wlf_inside(float px, float py, int H, int W) {
+  return px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1);
+}
+
+__global__ void warp_labels_full_claim_kernel(const float* __restrict__ labels, const float* __restrict__ hn,
+                                              const float* __restrict__ hpx, float* __restrict__ out_lab,
+                                              float* __restrict__ out_res, float* __restrict__ out_bi, int B, int H, int W) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)B * H * W) return;
+  if (labels[idx] == 0.f) return;
+  const int x = (int)(idx % W), y = (int)((idx / W) % H), n = (int)(idx / ((long)W * H));
+  const WarpedPoint p = wlf_warp(hn, hpx, n, x, y, H, W);
+  const float wx = p.wx, wy = p.wy;
   const size_t img = (size_t)n * H * W;
-  auto inside = [&](float px, float py) { return px >= 0.f && px <= (float)(W - 1) && py >= 0.f && py <= (float)(H - 1); };
+  const unsigned src = (unsigned)(y * W + x) + 1u;
   if (out_bi != nullptr && fabsf(wx) < 1e9f && fabsf(wy) < 1e9f) {
     const float xi = truncf(wx), yi = truncf(wy);  // pnts.long(): truncation toward zero
-    const float rx = wx - xi, ry = wy - yi;
-    if (inside(xi, yi)) out_bi[img + (size_t)yi * W + (size_t)xi] = (1.f - rx) * (1.f - ry);
-    if (inside(xi, yi + 1.f)) out_bi[img + (size_t)(yi + 1.f) * W + (size_t)xi] = (1.f - rx) * ry;
-    if (inside(xi + 1.f, yi)) out_bi[img + (size_t)yi * W + (size_t)(xi + 1.f)] = rx * (1.f - ry);
-    if (inside(xi + 1.f, yi + 1.f)) out_bi[img + (size_t)(yi + 1.f) * W + (size_t)(xi + 1.f)] = rx * ry;
+    unsigned* bi = reinterpret_cast<unsigned*>(out_bi) + img;
+#pragma unroll
+    for (unsigned l = 0; l < 4; ++l) {  // list l: (x, y), (x, y + 1), (x + 1, y), (x + 1, y + 1)
+      const float nx = xi + (float)(l >> 1), ny = yi + (float)(l & 1);
+      if (wlf_inside(nx, ny, H, W)) atomicMax(bi + (size_t)ny * W + (size_t)nx, (l << SSP_WLF_IDX_BITS) | src);
+    }
   }
-  if (inside(wx, wy)) {
+  if (wlf_inside(wx, wy, H, W)) {
     const float qx = rintf(wx), qy = rintf(wy);  // torch.round: half to even
     const size_t o = (size_t)qy * W + (size_t)qx;
     if (out_lab != nullptr) out_lab[img + o] = 1.f;
-    if (out_res != nullptr) {
-      out_res[2 * img + o] = wx - qx;
-      out_res[2 * img + (size_t)H * W + o] = wy - qy;
+    if (out_res != nullptr) atomicMax(reinterpret_cast<unsigned*>(out_res) + 2 * img + o, src);
+  }
+}
+
+__global__ void warp_labels_full_resolve_kernel(const float* __restrict__ hn, const float* __restrict__ hpx,
+                                                float* __restrict__ out_res, float* __restrict__ out_bi, int B, int H, int W) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)B * H * W) return;
+  const int n = (int)(idx / ((long)W * H));
+  const size_t img = (size_t)n * H * W, o = (size_t)(idx - (long)img);
+  if (out_bi != nullptr) {
+    const unsigned key = reinterpret_cast<const unsigned*>(out_bi)[idx];
+    if (key != 0u) {
+      const unsigned l = key >> SSP_WLF_IDX_BITS, s = (key & ((1u << SSP_WLF_IDX_BITS) - 1u)) - 1u;
+      const WarpedPoint p = wlf_warp(hn, hpx, n, (int)(s % (unsigned)W), (int)(s / (unsigned)W), H, W);
+      const float rx = p.wx - truncf(p.wx), ry = p.wy - truncf(p.wy);
+      const float fx = (l >> 1) ? rx : 1.f - rx, fy = (l & 1) ? ry : 1.f - ry;
+      out_bi[idx] = fx * fy;
+    }
+  }
+  if (out_res != nullptr) {
+    const unsigned key = reinterpret_cast<const unsigned*>(out_res)[2 * img + o];
+    if (key != 0u) {
+      const unsigned s = key - 1u;
+      const WarpedPoint p = wlf_warp(hn, hpx, n, (int)(s % (unsigned)W), (int)(s / (unsigned)W), H, W);
+      out_res[2 * img + o] = p.wx - rintf(p.wx);
+      out_res[2 * img + (size_t)H * W + o] = p.wy - rintf(p.wy);
     }
   }
 }
@@ -222,6 +268,11 @@ struct HsRng {
     }
   }
 };
+
+// np.linspace(-max_angle, max_angle, n_angles)[i]; a single angle is the START of the interval, -max_angle (not 0)
+__device__ __forceinline__ double hs_angle(double max_angle, int i, int na) {
+  return na > 1 ? -max_angle + 2.0 * max_angle * i / (na - 1) : -max_angle;
+}
 
 __global__ void sample_homographies_kernel(uint64_t seed, HomographyParams p, float* __restrict__ out_h,
                                            float* __restrict__ out_inv, int B) {
@@ -281,7 +332,7 @@ __global__ void sample_homographies_kernel(uint64_t seed, HomographyParams p, fl
     const int na = min(p.n_angles, 63);
     int valid[64], nv = 0;
     for (int i = 0; i <= na; ++i) {
-      const double ang = i < na ? (na > 1 ? -p.max_angle + 2.0 * p.max_angle * i / (na - 1) : 0.0) : 0.0;
+      const double ang = i < na ? hs_angle(p.max_angle, i, na) : 0.0;
       const double c = cos(ang), s = sin(ang);
       double q[4][2];
       for (int k = 0; k < 4; ++k) {  // (pts - centre) @ [[c, -s], [s, c]] + centre
@@ -293,7 +344,7 @@ __global__ void sample_homographies_kernel(uint64_t seed, HomographyParams p, fl
     }
     if (nv > 0) {
       const int i = valid[min((int)(rng.uniform() * nv), nv - 1)];
-      const double ang = i < na ? (na > 1 ? -p.max_angle + 2.0 * p.max_angle * i / (na - 1) : 0.0) : 0.0;
+      const double ang = i < na ? hs_angle(p.max_angle, i, na) : 0.0;
       const double c = cos(ang), s = sin(ang);
       for (int k = 0; k < 4; ++k) {
         const double dx = p2[k][0] - cx, dy = p2[k][1] - cy;

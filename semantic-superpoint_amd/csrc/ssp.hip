@@ -4086,13 +4086,20 @@ int ssp_op_sample_homographies(uint64_t seed, const ssp_homography_params* p, in
 
 static int warp_labels_full_impl(const float* labels_dev, const float* h_dev, const float* hpx_dev, float* labels_out_dev,
                                  float* res_out_dev, float* bi_out_dev, int b, int hh, int w, hipStream_t st) {
+  if (!labels_dev || b < 1 || hh < 1 || w < 1) return fail(-1, "warp_labels_full: bad argument");
+  if ((long)hh * w >= (1L << 29)) return fail(-1, "warp_labels_full: h * w < 2^29 required (29-bit source index in the scatter key)");
   const long n = (long)b * hh * w;
   if (labels_out_dev) HIPCHK(hipMemsetAsync(labels_out_dev, 0, n * sizeof(float), st));
   if (res_out_dev) HIPCHK(hipMemsetAsync(res_out_dev, 0, 2 * n * sizeof(float), st));
   if (bi_out_dev) HIPCHK(hipMemsetAsync(bi_out_dev, 0, n * sizeof(float), st));
-  hipLaunchKernelGGL(warp_labels_full_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, labels_dev, h_dev, hpx_dev, labels_out_dev,
+  hipLaunchKernelGGL(warp_labels_full_claim_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, labels_dev, h_dev, hpx_dev, labels_out_dev,
                      res_out_dev, bi_out_dev, b, hh, w);
   HIPCHK(hipGetLastError());
+  if (res_out_dev || bi_out_dev) {  // the priority keys pass 1 left in the maps become the winners' values
+    hipLaunchKernelGGL(warp_labels_full_resolve_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, h_dev, hpx_dev, res_out_dev,
+                       bi_out_dev, b, hh, w);
+    HIPCHK(hipGetLastError());
+  }
   return 0;
 }
 int ssp_op_warp_labels_full(const float* labels_dev, const float* h_dev, float* labels_out_dev, float* res_out_dev,

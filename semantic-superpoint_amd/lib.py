@@ -2014,15 +2014,19 @@ def op_sample_homographies(B, seed, device, perspective=True, scaling=True, rota
     return h, inv
 
 
-def op_warp_labels_full(labels, hn, exact=True):
+def op_warp_labels_full(labels, hn, exact=True, outputs=(True, True, True)):
     """warpLabels(bilinear=True) on a keypoint map [B,1,H,W]: (labels [B,1,H,W], res [B,2,H,W], labels_bi [B,1,H,W]).
-    exact: see op_warp_labels."""
+    Where several key points claim one pixel the winner is defined by the reference's write order, not by thread order: the
+    points are taken in row-major order of the map; labels / res keep the last point that rounds to the pixel, labels_bi the
+    later of the four neighbour lists (x,y), (x,y+1), (x+1,y), (x+1,y+1) and within a list the later point.  Two calls on the
+    same inputs are bit-identical.  exact: see op_warp_labels.  outputs: which of the three maps to produce (None otherwise:
+    the C ABI takes NULL for a map that is not wanted)."""
     lib = load_library()
     _need_gpu(labels, "labels")
     B, _, H, W = labels.shape
-    lab = torch.empty_like(labels)
-    res = torch.empty(B, 2, H, W, dtype=torch.float32, device=labels.device)
-    bi = torch.empty_like(labels)
+    lab = torch.empty_like(labels) if outputs[0] else None
+    res = torch.empty(B, 2, H, W, dtype=torch.float32, device=labels.device) if outputs[1] else None
+    bi = torch.empty_like(labels) if outputs[2] else None
     with torch.cuda.device(labels.device):
         if exact:
             hpx = scaled_homographies(hn, H, W).to(labels.device)

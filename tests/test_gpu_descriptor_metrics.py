@@ -304,8 +304,8 @@ def test_trainer_descriptor_metrics(tmp_path):
     samples = []
     for it in range(2):
         g = torch.Generator().manual_seed(20 + it)
-        # keypoints 8 pixels apart: no two of them scatter into one pixel of the warped label maps, where the last write wins by
-        # thread order (tests/test_gpu_trainer_device_pairs.py); with deterministic accumulation the steps then repeat bit for bit
+        # keypoints 8 pixels apart: no two of them scatter into one pixel of the warped label maps (colliding ones are covered by
+        # tests/test_gpu_trainer_device_pairs.py); with deterministic accumulation the steps repeat bit for bit
         lab = torch.zeros(B, 1, hh, ww)
         lab[:, :, 4::8, 4::8] = (torch.rand(B, 1, hh // 8, ww // 8, generator=g) < 0.3).float()
         samples.append({"image": torch.rand(B, 1, hh, ww, generator=g), "labels_2D": lab,

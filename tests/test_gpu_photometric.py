@@ -174,8 +174,8 @@ def test_draw_rejects_unknown_struct_size_and_repeated_primitives(golden_dir):
 def _pair_inputs(B=4, H=64, W=96):
     g = torch.Generator().manual_seed(0)
     img = torch.rand(B, 1, H, W, generator=g).to(_dev())
-    # keypoints 8 pixels apart: two keypoints landing on one pixel make the last-write-wins scatter of warped_labels_bi depend on
-    # thread order (an existing property of op_warp_labels_full), and these tests compare two calls bit for bit
+    # keypoints 8 pixels apart (chosen when colliding keypoints still made warped_labels_bi depend on thread order; the scatter is
+    # order-defined now: tests/test_gpu_pairs_exact.py); these tests compare two calls bit for bit
     lab = torch.zeros(B, 1, H, W)
     lab[:, :, 4::8, 4::8] = (torch.rand(B, 1, H // 8, W // 8, generator=g) < 0.3).float()
     sem = torch.randint(0, 134, (B, H, W), generator=g).to(_dev())

@@ -80,16 +80,15 @@ def _run(agent, samples):
     return losses, dict(agent.scalar_dict), eng.params.clone(), eng.bn_running.clone()
 
 
-def test_host_fed_and_device_fed_steps_are_bit_identical(tmp_path):
+def _host_fed_and_device_fed(tmp_path, spaced):
     """Two optimiser steps: trainer A is fed host dicts built by make_pairs and moved to the CPU, trainer B the raw image,
     labels and semantic with the same matrices in sample["homographies"] / ["inv_homographies"] (the sampler's inverse pair;
     re-inverting in fp32 would change the last bit of the warp).  Both hand the engine the same arrays: losses and every
     parameter are equal bit for bit under deterministic accumulation.  Variants of B: uint8 image + uint8 semantic (the
     reduced wire format) against float / int64, and every other key of the loader's dict poisoned.
-    The keypoints are kept 8 pixels apart: with two keypoints landing on one pixel the last-write-wins scatter of
-    warped_labels_bi (warp_labels_full_kernel, like torch's index_put) picks its winner by thread order, so two calls of
-    make_pairs on the SAME inputs can differ there - found while building this test (random 1 % label maps differed in
-    warped_labels_bi / warped_labels_gaussian only); that is a property of the existing operator, not of the feed mode."""
+    spaced: keypoints 8 pixels apart, so that no two of them claim one pixel of the warped maps; unspaced: a random 1 % map,
+    where they do - the label scatter picks its winners by the reference's write order, not by thread order
+    (ssp_op_warp_labels_full), so the two feeds agree there as well."""
     from semantic_superpoint_amd import lib as L
     from semantic_superpoint_amd import pairs
     B, H, W = 4, 120, 160
@@ -97,7 +96,7 @@ def test_host_fed_and_device_fed_steps_are_bit_identical(tmp_path):
     try:
         host, dev_f, dev_u8 = [], [], []
         for it in range(2):
-            img, lab, sem = _raw(B, H, W, seed=it, spaced=True)
+            img, lab, sem = _raw(B, H, W, seed=it, spaced=spaced)
             imgf = img.float() / 255.0
             s = pairs.make_pairs(imgf.to(_dev()), lab.to(_dev()), seed=40 + it, warp_params=WARP, erosion_radius=3, semantic=sem.to(_dev()))
             host.append({k: v.cpu() for k, v in s.items()})
@@ -115,6 +114,15 @@ def test_host_fed_and_device_fed_steps_are_bit_identical(tmp_path):
     assert torch.equal(pa, pb) and torch.equal(ra, rb)
     assert la == lc and sa == sc and torch.equal(pa, pc) and torch.equal(ra, rc)
     assert np.isfinite(la).all() and la[0] != la[1]
+
+
+def test_host_fed_and_device_fed_steps_are_bit_identical(tmp_path):
+    _host_fed_and_device_fed(tmp_path, spaced=True)
+
+
+def test_host_fed_and_device_fed_steps_are_bit_identical_unspaced(tmp_path):
+    """the same on random label maps whose keypoints collide in warped_labels_bi / warped_res"""
+    _host_fed_and_device_fed(tmp_path, spaced=False)
 
 
 def test_photometric_runs_in_training_only(tmp_path, golden_dir):
