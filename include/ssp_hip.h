@@ -590,6 +590,50 @@ int ssp_op_filter_matches(const float* match_dev, const int32_t* n_match_dev, co
                           const int32_t* n_inlier_dev, int min_inliers, int cap, int n_pairs, float* match_out_dev,
                           int32_t* n_match_out_dev, void* stream);
 
+/* ---- two-view pose --------------------------------------------------------------------------
+ * The camera motion of a calibrated pair from ssp_epi_ransac's F, mask, n_inlier and status, and the trajectory over
+ * consecutive pairs.  Camera model a ~ K1 X1, b ~ K2 X2, X2 = R X1 + t, so F ~ K2^-T [t]x R K1^-1.  fp64 without
+ * contraction; the rules are DESIGN.md section 24 and are restated in numpy by tests/pose_ref.py.  No call synchronises with
+ * the host or allocates.
+ * ssp_pose_from_fundamental: pts / match / n_match / pt_stride / cap / pair_stride as for ssp_epi_ransac (the same gathered
+ *   rows, the same clamping); f_dev [n_pairs][9], mask_dev [n_pairs][cap], n_inlier_dev, status_in_dev [n_pairs] as it wrote
+ *   them.  intr_dev: fp64 [n_intr][2][4] = (fx, fy, cx, cy) of view 1 and view 2, n_intr = 1 (shared by all pairs) or
+ *   n_pairs.  E0 = K2^T F K1 scaled to unit Frobenius norm; V from 8 sweeps of cyclic Jacobi on E0^T E0 (v0, v1: the columns
+ *   of the two largest diagonal entries, v2 = v0 x v1), u0 = E0 v0 / |.|, u1 = E0 v1 made orthogonal to u0 and normalised,
+ *   u2 = u0 x u1; e_dev [n_pairs][9] = u0 v0^T + u1 v1^T (singular values 1, 1, 0).  Candidates 0..3 = (Ra, +u2),
+ *   (Ra, -u2), (Rb, +u2), (Rb, -u2) with Ra = U W V^T, Rb = U W^T V^T.  A match is in front when the least-squares meeting
+ *   point of its two rays has finite positive depths z1, z2 and the rays are not parallel (det > 1e-12 A11 A22).  Only rows
+ *   whose mask byte is set count; the most in-front rows win, ties to the lowest candidate.  r_dev [n_pairs][9],
+ *   t_dev [n_pairs][3] (unit length: the baseline is the unit of every depth), cand_dev [n_pairs] (the winner, -1),
+ *   counts_dev [n_pairs][4], n_front_dev [n_pairs].  status_dev [n_pairs]: 0; 1 = no pose (status_in != 0, n_inlier < 8 or a
+ *   degenerate matrix: R = I, t = 0, E = 0, counts 0, per-row outputs 0); 2 = ambiguous (fewer than 8 rows in front, or fewer
+ *   than half of n_inlier; the winner is still written).  Per match row, aligned with the UNFILTERED rows as the mask is:
+ *   front_dev [n_pairs][cap], depth_dev [n_pairs][cap][2] = (z1, z2), x_dev [n_pairs][cap][3] = z1 * ((ax-cx1)/fx1,
+ *   (ay-cy1)/fy1, 1), the point in camera 1's frame; zero where front is 0.  One workgroup per pair: a pair's result does
+ *   not depend on its batch.
+ * ssp_pose_chain: one frame of n_seq sequences.  Pair A = (f-1, f) ("prev": its front / depth / status / match / n_match /
+ *   cap; all NULL when there is no such pair) and pair B = (f, f+1) (the same plus r_dev, t_dev).  A point of frame f is row
+ *   j of A's matches and row i of B's: zprev[j] = z2 of A's in-front rows (the lowest row wins), the shared points are B's
+ *   in-front rows whose i has an entry, ratio = sum(zprev) / sum(z1) over them (sums in a fixed order).  state_dev
+ *   [n_seq][SSP_POSE_STATE_WORDS] fp64 = (n_frames, s, Rw [9], tw [3], 2 spare); a new sequence starts from
+ *   (0, 1, identity, 0).  s <- s * ratio when both poses have status 0, at least 8 points are shared and the ratio is finite
+ *   and positive; otherwise s is carried and flag bit 1 is set.  Rw <- R Rw, tw <- R tw + s t (R = I, t = 0 and flag bit 0
+ *   when B's status is not 0), C = -(Rw^T tw).  The row (Rw [9], C [3], s, n_shared, flags, ratio) is written to table_dev
+ *   [n_seq][capacity][SSP_POSE_ROW_WORDS] at row n_frames, which then grows by one; a full table stops growing (the state
+ *   still advances). */
+#define SSP_POSE_ROW_WORDS 16
+#define SSP_POSE_STATE_WORDS 16
+int ssp_pose_from_fundamental(const double* f_dev, const uint8_t* mask_dev, const int32_t* n_inlier_dev, const int32_t* status_in_dev,
+                              const double* pts1_dev, const double* pts2_dev, int pt_stride, int cap, int n_pairs, int pair_stride,
+                              const float* match_dev, const int32_t* n_match_dev, const double* intr_dev, int n_intr, double* r_dev,
+                              double* t_dev, double* e_dev, int32_t* cand_dev, int32_t* counts_dev, int32_t* n_front_dev,
+                              int32_t* status_dev, uint8_t* front_dev, double* depth_dev, double* x_dev, void* stream);
+int ssp_pose_chain(const uint8_t* front_prev_dev, const double* depth_prev_dev, const int32_t* status_prev_dev,
+                   const float* match_prev_dev, const int32_t* n_match_prev_dev, int cap_prev, const uint8_t* front_dev,
+                   const double* depth_dev, const int32_t* status_dev, const double* r_dev, const double* t_dev,
+                   const float* match_dev, const int32_t* n_match_dev, int cap, int n_seq, double* state_dev, double* table_dev,
+                   int capacity, void* stream);
+
 /* ---- streamed descriptor metrics ----------------------------------------------------------
  * The per-pair metrics of evaluation.py -r -homo for a set that is fed batch by batch and never leaves the device, on
  * top of ssp_eval_repeatability, ssp_match_two_way and ssp_eval_ransac.  fp64 without contraction.  No call

@@ -35,6 +35,7 @@
 #include "track_kernels.hip.h"
 #include "eval_kernels.hip.h"
 #include "epipolar_kernels.hip.h"
+#include "pose_kernels.hip.h"
 #include "detector_eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
@@ -3880,6 +3881,52 @@ int ssp_op_filter_matches(const float* match_dev, const int32_t* n_match_dev, co
     return fail(-1, "filter_matches: the matches are not filtered in place (pass a second set of arrays)");
   hipLaunchKernelGGL(match_filter_kernel, dim3(n_pairs), dim3(TRACK_BLOCK), 0, (hipStream_t)stream, match_dev, n_match_dev, mask_dev,
                      status_dev, n_inlier_dev, min_inliers, cap, match_out_dev, n_match_out_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- two-view pose: essential matrix, cheirality, scale chain and trajectory ----
+static_assert(POSE_ROW_WORDS == SSP_POSE_ROW_WORDS && POSE_STATE_WORDS == SSP_POSE_STATE_WORDS,
+              "include/ssp_hip.h and pose_kernels.hip.h disagree");
+int ssp_pose_from_fundamental(const double* f_dev, const uint8_t* mask_dev, const int32_t* n_inlier_dev, const int32_t* status_in_dev,
+                              const double* pts1_dev, const double* pts2_dev, int pt_stride, int cap, int n_pairs, int pair_stride,
+                              const float* match_dev, const int32_t* n_match_dev, const double* intr_dev, int n_intr, double* r_dev,
+                              double* t_dev, double* e_dev, int32_t* cand_dev, int32_t* counts_dev, int32_t* n_front_dev,
+                              int32_t* status_dev, uint8_t* front_dev, double* depth_dev, double* x_dev, void* stream) {
+  CHK(epi_check("pose_from_fundamental", cap, n_pairs, pair_stride, pt_stride));
+  if (!f_dev || !mask_dev || !n_inlier_dev || !status_in_dev || !pts1_dev || !pts2_dev || !match_dev || !n_match_dev || !intr_dev ||
+      !r_dev || !t_dev || !e_dev || !cand_dev || !counts_dev || !n_front_dev || !status_dev || !front_dev || !depth_dev || !x_dev)
+    return fail(-1, "pose_from_fundamental: null pointer");
+  if (n_intr != 1 && n_intr != n_pairs)
+    return fail(-1, "pose_from_fundamental: n_intr must be 1 or n_pairs (got %d for %d pairs)", n_intr, n_pairs);
+  hipLaunchKernelGGL(pose_kernel, dim3(n_pairs), dim3(POSE_THREADS), 0, (hipStream_t)stream, f_dev, mask_dev, n_inlier_dev,
+                     status_in_dev, pts1_dev, pts2_dev, pt_stride, cap, pair_stride, match_dev, n_match_dev, intr_dev, n_intr, r_dev,
+                     t_dev, e_dev, cand_dev, counts_dev, n_front_dev, status_dev, front_dev, depth_dev, x_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_pose_chain(const uint8_t* front_prev_dev, const double* depth_prev_dev, const int32_t* status_prev_dev,
+                   const float* match_prev_dev, const int32_t* n_match_prev_dev, int cap_prev, const uint8_t* front_dev,
+                   const double* depth_dev, const int32_t* status_dev, const double* r_dev, const double* t_dev,
+                   const float* match_dev, const int32_t* n_match_dev, int cap, int n_seq, double* state_dev, double* table_dev,
+                   int capacity, void* stream) {
+  if (cap < 1 || cap > SSP_MATCH_MAX_POINTS || n_seq < 1 || n_seq > 65535 || capacity < 0)
+    return fail(-1, "pose_chain: 1 <= cap <= %d, 1 <= n_seq <= 65535 and capacity >= 0 required (cap %d, n_seq %d)",
+                SSP_MATCH_MAX_POINTS, cap, n_seq);
+  if (!front_dev || !depth_dev || !status_dev || !r_dev || !t_dev || !match_dev || !n_match_dev || !state_dev ||
+      (capacity > 0 && !table_dev))
+    return fail(-1, "pose_chain: null pointer");
+  const bool have_prev = front_prev_dev != nullptr;
+  if (have_prev && (!depth_prev_dev || !status_prev_dev || !match_prev_dev || !n_match_prev_dev))
+    return fail(-1, "pose_chain: the previous pair is given whole or not at all");
+  if (have_prev && (cap_prev < 1 || cap_prev > SSP_MATCH_MAX_POINTS))
+    return fail(-1, "pose_chain: 1 <= cap_prev <= %d required (got %d)", SSP_MATCH_MAX_POINTS, cap_prev);
+  if (!have_prev) cap_prev = 1;
+  const size_t lds = (size_t)(cap_prev > cap ? cap_prev : cap) * (sizeof(double) + sizeof(int));   // <= 48 KB
+  hipLaunchKernelGGL(pose_chain_kernel, dim3(n_seq), dim3(POSE_THREADS), lds, (hipStream_t)stream, front_prev_dev, depth_prev_dev,
+                     status_prev_dev, match_prev_dev, n_match_prev_dev, cap_prev, front_dev, depth_dev, status_dev, r_dev, t_dev,
+                     match_dev, n_match_dev, cap, state_dev, table_dev, capacity);
   HIPCHK(hipGetLastError());
   return 0;
 }

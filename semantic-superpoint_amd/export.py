@@ -244,12 +244,28 @@ class PointTracker(object):
     distance) and "homography" a homography (lib.op_eval_ransac with its own 3 px rule); only the inliers continue tracks and
     are reported by get_matches / get_mscores.  A frame with no model or fewer than min_inliers inliers keeps all its
     matches; that is decided on the device.  Frame f (0-based) uses seed check_seed + f.  last_geometry() is the newest
-    frame's result."""
+    frame's result.
+    intrinsics (needs geometric_check="fundamental"): (fx, fy, cx, cy) of the camera, or a pair of such
+    tuples (the camera of the previous frame, the camera of the new frame).  Every frame's fundamental matrix then gives the
+    camera motion from the previous frame (lib.op_two_view_pose: last_geometry() gains its keys, "status" as "pose_status")
+    and one row of the trajectory (lib.op_pose_chain), read with trajectory(); trajectory_rows sizes that table.  All of it is
+    queued on the device like the check itself.  None runs none of it."""
 
     def __init__(self, max_length, nn_thresh, device=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
-                 min_inliers=16, check_seed=0):
+                 min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096):
         if geometric_check not in (None, "fundamental", "homography"):
             raise ValueError("geometric_check must be None, 'fundamental' or 'homography' (got %r)" % (geometric_check,))
+        if intrinsics is not None:
+            if geometric_check != "fundamental":
+                raise ValueError("intrinsics need geometric_check='fundamental': the pose is read off its fundamental matrix")
+            k = np.asarray(intrinsics, dtype=np.float64)
+            if k.shape == (4,):
+                k = np.stack([k, k])
+            if k.shape != (2, 4) or not np.all(np.isfinite(k)) or not np.all(k[:, :2] > 0.0):
+                raise ValueError("intrinsics must be (fx, fy, cx, cy), or a pair of them, with positive focal lengths")
+            if trajectory_rows < 1:
+                raise ValueError("trajectory_rows must be positive")
+            intrinsics = k
         if geometric_check is not None and not (check_thresh >= 0.0 and min_inliers >= 0):
             raise ValueError("check_thresh and min_inliers must be non-negative")
         if max_length < 2:
@@ -280,6 +296,11 @@ class PointTracker(object):
         self.check_thresh, self.min_inliers, self.check_seed = float(check_thresh), int(min_inliers), int(check_seed)
         self._seed = None         # int64 [1] on the device: the seed of the next frame's check
         self._geometry = None
+        self.intrinsics = intrinsics     # float64 [2, 4] (numpy) or None
+        self.trajectory_rows = int(trajectory_rows)
+        self._intr = None         # float64 [1, 2, 4] on the device
+        self._traj_state = self._traj_table = None
+        self._pose_prev = None    # (pose dict, unfiltered match [1, cap, 3], n_match) of the previous frame's pair
 
     # ---- device buffers -------------------------------------------------------------------------------------------
     def _ensure(self, n):
@@ -364,8 +385,33 @@ class PointTracker(object):
             p12 = torch.cat([torch.cat([p1, p2]), pad], dim=2)
             g = L.op_eval_ransac(p12[0:1], p12[1:2], m[None], nm, self._seed)
         self._seed = self._seed + 1
+        if self.intrinsics is not None:
+            g = self._pose_device(g, p1, p2, m[None], nm)
         self._geometry = g
         return L.op_filter_matches(m, nm, g["mask"], g["status"], g["n_inliers"], self.min_inliers)
+
+    def _pose_device(self, g, p1, p2, m, nm):
+        """The pose of the newest frame against the previous one and its trajectory row; returns g with the pose keys."""
+        if self._intr is None:
+            self._intr = torch.from_numpy(self.intrinsics[None].copy()).to(self.device)
+            self._traj_state = L.pose_state(self.device)
+            self._traj_table = L.pose_table(self.trajectory_rows, self.device)
+        pose = L.op_two_view_pose(g, p1, p2, m, nm, self._intr)
+        prev, m_prev, nm_prev = self._pose_prev if self._pose_prev is not None else (None, None, None)
+        L.op_pose_chain(prev, pose, m_prev, m, nm_prev, nm, self._traj_state, self._traj_table)
+        self._pose_prev = (pose, m, nm)
+        g = dict(g)
+        g.update(("pose_status" if k == "status" else k, v) for k, v in pose.items())
+        return g
+
+    def trajectory(self):
+        """(table, n_frames) on the device: float64 [trajectory_rows, lib.POSE_ROW_WORDS] rows (Rw [9], C [3], s, n_shared, flags,
+        ratio), one per frame given so far (row 0, the first frame, is the world: identity, flag bit 0), and the float64 [1]
+        number of rows written.  World = the first camera; C is the camera centre with the first baseline as the unit.  None
+        without intrinsics or before the first frame.  No synchronisation."""
+        if self._traj_table is None:
+            return None
+        return self._traj_table, self._traj_state[0:1]
 
     def last_geometry(self):
         """The device dict of the newest frame's geometric check (lib.op_epipolar_ransac or lib.op_eval_ransac), None before
@@ -565,11 +611,13 @@ class SequenceTracker:
     remove the keypoints of unwanted classes on the device before they enter the track table; class_consistent matches only
     points of equal class.  Neither adds a host copy or a synchronisation.
     geometric_check / check_thresh / min_inliers / check_seed: PointTracker's epipolar or homography check of every frame's
-    matches, also without a host copy or a synchronisation."""
+    matches, also without a host copy or a synchronisation.
+    intrinsics / trajectory_rows: PointTracker's two-view pose and trajectory of a calibrated camera (DESIGN.md section 24;
+    needs geometric_check="fundamental"); read them with tracker.last_geometry() and trajectory()."""
 
     def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4,
                  keep_classes=None, drop_classes=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
-                 min_inliers=16, check_seed=0):
+                 min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096):
         if nn_thresh < 0.0:
             raise ValueError("'nn_thresh' should be non-negative")
         self.class_consistent = bool(class_consistent)
@@ -584,7 +632,7 @@ class SequenceTracker:
         self.border_remove = border_remove
         self.tracker = PointTracker(max_length, nn_thresh, self.device, class_consistent=self.class_consistent,
                                     geometric_check=geometric_check, check_thresh=check_thresh, min_inliers=min_inliers,
-                                    check_seed=check_seed)
+                                    check_seed=check_seed, intrinsics=intrinsics, trajectory_rows=trajectory_rows)
 
     def describe(self, image):
         """image [H,W] / [1,H,W] / [1,1,H,W] -> the device tensors of Engine.describe_points for this one image (with "cls",
@@ -616,6 +664,9 @@ class SequenceTracker:
 
     def track_points(self, tracks):
         return self.tracker.track_points(tracks)
+
+    def trajectory(self):
+        return self.tracker.trajectory()
 
 
 def _matches_to_numpy(m, n):

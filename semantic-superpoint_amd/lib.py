@@ -132,7 +132,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_det_eval_workspace_bytes", "ssp_op_det_tp_fp", "ssp_op_det_tp_fp_points", "ssp_det_pr_curve_workspace_bytes",
            "ssp_op_det_pr_curve", "ssp_op_sparse_loss_path",
            "ssp_eval_pixel_homographies", "ssp_eval_accumulate",
-           "ssp_epi_ransac_workspace_bytes", "ssp_epi_ransac", "ssp_op_filter_matches"]
+           "ssp_epi_ransac_workspace_bytes", "ssp_epi_ransac", "ssp_op_filter_matches",
+           "ssp_pose_from_fundamental", "ssp_pose_chain"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -146,6 +147,9 @@ DET_CURVE_TILE = 1024  # DET_CURVE_TILE (csrc/detector_eval_kernels.hip.h): reco
 EVAL_ACC_MAX_PAIRS = 128  # SSP_EVAL_ACC_MAX_PAIRS (include/ssp_hip.h): pairs per ssp_eval_accumulate call
 EVAL_ROW_WORDS = 16  # SSP_EVAL_ROW_WORDS: fp64 words of a pair's row of the streamed descriptor metrics
 EVAL_STATE_WORDS = 16  # SSP_EVAL_STATE_WORDS: fp64 words of their state block
+POSE_ROW_WORDS = 16  # SSP_POSE_ROW_WORDS: fp64 words of a trajectory row (Rw [9], C [3], s, n_shared, flags, ratio)
+POSE_STATE_WORDS = 16  # SSP_POSE_STATE_WORDS: fp64 words of a pose chain state (n_frames, s, Rw [9], tw [3], 2 spare)
+POSE_FLAG_NO_POSE, POSE_FLAG_SCALE_CARRIED = 1, 2  # flag bits of a trajectory row
 
 
 def load_library(path=None):
@@ -346,6 +350,12 @@ def load_library(path=None):
         lib.ssp_epi_ransac_workspace_bytes.restype = C.c_size_t
         lib.ssp_epi_ransac.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, C.c_double, i, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.ssp_op_filter_matches.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_pose_from_fundamental.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, i] + [vp] * 11
+        lib.ssp_pose_chain.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp, i, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -1901,6 +1911,126 @@ def op_filter_matches(match, n_match, mask, status, n_inliers, min_inliers):
         _check(lib.ssp_op_filter_matches(_ptr(m3), _ptr(n_match), _ptr(mask), _ptr(status), _ptr(n_inliers), int(min_inliers),
                                          cap, P, _ptr(out), _ptr(n_out), _stream()))
     return (out if match.dim() == 3 else out[0]), n_out
+
+
+POSE_KEYS = ("R", "t", "E", "cand", "counts", "n_front", "status", "front", "depth", "X")
+
+
+def op_two_view_pose(geometry, pts1, pts2, match, n_match, intrinsics, pair_stride=1):
+    """The camera motion of P calibrated pairs from their epipolar check (ssp_pose_from_fundamental).
+    geometry: the dict of op_epipolar_ransac ("F", "mask", "n_inliers", "status"); pts1, pts2, match, n_match, pair_stride: what
+    that call was given.  intrinsics: float64 [1, 2, 4] (shared by all pairs) or [P, 2, 4] rows (fx, fy, cx, cy) of view 1 and
+    view 2.  Camera model X2 = R X1 + t.  Returns device tensors {"R": float64 [P,3,3], "t": float64 [P,3] (unit length), "E":
+    float64 [P,3,3] (singular values 1, 1, 0), "cand": int32 [P] (the winning candidate, -1), "counts": int32 [P,4], "n_front":
+    int32 [P], "status": int32 [P] (1 = no pose, 2 = ambiguous), "front": uint8 [P,cap], "depth": float64 [P,cap,2] = (z1, z2),
+    "X": float64 [P,cap,3] (the point in camera 1's frame, the baseline as the unit)}; the per-row outputs are aligned with
+    the UNFILTERED match rows, as the mask is.  No host synchronisation."""
+    lib = load_library()
+    for k in ("F", "mask", "n_inliers", "status"):
+        if k not in geometry:
+            raise ValueError("geometry must be the dict of op_epipolar_ransac (no %r)" % k)
+    F, mask, n_inl, status = (geometry[k] for k in ("F", "mask", "n_inliers", "status"))
+    for t, nm in ((F, "F"), (mask, "mask"), (n_inl, "n_inliers"), (status, "status"), (pts1, "pts1"), (pts2, "pts2"), (match, "match"),
+                  (n_match, "n_match"), (intrinsics, "intrinsics")):
+        _need_gpu(t, nm)
+    if match.dtype != torch.float32 or match.dim() != 3 or match.shape[2] != 3 or not match.is_contiguous():
+        raise ValueError("match must be contiguous float32 [P, cap, 3]")
+    P, cap = match.shape[0], match.shape[1]
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
+    if pts1.dim() != 3 or pts1.shape[2] < 2 or pts2.shape[2] != pts1.shape[2]:
+        raise ValueError("pts1 and pts2 must be float64 [., cap, pt_stride >= 2] with one pt_stride")
+    for t, nm in ((pts1, "pts1"), (pts2, "pts2")):
+        if t.dtype != torch.float64 or t.shape[1] != cap or t.shape[0] < (P - 1) * pair_stride + 1 or not t.is_contiguous():
+            raise ValueError("%s must be contiguous float64 [P*pair_stride, %d, pt_stride]" % (nm, cap))
+    if F.dtype != torch.float64 or F.numel() != P * 9 or not F.is_contiguous():
+        raise ValueError("geometry['F'] must be contiguous float64 [%d, 3, 3]" % P)
+    if mask.dtype != torch.uint8 or mask.numel() != P * cap or not mask.is_contiguous():
+        raise ValueError("geometry['mask'] must be contiguous uint8 [%d, %d]" % (P, cap))
+    for t, nm in ((n_match, "n_match"), (n_inl, "geometry['n_inliers']"), (status, "geometry['status']")):
+        if t.dtype != torch.int32 or t.numel() != P:
+            raise ValueError("%s must be int32 [%d]" % (nm, P))
+    if (intrinsics.dtype != torch.float64 or intrinsics.dim() != 3 or tuple(intrinsics.shape[1:]) != (2, 4)
+            or intrinsics.shape[0] not in (1, P) or not intrinsics.is_contiguous()):
+        raise ValueError("intrinsics must be contiguous float64 [1, 2, 4] or [%d, 2, 4] rows (fx, fy, cx, cy)" % P)
+    dev = match.device
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    o = {"R": torch.empty(P, 3, 3, **f64), "t": torch.empty(P, 3, **f64), "E": torch.empty(P, 3, 3, **f64),
+         "cand": torch.empty(P, **i32), "counts": torch.empty(P, 4, **i32), "n_front": torch.empty(P, **i32),
+         "status": torch.empty(P, **i32), "front": torch.empty(P, cap, dtype=torch.uint8, device=dev),
+         "depth": torch.empty(P, cap, 2, **f64), "X": torch.empty(P, cap, 3, **f64)}
+    with torch.cuda.device(dev):
+        _check(lib.ssp_pose_from_fundamental(_ptr(F), _ptr(mask), _ptr(n_inl), _ptr(status), _ptr(pts1), _ptr(pts2),
+                                             int(pts1.shape[2]), cap, P, int(pair_stride), _ptr(match), _ptr(n_match),
+                                             _ptr(intrinsics), int(intrinsics.shape[0]), *[_ptr(o[k]) for k in POSE_KEYS], _stream()))
+    return o
+
+
+def pose_state(device, n_seq=None):
+    """The state of a new pose chain: float64 [POSE_STATE_WORDS] (or [n_seq, .]) = (0 frames, s = 1, Rw = identity, tw = 0)."""
+    st = torch.zeros(POSE_STATE_WORDS, dtype=torch.float64)
+    st[1] = st[2] = st[6] = st[10] = 1.0
+    return (st if n_seq is None else st.repeat(n_seq, 1)).to(device)
+
+
+def pose_table(capacity, device, n_seq=None):
+    """An empty trajectory table: float64 [capacity, POSE_ROW_WORDS] (or [n_seq, ., .]) of zeros."""
+    shape = (capacity, POSE_ROW_WORDS) if n_seq is None else (n_seq, capacity, POSE_ROW_WORDS)
+    return torch.zeros(*shape, dtype=torch.float64, device=device)
+
+
+def op_pose_chain(prev, cur, match_prev, match_cur, n_match_prev, n_match_cur, state, table):
+    """One frame of the scale chain and the trajectory on the device (ssp_pose_chain).  prev / cur: the
+    op_two_view_pose dicts of the pairs (f-1, f) and (f, f+1) of S sequences (S = their leading dimension); match_* float32
+    [S, cap, 3] and n_match_* int32 [S]: the UNFILTERED matches those calls were given (the two pairs may have different
+    caps).  prev = None: there is no pair before `cur` (match_prev and n_match_prev are ignored).  state: pose_state(), table:
+    pose_table(); both are updated in place: the scale s <- s * ratio (or carried), Rw <- R Rw, tw <- R tw + s t, and the row
+    (Rw [9], C [3], s, n_shared, flags, ratio) is appended at row state[0].  Flag bit 0 (POSE_FLAG_NO_POSE): cur has no pose
+    (the centre repeats); bit 1 (POSE_FLAG_SCALE_CARRIED): the scale was carried, not measured.  Returns (state, table).  No
+    host synchronisation."""
+    lib = load_library()
+    S = cur["front"].shape[0]
+
+    def pair(d, m, nm, what):
+        for k in ("front", "depth", "status"):
+            _need_gpu(d[k], "%s[%r]" % (what, k))
+        _need_gpu(m, "match_" + what)
+        _need_gpu(nm, "n_match_" + what)
+        if m.dtype != torch.float32 or m.dim() != 3 or m.shape[0] != S or m.shape[2] != 3 or not m.is_contiguous():
+            raise ValueError("match_%s must be contiguous float32 [%d, cap, 3]" % (what, S))
+        cap = m.shape[1]
+        if not 1 <= cap <= MATCH_MAX_POINTS:
+            raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
+        if d["front"].dtype != torch.uint8 or tuple(d["front"].shape) != (S, cap) or not d["front"].is_contiguous():
+            raise ValueError("%s['front'] must be contiguous uint8 [%d, %d]" % (what, S, cap))
+        if d["depth"].dtype != torch.float64 or tuple(d["depth"].shape) != (S, cap, 2) or not d["depth"].is_contiguous():
+            raise ValueError("%s['depth'] must be contiguous float64 [%d, %d, 2]" % (what, S, cap))
+        for t, n in ((nm, "n_match_" + what), (d["status"], "%s['status']" % what)):
+            if t.dtype != torch.int32 or t.numel() != S:
+                raise ValueError("%s must be int32 [%d]" % (n, S))
+        return cap
+
+    cap = pair(cur, match_cur, n_match_cur, "cur")
+    cap_prev = pair(prev, match_prev, n_match_prev, "prev") if prev is not None else 0
+    for k in ("R", "t"):
+        _need_gpu(cur[k], "cur[%r]" % k)
+        if cur[k].dtype != torch.float64 or cur[k].numel() != S * (9 if k == "R" else 3) or not cur[k].is_contiguous():
+            raise ValueError("cur[%r] must be the contiguous float64 tensor of op_two_view_pose" % k)
+    _need_gpu(state, "state")
+    _need_gpu(table, "table")
+    if state.dtype != torch.float64 or state.numel() != S * POSE_STATE_WORDS or not state.is_contiguous():
+        raise ValueError("state must be contiguous float64 [%d, %d] (pose_state)" % (S, POSE_STATE_WORDS))
+    if (table.dtype != torch.float64 or table.dim() not in (2, 3) or table.shape[-1] != POSE_ROW_WORDS or not table.is_contiguous()
+            or table.numel() != S * table.shape[-2] * POSE_ROW_WORDS):
+        raise ValueError("table must be contiguous float64 [%d, capacity, %d] (pose_table)" % (S, POSE_ROW_WORDS))
+    have = prev is not None
+    with torch.cuda.device(state.device):
+        _check(lib.ssp_pose_chain(_ptr(prev["front"]) if have else None, _ptr(prev["depth"]) if have else None,
+                                  _ptr(prev["status"]) if have else None, _ptr(match_prev) if have else None,
+                                  _ptr(n_match_prev) if have else None, cap_prev, _ptr(cur["front"]), _ptr(cur["depth"]),
+                                  _ptr(cur["status"]), _ptr(cur["R"]), _ptr(cur["t"]), _ptr(match_cur), _ptr(n_match_cur), cap, S,
+                                  _ptr(state), _ptr(table), int(table.shape[-2]), _stream()))
+    return state, table
 
 
 def op_eval_pixel_homographies(hn, height, width):
