@@ -119,8 +119,10 @@ __global__ __launch_bounds__(256) void match_dist_kernel(const float* __restrict
       const int c1 = __builtin_amdgcn_readlane(ci_rows, (t & 3) + 8 * (t >> 2) + 4);
       ok = ok && (h ? c1 : c0) == cj;
     }
-    // np.sqrt(2 - 2 * np.clip(dmat, -1, 1)) in fp32: 2 * clip is exact, one rounding for the difference, one for sqrt
-    const float dd = __fsqrt_rn(2.f - 2.f * fminf(fmaxf(acc[t], -1.f), 1.f));
+    // np.sqrt(2 - 2 * np.clip(dmat, -1, 1)) in fp32: 2 * clip is exact, one rounding for the difference, one for sqrt.
+    // sqrtf is the correctly rounded root; __fsqrt_rn compiles to the native one, which may be an ulp off: enough to move a
+    // distance across nn_thresh or to order two candidates otherwise than the reference does
+    const float dd = sqrtf(2.f - 2.f * fminf(fmaxf(acc[t], -1.f), 1.f));
     const uint64_t hi = (uint64_t)__float_as_uint(dd) << 32;
     uint64_t kr = ok ? hi | (uint32_t)j : ~0ull;
     cbest = min_u64(cbest, ok ? hi | (uint32_t)i : ~0ull);

@@ -191,12 +191,20 @@ __device__ __forceinline__ uint8_t ld_state(const uint8_t* p) {
 __device__ __forceinline__ void st_state(uint8_t* p, uint8_t v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// Sort key of a confidence: unsigned order == float order for every non-NaN value.  -0.0 and +0.0 compare equal in the
+// reference's argsort and tie on the pixel index there, so both map to the key of +0.0 (a threshold of 0 admits -0.0, whose raw
+// bit pattern would sort above every positive value); negative values (a negative threshold) get their bits inverted.
+// Never 0, the key of an empty sort slot.
+__device__ __forceinline__ uint32_t conf_sort_bits(float v) {
+  const uint32_t b = __float_as_uint(v == 0.f ? 0.f : v);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
 // a kept point inside the border band still suppresses its neighbours but is not exported (model_wrap.py:286-292)
 __device__ __forceinline__ void push_kept(const PointsWork& w, int i, int x, int y, float v, int H, int W, int border,
                                           int cap2) {
   if (x >= border && x < W - border && y >= border && y < H - border) {
     const int pos = atomicAdd(w.counters + 1, 1);
-    if (pos < cap2) w.keys[pos] = ((uint64_t)__float_as_uint(v) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
+    if (pos < cap2) w.keys[pos] = ((uint64_t)conf_sort_bits(v) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)i);
   }
 }
 
@@ -342,7 +350,7 @@ __global__ __launch_bounds__(1024) void nms_points_kernel(const float* __restric
   }
   __threadfence();
   const int n_kept = __hip_atomic_load(w.counters + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  // descending sort: confidence (positive floats order like their bit patterns), then ascending pixel index
+  // descending sort: confidence (conf_sort_bits), then ascending pixel index
   int p2 = 1;
   const int nk = min(n_kept, cap2);
   while (p2 < nk) p2 <<= 1;
