@@ -634,6 +634,51 @@ int ssp_pose_chain(const uint8_t* front_prev_dev, const double* depth_prev_dev, 
                    const float* match_dev, const int32_t* n_match_dev, int cap, int n_seq, double* state_dev, double* table_dev,
                    int capacity, void* stream);
 
+/* ---- landmarks from tracks ---------------------------------------------------------------------
+ * One point in the world frame per track row: the row's observations in the L retained frames (the track table and the ring
+ * of point sets of ssp_op_track_update / ssp_op_track_points) under the cameras of the trajectory (ssp_pose_chain).  World =
+ * the first camera of the sequence, unit = the first baseline.  fp64 without contraction; the rules are DESIGN.md section 26
+ * and are restated in numpy by tests/landmarks_ref.py.  No call synchronises with the host or allocates.
+ * ssp_map_window: state_dev [SSP_POSE_STATE_WORDS] and table_dev [capacity][SSP_POSE_ROW_WORDS] of one sequence; intr_dev fp64
+ *   [n_intr][4] = (fx, fy, cx, cy), n_intr = 1 (shared) or max_length (per retained frame).  n_frames >= 0: the number of frames
+ *   given so far, as the caller counted them; -1: the state's count, which stops at `capacity`.  Retained frame c (0 = oldest)
+ *   is frame f = n_frames - L + c.  cams_dev [max_length][SSP_CAM_WORDS] = (Rw [9], C [3], fx, fy, cx, cy, valid, 3 spare); a
+ *   view is valid when 0 <= f < capacity, f >= w and the focal lengths are finite and positive, else its record is zero.  w is
+ *   the start of the newest consistent window: the smallest w such that every row in (w, n-1] has flag bit 0 clear and every
+ *   row in (w+1, n-1] flag bit 1; a row the table does not hold breaks it.
+ * ssp_op_triangulate_tracks: ids_dev [row_cap][max_length], state_dev [2 + max_length], pts_dev [max_length][point_cap][2]
+ *   with first_slot as for ssp_op_track_points.  A retained frame gives an observation when its id is >= 0, its camera is
+ *   valid and the id names a point of its frame.  Per row below n_rows: n_views_dev, status_dev (int32), x_dev [3], rms_dev,
+ *   cos_parallax_dev.  status: SSP_LANDMARK_FEW_VIEWS fewer than min_views (>= 2) observations; SSP_LANDMARK_DEGENERATE the
+ *   smallest d_i . d_j over the pairs of unit rays is above cos_min_parallax (the caller's cos(min angle)), or the midpoint
+ *   system / a Gauss-Newton step is singular (det not finite or <= 1e-12 * the product of the diagonal) or not finite;
+ *   SSP_LANDMARK_BEHIND the depth in a used view is not finite and positive at the midpoint or after the last step;
+ *   SSP_LANDMARK_REPROJ rms = sqrt(sum r^2 / (2 n_views)) of the pixel residuals is above max_reproj; in that order, else 0.
+ *   The point is the midpoint of the rays (A = sum(I - d d^T), b = sum((I - d d^T) C)) refined by exactly 4 Gauss-Newton steps
+ *   on the pixel reprojection error.  x, rms and cos_parallax are written whenever they were computed and are finite (also
+ *   under status 2 to 4), else zero.  Rows at or past n_rows are not written.  A row's result depends on nothing but its own
+ *   inputs.
+ * ssp_op_landmarks_select: the status-0 rows in table order -> landmarks_dev [row_cap][SSP_LANDMARK_WORDS] fp64 rows (track
+ *   id, X, Y, Z, n_views, rms, cos_parallax, index of the track's point in the newest frame or -1) and n_landmarks_dev [1];
+ *   workspace_dev: ssp_landmark_workspace_bytes(max_length, row_cap) bytes. */
+#define SSP_CAM_WORDS 20
+#define SSP_LANDMARK_WORDS 8
+#define SSP_LANDMARK_FEW_VIEWS 1
+#define SSP_LANDMARK_DEGENERATE 2
+#define SSP_LANDMARK_BEHIND 3
+#define SSP_LANDMARK_REPROJ 4
+size_t ssp_landmark_workspace_bytes(int max_length, int row_cap);
+int ssp_map_window(const double* state_dev, const double* table_dev, int capacity, const double* intr_dev, int n_intr, int max_length,
+                   int n_frames, double* cams_dev, void* stream);
+int ssp_op_triangulate_tracks(const int32_t* ids_dev, const int32_t* state_dev, const double* pts_dev, int first_slot,
+                              const double* cams_dev, int max_length, int point_cap, int row_cap, int min_views,
+                              double cos_min_parallax, double max_reproj, double* x_dev, int32_t* n_views_dev, double* rms_dev,
+                              double* cos_parallax_dev, int32_t* status_dev, void* stream);
+int ssp_op_landmarks_select(const int32_t* ids_dev, const int32_t* tid_dev, const int32_t* state_dev, const int32_t* status_dev,
+                            const double* x_dev, const int32_t* n_views_dev, const double* rms_dev, const double* cos_parallax_dev,
+                            int max_length, int point_cap, int row_cap, void* workspace_dev, double* landmarks_dev,
+                            int32_t* n_landmarks_dev, void* stream);
+
 /* ---- streamed descriptor metrics ----------------------------------------------------------
  * The per-pair metrics of evaluation.py -r -homo for a set that is fed batch by batch and never leaves the device, on
  * top of ssp_eval_repeatability, ssp_match_two_way and ssp_eval_ransac.  fp64 without contraction.  No call

@@ -36,6 +36,7 @@
 #include "eval_kernels.hip.h"
 #include "epipolar_kernels.hip.h"
 #include "pose_kernels.hip.h"
+#include "landmark_kernels.hip.h"
 #include "detector_eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
@@ -3927,6 +3928,68 @@ int ssp_pose_chain(const uint8_t* front_prev_dev, const double* depth_prev_dev, 
   hipLaunchKernelGGL(pose_chain_kernel, dim3(n_seq), dim3(POSE_THREADS), lds, (hipStream_t)stream, front_prev_dev, depth_prev_dev,
                      status_prev_dev, match_prev_dev, n_match_prev_dev, cap_prev, front_dev, depth_dev, status_dev, r_dev, t_dev,
                      match_dev, n_match_dev, cap, state_dev, table_dev, capacity);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- landmarks from tracks: cameras of the retained frames, N-view triangulation, the accepted rows ----
+static_assert(LM_CAM_WORDS == SSP_CAM_WORDS && LM_WORDS == SSP_LANDMARK_WORDS, "include/ssp_hip.h and landmark_kernels.hip.h disagree");
+size_t ssp_landmark_workspace_bytes(int max_length, int row_cap) {
+  if (track_check("landmark_workspace_bytes", max_length, 1, row_cap)) return 0;
+  return align_up((size_t)cdiv(row_cap, TRACK_BLOCK) * sizeof(int32_t), 256);
+}
+
+int ssp_map_window(const double* state_dev, const double* table_dev, int capacity, const double* intr_dev, int n_intr, int max_length,
+                   int n_frames, double* cams_dev, void* stream) {
+  CHK(track_check("map_window", max_length, 1, 1));
+  if (capacity < 0) return fail(-1, "map_window: capacity >= 0 required (got %d)", capacity);
+  if (n_intr != 1 && n_intr != max_length)
+    return fail(-1, "map_window: n_intr must be 1 or max_length (got %d for %d retained frames)", n_intr, max_length);
+  if (!state_dev || (capacity > 0 && !table_dev) || !intr_dev || !cams_dev) return fail(-1, "map_window: null pointer");
+  hipLaunchKernelGGL(map_window_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state_dev, table_dev, capacity, intr_dev, n_intr,
+                     max_length, n_frames, cams_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_op_triangulate_tracks(const int32_t* ids_dev, const int32_t* state_dev, const double* pts_dev, int first_slot,
+                              const double* cams_dev, int max_length, int point_cap, int row_cap, int min_views,
+                              double cos_min_parallax, double max_reproj, double* x_dev, int32_t* n_views_dev, double* rms_dev,
+                              double* cos_parallax_dev, int32_t* status_dev, void* stream) {
+  CHK(track_check("triangulate_tracks", max_length, point_cap, row_cap));
+  if (first_slot < 0 || first_slot >= max_length)
+    return fail(-1, "triangulate_tracks: 0 <= first_slot < max_length required (got %d)", first_slot);
+  if (min_views < 2) return fail(-1, "triangulate_tracks: min_views >= 2 required (got %d)", min_views);
+  if (!(cos_min_parallax >= -1.0 && cos_min_parallax <= 1.0) || !(max_reproj >= 0.0))
+    return fail(-1, "triangulate_tracks: -1 <= cos_min_parallax <= 1 and max_reproj >= 0 required");
+  if (!ids_dev || !state_dev || !pts_dev || !cams_dev || !x_dev || !n_views_dev || !rms_dev || !cos_parallax_dev || !status_dev)
+    return fail(-1, "triangulate_tracks: null pointer");
+  static AttrOnce attr_once;
+  if (attr_once.need())
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(triangulate_tracks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)lm_lds_bytes(SSP_TRACK_MAX_LENGTH)));
+  hipLaunchKernelGGL(triangulate_tracks_kernel, dim3(cdiv(row_cap, LM_THREADS)), dim3(LM_THREADS), lm_lds_bytes(max_length),
+                     (hipStream_t)stream, ids_dev, state_dev, pts_dev, first_slot, cams_dev, max_length, point_cap, row_cap, min_views,
+                     cos_min_parallax, max_reproj, x_dev, n_views_dev, rms_dev, cos_parallax_dev, status_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_op_landmarks_select(const int32_t* ids_dev, const int32_t* tid_dev, const int32_t* state_dev, const int32_t* status_dev,
+                            const double* x_dev, const int32_t* n_views_dev, const double* rms_dev, const double* cos_parallax_dev,
+                            int max_length, int point_cap, int row_cap, void* workspace_dev, double* landmarks_dev,
+                            int32_t* n_landmarks_dev, void* stream) {
+  CHK(track_check("landmarks_select", max_length, point_cap, row_cap));
+  if (!ids_dev || !tid_dev || !state_dev || !status_dev || !x_dev || !n_views_dev || !rms_dev || !cos_parallax_dev || !workspace_dev ||
+      !landmarks_dev || !n_landmarks_dev)
+    return fail(-1, "landmarks_select: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* block_sums = reinterpret_cast<int32_t*>(workspace_dev);
+  const int nb = cdiv(row_cap, TRACK_BLOCK);
+  hipLaunchKernelGGL(landmark_count_kernel, dim3(nb), dim3(TRACK_BLOCK), 0, st, state_dev, status_dev, row_cap, block_sums);
+  hipLaunchKernelGGL(landmark_scatter_kernel, dim3(nb), dim3(TRACK_BLOCK), 0, st, ids_dev, tid_dev, state_dev, status_dev, x_dev,
+                     n_views_dev, rms_dev, cos_parallax_dev, (const int32_t*)block_sums, max_length, point_cap, row_cap, landmarks_dev,
+                     n_landmarks_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }

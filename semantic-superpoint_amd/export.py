@@ -249,7 +249,10 @@ class PointTracker(object):
     tuples (the camera of the previous frame, the camera of the new frame).  Every frame's fundamental matrix then gives the
     camera motion from the previous frame (lib.op_two_view_pose: last_geometry() gains its keys, "status" as "pose_status")
     and one row of the trajectory (lib.op_pose_chain), read with trajectory(); trajectory_rows sizes that table.  All of it is
-    queued on the device like the check itself.  None runs none of it."""
+    queued on the device like the check itself.  None runs none of it.
+    landmarks / landmarks_device / landmark_rows_device (need intrinsics of ONE camera): one point in the
+    world frame per track, from its observations in the retained frames under the trajectory's cameras.  On demand: update /
+    update_device run none of it."""
 
     def __init__(self, max_length, nn_thresh, device=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096):
@@ -301,6 +304,7 @@ class PointTracker(object):
         self._intr = None         # float64 [1, 2, 4] on the device
         self._traj_state = self._traj_table = None
         self._pose_prev = None    # (pose dict, unfiltered match [1, cap, 3], n_match) of the previous frame's pair
+        self._lm = None           # lib.landmark_buffers of the table's row_cap (landmarks_device; allocated on first use)
 
     # ---- device buffers -------------------------------------------------------------------------------------------
     def _ensure(self, n):
@@ -412,6 +416,49 @@ class PointTracker(object):
         if self._traj_table is None:
             return None
         return self._traj_table, self._traj_state[0:1]
+
+    # ---- landmarks ------------------------------------------------------------------------------
+    def landmark_rows_device(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
+        """The N-view triangulation of every row of the track table (lib.op_map_window + lib.op_triangulate_tracks): the device
+        dict {"X": float64 [row_cap, 3], "n_views": int32, "rms": float64, "cos_parallax": float64, "status": int32 [row_cap]}
+        aligned with `table`'s rows (rows at or past its n_rows are stale).  World = the first camera of the sequence, unit = the
+        first baseline.  After a break in the chain (a frame without a pose, a carried scale) only the frames of the newest
+        consistent window are used, and the points are in that window's own scale.  Needs `intrinsics`, and one camera: a fixed
+        (previous, new) pair of two different cameras cannot describe more than two views (ValueError; lib.op_map_window takes
+        per-frame intrinsics).  Before the second frame every array has zero rows.  No host copy, no synchronisation; the
+        buffers are allocated once per capacity and overwritten by the next call."""
+        if self.intrinsics is None:
+            raise ValueError("landmarks need intrinsics (and geometric_check='fundamental'): the cameras come from the trajectory")
+        if not np.array_equal(self.intrinsics[0], self.intrinsics[1]):
+            raise ValueError("landmarks need ONE camera: a fixed (previous, new) pair of different intrinsics cannot describe more "
+                             "than two views (lib.op_map_window takes per-frame intrinsics)")
+        if int(min_views) < 2:
+            raise ValueError("min_views >= 2 required (got %d)" % min_views)
+        if self._frames < 2 or self._traj_table is None:
+            f64, i32 = dict(dtype=torch.float64, device=self.device), dict(dtype=torch.int32, device=self.device)
+            return {"X": torch.zeros(0, 3, **f64), "n_views": torch.zeros(0, **i32), "rms": torch.zeros(0, **f64),
+                    "cos_parallax": torch.zeros(0, **f64), "status": torch.zeros(0, **i32)}
+        if self._lm is None or self._lm["status"].shape[0] != self._table["row_cap"]:
+            self._lm = L.landmark_buffers(self.maxl, self._table["row_cap"], self.device)
+        cams = L.op_map_window(self._traj_state, self._traj_table, self._intr[0, 1:2], self.maxl, n_frames=self._frames, out=self._lm)
+        return L.op_triangulate_tracks(self._table, self._pts, self._frames % self.maxl, cams, min_views, min_parallax_deg,
+                                       max_reproj, out=self._lm)
+
+    def landmarks_device(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
+        """The accepted landmarks on the device: (landmarks float64 [row_cap, lib.LANDMARK_WORDS] rows (track id, X, Y, Z,
+        n_views, rms, cos_parallax, index of the track's point in the newest frame or -1) in table order, n_landmarks int32 [1]).
+        A track is accepted when at least min_views retained frames of the newest consistent window see it, two of its rays are
+        at least min_parallax_deg apart, it lies in front of every camera that sees it and its rms reprojection error is at most
+        max_reproj pixels.  Frame, unit, errors and cost: landmark_rows_device.  Before the second frame: zero rows, n = 0."""
+        rows = self.landmark_rows_device(min_views, min_parallax_deg, max_reproj)
+        if rows["status"].shape[0] == 0:
+            return (torch.zeros(0, L.LANDMARK_WORDS, dtype=torch.float64, device=self.device),
+                    torch.zeros(1, dtype=torch.int32, device=self.device))
+        return L.op_landmarks_select(self._table, rows, out=self._lm)
+
+    def landmarks(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
+        """landmarks_device as numpy: float64 [M, lib.LANDMARK_WORDS] (one host synchronisation)."""
+        return L.landmarks_to_numpy(*self.landmarks_device(min_views, min_parallax_deg, max_reproj))
 
     def last_geometry(self):
         """The device dict of the newest frame's geometric check (lib.op_epipolar_ransac or lib.op_eval_ransac), None before
@@ -613,7 +660,8 @@ class SequenceTracker:
     geometric_check / check_thresh / min_inliers / check_seed: PointTracker's epipolar or homography check of every frame's
     matches, also without a host copy or a synchronisation.
     intrinsics / trajectory_rows: PointTracker's two-view pose and trajectory of a calibrated camera (DESIGN.md section 24;
-    needs geometric_check="fundamental"); read them with tracker.last_geometry() and trajectory()."""
+    needs geometric_check="fundamental"); read them with tracker.last_geometry() and trajectory().
+    landmarks / landmarks_device / landmark_rows_device: PointTracker's, on demand."""
 
     def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4,
                  keep_classes=None, drop_classes=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
@@ -667,6 +715,15 @@ class SequenceTracker:
 
     def trajectory(self):
         return self.tracker.trajectory()
+
+    def landmarks_device(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
+        return self.tracker.landmarks_device(min_views, min_parallax_deg, max_reproj)
+
+    def landmarks(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
+        return self.tracker.landmarks(min_views, min_parallax_deg, max_reproj)
+
+    def landmark_rows_device(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
+        return self.tracker.landmark_rows_device(min_views, min_parallax_deg, max_reproj)
 
 
 def _matches_to_numpy(m, n):

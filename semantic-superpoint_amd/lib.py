@@ -5,6 +5,7 @@ arithmetic step runs in csrc/libssp_hip.so.  There is NO CPU / eager fallback: i
 loaded or the tensors are not on a HIP device, calls raise.
 """
 import ctypes as C
+import math
 import os
 from collections import OrderedDict
 
@@ -133,7 +134,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_op_det_pr_curve", "ssp_op_sparse_loss_path",
            "ssp_eval_pixel_homographies", "ssp_eval_accumulate",
            "ssp_epi_ransac_workspace_bytes", "ssp_epi_ransac", "ssp_op_filter_matches",
-           "ssp_pose_from_fundamental", "ssp_pose_chain"]
+           "ssp_pose_from_fundamental", "ssp_pose_chain",
+           "ssp_landmark_workspace_bytes", "ssp_map_window", "ssp_op_triangulate_tracks", "ssp_op_landmarks_select"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -150,6 +152,9 @@ EVAL_STATE_WORDS = 16  # SSP_EVAL_STATE_WORDS: fp64 words of their state block
 POSE_ROW_WORDS = 16  # SSP_POSE_ROW_WORDS: fp64 words of a trajectory row (Rw [9], C [3], s, n_shared, flags, ratio)
 POSE_STATE_WORDS = 16  # SSP_POSE_STATE_WORDS: fp64 words of a pose chain state (n_frames, s, Rw [9], tw [3], 2 spare)
 POSE_FLAG_NO_POSE, POSE_FLAG_SCALE_CARRIED = 1, 2  # flag bits of a trajectory row
+CAM_WORDS = 20  # SSP_CAM_WORDS: fp64 words of a camera record (Rw [9], C [3], fx, fy, cx, cy, valid, 3 spare)
+LANDMARK_WORDS = 8  # SSP_LANDMARK_WORDS: track id, X, Y, Z, n_views, rms, cos_parallax, index of the point in the newest frame
+LANDMARK_OK, LANDMARK_FEW_VIEWS, LANDMARK_DEGENERATE, LANDMARK_BEHIND, LANDMARK_REPROJ = 0, 1, 2, 3, 4  # SSP_LANDMARK_*
 
 
 def load_library(path=None):
@@ -356,6 +361,15 @@ def load_library(path=None):
     try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
         lib.ssp_pose_from_fundamental.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, i] + [vp] * 11
         lib.ssp_pose_chain.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp, i, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_landmark_workspace_bytes.argtypes = [i, i]
+        lib.ssp_landmark_workspace_bytes.restype = C.c_size_t
+        lib.ssp_map_window.argtypes = [vp, vp, i, vp, i, i, i, vp, vp]
+        lib.ssp_op_triangulate_tracks.argtypes = [vp, vp, vp, i, vp, i, i, i, i, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
+        lib.ssp_op_landmarks_select.argtypes = [vp] * 8 + [i, i, i, vp, vp, vp, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -2031,6 +2045,138 @@ def op_pose_chain(prev, cur, match_prev, match_cur, n_match_prev, n_match_cur, s
                                   _ptr(cur["status"]), _ptr(cur["R"]), _ptr(cur["t"]), _ptr(match_cur), _ptr(n_match_cur), cap, S,
                                   _ptr(state), _ptr(table), int(table.shape[-2]), _stream()))
     return state, table
+
+
+# ---- landmarks from tracks ----
+LANDMARK_ROW_KEYS = ("X", "n_views", "rms", "cos_parallax", "status")
+
+
+def landmark_buffers(max_length, row_cap, device):
+    """The device arrays of the landmark operators for a track table of row_cap rows of max_length ids, zeroed: {"cams": float64
+    [L, CAM_WORDS], "X": float64 [row_cap, 3], "n_views": int32 [row_cap], "rms", "cos_parallax": float64 [row_cap], "status":
+    int32 [row_cap], "landmarks": float64 [row_cap, LANDMARK_WORDS], "n_landmarks": int32 [1], "ws": the scratch of
+    op_landmarks_select}.  Pass it as `out` to keep the operators from allocating."""
+    lib = load_library()
+    L, row_cap = int(max_length), int(row_cap)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("landmark_buffers needs a HIP device: the MI355X path has no CPU fallback")
+    wsb = lib.ssp_landmark_workspace_bytes(L, row_cap)
+    if wsb == 0:
+        _check(-1)
+    f64, i32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int32, device=device)
+    return {"cams": torch.zeros(L, CAM_WORDS, **f64), "X": torch.zeros(row_cap, 3, **f64), "n_views": torch.zeros(row_cap, **i32),
+            "rms": torch.zeros(row_cap, **f64), "cos_parallax": torch.zeros(row_cap, **f64), "status": torch.zeros(row_cap, **i32),
+            "landmarks": torch.zeros(row_cap, LANDMARK_WORDS, **f64), "n_landmarks": torch.zeros(1, **i32),
+            "ws": torch.empty(wsb, dtype=torch.uint8, device=device)}
+
+
+def _landmark_out(out, keys, L, row_cap, device):
+    if out is None:
+        return landmark_buffers(L, row_cap, device)
+    shapes = {"cams": (L, CAM_WORDS), "X": (row_cap, 3), "n_views": (row_cap,), "rms": (row_cap,), "cos_parallax": (row_cap,),
+              "status": (row_cap,), "landmarks": (row_cap, LANDMARK_WORDS), "n_landmarks": (1,)}
+    for k in keys:
+        if k not in out:
+            raise ValueError("out must be the dict of landmark_buffers (no %r)" % k)
+        _need_gpu(out[k], "out[%r]" % k)
+        want = torch.int32 if k in ("n_views", "status", "n_landmarks") else torch.float64
+        if k != "ws" and (out[k].dtype != want or tuple(out[k].shape) != shapes[k]):
+            raise ValueError("out[%r] must be %s %s" % (k, want, list(shapes[k])))
+    return out
+
+
+def op_map_window(state, table, intrinsics, max_length, n_frames=None, out=None):
+    """The cameras of the max_length retained frames of one sequence (ssp_map_window).  state: float64
+    [POSE_STATE_WORDS] and table: float64 [capacity, POSE_ROW_WORDS] of op_pose_chain; intrinsics: float64 [1, 4] (shared) or
+    [max_length, 4] rows (fx, fy, cx, cy), one per retained frame, oldest first.  n_frames: the number of frames given so far when
+    the caller counted them (the state's own count stops when the table is full); None reads the state.  Returns float64
+    [max_length, CAM_WORDS] records (Rw [9], C [3], fx, fy, cx, cy, valid, 3 spare) in out["cams"]; a frame outside the newest
+    consistent window, one the table does not hold, or one whose focal lengths are not finite and positive, is a zero record.
+    No host synchronisation."""
+    lib = load_library()
+    L = int(max_length)
+    if not 2 <= L <= TRACK_MAX_LENGTH:
+        raise ValueError("2 <= max_length <= %d required (got %d)" % (TRACK_MAX_LENGTH, L))
+    for t, nm in ((state, "state"), (table, "table"), (intrinsics, "intrinsics")):
+        _need_gpu(t, nm)
+    if state.dtype != torch.float64 or tuple(state.shape) != (POSE_STATE_WORDS,):
+        raise ValueError("state must be float64 [%d] (pose_state)" % POSE_STATE_WORDS)
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != POSE_ROW_WORDS:
+        raise ValueError("table must be float64 [capacity, %d] (pose_table)" % POSE_ROW_WORDS)
+    if intrinsics.dtype != torch.float64 or intrinsics.dim() != 2 or intrinsics.shape[1] != 4 or intrinsics.shape[0] not in (1, L):
+        raise ValueError("intrinsics must be float64 [1, 4] or [%d, 4] rows (fx, fy, cx, cy)" % L)
+    if n_frames is not None and int(n_frames) < 0:
+        raise ValueError("n_frames must be non-negative (None: the state's count)")
+    if out is None:
+        out = {"cams": torch.zeros(L, CAM_WORDS, dtype=torch.float64, device=state.device)}
+    cams = _landmark_out(out, ("cams",), L, 0, state.device)["cams"]
+    with torch.cuda.device(state.device):
+        _check(lib.ssp_map_window(_ptr(state), _ptr(table), int(table.shape[0]), _ptr(intrinsics), int(intrinsics.shape[0]), L,
+                                  -1 if n_frames is None else int(n_frames), _ptr(cams), _stream()))
+    return cams
+
+
+def op_triangulate_tracks(table, pts, first_slot, cams, min_views=2, min_parallax_deg=1.0, max_reproj=2.0, out=None):
+    """One point in the world frame per row of a track table (ssp_op_triangulate_tracks).  table: the dict
+    of track_table / op_track_update; pts: float64 [L, point_cap, 2] ring of (x, y), retained frame c in slot (first_slot + c) %
+    L; cams: float64 [L, CAM_WORDS] of op_map_window.  min_views >= 2 observations, min_parallax_deg: the largest angle between
+    two rays of the track must reach it (its cosine is taken here, on the host), max_reproj: pixels of rms reprojection error.
+    Returns the per-row device tensors {"X": float64 [row_cap, 3], "n_views": int32, "rms": float64, "cos_parallax": float64,
+    "status": int32 [row_cap] (LANDMARK_OK, _FEW_VIEWS, _DEGENERATE, _BEHIND, _REPROJ)} aligned with the table's rows (`out`: a
+    landmark_buffers dict; rows at or past the table's n_rows are left as they were).  No host synchronisation."""
+    lib = load_library()
+    L, point_cap, row_cap = table["L"], table["point_cap"], table["row_cap"]
+    for t, nm in ((table["ids"], "table['ids']"), (table["state"], "table['state']"), (pts, "pts"), (cams, "cams")):
+        _need_gpu(t, nm)
+    if pts.dtype != torch.float64 or tuple(pts.shape) != (L, point_cap, 2):
+        raise ValueError("pts must be float64 [%d, %d, 2]" % (L, point_cap))
+    if cams.dtype != torch.float64 or tuple(cams.shape) != (L, CAM_WORDS):
+        raise ValueError("cams must be float64 [%d, %d] (op_map_window)" % (L, CAM_WORDS))
+    if table["ids"].dtype != torch.int32 or tuple(table["ids"].shape) != (row_cap, L) or table["state"].dtype != torch.int32 \
+            or table["state"].numel() != 2 + L:
+        raise ValueError("table must be a track table: ids int32 [%d, %d], state int32 [%d]" % (row_cap, L, 2 + L))
+    if not 0 <= int(first_slot) < L:
+        raise ValueError("0 <= first_slot < %d required (got %d)" % (L, first_slot))
+    if int(min_views) < 2:
+        raise ValueError("min_views >= 2 required (got %d)" % min_views)
+    if not (0.0 <= float(min_parallax_deg) <= 180.0) or not float(max_reproj) >= 0.0:
+        raise ValueError("0 <= min_parallax_deg <= 180 and max_reproj >= 0 required")
+    out = _landmark_out(out, LANDMARK_ROW_KEYS, L, row_cap, pts.device)
+    with torch.cuda.device(pts.device):
+        _check(lib.ssp_op_triangulate_tracks(_ptr(table["ids"]), _ptr(table["state"]), _ptr(pts), int(first_slot), _ptr(cams), L,
+                                             point_cap, row_cap, int(min_views), math.cos(math.radians(float(min_parallax_deg))),
+                                             float(max_reproj), *[_ptr(out[k]) for k in LANDMARK_ROW_KEYS], _stream()))
+    return {k: out[k] for k in LANDMARK_ROW_KEYS}
+
+
+def op_landmarks_select(table, rows, out=None):
+    """The accepted rows of op_triangulate_tracks in table order (ssp_op_landmarks_select): (landmarks float64 [row_cap,
+    LANDMARK_WORDS] rows (track id, X, Y, Z, n_views, rms, cos_parallax, index of the track's point in the newest frame or -1),
+    n_landmarks int32 [1]) as device tensors.  rows: the dict op_triangulate_tracks returned for `table`; `out`: a
+    landmark_buffers dict.  No host synchronisation."""
+    lib = load_library()
+    L, point_cap, row_cap = table["L"], table["point_cap"], table["row_cap"]
+    dev = table["ids"].device
+    _landmark_out(rows, LANDMARK_ROW_KEYS, L, row_cap, dev)
+    for k in ("ids", "tid", "state"):
+        _need_gpu(table[k], "table[%r]" % k)
+    if out is None:
+        out = landmark_buffers(L, row_cap, dev)
+    _landmark_out(out, ("landmarks", "n_landmarks", "ws"), L, row_cap, dev)
+    if out["ws"].numel() < lib.ssp_landmark_workspace_bytes(L, row_cap):
+        raise ValueError("out['ws'] is smaller than ssp_landmark_workspace_bytes(%d, %d)" % (L, row_cap))
+    with torch.cuda.device(dev):
+        _check(lib.ssp_op_landmarks_select(_ptr(table["ids"]), _ptr(table["tid"]), _ptr(table["state"]), _ptr(rows["status"]),
+                                           _ptr(rows["X"]), _ptr(rows["n_views"]), _ptr(rows["rms"]), _ptr(rows["cos_parallax"]), L,
+                                           point_cap, row_cap, _ptr(out["ws"]), _ptr(out["landmarks"]), _ptr(out["n_landmarks"]),
+                                           _stream()))
+    return out["landmarks"], out["n_landmarks"]
+
+
+def landmarks_to_numpy(landmarks, n_landmarks):
+    """Device (landmarks, n_landmarks) of op_landmarks_select -> float64 [M, LANDMARK_WORDS] (one host synchronisation)."""
+    return landmarks[:int(n_landmarks.item())].cpu().numpy()
 
 
 def op_eval_pixel_homographies(hn, height, width):
