@@ -679,7 +679,46 @@ int ssp_op_landmarks_select(const int32_t* ids_dev, const int32_t* tid_dev, cons
                             int max_length, int point_cap, int row_cap, void* workspace_dev, double* landmarks_dev,
                             int32_t* n_landmarks_dev, void* stream);
 
-/* ---- streamed descriptor metrics ----------------------------------------------------------
+/* ---- absolute pose from landmarks -------------------------------------------------------------
+ * The camera of a frame from 3-D to 2-D correspondences: landmark rows joined with the matches of the next frame, a P3P RANSAC
+ * of 512 hypotheses with a Gauss-Newton refit, and the repair of a trajectory row the two-view chain could not determine.
+ * Camera model y = Rw (X - C), u = fx y0 / y2 + cx.  fp64 without contraction; the rules are DESIGN.md section 27 and are
+ * restated in numpy by tests/pnp_ref.py.  No call synchronises with the host or allocates.
+ * ssp_op_landmark_matches: landmarks_dev [row_cap][SSP_LANDMARK_WORDS] and n_landmarks_dev [1] of ssp_op_landmarks_select for
+ *   the window ending at the previous frame; match_dev [cap][3] fp32 rows (i, j, distance) and n_match_dev [1] of the pair
+ *   (previous, new), unfiltered; pts_new_dev [point_cap][pt_stride] fp64 rows starting (x, y).  Indices are clamped to
+ *   [0, point_cap).  The landmark of point i is the LOWEST landmark row whose eighth word is i.  corr_dev
+ *   [cap][SSP_CORR_WORDS] fp64 rows (X, Y, Z, px, py, landmark row, valid, 0), one per match row, zero where the row has no
+ *   landmark, lies at or past n_match or holds a non-finite value; n_corr_dev [2] = (rows, valid rows).
+ * ssp_pnp_ransac: n_problems problems.  corr_dev [n_problems][cap][SSP_CORR_WORDS], n_dev [n_problems] rows used, intr_dev
+ *   fp64 [n_intr][4] = (fx, fy, cx, cy), n_intr = 1 (shared) or n_problems, seeds_dev [n_problems].  Hypothesis h draws 4
+ *   distinct valid rows from the counter-based stream of ssp_epi_ransac (4 rows: the one direct solve; fewer: none); three
+ *   give up to four P3P solutions, the fourth keeps the one that reprojects it best.  The score counts the valid rows in front
+ *   of the camera whose reprojection error is <= thresh pixels; the highest score wins, ties to the lowest h, and needs
+ *   max(min_inliers, 4) rows.  4 Gauss-Newton steps over the winner's inliers (Cayley rotation update), then the mask once more:
+ *   if it keeps fewer rows the winner's pose and mask stand.  rw_dev [n_problems][9], c_dev [n_problems][3], mask_dev
+ *   [n_problems][cap], n_inlier_dev, winner_dev (-1), rms_dev = sqrt(sum e^2 / (2 k)), status_dev (1 = no pose: Rw = I, C = 0,
+ *   empty mask).  groups: workgroups per problem (0 = the library's choice, at most 64); a problem's result depends on its
+ *   own inputs and seed only.  workspace_dev: ssp_pnp_workspace_bytes(n_problems) bytes (0 = bad arguments).
+ * ssp_pose_repair: n_seq sequences; rw_dev [n_seq][9], c_dev [n_seq][3], status_dev [n_seq] of ssp_pnp_ransac; state_dev and
+ *   table_dev of ssp_pose_chain.  Acts on row n - 1 of a table holding 1 <= n < capacity rows (a full table is left alone) when
+ *   that row carries flag bit 0 or 1 and the absolute pose has status 0 and is finite: Rw and C are replaced in the row and
+ *   the state, tw = -(Rw C), s = |C - C of row n - 2| when that is finite and above 1/64 of the previous s (bit 1 is cleared),
+ *   else s is kept (bit 1 stays as it was); bit 0 is cleared and SSP_POSE_FLAG_ABSOLUTE set.  Otherwise nothing is written. */
+#define SSP_CORR_WORDS 8
+#define SSP_POSE_FLAG_ABSOLUTE 4
+size_t ssp_pnp_workspace_bytes(int n_problems);
+int ssp_op_landmark_matches(const double* landmarks_dev, const int32_t* n_landmarks_dev, int row_cap, const float* match_dev,
+                            const int32_t* n_match_dev, int cap, const double* pts_new_dev, int pt_stride, int point_cap,
+                            double* corr_dev, int32_t* n_corr_dev, void* stream);
+int ssp_pnp_ransac(const double* corr_dev, const int32_t* n_dev, int cap, int n_problems, const double* intr_dev, int n_intr,
+                   const uint64_t* seeds_dev, double thresh, int min_inliers, int groups, void* workspace_dev, double* rw_dev,
+                   double* c_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* winner_dev, double* rms_dev,
+                   int32_t* status_dev, void* stream);
+int ssp_pose_repair(const double* rw_dev, const double* c_dev, const int32_t* status_dev, int n_seq, double* state_dev,
+                    double* table_dev, int capacity, void* stream);
+
+/* ---- streamed descriptor metrics----------------------------------------------------------
  * The per-pair metrics of evaluation.py -r -homo for a set that is fed batch by batch and never leaves the device, on
  * top of ssp_eval_repeatability, ssp_match_two_way and ssp_eval_ransac.  fp64 without contraction.  No call
  * synchronises with the host.

@@ -37,6 +37,7 @@
 #include "epipolar_kernels.hip.h"
 #include "pose_kernels.hip.h"
 #include "landmark_kernels.hip.h"
+#include "pnp_kernels.hip.h"
 #include "detector_eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
@@ -3990,6 +3991,77 @@ int ssp_op_landmarks_select(const int32_t* ids_dev, const int32_t* tid_dev, cons
   hipLaunchKernelGGL(landmark_scatter_kernel, dim3(nb), dim3(TRACK_BLOCK), 0, st, ids_dev, tid_dev, state_dev, status_dev, x_dev,
                      n_views_dev, rms_dev, cos_parallax_dev, (const int32_t*)block_sums, max_length, point_cap, row_cap, landmarks_dev,
                      n_landmarks_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- absolute pose from landmarks: the join, the P3P RANSAC over several workgroups per problem, the repair ----
+// groups = 0: the measured choice (PERF_LOG.md, "Absolute pose"): 2 workgroups per problem, one hypothesis per lane.  One problem of 500 /
+// 1131 rows takes 215.1 / 364.1 us with 2 against 352.8 / 641.4 with 1 (two hypotheses per lane, one after the other), 217.2 / 367.4 with
+// 8, 218.0 / 368.1 with 16 and 219.5 / 370.5 with 32 (more workgroups, each with idle wavefronts); 16 problems 219.2 / 371.0 us with 2
+// against 274.9 / 472.1 with 32.  The result does not depend on the choice.
+#define PNP_GROUPS_DEFAULT 2
+static_assert(PNP_CORR_WORDS == SSP_CORR_WORDS && PNP_FLAG_ABSOLUTE == SSP_POSE_FLAG_ABSOLUTE && PNP_MAX_CAP == SSP_MATCH_MAX_POINTS,
+              "include/ssp_hip.h and pnp_kernels.hip.h disagree");
+size_t ssp_pnp_workspace_bytes(int n_problems) {
+  if (n_problems < 1 || n_problems > 65535) {
+    fail(-1, "pnp_workspace_bytes: 1 <= n_problems <= 65535 required (got %d)", n_problems);
+    return 0;
+  }
+  return align_up((size_t)n_problems * PNP_MAX_GROUPS * sizeof(uint64_t), 256);
+}
+
+int ssp_op_landmark_matches(const double* landmarks_dev, const int32_t* n_landmarks_dev, int row_cap, const float* match_dev,
+                            const int32_t* n_match_dev, int cap, const double* pts_new_dev, int pt_stride, int point_cap,
+                            double* corr_dev, int32_t* n_corr_dev, void* stream) {
+  if (row_cap < 1 || row_cap > SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS || cap < 1 || cap > SSP_MATCH_MAX_POINTS || point_cap < 1 ||
+      point_cap > SSP_MATCH_MAX_POINTS || pt_stride < 2)
+    return fail(-1, "landmark_matches: 1 <= row_cap <= %d, 1 <= cap, point_cap <= %d and pt_stride >= 2 required (row_cap %d, cap %d, "
+                "point_cap %d)", SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS, SSP_MATCH_MAX_POINTS, row_cap, cap, point_cap);
+  if (!landmarks_dev || !n_landmarks_dev || !match_dev || !n_match_dev || !pts_new_dev || !corr_dev || !n_corr_dev)
+    return fail(-1, "landmark_matches: null pointer");
+  hipLaunchKernelGGL(landmark_corr_kernel, dim3(1), dim3(PNP_THREADS), (size_t)point_cap * sizeof(int), (hipStream_t)stream,
+                     landmarks_dev, n_landmarks_dev, row_cap, match_dev, n_match_dev, cap, pts_new_dev, pt_stride, point_cap, corr_dev,
+                     n_corr_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_pnp_ransac(const double* corr_dev, const int32_t* n_dev, int cap, int n_problems, const double* intr_dev, int n_intr,
+                   const uint64_t* seeds_dev, double thresh, int min_inliers, int groups, void* workspace_dev, double* rw_dev,
+                   double* c_dev, uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* winner_dev, double* rms_dev,
+                   int32_t* status_dev, void* stream) {
+  if (cap < 1 || cap > SSP_MATCH_MAX_POINTS || n_problems < 1 || n_problems > 65535)
+    return fail(-1, "pnp_ransac: 1 <= cap <= %d and 1 <= n_problems <= 65535 required (cap %d, n_problems %d)", SSP_MATCH_MAX_POINTS,
+                cap, n_problems);
+  if (!corr_dev || !n_dev || !intr_dev || !seeds_dev || !workspace_dev || !rw_dev || !c_dev || !mask_dev || !n_inlier_dev ||
+      !winner_dev || !rms_dev || !status_dev)
+    return fail(-1, "pnp_ransac: null pointer");
+  if (n_intr != 1 && n_intr != n_problems)
+    return fail(-1, "pnp_ransac: n_intr must be 1 or n_problems (got %d for %d problems)", n_intr, n_problems);
+  if (!(thresh >= 0.0) || !std::isfinite(thresh)) return fail(-1, "pnp_ransac: a finite thresh >= 0 is required");
+  if (min_inliers < 4) return fail(-1, "pnp_ransac: min_inliers >= 4 required (got %d)", min_inliers);
+  if (groups < 0 || groups > PNP_MAX_GROUPS)
+    return fail(-1, "pnp_ransac: 0 (the library's choice) <= groups <= %d required (got %d)", PNP_MAX_GROUPS, groups);
+  if (groups == 0) groups = PNP_GROUPS_DEFAULT;
+  hipStream_t st = (hipStream_t)stream;
+  uint64_t* keys = reinterpret_cast<uint64_t*>(workspace_dev);
+  hipLaunchKernelGGL(pnp_hypotheses_kernel, dim3(groups, n_problems), dim3(PNP_THREADS), 0, st, corr_dev, n_dev, cap, intr_dev, n_intr,
+                     seeds_dev, thresh, keys);
+  hipLaunchKernelGGL(pnp_finish_kernel, dim3(n_problems), dim3(PNP_THREADS), 0, st, corr_dev, n_dev, cap, intr_dev, n_intr, seeds_dev,
+                     thresh, min_inliers, groups, (const uint64_t*)keys, rw_dev, c_dev, mask_dev, n_inlier_dev, winner_dev, rms_dev,
+                     status_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_pose_repair(const double* rw_dev, const double* c_dev, const int32_t* status_dev, int n_seq, double* state_dev,
+                    double* table_dev, int capacity, void* stream) {
+  if (n_seq < 1 || n_seq > 65535 || capacity < 0)
+    return fail(-1, "pose_repair: 1 <= n_seq <= 65535 and capacity >= 0 required (n_seq %d, capacity %d)", n_seq, capacity);
+  if (!rw_dev || !c_dev || !status_dev || !state_dev || (capacity > 0 && !table_dev)) return fail(-1, "pose_repair: null pointer");
+  hipLaunchKernelGGL(pose_repair_kernel, dim3(cdiv(n_seq, 64)), dim3(64), 0, (hipStream_t)stream, rw_dev, c_dev, status_dev, n_seq,
+                     state_dev, table_dev, capacity);
   HIPCHK(hipGetLastError());
   return 0;
 }

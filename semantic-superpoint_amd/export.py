@@ -252,12 +252,35 @@ class PointTracker(object):
     queued on the device like the check itself.  None runs none of it.
     landmarks / landmarks_device / landmark_rows_device (need intrinsics of ONE camera): one point in the
     world frame per track, from its observations in the retained frames under the trajectory's cameras.  On demand: update /
-    update_device run none of it."""
+    update_device run none of it.
+    absolute_pose (needs intrinsics of ONE camera): None runs none of it.  "observe": after every frame the
+    tracker keeps the landmarks of the window ending there (landmark_params = (min_views, min_parallax_deg, max_reproj), in buffers
+    of its own: landmarks_device neither sees nor disturbs them); the next frame's unfiltered matches join them to its points
+    (lib.op_landmark_matches) and a P3P RANSAC (lib.op_pnp_ransac, absolute_thresh pixels, absolute_min_inliers, the frame's
+    check seed) places its camera in the window's frame and scale: last_geometry() gains the "abs_*" keys and
+    absolute_trajectory() one row.  "repair" also rewrites the frame's trajectory row and the chain state from that pose
+    (lib.op_pose_repair) when the two-view chain could not determine them, so a frame without a two-view pose no longer breaks the
+    window.  All of it is queued on the device."""
 
     def __init__(self, max_length, nn_thresh, device=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
-                 min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096):
+                 min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
+                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0)):
         if geometric_check not in (None, "fundamental", "homography"):
             raise ValueError("geometric_check must be None, 'fundamental' or 'homography' (got %r)" % (geometric_check,))
+        if absolute_pose not in (None, "observe", "repair"):
+            raise ValueError("absolute_pose must be None, 'observe' or 'repair' (got %r)" % (absolute_pose,))
+        if absolute_pose is not None:
+            if intrinsics is None or geometric_check != "fundamental":
+                raise ValueError("absolute_pose needs intrinsics and geometric_check='fundamental': the landmarks come from the "
+                                 "trajectory's cameras")
+            k = np.asarray(intrinsics, dtype=np.float64)
+            if k.shape == (2, 4) and not np.array_equal(k[0], k[1]):
+                raise ValueError("absolute_pose needs ONE camera: a fixed (previous, new) pair of different intrinsics cannot describe "
+                                 "more than two views")
+            if not (absolute_thresh >= 0.0 and np.isfinite(absolute_thresh)) or int(absolute_min_inliers) < 4:
+                raise ValueError("absolute_thresh must be finite and non-negative, absolute_min_inliers at least 4")
+            if len(landmark_params) != 3 or int(landmark_params[0]) < 2:
+                raise ValueError("landmark_params must be (min_views >= 2, min_parallax_deg, max_reproj)")
         if intrinsics is not None:
             if geometric_check != "fundamental":
                 raise ValueError("intrinsics need geometric_check='fundamental': the pose is read off its fundamental matrix")
@@ -305,6 +328,13 @@ class PointTracker(object):
         self._traj_state = self._traj_table = None
         self._pose_prev = None    # (pose dict, unfiltered match [1, cap, 3], n_match) of the previous frame's pair
         self._lm = None           # lib.landmark_buffers of the table's row_cap (landmarks_device; allocated on first use)
+        self.absolute_pose = absolute_pose
+        self.absolute_thresh, self.absolute_min_inliers = float(absolute_thresh), int(absolute_min_inliers)
+        self.landmark_params = (int(landmark_params[0]), float(landmark_params[1]), float(landmark_params[2]))
+        self._abs_lm = None       # lib.landmark_buffers of the tracker's own: the landmarks of the window ending at the previous frame
+        self._abs_have = False    # _abs_lm holds such landmarks
+        self._abs = None          # lib.pnp_buffers of one problem
+        self._abs_table = None    # float64 [trajectory_rows, POSE_ROW_WORDS]: absolute_trajectory()
 
     # ---- device buffers -------------------------------------------------------------------------------------------
     def _ensure(self, n):
@@ -360,6 +390,8 @@ class PointTracker(object):
         if self.geometric_check is not None:
             m, nm = self._check_device(m, nm)
         self._track_device(m, nm)
+        if self.absolute_pose is not None:
+            self._keep_landmarks_device()
         had_prev, self._prev_ok = self._prev_ok, True
         return m, nm, had_prev
 
@@ -388,9 +420,11 @@ class PointTracker(object):
             pad = torch.zeros(2, self._cap, 1, dtype=torch.float64, device=self.device)
             p12 = torch.cat([torch.cat([p1, p2]), pad], dim=2)
             g = L.op_eval_ransac(p12[0:1], p12[1:2], m[None], nm, self._seed)
-        self._seed = self._seed + 1
+        seed, self._seed = self._seed, self._seed + 1
         if self.intrinsics is not None:
             g = self._pose_device(g, p1, p2, m[None], nm)
+        if self.absolute_pose is not None:
+            g = self._absolute_device(g, m, nm, p2[0], seed)
         self._geometry = g
         return L.op_filter_matches(m, nm, g["mask"], g["status"], g["n_inliers"], self.min_inliers)
 
@@ -407,6 +441,63 @@ class PointTracker(object):
         g = dict(g)
         g.update(("pose_status" if k == "status" else k, v) for k, v in pose.items())
         return g
+
+    def _absolute_device(self, g, m, nm, pts_new, seed):
+        """The absolute pose of the newest frame from the landmarks kept after the previous one, its row of absolute_trajectory()
+        and, with "repair", the repair of the newest trajectory row; returns g with the abs_* keys."""
+        f = self._frames - 1
+        if self._abs_table is None:
+            self._abs_table = L.pose_table(self.trajectory_rows, self.device)
+        if self._abs is None or self._abs["corr"].shape[1] != m.shape[0]:
+            self._abs = L.pnp_buffers(1, m.shape[0], self.device)
+        a = self._abs
+        g = dict(g)
+        if self._abs_have and self._abs_lm["landmarks"].shape[0] == self._table["row_cap"]:
+            corr, n = L.op_landmark_matches(self._abs_lm["landmarks"], self._abs_lm["n_landmarks"], m, nm, pts_new, out=a)
+            res = L.op_pnp_ransac(a["corr"], n[0:1], self._intr[0, 1:2], seed, thresh=self.absolute_thresh,
+                                  min_inliers=self.absolute_min_inliers, out=a)
+            if self.absolute_pose == "repair":
+                L.op_pose_repair(res, self._traj_state, self._traj_table)
+        else:                         # no landmarks yet: the row of a frame without a pose
+            for k in ("corr", "n", "C", "mask", "n_inliers", "rms"):
+                a[k].zero_()
+            a["Rw"].copy_(torch.eye(3, dtype=torch.float64, device=self.device)[None])
+            a["winner"].fill_(-1)
+            a["status"].fill_(1)
+            res = {k: a[k] for k in L.PNP_KEYS}
+        if f < self.trajectory_rows:
+            row = self._abs_table[f]
+            row[0:9] = res["Rw"].reshape(9)
+            row[9:12] = res["C"].reshape(3)
+            row[12:13] = res["n_inliers"]
+            row[13:14] = res["rms"]
+            row[14:15] = res["status"]
+            row[15:16] = a["n"][0, 1:2]
+        g.update(("abs_" + k, v) for k, v in res.items())
+        g["abs_corr"], g["abs_n_corr"] = a["corr"][0], a["n"][0]
+        return g
+
+    def _keep_landmarks_device(self):
+        """The landmarks of the window ending at the newest frame into the tracker's own buffers (after _track_device)."""
+        self._abs_have = False
+        if self._frames < 2 or self._traj_table is None:
+            return
+        if self._abs_lm is None or self._abs_lm["status"].shape[0] != self._table["row_cap"]:
+            self._abs_lm = L.landmark_buffers(self.maxl, self._table["row_cap"], self.device)
+        mv, par, rep = self.landmark_params
+        cams = L.op_map_window(self._traj_state, self._traj_table, self._intr[0, 1:2], self.maxl, n_frames=self._frames, out=self._abs_lm)
+        rows = L.op_triangulate_tracks(self._table, self._pts, self._frames % self.maxl, cams, mv, par, rep, out=self._abs_lm)
+        L.op_landmarks_select(self._table, rows, out=self._abs_lm)
+        self._abs_have = True
+
+    def absolute_trajectory(self):
+        """(table, n_frames) on the device: float64 [trajectory_rows, lib.POSE_ROW_WORDS] rows (Rw [9], C [3], n_inliers, rms,
+        status, n_corr), one per frame given so far: the camera of that frame against the landmarks of the window ending at the
+        frame before it (status 1, Rw = I, C = 0 where there was none), and trajectory()'s float64 [1] number of rows.  None
+        without absolute_pose or before the first frame.  No synchronisation."""
+        if self._abs_table is None:
+            return None
+        return self._abs_table, self._traj_state[0:1]
 
     def trajectory(self):
         """(table, n_frames) on the device: float64 [trajectory_rows, lib.POSE_ROW_WORDS] rows (Rw [9], C [3], s, n_shared, flags,
@@ -661,11 +752,15 @@ class SequenceTracker:
     matches, also without a host copy or a synchronisation.
     intrinsics / trajectory_rows: PointTracker's two-view pose and trajectory of a calibrated camera (DESIGN.md section 24;
     needs geometric_check="fundamental"); read them with tracker.last_geometry() and trajectory().
-    landmarks / landmarks_device / landmark_rows_device: PointTracker's, on demand."""
+    landmarks / landmarks_device / landmark_rows_device: PointTracker's, on demand.
+    absolute_pose / absolute_thresh / absolute_min_inliers / landmark_params: PointTracker's absolute pose of every frame from the
+    landmarks of the window before it, and with "repair" the repair of the trajectory; read it with
+    tracker.last_geometry() and absolute_trajectory().  A step stays free of host copies and synchronisation."""
 
     def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4,
                  keep_classes=None, drop_classes=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
-                 min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096):
+                 min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
+                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0)):
         if nn_thresh < 0.0:
             raise ValueError("'nn_thresh' should be non-negative")
         self.class_consistent = bool(class_consistent)
@@ -680,7 +775,9 @@ class SequenceTracker:
         self.border_remove = border_remove
         self.tracker = PointTracker(max_length, nn_thresh, self.device, class_consistent=self.class_consistent,
                                     geometric_check=geometric_check, check_thresh=check_thresh, min_inliers=min_inliers,
-                                    check_seed=check_seed, intrinsics=intrinsics, trajectory_rows=trajectory_rows)
+                                    check_seed=check_seed, intrinsics=intrinsics, trajectory_rows=trajectory_rows,
+                                    absolute_pose=absolute_pose, absolute_thresh=absolute_thresh,
+                                    absolute_min_inliers=absolute_min_inliers, landmark_params=landmark_params)
 
     def describe(self, image):
         """image [H,W] / [1,H,W] / [1,1,H,W] -> the device tensors of Engine.describe_points for this one image (with "cls",
@@ -715,6 +812,9 @@ class SequenceTracker:
 
     def trajectory(self):
         return self.tracker.trajectory()
+
+    def absolute_trajectory(self):
+        return self.tracker.absolute_trajectory()
 
     def landmarks_device(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
         return self.tracker.landmarks_device(min_views, min_parallax_deg, max_reproj)

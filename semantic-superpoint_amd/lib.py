@@ -135,7 +135,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_eval_pixel_homographies", "ssp_eval_accumulate",
            "ssp_epi_ransac_workspace_bytes", "ssp_epi_ransac", "ssp_op_filter_matches",
            "ssp_pose_from_fundamental", "ssp_pose_chain",
-           "ssp_landmark_workspace_bytes", "ssp_map_window", "ssp_op_triangulate_tracks", "ssp_op_landmarks_select"]
+           "ssp_landmark_workspace_bytes", "ssp_map_window", "ssp_op_triangulate_tracks", "ssp_op_landmarks_select",
+           "ssp_pnp_workspace_bytes", "ssp_op_landmark_matches", "ssp_pnp_ransac", "ssp_pose_repair"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -155,6 +156,8 @@ POSE_FLAG_NO_POSE, POSE_FLAG_SCALE_CARRIED = 1, 2  # flag bits of a trajectory r
 CAM_WORDS = 20  # SSP_CAM_WORDS: fp64 words of a camera record (Rw [9], C [3], fx, fy, cx, cy, valid, 3 spare)
 LANDMARK_WORDS = 8  # SSP_LANDMARK_WORDS: track id, X, Y, Z, n_views, rms, cos_parallax, index of the point in the newest frame
 LANDMARK_OK, LANDMARK_FEW_VIEWS, LANDMARK_DEGENERATE, LANDMARK_BEHIND, LANDMARK_REPROJ = 0, 1, 2, 3, 4  # SSP_LANDMARK_*
+CORR_WORDS = 8  # SSP_CORR_WORDS: fp64 words of a 3-D to 2-D correspondence (X, Y, Z, px, py, landmark row, valid, 0)
+POSE_FLAG_ABSOLUTE = 4  # SSP_POSE_FLAG_ABSOLUTE: flag bit of a trajectory row rewritten from an absolute pose
 
 
 def load_library(path=None):
@@ -370,6 +373,15 @@ def load_library(path=None):
         lib.ssp_map_window.argtypes = [vp, vp, i, vp, i, i, i, vp, vp]
         lib.ssp_op_triangulate_tracks.argtypes = [vp, vp, vp, i, vp, i, i, i, i, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
         lib.ssp_op_landmarks_select.argtypes = [vp] * 8 + [i, i, i, vp, vp, vp, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_pnp_workspace_bytes.argtypes = [i]
+        lib.ssp_pnp_workspace_bytes.restype = C.c_size_t
+        lib.ssp_op_landmark_matches.argtypes = [vp, vp, i, vp, vp, i, vp, i, i, vp, vp, vp]
+        lib.ssp_pnp_ransac.argtypes = [vp, vp, i, i, vp, i, vp, C.c_double, i, i] + [vp] * 9
+        lib.ssp_pose_repair.argtypes = [vp, vp, vp, i, vp, vp, i, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -2177,6 +2189,146 @@ def op_landmarks_select(table, rows, out=None):
 def landmarks_to_numpy(landmarks, n_landmarks):
     """Device (landmarks, n_landmarks) of op_landmarks_select -> float64 [M, LANDMARK_WORDS] (one host synchronisation)."""
     return landmarks[:int(n_landmarks.item())].cpu().numpy()
+
+
+# ---- absolute pose from landmarks (DESIGN.md section 27) ----
+PNP_KEYS = ("Rw", "C", "mask", "n_inliers", "winner", "rms", "status")
+
+
+def pnp_buffers(n_problems, cap, device):
+    """The device arrays of the absolute-pose operators for n_problems problems of cap correspondence rows: {"corr": float64
+    [n_problems, cap, CORR_WORDS], "n": int32 [n_problems, 2] (rows, valid rows), "Rw": float64 [n_problems, 3, 3], "C": float64
+    [n_problems, 3], "mask": uint8 [n_problems, cap], "n_inliers" / "winner" / "status": int32 [n_problems], "rms": float64
+    [n_problems], "ws": the scratch of op_pnp_ransac}.  Pass it as `out` to keep the operators from allocating."""
+    lib = load_library()
+    P, cap = int(n_problems), int(cap)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("pnp_buffers needs a HIP device: the MI355X path has no CPU fallback")
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d rows per problem (got %d)" % (MATCH_MAX_POINTS, cap))
+    wsb = lib.ssp_pnp_workspace_bytes(P)
+    if wsb == 0:
+        _check(-1)
+    f64, i32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int32, device=device)
+    return {"corr": torch.zeros(P, cap, CORR_WORDS, **f64), "n": torch.zeros(P, 2, **i32), "Rw": torch.zeros(P, 3, 3, **f64),
+            "C": torch.zeros(P, 3, **f64), "mask": torch.zeros(P, cap, dtype=torch.uint8, device=device),
+            "n_inliers": torch.zeros(P, **i32), "winner": torch.zeros(P, **i32), "rms": torch.zeros(P, **f64),
+            "status": torch.zeros(P, **i32), "ws": torch.zeros(wsb, dtype=torch.uint8, device=device)}
+
+
+def _pnp_out(out, keys, P, cap, device):
+    if out is None:
+        return pnp_buffers(P, cap, device)
+    shapes = {"corr": (P, cap, CORR_WORDS), "n": (P, 2), "Rw": (P, 3, 3), "C": (P, 3), "mask": (P, cap), "n_inliers": (P,),
+              "winner": (P,), "rms": (P,), "status": (P,)}
+    for k in keys:
+        if k not in out:
+            raise ValueError("out must be the dict of pnp_buffers (no %r)" % k)
+        _need_gpu(out[k], "out[%r]" % k)
+        want = torch.uint8 if k == "mask" else (torch.int32 if k in ("n", "n_inliers", "winner", "status") else torch.float64)
+        if out[k].dtype != want or tuple(out[k].shape) != shapes[k] or not out[k].is_contiguous():
+            raise ValueError("out[%r] must be contiguous %s %s (pnp_buffers)" % (k, want, list(shapes[k])))
+    return out
+
+
+def op_landmark_matches(landmarks, n_landmarks, match, n_match, pts_new, out=None):
+    """The 3-D to 2-D correspondences of a new frame (ssp_op_landmark_matches): the landmarks of the window
+    ending at the previous frame (landmarks float64 [row_cap, LANDMARK_WORDS], n_landmarks int32 [1] of op_landmarks_select) joined
+    with the UNFILTERED matches of the pair (previous, new) (match float32 [cap, 3] rows (i, j, distance), n_match int32 [1]) and
+    the new frame's points pts_new float64 [point_cap, >= 2].  The landmark of point i is the lowest landmark row whose eighth word
+    is i.  Returns (corr float64 [cap, CORR_WORDS] rows (X, Y, Z, px, py, landmark row, valid, 0) aligned with the match rows, n
+    int32 [2] = (rows, valid rows)); `out`: a pnp_buffers dict of one problem (its "corr" and "n" are filled and views of them
+    returned).  No host synchronisation."""
+    lib = load_library()
+    for t, nm in ((landmarks, "landmarks"), (n_landmarks, "n_landmarks"), (match, "match"), (n_match, "n_match"), (pts_new, "pts_new")):
+        _need_gpu(t, nm)
+    if landmarks.dtype != torch.float64 or landmarks.dim() != 2 or landmarks.shape[1] != LANDMARK_WORDS or not landmarks.is_contiguous():
+        raise ValueError("landmarks must be contiguous float64 [row_cap, %d] (op_landmarks_select)" % LANDMARK_WORDS)
+    if match.dtype != torch.float32 or match.dim() != 2 or match.shape[1] != 3 or not match.is_contiguous():
+        raise ValueError("match must be contiguous float32 [cap, 3]")
+    if pts_new.dtype != torch.float64 or pts_new.dim() != 2 or pts_new.shape[1] < 2 or not pts_new.is_contiguous():
+        raise ValueError("pts_new must be contiguous float64 [point_cap, >= 2]")
+    for t, nm in ((n_landmarks, "n_landmarks"), (n_match, "n_match")):
+        if t.dtype != torch.int32 or t.numel() != 1:
+            raise ValueError("%s must be int32 [1]" % nm)
+    row_cap, cap, point_cap = landmarks.shape[0], match.shape[0], pts_new.shape[0]
+    if not (1 <= cap <= MATCH_MAX_POINTS and 1 <= point_cap <= MATCH_MAX_POINTS and 1 <= row_cap <= TRACK_MAX_LENGTH * MATCH_MAX_POINTS):
+        raise ValueError("1 <= cap, point_cap <= %d and 1 <= row_cap <= %d required" % (MATCH_MAX_POINTS, TRACK_MAX_LENGTH * MATCH_MAX_POINTS))
+    out = _pnp_out(out, ("corr", "n"), 1, cap, match.device)
+    with torch.cuda.device(match.device):
+        _check(lib.ssp_op_landmark_matches(_ptr(landmarks), _ptr(n_landmarks), row_cap, _ptr(match), _ptr(n_match), cap, _ptr(pts_new),
+                                           int(pts_new.shape[1]), point_cap, _ptr(out["corr"]), _ptr(out["n"]), _stream()))
+    return out["corr"][0], out["n"][0]
+
+
+def op_pnp_ransac(corr, n, intrinsics, seeds, thresh=2.0, min_inliers=6, groups=0, out=None):
+    """The cameras of P problems from their 3-D to 2-D correspondences (ssp_pnp_ransac): a P3P RANSAC of 512
+    hypotheses, a Gauss-Newton refit over the winner's inliers, the final mask.  corr: float64 [P, cap, CORR_WORDS] (or [cap, .]
+    for one problem) rows (X, Y, Z, px, py, landmark row, valid, 0); n: int32 [P] rows used; intrinsics: float64 [1, 4] (shared) or
+    [P, 4] rows (fx, fy, cx, cy); seeds: int64 [P]; thresh: the reprojection error of an inlier in pixels; min_inliers: what a pose
+    needs (never below 4); groups: workgroups per problem (0 = the library's choice; the result does not depend on it).  Camera
+    model y = Rw (X - C).  Returns device tensors {"Rw": float64 [P,3,3], "C": float64 [P,3], "mask": uint8 [P,cap], "n_inliers":
+    int32 [P], "winner": int32 [P] (the hypothesis, -1), "rms": float64 [P] (pixels), "status": int32 [P] (1 = no pose: Rw = I,
+    C = 0, empty mask)}; `out`: a pnp_buffers dict.  No host synchronisation."""
+    lib = load_library()
+    for t, nm in ((corr, "corr"), (n, "n"), (intrinsics, "intrinsics"), (seeds, "seeds")):
+        _need_gpu(t, nm)
+    c3 = corr if corr.dim() == 3 else corr[None]
+    if c3.dtype != torch.float64 or c3.dim() != 3 or c3.shape[2] != CORR_WORDS or not c3.is_contiguous():
+        raise ValueError("corr must be contiguous float64 [P, cap, %d] or [cap, %d]" % (CORR_WORDS, CORR_WORDS))
+    P, cap = c3.shape[0], c3.shape[1]
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d rows per problem (got %d)" % (MATCH_MAX_POINTS, cap))
+    if n.dtype != torch.int32 or n.numel() != P or not n.is_contiguous():
+        raise ValueError("n must be contiguous int32 [%d]" % P)
+    if seeds.dtype != torch.int64 or seeds.numel() != P or not seeds.is_contiguous():
+        raise ValueError("seeds must be contiguous int64 [%d]" % P)
+    if (intrinsics.dtype != torch.float64 or intrinsics.dim() != 2 or intrinsics.shape[1] != 4 or intrinsics.shape[0] not in (1, P)
+            or not intrinsics.is_contiguous()):
+        raise ValueError("intrinsics must be contiguous float64 [1, 4] or [%d, 4] rows (fx, fy, cx, cy)" % P)
+    if int(min_inliers) < 4:
+        raise ValueError("min_inliers >= 4 required (got %d)" % int(min_inliers))
+    out = _pnp_out(out, PNP_KEYS, P, cap, c3.device)
+    if "ws" not in out or out["ws"].numel() < lib.ssp_pnp_workspace_bytes(P):
+        raise ValueError("out['ws'] is smaller than ssp_pnp_workspace_bytes(%d)" % P)
+    with torch.cuda.device(c3.device):
+        _check(lib.ssp_pnp_ransac(_ptr(c3), _ptr(n), cap, P, _ptr(intrinsics), int(intrinsics.shape[0]), _ptr(seeds), float(thresh),
+                                  int(min_inliers), int(groups), _ptr(out["ws"]), *[_ptr(out[k]) for k in PNP_KEYS], _stream()))
+    return {k: out[k] for k in PNP_KEYS}
+
+
+def op_pose_repair(absolute, state, table):
+    """The newest trajectory row and the chain state rewritten from an absolute pose (ssp_pose_repair).
+    absolute: the dict of op_pnp_ransac for S problems, one per sequence; state: float64 [S, POSE_STATE_WORDS] (or
+    [POSE_STATE_WORDS]) and table: float64 [S, capacity, POSE_ROW_WORDS] (or [capacity, .]) of op_pose_chain, updated in place.
+    Acts on row n - 1 of a table holding 1 <= n < capacity rows when that row carries POSE_FLAG_NO_POSE or
+    POSE_FLAG_SCALE_CARRIED and the absolute pose has status 0: Rw and C are replaced, tw = -(Rw C), s = the distance to the
+    previous centre when that is above 1/64 of the previous s (else s is kept and POSE_FLAG_SCALE_CARRIED stays as it was),
+    POSE_FLAG_NO_POSE is cleared and POSE_FLAG_ABSOLUTE set.  Otherwise nothing changes.  Returns (state, table).  No host
+    synchronisation."""
+    lib = load_library()
+    for k in ("Rw", "C", "status"):
+        if k not in absolute:
+            raise ValueError("absolute must be the dict of op_pnp_ransac (no %r)" % k)
+        _need_gpu(absolute[k], "absolute[%r]" % k)
+    _need_gpu(state, "state")
+    _need_gpu(table, "table")
+    S = absolute["status"].numel()
+    if absolute["status"].dtype != torch.int32 or not absolute["status"].is_contiguous():
+        raise ValueError("absolute['status'] must be contiguous int32 [%d]" % S)
+    for k, m in (("Rw", 9), ("C", 3)):
+        if absolute[k].dtype != torch.float64 or absolute[k].numel() != S * m or not absolute[k].is_contiguous():
+            raise ValueError("absolute[%r] must be the contiguous float64 tensor of op_pnp_ransac" % k)
+    if state.dtype != torch.float64 or state.numel() != S * POSE_STATE_WORDS or not state.is_contiguous():
+        raise ValueError("state must be contiguous float64 [%d, %d] (pose_state)" % (S, POSE_STATE_WORDS))
+    if (table.dtype != torch.float64 or table.dim() not in (2, 3) or table.shape[-1] != POSE_ROW_WORDS or not table.is_contiguous()
+            or table.numel() != S * table.shape[-2] * POSE_ROW_WORDS):
+        raise ValueError("table must be contiguous float64 [%d, capacity, %d] (pose_table)" % (S, POSE_ROW_WORDS))
+    with torch.cuda.device(state.device):
+        _check(lib.ssp_pose_repair(_ptr(absolute["Rw"]), _ptr(absolute["C"]), _ptr(absolute["status"]), S, _ptr(state), _ptr(table),
+                                   int(table.shape[-2]), _stream()))
+    return state, table
 
 
 def op_eval_pixel_homographies(hn, height, width):
