@@ -718,6 +718,44 @@ int ssp_pnp_ransac(const double* corr_dev, const int32_t* n_dev, int cap, int n_
 int ssp_pose_repair(const double* rw_dev, const double* c_dev, const int32_t* status_dev, int n_seq, double* state_dev,
                     double* table_dev, int capacity, void* stream);
 
+/* ---- windowed bundle adjustment ------------------------------------------------------------------
+ * The cameras of the retained frames (ssp_map_window) and the status-0 rows of ssp_op_triangulate_tracks refined together:
+ * Levenberg-Marquardt on the pixel reprojection error, the points eliminated by the Schur complement, plain least squares.
+ * fp64 without contraction; the rules are DESIGN.md section 28 and are restated in numpy by tests/ba_ref.py.  Every sum over
+ * the rows runs in one fixed order, so a result depends on nothing but the call's inputs (not on row_cap, the run or the
+ * batch).  No call synchronises with the host or allocates; the number of launches depends on `iterations` alone.
+ * ssp_bundle_adjust: the arguments of ssp_op_triangulate_tracks, its x_dev [row_cap][3] and status_dev [row_cap] as inputs.
+ *   Unknowns: (w, dC) of every valid view (Rw <- renormalised Cay(w) Rw, C <- C + dC, section 27's update) and X of every row
+ *   below n_rows with status 0; the observations are section 26's.  Held: every invalid view, the first valid view a, and
+ *   coordinate k* of the centre of the last valid view b (the component of C_b - C_a of largest magnitude, lowest on ties).
+ *   lambda starts at 1e-4 and scales the diagonals of U and V by (1 + lambda); V_r is inverted by section 26's cofactor solve
+ *   (a refused row contributes nothing in that iteration); the reduced 6L x 6L system is solved by Cholesky without pivoting
+ *   (a pivot that is not finite or <= 0 rejects the step).  A step is accepted when its cost is finite, every used view keeps
+ *   the point in front and the cost falls: lambda / 10 (at least 1e-12), else lambda * 10 (at most 1e6).  After an accepted
+ *   step the loop is done when cur - new <= 1e-10 cur or new <= 2 n_obs (1e-9)^2.  1 <= iterations <= SSP_BA_MAX_ITERATIONS.
+ *   cams_out_dev [max_length][SSP_CAM_WORDS] (invalid views zero), x_out_dev [row_cap][3] (rows not used are copies),
+ *   rms_out_dev [row_cap] (0 where the row is not used), info_dev [SSP_BA_INFO_WORDS] fp64 = (status, cost before, cost
+ *   after, n_obs, rows used, accepted steps, refused V solves, final lambda).  status 0: adjusted; 1: nothing to adjust (fewer
+ *   than 2 valid views, no used row, or 2 n_obs < 6 (valid - 1) - 1 + 3 rows); 2: no step accepted.  Under 1 and 2 the outputs
+ *   are copies of the inputs.  The outputs must not alias the inputs.  workspace_dev: ssp_ba_workspace_bytes(max_length,
+ *   row_cap) bytes (0 = bad arguments).
+ * ssp_ba_apply: n_seq sequences; info_dev [n_seq][SSP_BA_INFO_WORDS], cams_dev [n_seq][max_length][SSP_CAM_WORDS] of
+ *   ssp_bundle_adjust; state_dev and table_dev of ssp_pose_chain.  n_frames as for ssp_map_window.  Acts only under status 0:
+ *   for every valid view c other than a with 0 <= f = n - L + c < capacity, row f takes Rw and C and flag bit 3
+ *   (SSP_POSE_FLAG_ADJUSTED); s becomes |C_f - C_(f-1)| when view c - 1 is valid and the length is finite and above 1/64 of
+ *   the row's s.  When row n - 1 is the state's newest frame and the table is not full, the state's Rw, tw = -(Rw C) and s
+ *   follow it.  Bits 0 and 1 are not touched. */
+#define SSP_BA_INFO_WORDS 8
+#define SSP_BA_MAX_ITERATIONS 16
+#define SSP_POSE_FLAG_ADJUSTED 8
+size_t ssp_ba_workspace_bytes(int max_length, int row_cap);
+int ssp_bundle_adjust(const int32_t* ids_dev, const int32_t* state_dev, const double* pts_dev, int first_slot, const double* cams_dev,
+                      int max_length, int point_cap, int row_cap, const double* x_dev, const int32_t* status_dev, int iterations,
+                      double* cams_out_dev, double* x_out_dev, double* rms_out_dev, double* info_dev, void* workspace_dev,
+                      void* stream);
+int ssp_ba_apply(const double* info_dev, const double* cams_dev, int max_length, int n_seq, int n_frames, double* state_dev,
+                 double* table_dev, int capacity, void* stream);
+
 /* ---- streamed descriptor metrics----------------------------------------------------------
  * The per-pair metrics of evaluation.py -r -homo for a set that is fed batch by batch and never leaves the device, on
  * top of ssp_eval_repeatability, ssp_match_two_way and ssp_eval_ransac.  fp64 without contraction.  No call

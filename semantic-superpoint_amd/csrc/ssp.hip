@@ -38,6 +38,7 @@
 #include "pose_kernels.hip.h"
 #include "landmark_kernels.hip.h"
 #include "pnp_kernels.hip.h"
+#include "ba_kernels.hip.h"
 #include "detector_eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
@@ -4062,6 +4063,68 @@ int ssp_pose_repair(const double* rw_dev, const double* c_dev, const int32_t* st
   if (!rw_dev || !c_dev || !status_dev || !state_dev || (capacity > 0 && !table_dev)) return fail(-1, "pose_repair: null pointer");
   hipLaunchKernelGGL(pose_repair_kernel, dim3(cdiv(n_seq, 64)), dim3(64), 0, (hipStream_t)stream, rw_dev, c_dev, status_dev, n_seq,
                      state_dev, table_dev, capacity);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- windowed bundle adjustment: Levenberg-Marquardt over the window's cameras and landmarks, the write-back ----
+static_assert(BA_INFO_WORDS == SSP_BA_INFO_WORDS && BA_FLAG_ADJUSTED == SSP_POSE_FLAG_ADJUSTED && BA_MAX_ITERATIONS == SSP_BA_MAX_ITERATIONS,
+              "include/ssp_hip.h and ba_kernels.hip.h disagree");
+size_t ssp_ba_workspace_bytes(int max_length, int row_cap) {
+  if (track_check("ba_workspace_bytes", max_length, 1, row_cap)) return 0;
+  return align_up(ba_ws_words(max_length, row_cap) * sizeof(double), 256);
+}
+
+int ssp_bundle_adjust(const int32_t* ids_dev, const int32_t* state_dev, const double* pts_dev, int first_slot, const double* cams_dev,
+                      int max_length, int point_cap, int row_cap, const double* x_dev, const int32_t* status_dev, int iterations,
+                      double* cams_out_dev, double* x_out_dev, double* rms_out_dev, double* info_dev, void* workspace_dev,
+                      void* stream) {
+  CHK(track_check("bundle_adjust", max_length, point_cap, row_cap));
+  if (first_slot < 0 || first_slot >= max_length)
+    return fail(-1, "bundle_adjust: 0 <= first_slot < max_length required (got %d)", first_slot);
+  if (iterations < 1 || iterations > SSP_BA_MAX_ITERATIONS)
+    return fail(-1, "bundle_adjust: 1 <= iterations <= %d required (got %d)", SSP_BA_MAX_ITERATIONS, iterations);
+  if (!ids_dev || !state_dev || !pts_dev || !cams_dev || !x_dev || !status_dev || !cams_out_dev || !x_out_dev || !rms_out_dev ||
+      !info_dev || !workspace_dev)
+    return fail(-1, "bundle_adjust: null pointer");
+  if (cams_out_dev == cams_dev || x_out_dev == x_dev) return fail(-1, "bundle_adjust: the outputs must not alias the inputs");
+  static AttrOnce attr_once;
+  if (attr_once.need())
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)ba_solve_lds_bytes(SSP_TRACK_MAX_LENGTH)));
+  hipStream_t st = (hipStream_t)stream;
+  const int L = max_length, tiles = cdiv(row_cap, BA_THREADS);
+  const BaWs w = ba_ws_of(reinterpret_cast<double*>(workspace_dev), L, row_cap);
+  const size_t stage = ba_stage_bytes(L);
+  hipLaunchKernelGGL(ba_init_kernel, dim3(tiles), dim3(BA_THREADS), 0, st, cams_dev, x_dev, L, row_cap, cams_out_dev, x_out_dev, w.ctl);
+  for (int it = 0; it < iterations; ++it) {
+    const double* ctl = w.ctl + (size_t)it * BA_CTL_WORDS;
+    hipLaunchKernelGGL(ba_linearise_kernel, dim3(tiles), dim3(BA_THREADS), stage, st, ids_dev, state_dev, pts_dev, first_slot,
+                       (const double*)cams_out_dev, (const double*)x_out_dev, status_dev, L, point_cap, row_cap, ctl, w.part);
+    hipLaunchKernelGGL(ba_solve_kernel, dim3(1), dim3(BA_THREADS), ba_solve_lds_bytes(L), st, (const double*)w.part, tiles,
+                       (const double*)cams_out_dev, L, ctl, w.sol, w.cand_cams);
+    hipLaunchKernelGGL(ba_backsub_kernel, dim3(tiles), dim3(BA_THREADS), stage, st, ids_dev, state_dev, pts_dev, first_slot,
+                       (const double*)cams_out_dev, (const double*)x_out_dev, status_dev, L, point_cap, row_cap, ctl,
+                       (const double*)w.sol, (const double*)w.cand_cams, w.x_cand, w.cpart);
+    hipLaunchKernelGGL(ba_accept_kernel, dim3(tiles), dim3(BA_THREADS), 0, st, state_dev, status_dev, L, row_cap, it, ctl,
+                       w.ctl + (size_t)(it + 1) * BA_CTL_WORDS, (const double*)w.sol, (const double*)w.cpart,
+                       (const double*)w.cand_cams, (const double*)w.x_cand, cams_out_dev, x_out_dev);
+  }
+  hipLaunchKernelGGL(ba_finish_kernel, dim3(tiles), dim3(BA_THREADS), stage, st, ids_dev, state_dev, pts_dev, first_slot,
+                     (const double*)cams_out_dev, (const double*)x_out_dev, status_dev, L, point_cap, row_cap,
+                     (const double*)(w.ctl + (size_t)iterations * BA_CTL_WORDS), rms_out_dev, info_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_ba_apply(const double* info_dev, const double* cams_dev, int max_length, int n_seq, int n_frames, double* state_dev,
+                 double* table_dev, int capacity, void* stream) {
+  CHK(track_check("ba_apply", max_length, 1, 1));
+  if (n_seq < 1 || n_seq > 65535 || capacity < 0)
+    return fail(-1, "ba_apply: 1 <= n_seq <= 65535 and capacity >= 0 required (n_seq %d, capacity %d)", n_seq, capacity);
+  if (!info_dev || !cams_dev || !state_dev || (capacity > 0 && !table_dev)) return fail(-1, "ba_apply: null pointer");
+  hipLaunchKernelGGL(ba_apply_kernel, dim3(cdiv(n_seq, 64)), dim3(64), 0, (hipStream_t)stream, info_dev, cams_dev, max_length, n_seq,
+                     n_frames, state_dev, table_dev, capacity);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -260,11 +260,17 @@ class PointTracker(object):
     check seed) places its camera in the window's frame and scale: last_geometry() gains the "abs_*" keys and
     absolute_trajectory() one row.  "repair" also rewrites the frame's trajectory row and the chain state from that pose
     (lib.op_pose_repair) when the two-view chain could not determine them, so a frame without a two-view pose no longer breaks the
-    window.  All of it is queued on the device."""
+    window.  All of it is queued on the device.
+    bundle_adjust (needs intrinsics of ONE camera): None runs none of it.  "observe": after the track update
+    of every bundle_every-th frame the cameras of the newest consistent window and the landmarks triangulated under them
+    (landmark_params, buffers of the tracker's own) are refined together (lib.op_bundle_adjust, bundle_iterations);
+    bundle_adjusted() returns the result and last_geometry() gains "ba_info".  "apply" also writes the refined cameras back into
+    the trajectory and the chain state (lib.op_ba_apply), so the next frame's chain, the kept landmarks of absolute_pose and
+    landmarks_device see them.  All of it is queued on the device."""
 
     def __init__(self, max_length, nn_thresh, device=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
-                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0)):
+                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1):
         if geometric_check not in (None, "fundamental", "homography"):
             raise ValueError("geometric_check must be None, 'fundamental' or 'homography' (got %r)" % (geometric_check,))
         if absolute_pose not in (None, "observe", "repair"):
@@ -279,6 +285,20 @@ class PointTracker(object):
                                  "more than two views")
             if not (absolute_thresh >= 0.0 and np.isfinite(absolute_thresh)) or int(absolute_min_inliers) < 4:
                 raise ValueError("absolute_thresh must be finite and non-negative, absolute_min_inliers at least 4")
+            if len(landmark_params) != 3 or int(landmark_params[0]) < 2:
+                raise ValueError("landmark_params must be (min_views >= 2, min_parallax_deg, max_reproj)")
+        if bundle_adjust not in (None, "observe", "apply"):
+            raise ValueError("bundle_adjust must be None, 'observe' or 'apply' (got %r)" % (bundle_adjust,))
+        if bundle_adjust is not None:
+            if intrinsics is None or geometric_check != "fundamental":
+                raise ValueError("bundle_adjust needs intrinsics and geometric_check='fundamental': the cameras come from the "
+                                 "trajectory")
+            k = np.asarray(intrinsics, dtype=np.float64)
+            if k.shape == (2, 4) and not np.array_equal(k[0], k[1]):
+                raise ValueError("bundle_adjust needs ONE camera: a fixed (previous, new) pair of different intrinsics cannot describe "
+                                 "more than two views")
+            if not 1 <= int(bundle_iterations) <= L.BA_MAX_ITERATIONS or int(bundle_every) < 1:
+                raise ValueError("1 <= bundle_iterations <= %d and bundle_every >= 1 required" % L.BA_MAX_ITERATIONS)
             if len(landmark_params) != 3 or int(landmark_params[0]) < 2:
                 raise ValueError("landmark_params must be (min_views >= 2, min_parallax_deg, max_reproj)")
         if intrinsics is not None:
@@ -335,6 +355,11 @@ class PointTracker(object):
         self._abs_have = False    # _abs_lm holds such landmarks
         self._abs = None          # lib.pnp_buffers of one problem
         self._abs_table = None    # float64 [trajectory_rows, POSE_ROW_WORDS]: absolute_trajectory()
+        self.bundle_adjust = bundle_adjust
+        self.bundle_iterations, self.bundle_every = int(bundle_iterations), int(bundle_every)
+        self._ba_lm = None        # lib.landmark_buffers of the tracker's own: what the bundle adjustment starts from
+        self._ba = None           # lib.ba_buffers: its result
+        self._ba_ran = False
 
     # ---- device buffers -------------------------------------------------------------------------------------------
     def _ensure(self, n):
@@ -390,6 +415,8 @@ class PointTracker(object):
         if self.geometric_check is not None:
             m, nm = self._check_device(m, nm)
         self._track_device(m, nm)
+        if self.bundle_adjust is not None:
+            self._bundle_device()
         if self.absolute_pose is not None:
             self._keep_landmarks_device()
         had_prev, self._prev_ok = self._prev_ok, True
@@ -490,6 +517,37 @@ class PointTracker(object):
         L.op_landmarks_select(self._table, rows, out=self._abs_lm)
         self._abs_have = True
 
+    def _bundle_device(self):
+        """The bundle adjustment of the window ending at the newest frame (after _track_device): map window, triangulate, adjust
+        and, with "apply", the write-back into the trajectory."""
+        row_cap = self._table["row_cap"]
+        if self._ba is None or self._ba["rms"].shape[0] != row_cap:
+            self._ba_lm = L.landmark_buffers(self.maxl, row_cap, self.device)
+            self._ba = L.ba_buffers(self.maxl, row_cap, self.device)
+            self._ba["info"][0:1] = L.BA_NOTHING
+            self._ba["info"][7:8] = 1e-4
+            self._ba_ran = False
+        if self._frames >= 2 and self._traj_table is not None and self._frames % self.bundle_every == 0:
+            mv, par, rep = self.landmark_params
+            first_slot = self._frames % self.maxl
+            cams = L.op_map_window(self._traj_state, self._traj_table, self._intr[0, 1:2], self.maxl, n_frames=self._frames,
+                                   out=self._ba_lm)
+            rows = L.op_triangulate_tracks(self._table, self._pts, first_slot, cams, mv, par, rep, out=self._ba_lm)
+            res = L.op_bundle_adjust(self._table, self._pts, first_slot, cams, rows, self.bundle_iterations, out=self._ba)
+            if self.bundle_adjust == "apply":
+                L.op_ba_apply(res, self._traj_state, self._traj_table, self.maxl, n_frames=self._frames)
+            self._ba_ran = True
+        if self._geometry is not None:
+            self._geometry = dict(self._geometry, ba_info=self._ba["info"])
+
+    def bundle_adjusted(self):
+        """(cams float64 [max_length, lib.CAM_WORDS], X float64 [row_cap, 3], rms float64 [row_cap], info float64
+        [lib.BA_INFO_WORDS]) of the newest bundle adjustment on the device (lib.op_bundle_adjust; X and rms are aligned with the
+        track table's rows at that frame), None without bundle_adjust or before it first ran.  No synchronisation."""
+        if not self._ba_ran:
+            return None
+        return self._ba["cams"], self._ba["X"], self._ba["rms"], self._ba["info"]
+
     def absolute_trajectory(self):
         """(table, n_frames) on the device: float64 [trajectory_rows, lib.POSE_ROW_WORDS] rows (Rw [9], C [3], n_inliers, rms,
         status, n_corr), one per frame given so far: the camera of that frame against the landmarks of the window ending at the
@@ -553,7 +611,8 @@ class PointTracker(object):
 
     def last_geometry(self):
         """The device dict of the newest frame's geometric check (lib.op_epipolar_ransac or lib.op_eval_ransac), None before
-        the first checked frame or without a check.  Its mask indexes the UNFILTERED matches of that frame."""
+        the first checked frame or without a check.  Its mask indexes the UNFILTERED matches of that frame.  With bundle_adjust
+        it also holds "ba_info" (float64 [lib.BA_INFO_WORDS]) of the newest adjustment (status lib.BA_NOTHING before the first)."""
         return self._geometry
 
     def _track_device(self, m, nm):
@@ -755,12 +814,15 @@ class SequenceTracker:
     landmarks / landmarks_device / landmark_rows_device: PointTracker's, on demand.
     absolute_pose / absolute_thresh / absolute_min_inliers / landmark_params: PointTracker's absolute pose of every frame from the
     landmarks of the window before it, and with "repair" the repair of the trajectory; read it with
-    tracker.last_geometry() and absolute_trajectory().  A step stays free of host copies and synchronisation."""
+    tracker.last_geometry() and absolute_trajectory().  A step stays free of host copies and synchronisation.
+    bundle_adjust / bundle_iterations / bundle_every: PointTracker's windowed bundle adjustment of the cameras and the landmarks,
+    and with "apply" its write-back into the trajectory; read it with bundle_adjusted().  A step stays
+    free of host copies and synchronisation."""
 
     def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4,
                  keep_classes=None, drop_classes=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
-                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0)):
+                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1):
         if nn_thresh < 0.0:
             raise ValueError("'nn_thresh' should be non-negative")
         self.class_consistent = bool(class_consistent)
@@ -777,7 +839,8 @@ class SequenceTracker:
                                     geometric_check=geometric_check, check_thresh=check_thresh, min_inliers=min_inliers,
                                     check_seed=check_seed, intrinsics=intrinsics, trajectory_rows=trajectory_rows,
                                     absolute_pose=absolute_pose, absolute_thresh=absolute_thresh,
-                                    absolute_min_inliers=absolute_min_inliers, landmark_params=landmark_params)
+                                    absolute_min_inliers=absolute_min_inliers, landmark_params=landmark_params,
+                                    bundle_adjust=bundle_adjust, bundle_iterations=bundle_iterations, bundle_every=bundle_every)
 
     def describe(self, image):
         """image [H,W] / [1,H,W] / [1,1,H,W] -> the device tensors of Engine.describe_points for this one image (with "cls",
@@ -815,6 +878,9 @@ class SequenceTracker:
 
     def absolute_trajectory(self):
         return self.tracker.absolute_trajectory()
+
+    def bundle_adjusted(self):
+        return self.tracker.bundle_adjusted()
 
     def landmarks_device(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
         return self.tracker.landmarks_device(min_views, min_parallax_deg, max_reproj)

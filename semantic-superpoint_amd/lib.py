@@ -136,7 +136,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_epi_ransac_workspace_bytes", "ssp_epi_ransac", "ssp_op_filter_matches",
            "ssp_pose_from_fundamental", "ssp_pose_chain",
            "ssp_landmark_workspace_bytes", "ssp_map_window", "ssp_op_triangulate_tracks", "ssp_op_landmarks_select",
-           "ssp_pnp_workspace_bytes", "ssp_op_landmark_matches", "ssp_pnp_ransac", "ssp_pose_repair"]
+           "ssp_pnp_workspace_bytes", "ssp_op_landmark_matches", "ssp_pnp_ransac", "ssp_pose_repair",
+           "ssp_ba_workspace_bytes", "ssp_bundle_adjust", "ssp_ba_apply"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -158,6 +159,10 @@ LANDMARK_WORDS = 8  # SSP_LANDMARK_WORDS: track id, X, Y, Z, n_views, rms, cos_p
 LANDMARK_OK, LANDMARK_FEW_VIEWS, LANDMARK_DEGENERATE, LANDMARK_BEHIND, LANDMARK_REPROJ = 0, 1, 2, 3, 4  # SSP_LANDMARK_*
 CORR_WORDS = 8  # SSP_CORR_WORDS: fp64 words of a 3-D to 2-D correspondence (X, Y, Z, px, py, landmark row, valid, 0)
 POSE_FLAG_ABSOLUTE = 4  # SSP_POSE_FLAG_ABSOLUTE: flag bit of a trajectory row rewritten from an absolute pose
+POSE_FLAG_ADJUSTED = 8  # SSP_POSE_FLAG_ADJUSTED: flag bit of a trajectory row rewritten by the bundle adjustment
+BA_INFO_WORDS = 8  # SSP_BA_INFO_WORDS: status, cost before, cost after, n_obs, rows used, accepted steps, refused V solves, lambda
+BA_MAX_ITERATIONS = 16  # SSP_BA_MAX_ITERATIONS
+BA_ADJUSTED, BA_NOTHING, BA_NO_STEP = 0, 1, 2  # info[0] of op_bundle_adjust
 
 
 def load_library(path=None):
@@ -382,6 +387,14 @@ def load_library(path=None):
         lib.ssp_op_landmark_matches.argtypes = [vp, vp, i, vp, vp, i, vp, i, i, vp, vp, vp]
         lib.ssp_pnp_ransac.argtypes = [vp, vp, i, i, vp, i, vp, C.c_double, i, i] + [vp] * 9
         lib.ssp_pose_repair.argtypes = [vp, vp, vp, i, vp, vp, i, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_ba_workspace_bytes.argtypes = [i, i]
+        lib.ssp_ba_workspace_bytes.restype = C.c_size_t
+        lib.ssp_bundle_adjust.argtypes = [vp, vp, vp, i, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp]
+        lib.ssp_ba_apply.argtypes = [vp, vp, i, i, i, vp, vp, i, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -2328,6 +2341,118 @@ def op_pose_repair(absolute, state, table):
     with torch.cuda.device(state.device):
         _check(lib.ssp_pose_repair(_ptr(absolute["Rw"]), _ptr(absolute["C"]), _ptr(absolute["status"]), S, _ptr(state), _ptr(table),
                                    int(table.shape[-2]), _stream()))
+    return state, table
+
+
+# ---- windowed bundle adjustment ----
+BA_KEYS = ("cams", "X", "rms", "info")
+
+
+def ba_buffers(max_length, row_cap, device):
+    """The device arrays of op_bundle_adjust for a track table of row_cap rows of max_length ids, zeroed: {"cams": float64 [L,
+    CAM_WORDS], "X": float64 [row_cap, 3], "rms": float64 [row_cap], "info": float64 [BA_INFO_WORDS], "ws": its scratch}.  Pass it
+    as `out` to keep the operator from allocating."""
+    lib = load_library()
+    L, row_cap = int(max_length), int(row_cap)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("ba_buffers needs a HIP device: the MI355X path has no CPU fallback")
+    wsb = lib.ssp_ba_workspace_bytes(L, row_cap)
+    if wsb == 0:
+        _check(-1)
+    f64 = dict(dtype=torch.float64, device=device)
+    return {"cams": torch.zeros(L, CAM_WORDS, **f64), "X": torch.zeros(row_cap, 3, **f64), "rms": torch.zeros(row_cap, **f64),
+            "info": torch.zeros(BA_INFO_WORDS, **f64), "ws": torch.zeros(wsb, dtype=torch.uint8, device=device)}
+
+
+def op_bundle_adjust(table, pts, first_slot, cams, rows, iterations=10, out=None):
+    """The cameras of the window and the accepted landmarks refined together (ssp_bundle_adjust):
+    Levenberg-Marquardt on the pixel reprojection error over (w, dC) of every valid view but the first and X of every row with
+    status 0, plain least squares.  table, pts, first_slot, cams: as for op_triangulate_tracks; rows: the dict it returned for
+    them ("X" and "status" are read).  1 <= iterations <= BA_MAX_ITERATIONS fixes the number of launches.  Returns device tensors
+    {"cams": float64 [L, CAM_WORDS] (invalid views zero), "X": float64 [row_cap, 3] (rows not used are copies), "rms": float64
+    [row_cap] (0 where the row is not used), "info": float64 [BA_INFO_WORDS] = (status, cost before, cost after, n_obs, rows used,
+    accepted steps, refused V solves, final lambda)}; status BA_ADJUSTED, BA_NOTHING (nothing to adjust) or BA_NO_STEP (no step
+    accepted): under the last two the outputs are copies of the inputs.  `out`: a ba_buffers dict (not the inputs' own arrays).
+    No host synchronisation."""
+    lib = load_library()
+    L, point_cap, row_cap = table["L"], table["point_cap"], table["row_cap"]
+    for k in ("X", "status"):
+        if k not in rows:
+            raise ValueError("rows must be the dict of op_triangulate_tracks (no %r)" % k)
+    for t, nm in ((table["ids"], "table['ids']"), (table["state"], "table['state']"), (pts, "pts"), (cams, "cams"), (rows["X"], "rows['X']"),
+                  (rows["status"], "rows['status']")):
+        _need_gpu(t, nm)
+    if pts.dtype != torch.float64 or tuple(pts.shape) != (L, point_cap, 2) or not pts.is_contiguous():
+        raise ValueError("pts must be contiguous float64 [%d, %d, 2]" % (L, point_cap))
+    if cams.dtype != torch.float64 or tuple(cams.shape) != (L, CAM_WORDS) or not cams.is_contiguous():
+        raise ValueError("cams must be contiguous float64 [%d, %d] (op_map_window)" % (L, CAM_WORDS))
+    if table["ids"].dtype != torch.int32 or tuple(table["ids"].shape) != (row_cap, L) or table["state"].dtype != torch.int32 \
+            or table["state"].numel() != 2 + L:
+        raise ValueError("table must be a track table: ids int32 [%d, %d], state int32 [%d]" % (row_cap, L, 2 + L))
+    if rows["X"].dtype != torch.float64 or tuple(rows["X"].shape) != (row_cap, 3) or not rows["X"].is_contiguous():
+        raise ValueError("rows['X'] must be contiguous float64 [%d, 3]" % row_cap)
+    if rows["status"].dtype != torch.int32 or tuple(rows["status"].shape) != (row_cap,) or not rows["status"].is_contiguous():
+        raise ValueError("rows['status'] must be contiguous int32 [%d]" % row_cap)
+    if not 0 <= int(first_slot) < L:
+        raise ValueError("0 <= first_slot < %d required (got %d)" % (L, first_slot))
+    if not 1 <= int(iterations) <= BA_MAX_ITERATIONS:
+        raise ValueError("1 <= iterations <= %d required (got %d)" % (BA_MAX_ITERATIONS, int(iterations)))
+    if out is None:
+        out = ba_buffers(L, row_cap, pts.device)
+    shapes = {"cams": (L, CAM_WORDS), "X": (row_cap, 3), "rms": (row_cap,), "info": (BA_INFO_WORDS,)}
+    for k in BA_KEYS + ("ws",):
+        if k not in out:
+            raise ValueError("out must be the dict of ba_buffers (no %r)" % k)
+        _need_gpu(out[k], "out[%r]" % k)
+        if k != "ws" and (out[k].dtype != torch.float64 or tuple(out[k].shape) != shapes[k] or not out[k].is_contiguous()):
+            raise ValueError("out[%r] must be contiguous float64 %s (ba_buffers)" % (k, list(shapes[k])))
+    if out["ws"].dtype != torch.uint8 or out["ws"].numel() < lib.ssp_ba_workspace_bytes(L, row_cap):
+        raise ValueError("out['ws'] is smaller than ssp_ba_workspace_bytes(%d, %d)" % (L, row_cap))
+    if out["cams"].data_ptr() == cams.data_ptr() or out["X"].data_ptr() == rows["X"].data_ptr():
+        raise ValueError("out must not share its arrays with cams or rows['X']")
+    with torch.cuda.device(pts.device):
+        _check(lib.ssp_bundle_adjust(_ptr(table["ids"]), _ptr(table["state"]), _ptr(pts), int(first_slot), _ptr(cams), L, point_cap,
+                                     row_cap, _ptr(rows["X"]), _ptr(rows["status"]), int(iterations), _ptr(out["cams"]),
+                                     _ptr(out["X"]), _ptr(out["rms"]), _ptr(out["info"]), _ptr(out["ws"]), _stream()))
+    return {k: out[k] for k in BA_KEYS}
+
+
+def op_ba_apply(adjusted, state, table, max_length, n_frames=None):
+    """The adjusted cameras written back into the trajectory (ssp_ba_apply).  adjusted: the dict of
+    op_bundle_adjust ("info" float64 [S, BA_INFO_WORDS] and "cams" float64 [S, L, CAM_WORDS] for S sequences; the leading
+    dimension may be missing for one); state: float64 [S, POSE_STATE_WORDS] and table: float64 [S, capacity, POSE_ROW_WORDS] of
+    op_pose_chain, updated in place; n_frames as for op_map_window (one count for every sequence).  Acts only where info has
+    status BA_ADJUSTED: every valid view c other than the first valid one, with frame f = n - L + c inside the table, gives row f
+    its Rw and C and POSE_FLAG_ADJUSTED; s becomes the distance to the previous view's centre when that view is valid and the
+    distance is finite and above 1/64 of the row's s; the state follows row n - 1 when that is its newest frame and the table is
+    not full.  Returns (state, table).  No host synchronisation."""
+    lib = load_library()
+    L = int(max_length)
+    if not 2 <= L <= TRACK_MAX_LENGTH:
+        raise ValueError("2 <= max_length <= %d required (got %d)" % (TRACK_MAX_LENGTH, L))
+    for k in ("info", "cams"):
+        if k not in adjusted:
+            raise ValueError("adjusted must be the dict of op_bundle_adjust (no %r)" % k)
+        _need_gpu(adjusted[k], "adjusted[%r]" % k)
+    _need_gpu(state, "state")
+    _need_gpu(table, "table")
+    info, cams = adjusted["info"], adjusted["cams"]
+    if info.dtype != torch.float64 or info.numel() % BA_INFO_WORDS or info.numel() == 0 or not info.is_contiguous():
+        raise ValueError("adjusted['info'] must be contiguous float64 [S, %d]" % BA_INFO_WORDS)
+    S = info.numel() // BA_INFO_WORDS
+    if cams.dtype != torch.float64 or cams.numel() != S * L * CAM_WORDS or not cams.is_contiguous():
+        raise ValueError("adjusted['cams'] must be contiguous float64 [%d, %d, %d]" % (S, L, CAM_WORDS))
+    if state.dtype != torch.float64 or state.numel() != S * POSE_STATE_WORDS or not state.is_contiguous():
+        raise ValueError("state must be contiguous float64 [%d, %d] (pose_state)" % (S, POSE_STATE_WORDS))
+    if (table.dtype != torch.float64 or table.dim() not in (2, 3) or table.shape[-1] != POSE_ROW_WORDS or not table.is_contiguous()
+            or table.numel() != S * table.shape[-2] * POSE_ROW_WORDS):
+        raise ValueError("table must be contiguous float64 [%d, capacity, %d] (pose_table)" % (S, POSE_ROW_WORDS))
+    if n_frames is not None and int(n_frames) < 0:
+        raise ValueError("n_frames must be non-negative (None: the states' counts)")
+    with torch.cuda.device(state.device):
+        _check(lib.ssp_ba_apply(_ptr(info), _ptr(cams), L, S, -1 if n_frames is None else int(n_frames), _ptr(state), _ptr(table),
+                                int(table.shape[-2]), _stream()))
     return state, table
 
 
