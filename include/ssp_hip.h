@@ -756,6 +756,56 @@ int ssp_bundle_adjust(const int32_t* ids_dev, const int32_t* state_dev, const do
 int ssp_ba_apply(const double* info_dev, const double* cams_dev, int max_length, int n_seq, int n_frames, double* state_dev,
                  double* table_dev, int capacity, void* stream);
 
+/* ---- world map ---------------------------------------------------------------------------------
+ * Landmarks that outlive their window: a store of one sequence (X and a descriptor per track), a matcher of a frame's descriptors
+ * against the whole store, the join of its matches with the store's points (the input of ssp_pnp_ransac) and the repair of the
+ * newest trajectory row from the pose found.  The rules are restated in numpy by tests/world_ref.py.  No call synchronises with the
+ * host or allocates.
+ * The store, 1 <= map_cap <= SSP_WORLD_MAX_ROWS rows and tid_cap >= 1 track ids: x_dev fp64 [map_cap][3], desc_dev fp32
+ *   [map_cap][256], tid_dev / views_dev / first_dev / last_dev int32 [map_cap], rms_dev fp64 [map_cap], slot_of_tid_dev int32
+ *   [tid_cap], state_dev int32 [SSP_WORLD_STATE_WORDS] = (n_rows, anchored, lost_frames, streak, rows dropped because the map was
+ *   full, rows dropped because their track id is >= tid_cap, rows appended by the last insert, rows updated by it).  Track t is in
+ *   the map iff s = slot_of_tid[t] has 0 <= s < n_rows and tid[s] == t: zeroed memory is an empty map and n_rows = 0 clears it.
+ * ssp_op_world_insert: once per frame, after every rewrite of the frame's trajectory row.  landmarks_dev [row_cap]
+ *   [SSP_LANDMARK_WORDS] and n_landmarks_dev [1] of ssp_op_landmarks_select for the window ending at the newest frame; desc_new_dev
+ *   fp32 [point_cap][256] and count_new_dev [1] of that frame; table_dev [capacity][SSP_POSE_ROW_WORDS] of ssp_pose_chain and the
+ *   caller's frame count n_frames (the newest row is n_frames - 1; without such a row the frame counts as flagged).
+ *   Anchor rule, from that row's flag word F: ok = (F & 3) == 0; anchored' = ok && (n_rows == 0 || anchored || streak >= 2); while
+ *   n_rows > 0 && !anchored', lost_frames counts up, and past `patience` the map is cleared (n_rows, lost_frames, streak and the
+ *   two drop counters 0; the next ok frame adopts its own frame of reference); otherwise lost_frames = 0.  Rows are inserted only
+ *   when anchored'.  A landmark row takes part iff its newest-frame index p has 0 <= p < count, its track id lies in [0, tid_cap)
+ *   and X is finite.  Found in the map: X, n_views, rms, last_frame = n_frames - 1 and the descriptor desc_new[p] are replaced.
+ *   Else appended in landmark order (first_frame = last_frame = n_frames - 1) while there is room; past map_cap dropped and counted.
+ *   Track ids must be unique within a call.  workspace_dev: ssp_world_insert_workspace_bytes(row_cap) bytes.
+ * ssp_match_world: ssp_match_two_way's rules with side 1 = the n_rows (state_dev[0], clamped to map_cap) rows of desc_dev and side
+ *   2 = the count2_dev[0] (clamped to cap, 1 <= cap <= SSP_MATCH_MAX_POINTS) rows of desc2_dev [cap][256]: the same fp32 chain per
+ *   dot product, the same keys, first index on ties on both sides, keep = d < nn_thresh && mutual; bit-identical to
+ *   ssp_match_two_way wherever both apply.  match_dev [cap][3] = (map row, frame row, d) in ascending map row, n_match_dev [1].
+ *   workspace_dev: ssp_match_world_workspace_bytes(map_cap, cap) bytes (0 = bad arguments).
+ * ssp_op_world_correspondences: corr_dev [cap][SSP_CORR_WORDS] = (X, Y, Z, px, py, map row, valid, 0) per match row, n_corr_dev [2]
+ *   = (rows, valid rows).  A row is valid iff it lies below n_match, its map row is < n_rows, its frame point is < count_new_dev[0]
+ *   (clamped to point_cap) and the five values are finite; every other row is zero.  pts_new_dev fp64 [point_cap][pt_stride].
+ * ssp_world_repair: ssp_pose_repair's rule for one sequence (rw_dev [9], c_dev [3], status_dev [1] of ssp_pnp_ransac), firing when
+ *   the pose has status 0 and is finite and either row n - 1 carries flag bit 0 or 1 or the map is lost (n_rows > 0 && !anchored).
+ *   Sets SSP_POSE_FLAG_ABSOLUTE and SSP_POSE_FLAG_WORLD; streak += 1 when it rewrites the row, streak = 0 when it does not. */
+#define SSP_WORLD_MAX_ROWS 65536
+#define SSP_WORLD_STATE_WORDS 8
+#define SSP_POSE_FLAG_WORLD 16
+size_t ssp_world_insert_workspace_bytes(int row_cap);
+size_t ssp_match_world_workspace_bytes(int map_cap, int cap);
+int ssp_op_world_insert(const double* landmarks_dev, const int32_t* n_landmarks_dev, int row_cap, const float* desc_new_dev,
+                        const int32_t* count_new_dev, int point_cap, const double* table_dev, int capacity, int n_frames, int patience,
+                        int map_cap, int tid_cap, double* x_dev, float* desc_dev, int32_t* tid_dev, int32_t* views_dev,
+                        int32_t* first_dev, int32_t* last_dev, double* rms_dev, int32_t* slot_of_tid_dev, int32_t* state_dev,
+                        void* workspace_dev, void* stream);
+int ssp_match_world(const float* desc_dev, const int32_t* state_dev, int map_cap, const float* desc2_dev, const int32_t* count2_dev,
+                    int cap, float nn_thresh, void* workspace_dev, float* match_dev, int32_t* n_match_dev, void* stream);
+int ssp_op_world_correspondences(const double* x_dev, const int32_t* state_dev, int map_cap, const float* match_dev,
+                                 const int32_t* n_match_dev, int cap, const double* pts_new_dev, int pt_stride,
+                                 const int32_t* count_new_dev, int point_cap, double* corr_dev, int32_t* n_corr_dev, void* stream);
+int ssp_world_repair(const double* rw_dev, const double* c_dev, const int32_t* status_dev, double* state_dev, double* table_dev,
+                     int capacity, int map_cap, int32_t* world_state_dev, void* stream);
+
 /* ---- streamed descriptor metrics----------------------------------------------------------
  * The per-pair metrics of evaluation.py -r -homo for a set that is fed batch by batch and never leaves the device, on
  * top of ssp_eval_repeatability, ssp_match_two_way and ssp_eval_ransac.  fp64 without contraction.  No call

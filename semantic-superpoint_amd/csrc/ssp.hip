@@ -39,6 +39,7 @@
 #include "landmark_kernels.hip.h"
 #include "pnp_kernels.hip.h"
 #include "ba_kernels.hip.h"
+#include "world_kernels.hip.h"
 #include "detector_eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
@@ -4125,6 +4126,103 @@ int ssp_ba_apply(const double* info_dev, const double* cams_dev, int max_length,
   if (!info_dev || !cams_dev || !state_dev || (capacity > 0 && !table_dev)) return fail(-1, "ba_apply: null pointer");
   hipLaunchKernelGGL(ba_apply_kernel, dim3(cdiv(n_seq, 64)), dim3(64), 0, (hipStream_t)stream, info_dev, cams_dev, max_length, n_seq,
                      n_frames, state_dev, table_dev, capacity);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- world map: the store, the map matcher, the join, the repair ----
+static_assert(WORLD_STATE_WORDS == SSP_WORLD_STATE_WORDS && WORLD_MAX_ROWS == SSP_WORLD_MAX_ROWS && WORLD_FLAG_WORLD == SSP_POSE_FLAG_WORLD &&
+              WORLD_MAX_BLOCKS * WORLD_BLOCK == SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS && WORLD_MAX_ROWS % WORLD_STRIP == 0,
+              "include/ssp_hip.h and world_kernels.hip.h disagree");
+static int world_check(const char* what, int map_cap, int cap) {
+  if (map_cap < 1 || map_cap > SSP_WORLD_MAX_ROWS || cap < 1 || cap > SSP_MATCH_MAX_POINTS)
+    return fail(-1, "%s: 1 <= map_cap <= %d and 1 <= cap <= %d required (map_cap %d, cap %d)", what, SSP_WORLD_MAX_ROWS,
+                SSP_MATCH_MAX_POINTS, map_cap, cap);
+  return 0;
+}
+
+size_t ssp_world_insert_workspace_bytes(int row_cap) {
+  if (row_cap < 1 || row_cap > SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS) {
+    fail(-1, "world_insert_workspace_bytes: 1 <= row_cap <= %d required (got %d)", SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS, row_cap);
+    return 0;
+  }
+  return align_up(((size_t)WORLD_HDR_WORDS + 3 * WORLD_MAX_BLOCKS + row_cap) * sizeof(int32_t), 256);
+}
+
+size_t ssp_match_world_workspace_bytes(int map_cap, int cap) {
+  if (world_check("match_world_workspace_bytes", map_cap, cap)) return 0;
+  return align_up(((size_t)map_cap + cap) * sizeof(uint64_t), 256);
+}
+
+int ssp_op_world_insert(const double* landmarks_dev, const int32_t* n_landmarks_dev, int row_cap, const float* desc_new_dev,
+                        const int32_t* count_new_dev, int point_cap, const double* table_dev, int capacity, int n_frames, int patience,
+                        int map_cap, int tid_cap, double* x_dev, float* desc_dev, int32_t* tid_dev, int32_t* views_dev,
+                        int32_t* first_dev, int32_t* last_dev, double* rms_dev, int32_t* slot_of_tid_dev, int32_t* state_dev,
+                        void* workspace_dev, void* stream) {
+  CHK(world_check("world_insert", map_cap, point_cap));
+  if (row_cap < 1 || row_cap > SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS || tid_cap < 1 || capacity < 0 || patience < 0)
+    return fail(-1, "world_insert: 1 <= row_cap <= %d, tid_cap >= 1, capacity >= 0 and patience >= 0 required (row_cap %d, tid_cap %d, "
+                "capacity %d, patience %d)", SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS, row_cap, tid_cap, capacity, patience);
+  if (!landmarks_dev || !n_landmarks_dev || !desc_new_dev || !count_new_dev || (capacity > 0 && !table_dev) || !x_dev || !desc_dev ||
+      !tid_dev || !views_dev || !first_dev || !last_dev || !rms_dev || !slot_of_tid_dev || !state_dev || !workspace_dev)
+    return fail(-1, "world_insert: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* hdr = reinterpret_cast<int32_t*>(workspace_dev);
+  int32_t* bcount = hdr + WORLD_HDR_WORDS;
+  int32_t* cls = bcount + 3 * WORLD_MAX_BLOCKS;
+  const int nb = cdiv(row_cap, WORLD_BLOCK);
+  hipLaunchKernelGGL(world_anchor_kernel, dim3(1), dim3(64), 0, st, state_dev, map_cap, table_dev, capacity, n_frames, patience, hdr);
+  hipLaunchKernelGGL(world_classify_kernel, dim3(nb), dim3(WORLD_BLOCK), 0, st, (const int32_t*)hdr, landmarks_dev, n_landmarks_dev,
+                     row_cap, count_new_dev, point_cap, (const int32_t*)tid_dev, (const int32_t*)slot_of_tid_dev, tid_cap, cls, bcount);
+  hipLaunchKernelGGL(world_scatter_kernel, dim3(nb), dim3(WORLD_BLOCK), 0, st, (const int32_t*)hdr, landmarks_dev, row_cap, desc_new_dev,
+                     point_cap, (const int32_t*)cls, (const int32_t*)bcount, nb, n_frames, map_cap, x_dev, desc_dev, tid_dev, views_dev,
+                     first_dev, last_dev, rms_dev, slot_of_tid_dev, state_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_match_world(const float* desc_dev, const int32_t* state_dev, int map_cap, const float* desc2_dev, const int32_t* count2_dev,
+                    int cap, float nn_thresh, void* workspace_dev, float* match_dev, int32_t* n_match_dev, void* stream) {
+  CHK(world_check("match_world", map_cap, cap));
+  if (!(nn_thresh >= 0.f)) return fail(-1, "match_world: nn_thresh must be non-negative");
+  if (!desc_dev || !state_dev || !desc2_dev || !count2_dev || !workspace_dev || !match_dev || !n_match_dev)
+    return fail(-1, "match_world: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  uint64_t* rowmin = reinterpret_cast<uint64_t*>(workspace_dev);
+  uint64_t* colmin = rowmin + map_cap;
+  HIPCHK(hipMemsetAsync(rowmin, 0xFF, ((size_t)map_cap + cap) * sizeof(uint64_t), st));
+  hipLaunchKernelGGL(world_match_kernel, dim3(cdiv(map_cap, WORLD_STRIP), WORLD_SPLIT_MAX), dim3(256), 0, st, desc_dev, state_dev, map_cap, desc2_dev,
+                     count2_dev, cap, rowmin, colmin);
+  hipLaunchKernelGGL(world_compact_kernel, dim3(1), dim3(WORLD_BLOCK), 0, st, (const uint64_t*)rowmin, (const uint64_t*)colmin, state_dev,
+                     map_cap, count2_dev, cap, nn_thresh, match_dev, n_match_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_op_world_correspondences(const double* x_dev, const int32_t* state_dev, int map_cap, const float* match_dev,
+                                 const int32_t* n_match_dev, int cap, const double* pts_new_dev, int pt_stride,
+                                 const int32_t* count_new_dev, int point_cap, double* corr_dev, int32_t* n_corr_dev, void* stream) {
+  CHK(world_check("world_correspondences", map_cap, cap));
+  if (point_cap < 1 || point_cap > SSP_MATCH_MAX_POINTS || pt_stride < 2)
+    return fail(-1, "world_correspondences: 1 <= point_cap <= %d and pt_stride >= 2 required (point_cap %d, pt_stride %d)",
+                SSP_MATCH_MAX_POINTS, point_cap, pt_stride);
+  if (!x_dev || !state_dev || !match_dev || !n_match_dev || !pts_new_dev || !count_new_dev || !corr_dev || !n_corr_dev)
+    return fail(-1, "world_correspondences: null pointer");
+  hipLaunchKernelGGL(world_corr_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x_dev, state_dev, map_cap, match_dev, n_match_dev, cap,
+                     pts_new_dev, pt_stride, count_new_dev, point_cap, corr_dev, n_corr_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_world_repair(const double* rw_dev, const double* c_dev, const int32_t* status_dev, double* state_dev, double* table_dev,
+                     int capacity, int map_cap, int32_t* world_state_dev, void* stream) {
+  if (capacity < 0 || map_cap < 1 || map_cap > SSP_WORLD_MAX_ROWS)
+    return fail(-1, "world_repair: capacity >= 0 and 1 <= map_cap <= %d required (capacity %d, map_cap %d)", SSP_WORLD_MAX_ROWS, capacity,
+                map_cap);
+  if (!rw_dev || !c_dev || !status_dev || !state_dev || (capacity > 0 && !table_dev) || !world_state_dev)
+    return fail(-1, "world_repair: null pointer");
+  hipLaunchKernelGGL(world_repair_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rw_dev, c_dev, status_dev, state_dev, table_dev,
+                     capacity, map_cap, world_state_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }

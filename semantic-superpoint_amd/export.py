@@ -266,13 +266,39 @@ class PointTracker(object):
     (landmark_params, buffers of the tracker's own) are refined together (lib.op_bundle_adjust, bundle_iterations);
     bundle_adjusted() returns the result and last_geometry() gains "ba_info".  "apply" also writes the refined cameras back into
     the trajectory and the chain state (lib.op_ba_apply), so the next frame's chain, the kept landmarks of absolute_pose and
-    landmarks_device see them.  All of it is queued on the device."""
+    landmarks_device see them.  All of it is queued on the device.
+    world_map (needs intrinsics of ONE camera): None runs none of it.  "observe": the landmarks of every
+    frame's window (landmark_params, buffers of the tracker's own) enter a map of world_cap rows that keeps X and the newest
+    descriptor of every track after the track has left the window (lib.op_world_insert, while the map is anchored to the
+    trajectory; world_patience frames without an anchor clear it).  Every frame's unfiltered descriptors are matched against the
+    whole map (lib.op_match_world with nn_thresh; with class_consistent=True the map matcher still ignores the classes), joined
+    with its points (lib.op_world_correspondences) and given to the P3P RANSAC (world_thresh pixels, world_min_inliers, the frame's
+    check seed): last_geometry() gains the "world_*" keys and world_trajectory() one row.  "relocalise" also rewrites the frame's
+    trajectory row and the chain state from that pose (lib.op_world_repair) when the two-view chain could not determine them or
+    the map has lost its anchor, so a frame without points no longer restarts the map.  All of it is queued on the device."""
 
     def __init__(self, max_length, nn_thresh, device=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
-                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1):
+                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1,
+                 world_map=None, world_cap=65536, world_patience=30, world_thresh=2.0, world_min_inliers=6):
         if geometric_check not in (None, "fundamental", "homography"):
             raise ValueError("geometric_check must be None, 'fundamental' or 'homography' (got %r)" % (geometric_check,))
+        if world_map not in (None, "observe", "relocalise"):
+            raise ValueError("world_map must be None, 'observe' or 'relocalise' (got %r)" % (world_map,))
+        if world_map is not None:
+            if intrinsics is None or geometric_check != "fundamental":
+                raise ValueError("world_map needs intrinsics and geometric_check='fundamental': the landmarks come from the "
+                                 "trajectory's cameras")
+            k = np.asarray(intrinsics, dtype=np.float64)
+            if k.shape == (2, 4) and not np.array_equal(k[0], k[1]):
+                raise ValueError("world_map needs ONE camera: a fixed (previous, new) pair of different intrinsics cannot describe "
+                                 "more than two views")
+            if not (world_thresh >= 0.0 and np.isfinite(world_thresh)) or int(world_min_inliers) < 4:
+                raise ValueError("world_thresh must be finite and non-negative, world_min_inliers at least 4")
+            if not 1 <= int(world_cap) <= L.WORLD_MAX_ROWS or int(world_patience) < 0:
+                raise ValueError("1 <= world_cap <= %d and world_patience >= 0 required" % L.WORLD_MAX_ROWS)
+            if len(landmark_params) != 3 or int(landmark_params[0]) < 2:
+                raise ValueError("landmark_params must be (min_views >= 2, min_parallax_deg, max_reproj)")
         if absolute_pose not in (None, "observe", "repair"):
             raise ValueError("absolute_pose must be None, 'observe' or 'repair' (got %r)" % (absolute_pose,))
         if absolute_pose is not None:
@@ -360,6 +386,14 @@ class PointTracker(object):
         self._ba_lm = None        # lib.landmark_buffers of the tracker's own: what the bundle adjustment starts from
         self._ba = None           # lib.ba_buffers: its result
         self._ba_ran = False
+        self.world_map_mode = world_map
+        self.world_cap, self.world_patience = int(world_cap), int(world_patience)
+        self.world_thresh, self.world_min_inliers = float(world_thresh), int(world_min_inliers)
+        self._world = None        # lib.world_buffers: the map
+        self._world_lm = None     # lib.landmark_buffers of the tracker's own: the landmarks of the window ending at the newest frame
+        self._world_pnp = None    # lib.pnp_buffers of one problem
+        self._world_match = None  # (match [cap, 3], n_match [1]) of the newest frame against the map
+        self._world_table = None  # float64 [trajectory_rows, POSE_ROW_WORDS]: world_trajectory()
 
     # ---- device buffers -------------------------------------------------------------------------------------------
     def _ensure(self, n):
@@ -419,6 +453,8 @@ class PointTracker(object):
             self._bundle_device()
         if self.absolute_pose is not None:
             self._keep_landmarks_device()
+        if self.world_map_mode is not None:
+            self._world_insert_device()
         had_prev, self._prev_ok = self._prev_ok, True
         return m, nm, had_prev
 
@@ -452,6 +488,8 @@ class PointTracker(object):
             g = self._pose_device(g, p1, p2, m[None], nm)
         if self.absolute_pose is not None:
             g = self._absolute_device(g, m, nm, p2[0], seed)
+        if self.world_map_mode is not None:
+            g = self._world_device(g, p2[0], seed)
         self._geometry = g
         return L.op_filter_matches(m, nm, g["mask"], g["status"], g["n_inliers"], self.min_inliers)
 
@@ -516,6 +554,78 @@ class PointTracker(object):
         rows = L.op_triangulate_tracks(self._table, self._pts, self._frames % self.maxl, cams, mv, par, rep, out=self._abs_lm)
         L.op_landmarks_select(self._table, rows, out=self._abs_lm)
         self._abs_have = True
+
+    def _world_device(self, g, pts_new, seed):
+        """The newest frame against the world map: match, join, P3P, its row of world_trajectory() and, with "relocalise", the
+        repair of the newest trajectory row; returns g with the world_* keys.  An empty map gives the status-1 row."""
+        f = self._frames - 1
+        _, dslot = self._slots()
+        cap = self._cap
+        if self._world is None:
+            self._world = L.world_buffers(self.world_cap, device=self.device)
+            self._world_table = L.pose_table(self.trajectory_rows, self.device)
+        if self._world_pnp is None or self._world_pnp["corr"].shape[1] != cap:
+            self._world_pnp = L.pnp_buffers(1, cap, self.device)
+            self._world_match = (torch.zeros(cap, 3, dtype=torch.float32, device=self.device),
+                                 torch.zeros(1, dtype=torch.int32, device=self.device))
+        w, a, count = self._world, self._world_pnp, self._counts[dslot:dslot + 1]
+        m, nm = L.op_match_world(w, self._desc[dslot], count, self.nn_thresh, out=self._world_match)
+        corr, n = L.op_world_correspondences(w, m, nm, pts_new, count, out=a)
+        res = L.op_pnp_ransac(a["corr"], n[0:1], self._intr[0, 1:2], seed, thresh=self.world_thresh,
+                              min_inliers=self.world_min_inliers, out=a)
+        if self.world_map_mode == "relocalise":
+            L.op_world_repair(w, res, self._traj_state, self._traj_table)
+        if f < self.trajectory_rows:
+            row = self._world_table[f]
+            row[0:9] = res["Rw"].reshape(9)
+            row[9:12] = res["C"].reshape(3)
+            row[12:13] = res["n_inliers"]
+            row[13:14] = res["rms"]
+            row[14:15] = res["status"]
+            row[15:16] = a["n"][0, 1:2]
+        g = dict(g)
+        g.update(("world_" + k, v) for k, v in res.items())
+        g["world_corr"], g["world_n_corr"], g["world_match"], g["world_n_match"] = a["corr"][0], a["n"][0], m, nm
+        return g
+
+    def _world_insert_device(self):
+        """The landmarks of the window ending at the newest frame into the world map (after _track_device and the bundle
+        adjustment): map window, triangulate, select, insert."""
+        if self._frames < 2 or self._traj_table is None or self._world is None:
+            return
+        if self._world_lm is None or self._world_lm["status"].shape[0] != self._table["row_cap"]:
+            self._world_lm = L.landmark_buffers(self.maxl, self._table["row_cap"], self.device)
+        _, dslot = self._slots()
+        mv, par, rep = self.landmark_params
+        cams = L.op_map_window(self._traj_state, self._traj_table, self._intr[0, 1:2], self.maxl, n_frames=self._frames, out=self._world_lm)
+        rows = L.op_triangulate_tracks(self._table, self._pts, self._frames % self.maxl, cams, mv, par, rep, out=self._world_lm)
+        lms, n_lms = L.op_landmarks_select(self._table, rows, out=self._world_lm)
+        L.op_world_insert(self._world, lms, n_lms, self._desc[dslot], self._counts[dslot:dslot + 1], self._traj_table, self._frames,
+                          self.world_patience)
+
+    def world_trajectory(self):
+        """(table, n_frames) on the device in absolute_trajectory()'s layout: rows (Rw [9], C [3], n_inliers, rms, status, n_corr),
+        one per frame given so far: the camera of that frame against the world map as it stood before the frame (status 1, Rw = I,
+        C = 0 where there was no pose).  None without world_map or before the first frame.  No synchronisation."""
+        if self._world_table is None:
+            return None
+        return self._world_table, self._traj_state[0:1]
+
+    def world_map_device(self):
+        """The map's device buffers (the dict of lib.world_buffers; "state"[0] rows are in use), None without world_map or before
+        the first frame.  No synchronisation."""
+        return self._world
+
+    def world_map(self):
+        """The map as numpy: (rows float64 [n_rows, 8] = (tid, X, Y, Z, n_views, rms, first_frame, last_frame), descriptors float32
+        [n_rows, 256]); one host synchronisation.  Zero rows without world_map or before the first frame."""
+        if self._world is None:
+            return np.zeros((0, 8)), np.zeros((0, 256), dtype=np.float32)
+        w = self._world
+        n = min(max(int(w["state"][0].item()), 0), w["map_cap"])
+        cols = [w["tid"][:n].double()[:, None], w["X"][:n], w["n_views"][:n].double()[:, None], w["rms"][:n, None],
+                w["first_frame"][:n].double()[:, None], w["last_frame"][:n].double()[:, None]]
+        return torch.cat(cols, dim=1).cpu().numpy(), w["desc"][:n].cpu().numpy()
 
     def _bundle_device(self):
         """The bundle adjustment of the window ending at the newest frame (after _track_device): map window, triangulate, adjust
@@ -817,12 +927,17 @@ class SequenceTracker:
     tracker.last_geometry() and absolute_trajectory().  A step stays free of host copies and synchronisation.
     bundle_adjust / bundle_iterations / bundle_every: PointTracker's windowed bundle adjustment of the cameras and the landmarks,
     and with "apply" its write-back into the trajectory; read it with bundle_adjusted().  A step stays
-    free of host copies and synchronisation."""
+    free of host copies and synchronisation.
+    world_map / world_cap / world_patience / world_thresh / world_min_inliers: PointTracker's world map of landmarks that outlive
+    their window, every frame's pose against it and, with "relocalise", the repair of the trajectory from it (DESIGN.md section
+    29; the map matcher ignores classes); read it with tracker.last_geometry(), world_trajectory(), world_map_device() and
+    world_map().  A step stays free of host copies and synchronisation once allocated."""
 
     def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4,
                  keep_classes=None, drop_classes=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
-                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1):
+                 absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1,
+                 world_map=None, world_cap=65536, world_patience=30, world_thresh=2.0, world_min_inliers=6):
         if nn_thresh < 0.0:
             raise ValueError("'nn_thresh' should be non-negative")
         self.class_consistent = bool(class_consistent)
@@ -840,7 +955,9 @@ class SequenceTracker:
                                     check_seed=check_seed, intrinsics=intrinsics, trajectory_rows=trajectory_rows,
                                     absolute_pose=absolute_pose, absolute_thresh=absolute_thresh,
                                     absolute_min_inliers=absolute_min_inliers, landmark_params=landmark_params,
-                                    bundle_adjust=bundle_adjust, bundle_iterations=bundle_iterations, bundle_every=bundle_every)
+                                    bundle_adjust=bundle_adjust, bundle_iterations=bundle_iterations, bundle_every=bundle_every,
+                                    world_map=world_map, world_cap=world_cap, world_patience=world_patience,
+                                    world_thresh=world_thresh, world_min_inliers=world_min_inliers)
 
     def describe(self, image):
         """image [H,W] / [1,H,W] / [1,1,H,W] -> the device tensors of Engine.describe_points for this one image (with "cls",
@@ -881,6 +998,15 @@ class SequenceTracker:
 
     def bundle_adjusted(self):
         return self.tracker.bundle_adjusted()
+
+    def world_trajectory(self):
+        return self.tracker.world_trajectory()
+
+    def world_map_device(self):
+        return self.tracker.world_map_device()
+
+    def world_map(self):
+        return self.tracker.world_map()
 
     def landmarks_device(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
         return self.tracker.landmarks_device(min_views, min_parallax_deg, max_reproj)

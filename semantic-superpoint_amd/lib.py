@@ -137,7 +137,9 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_pose_from_fundamental", "ssp_pose_chain",
            "ssp_landmark_workspace_bytes", "ssp_map_window", "ssp_op_triangulate_tracks", "ssp_op_landmarks_select",
            "ssp_pnp_workspace_bytes", "ssp_op_landmark_matches", "ssp_pnp_ransac", "ssp_pose_repair",
-           "ssp_ba_workspace_bytes", "ssp_bundle_adjust", "ssp_ba_apply"]
+           "ssp_ba_workspace_bytes", "ssp_bundle_adjust", "ssp_ba_apply",
+           "ssp_world_insert_workspace_bytes", "ssp_match_world_workspace_bytes", "ssp_op_world_insert", "ssp_match_world",
+           "ssp_op_world_correspondences", "ssp_world_repair"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -395,6 +397,18 @@ def load_library(path=None):
         lib.ssp_ba_workspace_bytes.restype = C.c_size_t
         lib.ssp_bundle_adjust.argtypes = [vp, vp, vp, i, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp]
         lib.ssp_ba_apply.argtypes = [vp, vp, i, i, i, vp, vp, i, vp]
+    except AttributeError:
+        if os.environ.get("SSP_HIP_LIB") is None:
+            raise
+    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
+        lib.ssp_world_insert_workspace_bytes.argtypes = [i]
+        lib.ssp_world_insert_workspace_bytes.restype = C.c_size_t
+        lib.ssp_match_world_workspace_bytes.argtypes = [i, i]
+        lib.ssp_match_world_workspace_bytes.restype = C.c_size_t
+        lib.ssp_op_world_insert.argtypes = [vp, vp, i, vp, vp, i, vp, i, i, i, i, i] + [vp] * 11
+        lib.ssp_match_world.argtypes = [vp, vp, i, vp, vp, i, C.c_float, vp, vp, vp, vp]
+        lib.ssp_op_world_correspondences.argtypes = [vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, vp]
+        lib.ssp_world_repair.argtypes = [vp, vp, vp, vp, vp, i, i, vp, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -2453,6 +2467,192 @@ def op_ba_apply(adjusted, state, table, max_length, n_frames=None):
     with torch.cuda.device(state.device):
         _check(lib.ssp_ba_apply(_ptr(info), _ptr(cams), L, S, -1 if n_frames is None else int(n_frames), _ptr(state), _ptr(table),
                                 int(table.shape[-2]), _stream()))
+    return state, table
+
+
+# ---- world map ----
+WORLD_MAX_ROWS = 65536  # SSP_WORLD_MAX_ROWS (include/ssp_hip.h)
+WORLD_STATE_WORDS = 8  # SSP_WORLD_STATE_WORDS: n_rows, anchored, lost_frames, streak, dropped (full), dropped (tid), appended, updated
+POSE_FLAG_WORLD = 16  # SSP_POSE_FLAG_WORLD: the trajectory row was rewritten from a pose against the world map
+WORLD_KEYS = ("X", "desc", "tid", "n_views", "first_frame", "last_frame", "rms", "slot_of_tid", "state")
+
+
+def world_buffers(map_cap=WORLD_MAX_ROWS, tid_cap=1 << 22, device="cuda"):
+    """An empty world map of one sequence, zeroed: {"X": float64 [map_cap, 3], "desc": float32 [map_cap, 256],
+    "tid" / "n_views" / "first_frame" / "last_frame": int32 [map_cap], "rms": float64 [map_cap], "slot_of_tid": int32 [tid_cap],
+    "state": int32 [WORLD_STATE_WORDS] = (n_rows, anchored, lost_frames, streak, rows dropped because the map was full, rows dropped
+    because tid >= tid_cap, rows appended by the last insert, rows updated by it)} plus the host-known sizes "map_cap", "tid_cap"
+    and the scratch "ws" of op_world_insert and op_match_world.  Track t is in the map iff s = slot_of_tid[t] has 0 <= s < n_rows
+    and tid[s] == t, so zeroed memory is an empty map and state[0] = 0 clears one."""
+    lib = load_library()
+    map_cap, tid_cap = int(map_cap), int(tid_cap)
+    if not 1 <= map_cap <= WORLD_MAX_ROWS:
+        raise ValueError("1 <= map_cap <= %d required (got %d)" % (WORLD_MAX_ROWS, map_cap))
+    if not 1 <= tid_cap < 2 ** 31:
+        raise ValueError("1 <= tid_cap < 2^31 required (got %d)" % tid_cap)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("world_buffers needs a HIP device: the MI355X path has no CPU fallback")
+    wsb = max(lib.ssp_match_world_workspace_bytes(map_cap, MATCH_MAX_POINTS),
+              lib.ssp_world_insert_workspace_bytes(TRACK_MAX_LENGTH * MATCH_MAX_POINTS))
+    if wsb == 0:
+        _check(-1)
+    f64, i32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int32, device=device)
+    return {"X": torch.zeros(map_cap, 3, **f64), "desc": torch.zeros(map_cap, 256, dtype=torch.float32, device=device),
+            "tid": torch.zeros(map_cap, **i32), "n_views": torch.zeros(map_cap, **i32), "first_frame": torch.zeros(map_cap, **i32),
+            "last_frame": torch.zeros(map_cap, **i32), "rms": torch.zeros(map_cap, **f64), "slot_of_tid": torch.zeros(tid_cap, **i32),
+            "state": torch.zeros(WORLD_STATE_WORDS, **i32), "ws": torch.zeros(wsb, dtype=torch.uint8, device=device),
+            "map_cap": map_cap, "tid_cap": tid_cap}
+
+
+def _world_map(world):
+    """checks a world_buffers dict; -> (map_cap, tid_cap)"""
+    if not isinstance(world, dict) or any(k not in world for k in WORLD_KEYS + ("ws", "map_cap", "tid_cap")):
+        raise ValueError("world must be the dict of world_buffers")
+    map_cap, tid_cap = int(world["map_cap"]), int(world["tid_cap"])
+    shapes = {"X": (map_cap, 3), "desc": (map_cap, 256), "tid": (map_cap,), "n_views": (map_cap,), "first_frame": (map_cap,),
+              "last_frame": (map_cap,), "rms": (map_cap,), "slot_of_tid": (tid_cap,), "state": (WORLD_STATE_WORDS,)}
+    for k in WORLD_KEYS:
+        _need_gpu(world[k], "world[%r]" % k)
+        want = torch.float64 if k in ("X", "rms") else (torch.float32 if k == "desc" else torch.int32)
+        if world[k].dtype != want or tuple(world[k].shape) != shapes[k]:
+            raise ValueError("world[%r] must be contiguous %s %s (world_buffers)" % (k, want, list(shapes[k])))
+    _need_gpu(world["ws"], "world['ws']")
+    if not 1 <= map_cap <= WORLD_MAX_ROWS or tid_cap < 1:
+        raise ValueError("1 <= map_cap <= %d and tid_cap >= 1 required" % WORLD_MAX_ROWS)
+    return map_cap, tid_cap
+
+
+def op_world_insert(world, landmarks, n_landmarks, desc_new, count_new, table, n_frames, patience=30):
+    """One frame's landmarks into the world map (ssp_op_world_insert), in place.  world: the dict of
+    world_buffers; landmarks float64 [row_cap, LANDMARK_WORDS] and n_landmarks int32 [1] of op_landmarks_select for the window
+    ending at the newest frame; desc_new float32 [point_cap, 256] and count_new int32 [1] of that frame; table float64 [capacity,
+    POSE_ROW_WORDS] of op_pose_chain; n_frames: the frames seen so far (the newest row is n_frames - 1).  Call it after every
+    rewrite of that row.  Anchor rule from the row's flag word F: ok = (F & 3) == 0; anchored' = ok and (n_rows == 0 or anchored or
+    streak >= 2); while the map has rows and is not anchored lost_frames counts up and past `patience` the map is cleared.  Rows are
+    inserted only when anchored': a row whose newest-frame index p has 0 <= p < count, whose track id lies in [0, tid_cap) and
+    whose X is finite replaces X, n_views, rms, last_frame and the descriptor of its track's row, or is appended in landmark order
+    while there is room (dropped and counted past map_cap).  Track ids must be unique within a call.  Returns world.  No host
+    synchronisation."""
+    lib = load_library()
+    map_cap, tid_cap = _world_map(world)
+    for t, nm in ((landmarks, "landmarks"), (n_landmarks, "n_landmarks"), (desc_new, "desc_new"), (count_new, "count_new"), (table, "table")):
+        _need_gpu(t, nm)
+    if landmarks.dtype != torch.float64 or landmarks.dim() != 2 or landmarks.shape[1] != LANDMARK_WORDS:
+        raise ValueError("landmarks must be contiguous float64 [row_cap, %d] (op_landmarks_select)" % LANDMARK_WORDS)
+    if desc_new.dtype != torch.float32 or desc_new.dim() != 2 or desc_new.shape[1] != 256:
+        raise ValueError("desc_new must be contiguous float32 [point_cap, 256]")
+    for t, nm in ((n_landmarks, "n_landmarks"), (count_new, "count_new")):
+        if t.dtype != torch.int32 or t.numel() != 1:
+            raise ValueError("%s must be int32 [1]" % nm)
+    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != POSE_ROW_WORDS:
+        raise ValueError("table must be contiguous float64 [capacity, %d] (pose_table of one sequence)" % POSE_ROW_WORDS)
+    row_cap, point_cap = landmarks.shape[0], desc_new.shape[0]
+    if not (1 <= row_cap <= TRACK_MAX_LENGTH * MATCH_MAX_POINTS and 1 <= point_cap <= MATCH_MAX_POINTS):
+        raise ValueError("1 <= row_cap <= %d and 1 <= point_cap <= %d required" % (TRACK_MAX_LENGTH * MATCH_MAX_POINTS, MATCH_MAX_POINTS))
+    if int(n_frames) < 0 or int(patience) < 0:
+        raise ValueError("n_frames and patience must be non-negative")
+    if world["ws"].numel() < lib.ssp_world_insert_workspace_bytes(row_cap):
+        raise ValueError("world['ws'] is smaller than ssp_world_insert_workspace_bytes(%d)" % row_cap)
+    with torch.cuda.device(landmarks.device):
+        _check(lib.ssp_op_world_insert(_ptr(landmarks), _ptr(n_landmarks), row_cap, _ptr(desc_new), _ptr(count_new), point_cap,
+                                       _ptr(table), int(table.shape[0]), int(n_frames), int(patience), map_cap, tid_cap,
+                                       _ptr(world["X"]), _ptr(world["desc"]), _ptr(world["tid"]), _ptr(world["n_views"]),
+                                       _ptr(world["first_frame"]), _ptr(world["last_frame"]), _ptr(world["rms"]),
+                                       _ptr(world["slot_of_tid"]), _ptr(world["state"]), _ptr(world["ws"]), _stream()))
+    return world
+
+
+def op_match_world(world, desc2, count2, nn_thresh, out=None):
+    """A frame's descriptors against the whole world map (ssp_match_world): op_match_two_way's rules with
+    side 1 = the map's n_rows rows (world["state"][0] on the device) and side 2 = the count2 (int32 [1]) rows of desc2 (float32
+    [cap, 256] unit rows, cap <= MATCH_MAX_POINTS).  Bit-identical to op_match_two_way wherever both apply.  Returns (match float32
+    [cap, 3] rows (map row, frame row, distance) in ascending map row, n_match int32 [1]); `out`: such a pair to fill.  The map's
+    "ws" is the scratch: no allocation with `out`, no host synchronisation."""
+    lib = load_library()
+    map_cap, _ = _world_map(world)
+    if nn_thresh < 0.0:
+        raise ValueError("'nn_thresh' should be non-negative")
+    _need_gpu(desc2, "desc2")
+    _need_gpu(count2, "count2")
+    if desc2.dtype != torch.float32 or desc2.dim() != 2 or desc2.shape[1] != 256:
+        raise ValueError("desc2 must be contiguous float32 [cap, 256]")
+    cap = desc2.shape[0]
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d frame rows (got %d)" % (MATCH_MAX_POINTS, cap))
+    if count2.dtype != torch.int32 or count2.numel() != 1:
+        raise ValueError("count2 must be int32 [1]")
+    if world["ws"].numel() < lib.ssp_match_world_workspace_bytes(map_cap, cap):
+        raise ValueError("world['ws'] is smaller than ssp_match_world_workspace_bytes(%d, %d)" % (map_cap, cap))
+    if out is None:
+        out = (torch.empty(cap, 3, dtype=torch.float32, device=desc2.device), torch.empty(1, dtype=torch.int32, device=desc2.device))
+    match, n_match = out
+    _need_gpu(match, "out[0]")
+    _need_gpu(n_match, "out[1]")
+    if match.dtype != torch.float32 or tuple(match.shape) != (cap, 3) or n_match.dtype != torch.int32 or n_match.numel() != 1:
+        raise ValueError("out must be (float32 [%d, 3], int32 [1])" % cap)
+    with torch.cuda.device(desc2.device):
+        _check(lib.ssp_match_world(_ptr(world["desc"]), _ptr(world["state"]), map_cap, _ptr(desc2), _ptr(count2), cap,
+                                   float(np.float32(nn_thresh)), _ptr(world["ws"]), _ptr(match), _ptr(n_match), _stream()))
+    return match, n_match
+
+
+def op_world_correspondences(world, match, n_match, pts_new, count_new, out=None):
+    """The 3-D to 2-D correspondences of a frame against the world map (ssp_op_world_correspondences): the
+    rows of op_match_world (match float32 [cap, 3], n_match int32 [1]) joined with the map's X and the frame's points pts_new
+    float64 [point_cap, >= 2] (count_new int32 [1] of them).  Returns (corr float64 [cap, CORR_WORDS] rows (X, Y, Z, px, py, map
+    row, valid, 0), n int32 [2] = (rows, valid rows)), the input of op_pnp_ransac; `out`: a pnp_buffers dict of one problem.  A row
+    is valid iff it lies below n_match, its map row is below n_rows, its frame point below count_new and the five values are
+    finite; every other row is zero.  No host synchronisation."""
+    lib = load_library()
+    map_cap, _ = _world_map(world)
+    for t, nm in ((match, "match"), (n_match, "n_match"), (pts_new, "pts_new"), (count_new, "count_new")):
+        _need_gpu(t, nm)
+    if match.dtype != torch.float32 or match.dim() != 2 or match.shape[1] != 3:
+        raise ValueError("match must be contiguous float32 [cap, 3]")
+    if pts_new.dtype != torch.float64 or pts_new.dim() != 2 or pts_new.shape[1] < 2:
+        raise ValueError("pts_new must be contiguous float64 [point_cap, >= 2]")
+    for t, nm in ((n_match, "n_match"), (count_new, "count_new")):
+        if t.dtype != torch.int32 or t.numel() != 1:
+            raise ValueError("%s must be int32 [1]" % nm)
+    cap, point_cap = match.shape[0], pts_new.shape[0]
+    if not (1 <= cap <= MATCH_MAX_POINTS and 1 <= point_cap <= MATCH_MAX_POINTS):
+        raise ValueError("1 <= cap, point_cap <= %d required" % MATCH_MAX_POINTS)
+    out = _pnp_out(out, ("corr", "n"), 1, cap, match.device)
+    with torch.cuda.device(match.device):
+        _check(lib.ssp_op_world_correspondences(_ptr(world["X"]), _ptr(world["state"]), map_cap, _ptr(match), _ptr(n_match), cap,
+                                                _ptr(pts_new), int(pts_new.shape[1]), _ptr(count_new), point_cap, _ptr(out["corr"]),
+                                                _ptr(out["n"]), _stream()))
+    return out["corr"][0], out["n"][0]
+
+
+def op_world_repair(world, absolute, state, table):
+    """op_pose_repair's rule with the world map's firing condition (ssp_world_repair), one sequence.
+    absolute: the dict of op_pnp_ransac for the frame's correspondences against the map; state float64 [POSE_STATE_WORDS] and table
+    float64 [capacity, POSE_ROW_WORDS] of op_pose_chain, updated in place.  Row n - 1 (1 <= n < capacity rows) is rewritten when
+    the pose has status 0 and is finite and either the row carries POSE_FLAG_NO_POSE or POSE_FLAG_SCALE_CARRIED or the map is lost
+    (it has rows and is not anchored).  The row gets POSE_FLAG_ABSOLUTE | POSE_FLAG_WORLD; the map's streak of consecutive
+    rewritten frames grows by one, and a call that writes nothing zeroes it.  Returns (state, table).  No host synchronisation."""
+    lib = load_library()
+    map_cap, _ = _world_map(world)
+    for k in ("Rw", "C", "status"):
+        if k not in absolute:
+            raise ValueError("absolute must be the dict of op_pnp_ransac (no %r)" % k)
+        _need_gpu(absolute[k], "absolute[%r]" % k)
+    _need_gpu(state, "state")
+    _need_gpu(table, "table")
+    if absolute["status"].dtype != torch.int32 or absolute["status"].numel() != 1:
+        raise ValueError("absolute['status'] must be int32 [1]: one sequence")
+    for k, m in (("Rw", 9), ("C", 3)):
+        if absolute[k].dtype != torch.float64 or absolute[k].numel() != m:
+            raise ValueError("absolute[%r] must be the contiguous float64 tensor of op_pnp_ransac for one problem" % k)
+    if state.dtype != torch.float64 or state.numel() != POSE_STATE_WORDS:
+        raise ValueError("state must be contiguous float64 [%d] (pose_state of one sequence)" % POSE_STATE_WORDS)
+    if table.dtype != torch.float64 or table.shape[-1] != POSE_ROW_WORDS or table.numel() != table.shape[-2] * POSE_ROW_WORDS:
+        raise ValueError("table must be contiguous float64 [capacity, %d] (pose_table of one sequence)" % POSE_ROW_WORDS)
+    with torch.cuda.device(state.device):
+        _check(lib.ssp_world_repair(_ptr(absolute["Rw"]), _ptr(absolute["C"]), _ptr(absolute["status"]), _ptr(state), _ptr(table),
+                                    int(table.shape[-2]), map_cap, _ptr(world["state"]), _stream()))
     return state, table
 
 
