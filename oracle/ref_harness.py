@@ -156,3 +156,54 @@ def make_trainer(config, state_dict=None):
         agent.net.load_state_dict({k: torch.as_tensor(v) for k, v in state_dict.items()})
     agent.dataParallel()
     return agent
+
+
+# --------------------------------------------------------------------------------------------------------------
+# datasets/synthetic_dataset.py with a RECORDING cv2: the draw logic of the reference itself, without its rasteriser
+# --------------------------------------------------------------------------------------------------------------
+class Cv2Recorder:
+    """What cv2.line / fillPoly / ellipse / circle were asked to draw, in call order, as plain Python values.  The image is
+    left alone, so every np.mean(img) of the reference keeps the value the caller put there."""
+
+    def __init__(self):
+        self.calls = []
+
+    @staticmethod
+    def _pt(p):
+        return (int(p[0]), int(p[1]))
+
+    def line(self, img, p1, p2, col, thickness=1, *a, **k):
+        self.calls.append(("line", self._pt(p1), self._pt(p2), int(col), int(thickness)))
+
+    def fillPoly(self, img, polys, col, *a, **k):
+        import numpy as np
+        for poly in polys:
+            self.calls.append(("fillPoly", [self._pt(q) for q in np.asarray(poly).reshape(-1, 2)], int(col)))
+
+    def fillConvexPoly(self, img, poly, col, *a, **k):
+        self.fillPoly(img, [poly], col)
+
+    def ellipse(self, img, center, axes, angle, start, end, col, thickness=1, *a, **k):
+        assert (start, end, thickness) == (0, 360, -1)
+        self.calls.append(("ellipse", self._pt(center), self._pt(axes), float(angle), int(col)))
+
+    def circle(self, img, center, radius, col, thickness=1, *a, **k):
+        self.calls.append(("circle", self._pt(center), int(radius), int(col)))
+
+
+def synthetic_dataset_recording():
+    """(the reference's datasets/synthetic_dataset module, imported in place, its Cv2Recorder).  The module draws its numbers
+    from whatever `set_random_state` is given: any object with `randint` and `rand`."""
+    install()
+    import importlib.util
+    cv = sys.modules["cv2"]
+    rec = Cv2Recorder()
+    for name in ("line", "fillPoly", "fillConvexPoly", "ellipse", "circle"):
+        setattr(cv, name, getattr(rec, name))
+    name = "_ssp_ref_synthetic_dataset"
+    if name not in sys.modules:
+        spec = importlib.util.spec_from_file_location(name, os.path.join(REF_ROOT, "datasets", "synthetic_dataset.py"))
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[name] = mod
+        spec.loader.exec_module(mod)
+    return sys.modules[name], rec

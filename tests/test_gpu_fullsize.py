@@ -387,7 +387,7 @@ def test_graph_replay_equals_eager():
             eb.adam_step(0.001)
         torch.cuda.current_stream().wait_stream(st)
         torch.cuda.synchronize()
-        seen_idx.append(eb._graph_idx[2].cpu().clone())
+        seen_idx.append([b.cpu().clone() for b in eb._graph_idx])
         assert bool(torch.isfinite(ea.grads).all()), it
         bad = [(k, float(v.abs().max())) for k, v in eb.grad_dict().items() if not bool(torch.isfinite(v).all()) or float(v.abs().max()) > 1e3]
         assert not bad, (it, bad[:10], len(bad))
@@ -397,7 +397,19 @@ def test_graph_replay_equals_eager():
         l2, _ = _rel(ea.bn_running, eb.bn_running)
         assert l2 < 1e-6, (it, l2)
     # the sampler seed lives in device memory: replays with another seed draw other indices, the same seed the same
-    assert not torch.equal(seen_idx[0], seen_idx[1]) and torch.equal(seen_idx[1], seen_idx[3])
+    assert not torch.equal(seen_idx[0][2], seen_idx[1][2]) and torch.equal(seen_idx[1][2], seen_idx[3][2])
+    # ... and they are THE indices of that seed: the captured sampler reads seed_arg + *seed_dev, so every replay must leave the
+    # index buffers of the restatement (tests/draws_ref.py) for its own seed, position by position
+    from tests import draws_ref as D
+    hn = ds["homographies"].cpu().numpy()
+    for (ma, mb, nm), seed in zip(seen_idx, (11, 12, 99, 12)):
+        left = [int((~D.analytic_targets(hn[b], H // 8, W // 8)[2]).sum()) for b in range(B)]
+        ref = D.sampler_nonmatches(seed, B * ea.n_match * ea.n_non, H // 8, W // 8).reshape(B, -1)
+        print("graph replay seed %d: %d match pairs and %d non-matches compared, %d cells left out for the margin, non-matches bit-equal %s"
+              % (seed, ma.numel(), nm.numel(), sum(left), torch.equal(nm, torch.from_numpy(ref))))
+        assert torch.equal(nm, torch.from_numpy(ref)), seed
+        for b in range(B):
+            D.check_analytic_matches(ma[b].numpy(), mb[b].numpy(), hn[b], seed, b, H // 8, W // 8, ea.n_match)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """GPU: photometric augmentation on the device (csrc/photo_kernels.hip.h).  The arithmetic of
 `ssp_op_photometric_apply` is tested exactly against the numpy restatement tests/photometric_ref.py on hand-made rows of
-draws; the per-pixel noise and `ssp_op_photometric_draw` are tested through their statistics (the device RNG stream differs
-from numpy's by construction); pairs.make_pairs is tested for its three new arguments."""
+draws; the per-pixel noise and `ssp_op_photometric_draw` are tested here through their statistics (the device RNG stream differs
+from numpy's by construction) and value by value in tests/test_gpu_draws_exact.py; pairs.make_pairs is tested for its three new
+arguments."""
 import json
 import os
 
