@@ -806,6 +806,56 @@ int ssp_op_world_correspondences(const double* x_dev, const int32_t* state_dev, 
 int ssp_world_repair(const double* rw_dev, const double* c_dev, const int32_t* status_dev, double* state_dev, double* table_dev,
                      int capacity, int map_cap, int32_t* world_state_dev, void* stream);
 
+/* ---- loop closure --------------------------------------------------------------------------------
+ * A frame's map matches against the OLD rows of the world map, the loop edge measured from the pose found against them, a Sim(3)
+ * pose graph over the trajectory rows since the old place was last seen, and the write-back.  The rules are restated in numpy by
+ * tests/loop_ref.py.  fp64 without contraction, no floating-point atomics, every sum in one fixed order.  No call synchronises with
+ * the host or allocates.  One sequence per call.
+ * ssp_op_loop_correspondences: ssp_op_world_correspondences restricted to match rows whose map row has last_frame <= f - min_gap,
+ *   plus xnew_dev [cap][4] = (X of the lowest landmark row whose eighth word is the row's frame point, 1) or zero, and n_dev [3] =
+ *   (rows, valid old rows, valid old rows with a landmark).  landmarks_dev [row_cap][SSP_LANDMARK_WORDS] / n_landmarks_dev [1] of
+ *   ssp_op_landmarks_select for the window ending at frame f.
+ * ssp_loop_edge: one candidate edge from the pose of ssp_pnp_ransac on those rows (rw_dev [9], c_dev [3], mask_dev [cap],
+ *   status_dev [1]).  Anchor a = the largest last_frame over the inlier rows; sigma = (sum of the inliers' depths under the loop
+ *   pose) / (sum of the depths of their window landmarks under row f), ssp_pose_chain's statistic, accepted when at least 8 inliers
+ *   have a landmark and it is finite and positive.  Refused (state word 2) unless status 0 and finite, inliers >= min_inliers, the
+ *   scale rule, 0 <= a < f, f - (frame of the last accepted edge) >= cooldown; dropped (word 3) when the table is full.  An accepted
+ *   edge (a, f, R [9] = Rw_L Rw_a^T, t [3] = Rw_a (C_L - C_a), log sigma, weight) is appended to edges_dev
+ *   [SSP_LOOP_MAX_EDGES][SSP_LOOP_EDGE_WORDS].  state_dev int32 [SSP_LOOP_STATE_WORDS] = (edges, frame of the last accepted edge,
+ *   refused, dropped, accepted by this call, its anchor, its inliers, map rows ssp_loop_apply left alone because the result was not
+ *   finite); cand_dev fp64 [SSP_LOOP_CAND_WORDS] = (f, a, inliers, shared depths, sigma, angle of R_c, |t_c|, accepted, reason).
+ * ssp_pose_graph: Levenberg-Marquardt (`iterations` steps, lambda from 1e-4, /10 on an accepted step, x10 otherwise) over the rows
+ *   a + 1 .. f with row a and every earlier row fixed; runs only when the last ssp_loop_edge accepted.  rw_out_dev [capacity][9],
+ *   c_out_dev [capacity][3], sigma_out_dev [capacity]: copies of the table (sigma 1) with the free rows replaced under status 0.
+ *   info_dev fp64 [SSP_LOOP_INFO_WORDS] = (status, cost before, cost after, nodes, edges used, accepted steps, both-ends-free edges
+ *   left out, lambda); status 1: nothing to do, 2: no step accepted.  workspace_dev: ssp_pose_graph_workspace_bytes(capacity).
+ * ssp_loop_apply: under status 0, rows a + 1 .. f take the corrected Rw and C, s = |C_k - C_(k-1)| when finite and above 1/64 of
+ *   the row's s, and SSP_POSE_FLAG_LOOP; the chain state follows row f when that is its newest frame and the table is not full; a map
+ *   row with last_frame = k in (a, f] becomes C'_k + sigma_k R'_k^T R_k (X - C_k). */
+#define SSP_LOOP_MAX_EDGES 256
+#define SSP_LOOP_EDGE_WORDS 16
+#define SSP_LOOP_STATE_WORDS 8
+#define SSP_LOOP_CAND_WORDS 16
+#define SSP_LOOP_MAX_INNER 8
+#define SSP_LOOP_INFO_WORDS 8
+#define SSP_LOOP_MAX_ITERATIONS 64
+#define SSP_POSE_FLAG_LOOP 32
+size_t ssp_pose_graph_workspace_bytes(int capacity);
+int ssp_op_loop_correspondences(const double* x_dev, const int32_t* last_dev, const int32_t* state_dev, int map_cap,
+                                const float* match_dev, const int32_t* n_match_dev, int cap, const double* pts_new_dev, int pt_stride,
+                                const int32_t* count_new_dev, int point_cap, const double* landmarks_dev,
+                                const int32_t* n_landmarks_dev, int row_cap, int f, int min_gap, double* corr_dev, double* xnew_dev,
+                                int32_t* n_dev, void* stream);
+int ssp_loop_edge(const double* rw_dev, const double* c_dev, const uint8_t* mask_dev, const int32_t* status_dev,
+                  const double* corr_dev, const double* xnew_dev, const int32_t* n_dev, int cap, const int32_t* last_dev, int map_cap,
+                  const double* table_dev, int capacity, int f, int min_inliers, int cooldown, double weight, double* edges_dev,
+                  int32_t* state_dev, double* cand_dev, void* stream);
+int ssp_pose_graph(const double* table_dev, int capacity, const double* edges_dev, const int32_t* state_dev, int f, int iterations,
+                   void* workspace_dev, double* rw_out_dev, double* c_out_dev, double* sigma_out_dev, double* info_dev, void* stream);
+int ssp_loop_apply(const double* info_dev, const double* rw_new_dev, const double* c_new_dev, const double* sigma_dev,
+                   int32_t* loop_state_dev, int f, double* state_dev, double* table_dev, int capacity, double* x_dev,
+                   const int32_t* last_dev, const int32_t* world_state_dev, int map_cap, void* stream);
+
 /* ---- streamed descriptor metrics----------------------------------------------------------
  * The per-pair metrics of evaluation.py -r -homo for a set that is fed batch by batch and never leaves the device, on
  * top of ssp_eval_repeatability, ssp_match_two_way and ssp_eval_ransac.  fp64 without contraction.  No call

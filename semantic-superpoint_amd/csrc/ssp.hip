@@ -40,6 +40,7 @@
 #include "pnp_kernels.hip.h"
 #include "ba_kernels.hip.h"
 #include "world_kernels.hip.h"
+#include "loop_kernels.hip.h"
 #include "detector_eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
 #include "sem_eval_kernels.hip.h"
@@ -4223,6 +4224,89 @@ int ssp_world_repair(const double* rw_dev, const double* c_dev, const int32_t* s
     return fail(-1, "world_repair: null pointer");
   hipLaunchKernelGGL(world_repair_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rw_dev, c_dev, status_dev, state_dev, table_dev,
                      capacity, map_cap, world_state_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- loop closure: the join against old rows, the loop edge, the pose graph, the write-back ----
+static_assert(LOOP_MAX_EDGES == SSP_LOOP_MAX_EDGES && LOOP_EDGE_WORDS == SSP_LOOP_EDGE_WORDS && LOOP_STATE_WORDS == SSP_LOOP_STATE_WORDS &&
+              LOOP_CAND_WORDS == SSP_LOOP_CAND_WORDS && LOOP_MAX_INNER == SSP_LOOP_MAX_INNER && LOOP_INFO_WORDS == SSP_LOOP_INFO_WORDS &&
+              LOOP_FLAG_LOOP == SSP_POSE_FLAG_LOOP && LOOP_MAX_ITERATIONS == SSP_LOOP_MAX_ITERATIONS && EVAL_THREADS == 256,
+              "include/ssp_hip.h and loop_kernels.hip.h disagree");
+size_t ssp_pose_graph_workspace_bytes(int capacity) {
+  if (capacity < 2 || capacity > (1 << 20)) {
+    fail(-1, "pose_graph_workspace_bytes: 2 <= capacity <= %d required (got %d)", 1 << 20, capacity);
+    return 0;
+  }
+  return align_up(loop_ws_words(capacity) * sizeof(double), 256);
+}
+
+int ssp_op_loop_correspondences(const double* x_dev, const int32_t* last_dev, const int32_t* state_dev, int map_cap,
+                                const float* match_dev, const int32_t* n_match_dev, int cap, const double* pts_new_dev, int pt_stride,
+                                const int32_t* count_new_dev, int point_cap, const double* landmarks_dev,
+                                const int32_t* n_landmarks_dev, int row_cap, int f, int min_gap, double* corr_dev, double* xnew_dev,
+                                int32_t* n_dev, void* stream) {
+  CHK(world_check("loop_correspondences", map_cap, cap));
+  if (point_cap < 1 || point_cap > SSP_MATCH_MAX_POINTS || pt_stride < 2 || row_cap < 1 || row_cap > SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS)
+    return fail(-1, "loop_correspondences: 1 <= point_cap <= %d, pt_stride >= 2 and 1 <= row_cap <= %d required (point_cap %d, pt_stride "
+                "%d, row_cap %d)", SSP_MATCH_MAX_POINTS, SSP_TRACK_MAX_LENGTH * SSP_MATCH_MAX_POINTS, point_cap, pt_stride, row_cap);
+  if (f < 0 || min_gap < 1) return fail(-1, "loop_correspondences: f >= 0 and min_gap >= 1 required (f %d, min_gap %d)", f, min_gap);
+  if (!x_dev || !last_dev || !state_dev || !match_dev || !n_match_dev || !pts_new_dev || !count_new_dev || !landmarks_dev ||
+      !n_landmarks_dev || !corr_dev || !xnew_dev || !n_dev)
+    return fail(-1, "loop_correspondences: null pointer");
+  hipLaunchKernelGGL(loop_corr_kernel, dim3(1), dim3(256), (size_t)point_cap * sizeof(int), (hipStream_t)stream, x_dev, last_dev, state_dev,
+                     map_cap, match_dev, n_match_dev, cap, pts_new_dev, pt_stride, count_new_dev, point_cap, landmarks_dev,
+                     n_landmarks_dev, row_cap, f, min_gap, corr_dev, xnew_dev, n_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_loop_edge(const double* rw_dev, const double* c_dev, const uint8_t* mask_dev, const int32_t* status_dev,
+                  const double* corr_dev, const double* xnew_dev, const int32_t* n_dev, int cap, const int32_t* last_dev, int map_cap,
+                  const double* table_dev, int capacity, int f, int min_inliers, int cooldown, double weight, double* edges_dev,
+                  int32_t* state_dev, double* cand_dev, void* stream) {
+  CHK(world_check("loop_edge", map_cap, cap));
+  if (capacity < 1 || f < 0 || min_inliers < 4 || cooldown < 0)
+    return fail(-1, "loop_edge: capacity >= 1, f >= 0, min_inliers >= 4 and cooldown >= 0 required (capacity %d, f %d, min_inliers %d, "
+                "cooldown %d)", capacity, f, min_inliers, cooldown);
+  if (!(weight > 0.0) || !std::isfinite(weight)) return fail(-1, "loop_edge: a finite weight > 0 is required");
+  if (!rw_dev || !c_dev || !mask_dev || !status_dev || !corr_dev || !xnew_dev || !n_dev || !last_dev || !table_dev || !edges_dev ||
+      !state_dev || !cand_dev)
+    return fail(-1, "loop_edge: null pointer");
+  hipLaunchKernelGGL(loop_edge_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rw_dev, c_dev, mask_dev, status_dev, corr_dev, xnew_dev,
+                     n_dev, cap, last_dev, map_cap, table_dev, capacity, f, min_inliers, cooldown, weight, edges_dev, state_dev, cand_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_pose_graph(const double* table_dev, int capacity, const double* edges_dev, const int32_t* state_dev, int f, int iterations,
+                   void* workspace_dev, double* rw_out_dev, double* c_out_dev, double* sigma_out_dev, double* info_dev, void* stream) {
+  if (capacity < 2 || capacity > (1 << 20) || f < 0)
+    return fail(-1, "pose_graph: 2 <= capacity <= %d and f >= 0 required (capacity %d, f %d)", 1 << 20, capacity, f);
+  if (iterations < 1 || iterations > SSP_LOOP_MAX_ITERATIONS)
+    return fail(-1, "pose_graph: 1 <= iterations <= %d required (got %d)", SSP_LOOP_MAX_ITERATIONS, iterations);
+  if (!table_dev || !edges_dev || !state_dev || !workspace_dev || !rw_out_dev || !c_out_dev || !sigma_out_dev || !info_dev)
+    return fail(-1, "pose_graph: null pointer");
+  hipLaunchKernelGGL(loop_graph_kernel, dim3(1), dim3(LOOP_THREADS), 0, (hipStream_t)stream, table_dev, capacity, edges_dev, state_dev, f,
+                     iterations, reinterpret_cast<double*>(workspace_dev), rw_out_dev, c_out_dev, sigma_out_dev, info_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_loop_apply(const double* info_dev, const double* rw_new_dev, const double* c_new_dev, const double* sigma_dev,
+                   int32_t* loop_state_dev, int f, double* state_dev, double* table_dev, int capacity, double* x_dev,
+                   const int32_t* last_dev, const int32_t* world_state_dev, int map_cap, void* stream) {
+  if (capacity < 2 || f < 0 || map_cap < 1 || map_cap > SSP_WORLD_MAX_ROWS)
+    return fail(-1, "loop_apply: capacity >= 2, f >= 0 and 1 <= map_cap <= %d required (capacity %d, f %d, map_cap %d)", SSP_WORLD_MAX_ROWS,
+                capacity, f, map_cap);
+  if (!info_dev || !rw_new_dev || !c_new_dev || !sigma_dev || !loop_state_dev || !state_dev || !table_dev || !x_dev || !last_dev ||
+      !world_state_dev)
+    return fail(-1, "loop_apply: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(loop_apply_map_kernel, dim3(cdiv(map_cap, 256)), dim3(256), 0, st, info_dev, rw_new_dev, c_new_dev, sigma_dev,
+                     loop_state_dev, f, (const double*)table_dev, capacity, x_dev, last_dev, world_state_dev, map_cap);
+  hipLaunchKernelGGL(loop_apply_rows_kernel, dim3(cdiv(capacity, 256)), dim3(256), 0, st, info_dev, rw_new_dev, c_new_dev,
+                     (const int32_t*)loop_state_dev, f, state_dev, table_dev, capacity);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -275,12 +275,22 @@ class PointTracker(object):
     with its points (lib.op_world_correspondences) and given to the P3P RANSAC (world_thresh pixels, world_min_inliers, the frame's
     check seed): last_geometry() gains the "world_*" keys and world_trajectory() one row.  "relocalise" also rewrites the frame's
     trajectory row and the chain state from that pose (lib.op_world_repair) when the two-view chain could not determine them or
-    the map has lost its anchor, so a frame without points no longer restarts the map.  All of it is queued on the device."""
+    the map has lost its anchor, so a frame without points no longer restarts the map.  All of it is queued on the device.
+    loop_closure (needs world_map): None runs none of it.  "observe": after the window's landmarks are
+    selected and before they enter the map, the frame's map matches whose map row was last seen loop_min_gap frames ago or earlier
+    are joined with the frame's points and window landmarks (lib.op_loop_correspondences) and given to the P3P RANSAC (world_thresh,
+    loop_min_inliers, the frame's check seed); lib.op_loop_edge measures the similarity between the chained frame and the old map
+    and appends an edge when its rule holds (at most one per loop_cooldown frames); lib.op_pose_graph distributes it over the rows
+    since the old place was last seen (loop_iterations Levenberg-Marquardt steps, loop edges weighted loop_weight).  Nothing is
+    written into the trajectory or the map.  "apply" also writes the corrected rows, the chain state and the map rows of that span
+    (lib.op_loop_apply; POSE_FLAG_LOOP) and selects the window's landmarks once more before the insert.  last_geometry() gains the
+    "loop_*" keys; loop_closures() and loop_edges_device() read the accepted edges."""
 
     def __init__(self, max_length, nn_thresh, device=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
                  absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1,
-                 world_map=None, world_cap=65536, world_patience=30, world_thresh=2.0, world_min_inliers=6):
+                 world_map=None, world_cap=65536, world_patience=30, world_thresh=2.0, world_min_inliers=6,
+                 loop_closure=None, loop_min_gap=32, loop_min_inliers=12, loop_cooldown=32, loop_iterations=10, loop_weight=1.0):
         if geometric_check not in (None, "fundamental", "homography"):
             raise ValueError("geometric_check must be None, 'fundamental' or 'homography' (got %r)" % (geometric_check,))
         if world_map not in (None, "observe", "relocalise"):
@@ -299,6 +309,19 @@ class PointTracker(object):
                 raise ValueError("1 <= world_cap <= %d and world_patience >= 0 required" % L.WORLD_MAX_ROWS)
             if len(landmark_params) != 3 or int(landmark_params[0]) < 2:
                 raise ValueError("landmark_params must be (min_views >= 2, min_parallax_deg, max_reproj)")
+        if loop_closure not in (None, "observe", "apply"):
+            raise ValueError("loop_closure must be None, 'observe' or 'apply' (got %r)" % (loop_closure,))
+        if loop_closure is not None:
+            if world_map is None:
+                raise ValueError("loop_closure needs world_map: the closure is detected from the frame's matches against the map")
+            if int(loop_min_gap) < 1 or int(loop_min_inliers) < 4 or int(loop_cooldown) < 0:
+                raise ValueError("loop_min_gap must be at least 1, loop_min_inliers at least 4, loop_cooldown non-negative")
+            if not 1 <= int(loop_iterations) <= L.LOOP_MAX_ITERATIONS:
+                raise ValueError("1 <= loop_iterations <= %d required" % L.LOOP_MAX_ITERATIONS)
+            if not (loop_weight > 0.0 and np.isfinite(loop_weight)):
+                raise ValueError("loop_weight must be finite and positive")
+            if int(trajectory_rows) < 2:
+                raise ValueError("loop_closure needs trajectory_rows >= 2")
         if absolute_pose not in (None, "observe", "repair"):
             raise ValueError("absolute_pose must be None, 'observe' or 'repair' (got %r)" % (absolute_pose,))
         if absolute_pose is not None:
@@ -394,6 +417,13 @@ class PointTracker(object):
         self._world_pnp = None    # lib.pnp_buffers of one problem
         self._world_match = None  # (match [cap, 3], n_match [1]) of the newest frame against the map
         self._world_table = None  # float64 [trajectory_rows, POSE_ROW_WORDS]: world_trajectory()
+        self.loop_closure = loop_closure
+        self.loop_min_gap, self.loop_min_inliers, self.loop_cooldown = int(loop_min_gap), int(loop_min_inliers), int(loop_cooldown)
+        self.loop_iterations, self.loop_weight = int(loop_iterations), float(loop_weight)
+        self._loop = None         # lib.loop_buffers: the edge table, its state, the pose graph's outputs
+        self._loop_pnp = None     # lib.pnp_buffers of one problem: the pose against the old rows
+        self._loop_log = None     # float64 [trajectory_rows, 11]: the candidate record and the graph's costs and status per frame
+        self._loop_seed = None    # the frame's check seed
 
     # ---- device buffers -------------------------------------------------------------------------------------------
     def _ensure(self, n):
@@ -569,6 +599,7 @@ class PointTracker(object):
             self._world_match = (torch.zeros(cap, 3, dtype=torch.float32, device=self.device),
                                  torch.zeros(1, dtype=torch.int32, device=self.device))
         w, a, count = self._world, self._world_pnp, self._counts[dslot:dslot + 1]
+        self._loop_seed = seed
         m, nm = L.op_match_world(w, self._desc[dslot], count, self.nn_thresh, out=self._world_match)
         corr, n = L.op_world_correspondences(w, m, nm, pts_new, count, out=a)
         res = L.op_pnp_ransac(a["corr"], n[0:1], self._intr[0, 1:2], seed, thresh=self.world_thresh,
@@ -600,8 +631,68 @@ class PointTracker(object):
         cams = L.op_map_window(self._traj_state, self._traj_table, self._intr[0, 1:2], self.maxl, n_frames=self._frames, out=self._world_lm)
         rows = L.op_triangulate_tracks(self._table, self._pts, self._frames % self.maxl, cams, mv, par, rep, out=self._world_lm)
         lms, n_lms = L.op_landmarks_select(self._table, rows, out=self._world_lm)
+        if self.loop_closure is not None:
+            self._loop_device(lms, n_lms)
+            if self.loop_closure == "apply":      # once more, unconditionally: the rows inserted stand under the corrected cameras
+                cams = L.op_map_window(self._traj_state, self._traj_table, self._intr[0, 1:2], self.maxl, n_frames=self._frames,
+                                       out=self._world_lm)
+                rows = L.op_triangulate_tracks(self._table, self._pts, self._frames % self.maxl, cams, mv, par, rep, out=self._world_lm)
+                lms, n_lms = L.op_landmarks_select(self._table, rows, out=self._world_lm)
         L.op_world_insert(self._world, lms, n_lms, self._desc[dslot], self._counts[dslot:dslot + 1], self._traj_table, self._frames,
                           self.world_patience)
+
+    def _loop_device(self, lms, n_lms):
+        """Loop closure of the newest frame, between the select and the insert: the frame's map matches
+        against the old rows, P3P, the edge, the pose graph and, with "apply", the write-back.  last_geometry() gains loop_* keys."""
+        f = self._frames - 1
+        slot, dslot = self._slots()
+        cap = self._cap
+        if self._loop is None or self._loop["cap"] != cap:
+            new = L.loop_buffers(cap, self.trajectory_rows, self.device)
+            if self._loop is not None:          # the match tables grew: the edges and the counters stay
+                new["edges"].copy_(self._loop["edges"])
+                new["state"].copy_(self._loop["state"])
+            self._loop = new
+            self._loop_pnp = L.pnp_buffers(1, cap, self.device)
+        if self._loop_log is None:
+            self._loop_log = torch.zeros(self.trajectory_rows, 11, dtype=torch.float64, device=self.device)
+        lp, w, count = self._loop, self._world, self._counts[dslot:dslot + 1]
+        m, nm = self._world_match
+        L.op_loop_correspondences(w, m, nm, self._pts[slot], count, lms, n_lms, f, self.loop_min_gap, lp)
+        res = L.op_pnp_ransac(lp["corr"], lp["n"][0:1], self._intr[0, 1:2], self._loop_seed, thresh=self.world_thresh,
+                              min_inliers=self.loop_min_inliers, out=self._loop_pnp)
+        g = dict(self._geometry)
+        g.update(("loop_" + k, v) for k, v in res.items())
+        g["loop_corr"], g["loop_xnew"], g["loop_n_corr"] = lp["corr"], lp["xnew"], lp["n"]
+        g["loop_cand"], g["loop_info"], g["loop_state"] = lp["cand"], lp["info"], lp["state"]
+        self._geometry = g
+        if f >= self.trajectory_rows:           # no row in the table: nothing to close
+            return
+        L.op_loop_edge(w, res, self._traj_table, f, lp, self.loop_min_inliers, self.loop_cooldown, self.loop_weight)
+        L.op_pose_graph(self._traj_table, f, lp, self.loop_iterations)
+        if self.loop_closure == "apply":
+            L.op_loop_apply(w, self._traj_state, self._traj_table, f, lp)
+        row = self._loop_log[f]
+        row[0:8] = lp["cand"][0:8]
+        row[8:10] = lp["info"][1:3]
+        row[10:11] = lp["info"][0:1]
+
+    def loop_edges_device(self):
+        """(edges float64 [LOOP_MAX_EDGES, LOOP_EDGE_WORDS] rows (i, j, R [9], t [3], log sigma, weight), state int32
+        [LOOP_STATE_WORDS]; state[0] rows are in use) on the device; None without loop_closure or before the third frame.  No
+        synchronisation."""
+        if self._loop is None:
+            return None
+        return self._loop["edges"], self._loop["state"]
+
+    def loop_closures(self):
+        """One numpy row per accepted edge: (frame, anchor, inliers, sigma, angle of R_c in radians, |t_c|, cost before, cost
+        after, status of the pose graph); one host synchronisation.  Zero rows without loop_closure."""
+        if self._loop_log is None:
+            return np.zeros((0, 9))
+        log = self._loop_log[:min(self._frames, self.trajectory_rows)].cpu().numpy()
+        log = log[log[:, 7] != 0.0]
+        return np.ascontiguousarray(log[:, [0, 1, 2, 4, 5, 6, 8, 9, 10]])
 
     def world_trajectory(self):
         """(table, n_frames) on the device in absolute_trajectory()'s layout: rows (Rw [9], C [3], n_inliers, rms, status, n_corr),
@@ -931,13 +1022,17 @@ class SequenceTracker:
     world_map / world_cap / world_patience / world_thresh / world_min_inliers: PointTracker's world map of landmarks that outlive
     their window, every frame's pose against it and, with "relocalise", the repair of the trajectory from it (DESIGN.md section
     29; the map matcher ignores classes); read it with tracker.last_geometry(), world_trajectory(), world_map_device() and
-    world_map().  A step stays free of host copies and synchronisation once allocated."""
+    world_map().  A step stays free of host copies and synchronisation once allocated.
+    loop_closure / loop_min_gap / loop_min_inliers / loop_cooldown / loop_iterations / loop_weight: PointTracker's loop closure
+    over the world map (needs world_map); read it with tracker.last_geometry(), loop_closures() and
+    loop_edges_device()."""
 
     def __init__(self, net, device, conf_thresh, nms_dist, subpixel, nn_thresh, max_length, border_remove=4,
                  keep_classes=None, drop_classes=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
                  absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1,
-                 world_map=None, world_cap=65536, world_patience=30, world_thresh=2.0, world_min_inliers=6):
+                 world_map=None, world_cap=65536, world_patience=30, world_thresh=2.0, world_min_inliers=6,
+                 loop_closure=None, loop_min_gap=32, loop_min_inliers=12, loop_cooldown=32, loop_iterations=10, loop_weight=1.0):
         if nn_thresh < 0.0:
             raise ValueError("'nn_thresh' should be non-negative")
         self.class_consistent = bool(class_consistent)
@@ -957,7 +1052,9 @@ class SequenceTracker:
                                     absolute_min_inliers=absolute_min_inliers, landmark_params=landmark_params,
                                     bundle_adjust=bundle_adjust, bundle_iterations=bundle_iterations, bundle_every=bundle_every,
                                     world_map=world_map, world_cap=world_cap, world_patience=world_patience,
-                                    world_thresh=world_thresh, world_min_inliers=world_min_inliers)
+                                    world_thresh=world_thresh, world_min_inliers=world_min_inliers, loop_closure=loop_closure,
+                                    loop_min_gap=loop_min_gap, loop_min_inliers=loop_min_inliers, loop_cooldown=loop_cooldown,
+                                    loop_iterations=loop_iterations, loop_weight=loop_weight)
 
     def describe(self, image):
         """image [H,W] / [1,H,W] / [1,1,H,W] -> the device tensors of Engine.describe_points for this one image (with "cls",
@@ -1007,6 +1104,12 @@ class SequenceTracker:
 
     def world_map(self):
         return self.tracker.world_map()
+
+    def loop_edges_device(self):
+        return self.tracker.loop_edges_device()
+
+    def loop_closures(self):
+        return self.tracker.loop_closures()
 
     def landmarks_device(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
         return self.tracker.landmarks_device(min_views, min_parallax_deg, max_reproj)

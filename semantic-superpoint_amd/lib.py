@@ -139,7 +139,8 @@ EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ss
            "ssp_pnp_workspace_bytes", "ssp_op_landmark_matches", "ssp_pnp_ransac", "ssp_pose_repair",
            "ssp_ba_workspace_bytes", "ssp_bundle_adjust", "ssp_ba_apply",
            "ssp_world_insert_workspace_bytes", "ssp_match_world_workspace_bytes", "ssp_op_world_insert", "ssp_match_world",
-           "ssp_op_world_correspondences", "ssp_world_repair"]
+           "ssp_op_world_correspondences", "ssp_world_repair",
+           "ssp_pose_graph_workspace_bytes", "ssp_op_loop_correspondences", "ssp_loop_edge", "ssp_pose_graph", "ssp_loop_apply"]
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -409,6 +410,12 @@ def load_library(path=None):
         lib.ssp_match_world.argtypes = [vp, vp, i, vp, vp, i, C.c_float, vp, vp, vp, vp]
         lib.ssp_op_world_correspondences.argtypes = [vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, vp]
         lib.ssp_world_repair.argtypes = [vp, vp, vp, vp, vp, i, i, vp, vp]
+        lib.ssp_pose_graph_workspace_bytes.argtypes = [i]
+        lib.ssp_pose_graph_workspace_bytes.restype = C.c_size_t
+        lib.ssp_op_loop_correspondences.argtypes = [vp, vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, i, i, i, vp, vp, vp, vp]
+        lib.ssp_loop_edge.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, i, i, i, i, C.c_double, vp, vp, vp, vp]
+        lib.ssp_pose_graph.argtypes = [vp, i, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
+        lib.ssp_loop_apply.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, i, vp, vp, vp, i, vp]
     except AttributeError:
         if os.environ.get("SSP_HIP_LIB") is None:
             raise
@@ -2654,6 +2661,188 @@ def op_world_repair(world, absolute, state, table):
         _check(lib.ssp_world_repair(_ptr(absolute["Rw"]), _ptr(absolute["C"]), _ptr(absolute["status"]), _ptr(state), _ptr(table),
                                     int(table.shape[-2]), map_cap, _ptr(world["state"]), _stream()))
     return state, table
+
+
+# ---- loop closure ----
+LOOP_MAX_EDGES = 256  # SSP_LOOP_MAX_EDGES (include/ssp_hip.h)
+LOOP_EDGE_WORDS = 16  # SSP_LOOP_EDGE_WORDS: i, j, R [9], t [3], log sigma, weight
+LOOP_STATE_WORDS = 8  # SSP_LOOP_STATE_WORDS: edges, last accepted frame, refused, dropped, accepted, anchor, inliers, non-finite map rows
+LOOP_CAND_WORDS = 16  # SSP_LOOP_CAND_WORDS: frame, anchor, inliers, shared depths, sigma, angle of R_c, |t_c|, accepted, reason
+LOOP_MAX_INNER = 8  # SSP_LOOP_MAX_INNER: both-ends-free loop edges one solve folds in
+LOOP_INFO_WORDS = 8  # SSP_LOOP_INFO_WORDS: status, cost before, cost after, nodes, edges, accepted steps, edges left out, lambda
+LOOP_MAX_ITERATIONS = 64  # SSP_LOOP_MAX_ITERATIONS
+POSE_FLAG_LOOP = 32  # SSP_POSE_FLAG_LOOP: the trajectory row was rewritten by a loop closure
+LOOP_KEYS = ("corr", "xnew", "n", "edges", "state", "cand", "Rw", "C", "sigma", "info")
+
+
+def loop_buffers(cap, capacity, device="cuda"):
+    """The device arrays of the loop-closure operators for match tables of cap rows and a trajectory table of capacity rows, zeroed
+    (DESIGN.md section 31): {"corr": float64 [cap, CORR_WORDS], "xnew": float64 [cap, 4], "n": int32 [3], "edges": float64
+    [LOOP_MAX_EDGES, LOOP_EDGE_WORDS], "state": int32 [LOOP_STATE_WORDS], "cand": float64 [LOOP_CAND_WORDS], "Rw": float64
+    [capacity, 9], "C": float64 [capacity, 3], "sigma": float64 [capacity], "info": float64 [LOOP_INFO_WORDS], "ws": the scratch of
+    op_pose_graph} plus the host-known "cap" and "capacity".  Zeroed memory is an empty edge table."""
+    lib = load_library()
+    cap, capacity = int(cap), int(capacity)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("loop_buffers needs a HIP device: the MI355X path has no CPU fallback")
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d rows (got %d)" % (MATCH_MAX_POINTS, cap))
+    if capacity < 2:
+        raise ValueError("capacity >= 2 required (got %d)" % capacity)
+    wsb = lib.ssp_pose_graph_workspace_bytes(capacity)
+    if wsb == 0:
+        _check(-1)
+    f64, i32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int32, device=device)
+    return {"corr": torch.zeros(cap, CORR_WORDS, **f64), "xnew": torch.zeros(cap, 4, **f64), "n": torch.zeros(3, **i32),
+            "edges": torch.zeros(LOOP_MAX_EDGES, LOOP_EDGE_WORDS, **f64), "state": torch.zeros(LOOP_STATE_WORDS, **i32),
+            "cand": torch.zeros(LOOP_CAND_WORDS, **f64), "Rw": torch.zeros(capacity, 9, **f64), "C": torch.zeros(capacity, 3, **f64),
+            "sigma": torch.zeros(capacity, **f64), "info": torch.zeros(LOOP_INFO_WORDS, **f64),
+            "ws": torch.zeros(wsb, dtype=torch.uint8, device=device), "cap": cap, "capacity": capacity}
+
+
+def _loop_bufs(loop):
+    """checks a loop_buffers dict; -> (cap, capacity)"""
+    if not isinstance(loop, dict) or any(k not in loop for k in LOOP_KEYS + ("ws", "cap", "capacity")):
+        raise ValueError("loop must be the dict of loop_buffers")
+    cap, capacity = int(loop["cap"]), int(loop["capacity"])
+    shapes = {"corr": (cap, CORR_WORDS), "xnew": (cap, 4), "n": (3,), "edges": (LOOP_MAX_EDGES, LOOP_EDGE_WORDS),
+              "state": (LOOP_STATE_WORDS,), "cand": (LOOP_CAND_WORDS,), "Rw": (capacity, 9), "C": (capacity, 3), "sigma": (capacity,),
+              "info": (LOOP_INFO_WORDS,)}
+    for k in LOOP_KEYS:
+        _need_gpu(loop[k], "loop[%r]" % k)
+        want = torch.int32 if k in ("n", "state") else torch.float64
+        if loop[k].dtype != want or tuple(loop[k].shape) != shapes[k] or not loop[k].is_contiguous():
+            raise ValueError("loop[%r] must be contiguous %s %s (loop_buffers)" % (k, want, list(shapes[k])))
+    _need_gpu(loop["ws"], "loop['ws']")
+    if not 1 <= cap <= MATCH_MAX_POINTS or capacity < 2:
+        raise ValueError("1 <= cap <= %d and capacity >= 2 required" % MATCH_MAX_POINTS)
+    return cap, capacity
+
+
+def _loop_table(table, capacity):
+    _need_gpu(table, "table")
+    if (table.dtype != torch.float64 or table.dim() != 2 or tuple(table.shape) != (capacity, POSE_ROW_WORDS)
+            or not table.is_contiguous()):
+        raise ValueError("table must be contiguous float64 [%d, %d] (pose_table of one sequence, loop['capacity'] rows)"
+                         % (capacity, POSE_ROW_WORDS))
+
+
+def op_loop_correspondences(world, match, n_match, pts_new, count_new, landmarks, n_landmarks, frame, min_gap, loop):
+    """op_world_correspondences restricted to OLD map rows, and the frame points' window landmarks (ssp_op_loop_correspondences;
+    DESIGN.md section 31).  world, match, n_match, pts_new, count_new as for op_world_correspondences; landmarks float64 [row_cap,
+    LANDMARK_WORDS] and n_landmarks int32 [1] of op_landmarks_select for the window ending at `frame`; a match row is old iff
+    last_frame[map row] <= frame - min_gap.  Fills and returns (loop["corr"], loop["xnew"], loop["n"]): corr as op_pnp_ransac takes
+    it (zero for every row that is not a valid old row), xnew = (X of the lowest landmark row naming the row's frame point, 1) or
+    zero, n = (rows, valid old rows, valid old rows with a landmark).  No host synchronisation."""
+    lib = load_library()
+    map_cap, _ = _world_map(world)
+    cap, _ = _loop_bufs(loop)
+    for t, nm in ((match, "match"), (n_match, "n_match"), (pts_new, "pts_new"), (count_new, "count_new"), (landmarks, "landmarks"),
+                  (n_landmarks, "n_landmarks")):
+        _need_gpu(t, nm)
+    if match.dtype != torch.float32 or tuple(match.shape) != (cap, 3) or not match.is_contiguous():
+        raise ValueError("match must be contiguous float32 [%d, 3] (loop['cap'] rows)" % cap)
+    if pts_new.dtype != torch.float64 or pts_new.dim() != 2 or pts_new.shape[1] < 2 or not pts_new.is_contiguous():
+        raise ValueError("pts_new must be contiguous float64 [point_cap, >= 2]")
+    if landmarks.dtype != torch.float64 or landmarks.dim() != 2 or landmarks.shape[1] != LANDMARK_WORDS or not landmarks.is_contiguous():
+        raise ValueError("landmarks must be contiguous float64 [row_cap, %d] (op_landmarks_select)" % LANDMARK_WORDS)
+    for t, nm in ((n_match, "n_match"), (count_new, "count_new"), (n_landmarks, "n_landmarks")):
+        if t.dtype != torch.int32 or t.numel() != 1:
+            raise ValueError("%s must be int32 [1]" % nm)
+    point_cap, row_cap = pts_new.shape[0], landmarks.shape[0]
+    if not (1 <= point_cap <= MATCH_MAX_POINTS and 1 <= row_cap <= TRACK_MAX_LENGTH * MATCH_MAX_POINTS):
+        raise ValueError("1 <= point_cap <= %d and 1 <= row_cap <= %d required" % (MATCH_MAX_POINTS, TRACK_MAX_LENGTH * MATCH_MAX_POINTS))
+    if int(frame) < 0 or int(min_gap) < 1:
+        raise ValueError("frame >= 0 and min_gap >= 1 required (got %d, %d)" % (int(frame), int(min_gap)))
+    with torch.cuda.device(match.device):
+        _check(lib.ssp_op_loop_correspondences(_ptr(world["X"]), _ptr(world["last_frame"]), _ptr(world["state"]), map_cap, _ptr(match),
+                                               _ptr(n_match), cap, _ptr(pts_new), int(pts_new.shape[1]), _ptr(count_new), point_cap,
+                                               _ptr(landmarks), _ptr(n_landmarks), row_cap, int(frame), int(min_gap),
+                                               _ptr(loop["corr"]), _ptr(loop["xnew"]), _ptr(loop["n"]), _stream()))
+    return loop["corr"], loop["xnew"], loop["n"]
+
+
+def op_loop_edge(world, absolute, table, frame, loop, min_inliers=12, cooldown=32, weight=1.0):
+    """One candidate loop edge from the pose of `frame` against the old rows (ssp_loop_edge).  absolute: the
+    dict of op_pnp_ransac on loop["corr"] (one problem); table float64 [loop["capacity"], POSE_ROW_WORDS].  Anchor a = the largest
+    last_frame over the inlier rows; sigma = the ratio of the sums of the inliers' depths under the loop pose and of their window
+    landmarks' depths under row `frame` (op_pose_chain's statistic: at least 8 shared points, finite, positive).  Accepted iff the
+    pose has status 0 and is finite, inliers >= min_inliers, the scale rule holds, 0 <= a < frame, frame - (frame of the last
+    accepted edge) >= cooldown and the table has room; then the row (a, frame, R, t, log sigma, weight) is appended to
+    loop["edges"].  loop["state"] counts and loop["cand"] describes the candidate.  Returns (edges, state, cand).  No host
+    synchronisation."""
+    lib = load_library()
+    map_cap, _ = _world_map(world)
+    cap, capacity = _loop_bufs(loop)
+    _loop_table(table, capacity)
+    for k in ("Rw", "C", "mask", "status"):
+        if k not in absolute:
+            raise ValueError("absolute must be the dict of op_pnp_ransac (no %r)" % k)
+        _need_gpu(absolute[k], "absolute[%r]" % k)
+    if absolute["status"].dtype != torch.int32 or absolute["status"].numel() != 1:
+        raise ValueError("absolute['status'] must be int32 [1]: one sequence")
+    for k, m in (("Rw", 9), ("C", 3)):
+        if absolute[k].dtype != torch.float64 or absolute[k].numel() != m or not absolute[k].is_contiguous():
+            raise ValueError("absolute[%r] must be the contiguous float64 tensor of op_pnp_ransac for one problem" % k)
+    if absolute["mask"].dtype != torch.uint8 or absolute["mask"].numel() != cap or not absolute["mask"].is_contiguous():
+        raise ValueError("absolute['mask'] must be contiguous uint8 [%d]" % cap)
+    if int(frame) < 0 or int(min_inliers) < 4 or int(cooldown) < 0:
+        raise ValueError("frame >= 0, min_inliers >= 4 and cooldown >= 0 required")
+    if not (float(weight) > 0.0 and np.isfinite(float(weight))):
+        raise ValueError("'weight' should be finite and positive")
+    with torch.cuda.device(table.device):
+        _check(lib.ssp_loop_edge(_ptr(absolute["Rw"]), _ptr(absolute["C"]), _ptr(absolute["mask"]), _ptr(absolute["status"]),
+                                 _ptr(loop["corr"]), _ptr(loop["xnew"]), _ptr(loop["n"]), cap, _ptr(world["last_frame"]), map_cap,
+                                 _ptr(table), capacity, int(frame), int(min_inliers), int(cooldown), float(weight), _ptr(loop["edges"]),
+                                 _ptr(loop["state"]), _ptr(loop["cand"]), _stream()))
+    return loop["edges"], loop["state"], loop["cand"]
+
+
+def op_pose_graph(table, frame, loop, iterations=10):
+    """The Sim(3) pose graph over the trajectory rows a + 1 .. frame, a = the anchor of the edge the last op_loop_edge accepted
+    (ssp_pose_graph): chain edges between consecutive rows as the table holds them, every stored loop edge
+    ending in (a, frame], Levenberg-Marquardt of `iterations` steps whose normal equations (block tridiagonal plus one rank-7 term
+    per loop edge with both ends free, at most LOOP_MAX_INNER) are solved by block cyclic reduction and the Woodbury identity.
+    Fills and returns {"Rw": loop["Rw"], "C": loop["C"], "sigma": loop["sigma"], "info": loop["info"]}: copies of the table's rows
+    (sigma 1) with the free rows replaced under status 0; info = (status, cost before, cost after, nodes, edges used, accepted steps,
+    both-ends-free edges left out, lambda); status 1: nothing to do, 2: no step accepted.  No host synchronisation."""
+    lib = load_library()
+    _, capacity = _loop_bufs(loop)
+    _loop_table(table, capacity)
+    if int(frame) < 0:
+        raise ValueError("frame >= 0 required (got %d)" % int(frame))
+    if not 1 <= int(iterations) <= LOOP_MAX_ITERATIONS:
+        raise ValueError("1 <= iterations <= %d required (got %d)" % (LOOP_MAX_ITERATIONS, int(iterations)))
+    if loop["ws"].numel() < lib.ssp_pose_graph_workspace_bytes(capacity):
+        raise ValueError("loop['ws'] is smaller than ssp_pose_graph_workspace_bytes(%d)" % capacity)
+    with torch.cuda.device(table.device):
+        _check(lib.ssp_pose_graph(_ptr(table), capacity, _ptr(loop["edges"]), _ptr(loop["state"]), int(frame), int(iterations),
+                                  _ptr(loop["ws"]), _ptr(loop["Rw"]), _ptr(loop["C"]), _ptr(loop["sigma"]), _ptr(loop["info"]),
+                                  _stream()))
+    return {k: loop[k] for k in ("Rw", "C", "sigma", "info")}
+
+
+def op_loop_apply(world, state, table, frame, loop):
+    """The pose graph's result written back (ssp_loop_apply), in place, only under status 0: trajectory rows
+    a + 1 .. frame take the corrected Rw and C, s = |C_k - C_(k-1)| when that is finite and above 1/64 of the row's s, and
+    POSE_FLAG_LOOP; the chain state (float64 [POSE_STATE_WORDS]) follows row `frame` when that is its newest frame and the table is
+    not full; a map row last seen in frame k of (a, frame] becomes C'_k + sigma_k R'_k^T R_k (X - C_k), and a non-finite result
+    leaves it unchanged and is counted in loop["state"][7].  Returns (state, table, world).  No host synchronisation."""
+    lib = load_library()
+    map_cap, _ = _world_map(world)
+    _, capacity = _loop_bufs(loop)
+    _loop_table(table, capacity)
+    _need_gpu(state, "state")
+    if state.dtype != torch.float64 or state.numel() != POSE_STATE_WORDS or not state.is_contiguous():
+        raise ValueError("state must be contiguous float64 [%d] (pose_state of one sequence)" % POSE_STATE_WORDS)
+    if int(frame) < 0:
+        raise ValueError("frame >= 0 required (got %d)" % int(frame))
+    with torch.cuda.device(table.device):
+        _check(lib.ssp_loop_apply(_ptr(loop["info"]), _ptr(loop["Rw"]), _ptr(loop["C"]), _ptr(loop["sigma"]), _ptr(loop["state"]),
+                                  int(frame), _ptr(state), _ptr(table), capacity, _ptr(world["X"]), _ptr(world["last_frame"]),
+                                  _ptr(world["state"]), map_cap, _stream()))
+    return state, table, world
 
 
 def op_eval_pixel_homographies(hn, height, width):
