@@ -32,7 +32,6 @@ namespace sspk {
 #define LOOP_LAMBDA_MIN 1e-12
 #define LOOP_LAMBDA_MAX 1e6
 #define LOOP_MAX_ITERATIONS 64
-#define LOOP_NO_OWNER 0x7FFFFFFF
 
 // grid (1), 256 threads, dynamic LDS point_cap ints.  corr [cap][PNP_CORR_WORDS], xnew [cap][4], n_out [3] = rows, valid old rows,
 // valid old rows with a landmark.
@@ -46,14 +45,7 @@ __global__ __launch_bounds__(256) void loop_corr_kernel(const double* __restrict
                                                         double* __restrict__ xnew, int32_t* __restrict__ n_out) {
   extern __shared__ int loop_owner[];
   const int tid = threadIdx.x;
-  for (int k = tid; k < point_cap; k += 256) loop_owner[k] = LOOP_NO_OWNER;
-  __syncthreads();
-  const int nl = min(max(n_landmarks[0], 0), row_cap);
-  for (int r = tid; r < nl; r += 256) {
-    const double w = landmarks[(size_t)r * LM_WORDS + 7];
-    if (isfinite(w) && w >= 0.0 && w < (double)point_cap) atomicMin(&loop_owner[(int)w], r);   // the lowest row wins
-  }
-  __syncthreads();
+  pnp_owner_table(loop_owner, point_cap, landmarks, min(max(n_landmarks[0], 0), row_cap), tid, 256);
   const int n_rows = min(max(world_state[0], 0), map_cap), count = min(max(count_new[0], 0), point_cap);
   const int n = min(max(n_match[0], 0), cap);
   const long long newest_old = (long long)f - (long long)min_gap;
@@ -75,9 +67,9 @@ __global__ __launch_bounds__(256) void loop_corr_kernel(const double* __restrict
           v[2] = map_x[(size_t)row * 3 + 2];
           v[3] = px[0];
           v[4] = px[1];
-          valid = isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]) && isfinite(v[4]);
+          valid = pnp_finite5(v);
           const int r = loop_owner[j];
-          if (valid && r != LOOP_NO_OWNER) {
+          if (valid && r != PNP_NO_OWNER) {
             const double* lm = landmarks + (size_t)r * LM_WORDS;
             x[0] = lm[1];
             x[1] = lm[2];
@@ -88,12 +80,7 @@ __global__ __launch_bounds__(256) void loop_corr_kernel(const double* __restrict
       }
     }
     if (k < cap) {
-      double* o = corr + (size_t)k * PNP_CORR_WORDS;
-#pragma unroll
-      for (int c = 0; c < 5; ++c) o[c] = valid ? v[c] : 0.0;
-      o[5] = valid ? (double)row : 0.0;
-      o[6] = valid ? 1.0 : 0.0;
-      o[7] = 0.0;
+      pnp_store_corr(corr + (size_t)k * PNP_CORR_WORDS, v, row, valid);
       double* q = xnew + (size_t)k * 4;
 #pragma unroll
       for (int c = 0; c < 3; ++c) q[c] = has ? x[c] : 0.0;

@@ -39,6 +39,81 @@ struct PnpIntr {
   double fx, fy, cx, cy;
 };
 
+// ---- what the joins and the repairs of the absolute pose, the world map and the loop closure share ----
+// The "point of the newest frame -> lowest landmark row" table in LDS: owner [point_cap], PNP_NO_OWNER where no landmark carries the
+// point.  Called by every thread of a block of `threads`; the table is complete when it returns.
+__device__ __forceinline__ void pnp_owner_table(int* owner, int point_cap, const double* __restrict__ landmarks, int nl, int tid,
+                                                int threads) {
+  for (int k = tid; k < point_cap; k += threads) owner[k] = PNP_NO_OWNER;
+  __syncthreads();
+  for (int r = tid; r < nl; r += threads) {
+    const double w = landmarks[(size_t)r * LM_WORDS + 7];
+    if (isfinite(w) && w >= 0.0 && w < (double)point_cap) atomicMin(&owner[(int)w], r);   // the lowest row wins
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ bool pnp_finite5(const double (&v)[5]) {
+  return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]) && isfinite(v[4]);
+}
+
+// One row of corr [cap][PNP_CORR_WORDS]: (X, Y, Z, px, py), the row they came from and 1 when valid, zeros otherwise.
+__device__ __forceinline__ void pnp_store_corr(double* __restrict__ o, const double (&v)[5], int row, bool valid) {
+#pragma unroll
+  for (int c = 0; c < 5; ++c) o[c] = valid ? v[c] : 0.0;
+  o[5] = valid ? (double)row : 0.0;
+  o[6] = valid ? 1.0 : 0.0;
+  o[7] = 0.0;
+}
+
+// Rw [9] and C [3] of one absolute pose; true when all twelve values are finite.
+__device__ __forceinline__ bool pnp_load_pose(const double* __restrict__ rw_in, const double* __restrict__ c_in, double (&Rw)[9],
+                                              double (&C)[3]) {
+  bool fin = true;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    Rw[k] = rw_in[k];
+    fin = fin && isfinite(Rw[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    C[k] = c_in[k];
+    fin = fin && isfinite(C[k]);
+  }
+  return fin;
+}
+
+// The rewrite of trajectory row n - 1 (`row`, flags `flags`) and the chain state `st` from the absolute pose (Rw, C): tw = -(Rw C);
+// the scale becomes the step from the previous row's centre when that is finite and longer than PNP_SCALE_FRACTION of the carried
+// scale (the carried-scale flag is then dropped, otherwise kept); the row's flags become that bit | set_flags.
+__device__ __forceinline__ void pnp_rewrite_row(double* __restrict__ st, double* __restrict__ row, int n, int flags,
+                                                const double (&Rw)[9], const double (&C)[3], int set_flags) {
+#pragma clang fp contract(off)
+  double tw[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) tw[i] = -pose_dot(Rw[3 * i], Rw[3 * i + 1], Rw[3 * i + 2], C[0], C[1], C[2]);
+  double s = st[1];
+  int keep = flags & 2;
+  if (n >= 2) {
+    const double* prev = row - POSE_ROW_WORDS;
+    const double d0 = C[0] - prev[9], d1 = C[1] - prev[10], d2 = C[2] - prev[11];
+    const double len = sqrt(pose_dot(d0, d1, d2, d0, d1, d2));
+    if (isfinite(len) && len > PNP_SCALE_FRACTION * s) {
+      s = len;
+      keep = 0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) row[k] = st[2 + k] = Rw[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    row[9 + k] = C[k];
+    st[11 + k] = tw[k];
+  }
+  row[12] = st[1] = s;
+  row[14] = (double)(keep | set_flags);
+}
+
 // grid (1), 256 threads, dynamic LDS point_cap ints.  landmarks [row_cap][LM_WORDS], match [cap][3] rows (i, j, d) of the pair
 // (previous, new), pts_new [point_cap][pt_stride] rows starting (x, y).  corr [cap][PNP_CORR_WORDS]; n_out [2] = rows, valid rows.
 __global__ __launch_bounds__(PNP_THREADS) void landmark_corr_kernel(const double* __restrict__ landmarks,
@@ -49,14 +124,7 @@ __global__ __launch_bounds__(PNP_THREADS) void landmark_corr_kernel(const double
   extern __shared__ int pnp_owner[];
   __shared__ double red[PNP_THREADS / 64];
   const int tid = threadIdx.x;
-  for (int k = tid; k < point_cap; k += PNP_THREADS) pnp_owner[k] = PNP_NO_OWNER;
-  __syncthreads();
-  const int nl = min(max(n_landmarks[0], 0), row_cap);
-  for (int r = tid; r < nl; r += PNP_THREADS) {
-    const double w = landmarks[(size_t)r * LM_WORDS + 7];
-    if (isfinite(w) && w >= 0.0 && w < (double)point_cap) atomicMin(&pnp_owner[(int)w], r);   // the lowest row wins
-  }
-  __syncthreads();
+  pnp_owner_table(pnp_owner, point_cap, landmarks, min(max(n_landmarks[0], 0), row_cap), tid, PNP_THREADS);
   const int n = min(max(n_match[0], 0), cap);
   double cnt = 0.0;
   for (int k = tid; k < cap; k += PNP_THREADS) {
@@ -74,15 +142,10 @@ __global__ __launch_bounds__(PNP_THREADS) void landmark_corr_kernel(const double
         v[2] = lm[3];
         v[3] = px[0];
         v[4] = px[1];
-        valid = isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]) && isfinite(v[4]);
+        valid = pnp_finite5(v);
       }
     }
-    double* o = corr + (size_t)k * PNP_CORR_WORDS;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) o[c] = valid ? v[c] : 0.0;
-    o[5] = valid ? (double)r : 0.0;
-    o[6] = valid ? 1.0 : 0.0;
-    o[7] = 0.0;
+    pnp_store_corr(corr + (size_t)k * PNP_CORR_WORDS, v, r, valid);
     cnt = cnt + (valid ? 1.0 : 0.0);
   }
   const double total = eval_block_sum(cnt, red);   // (a count: exact)
@@ -652,41 +715,10 @@ __global__ __launch_bounds__(64) void pose_repair_kernel(const double* __restric
   if (n < 1 || n >= capacity || status_in[q] != 0) return;
   double* row = table + ((size_t)q * capacity + (n - 1)) * POSE_ROW_WORDS;
   const int flags = (int)row[14];
-  double Rw[9], C[3], tw[3];
-  bool fin = true;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    Rw[k] = rw_in[(size_t)q * 9 + k];
-    fin = fin && isfinite(Rw[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    C[k] = c_in[(size_t)q * 3 + k];
-    fin = fin && isfinite(C[k]);
-  }
+  double Rw[9], C[3];
+  const bool fin = pnp_load_pose(rw_in + (size_t)q * 9, c_in + (size_t)q * 3, Rw, C);
   if (!(flags & 3) || !fin) return;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) tw[i] = -pose_dot(Rw[3 * i], Rw[3 * i + 1], Rw[3 * i + 2], C[0], C[1], C[2]);
-  double s = st[1];
-  int keep = flags & 2;
-  if (n >= 2) {
-    const double* prev = row - POSE_ROW_WORDS;
-    const double d0 = C[0] - prev[9], d1 = C[1] - prev[10], d2 = C[2] - prev[11];
-    const double len = sqrt(pose_dot(d0, d1, d2, d0, d1, d2));
-    if (isfinite(len) && len > PNP_SCALE_FRACTION * s) {
-      s = len;
-      keep = 0;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) row[k] = st[2 + k] = Rw[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    row[9 + k] = C[k];
-    st[11 + k] = tw[k];
-  }
-  row[12] = st[1] = s;
-  row[14] = (double)(keep | PNP_FLAG_ABSOLUTE);
+  pnp_rewrite_row(st, row, n, flags, Rw, C, PNP_FLAG_ABSOLUTE);
 }
 
 }  // namespace sspk

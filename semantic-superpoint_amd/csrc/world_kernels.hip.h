@@ -376,17 +376,10 @@ __global__ __launch_bounds__(256) void world_corr_kernel(const double* __restric
         v[2] = map_x[(size_t)row * 3 + 2];
         v[3] = px[0];
         v[4] = px[1];
-        valid = isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]) && isfinite(v[3]) && isfinite(v[4]);
+        valid = pnp_finite5(v);
       }
     }
-    if (k < cap) {
-      double* o = corr + (size_t)k * PNP_CORR_WORDS;
-#pragma unroll
-      for (int c = 0; c < 5; ++c) o[c] = valid ? v[c] : 0.0;
-      o[5] = valid ? (double)row : 0.0;
-      o[6] = valid ? 1.0 : 0.0;
-      o[7] = 0.0;
-    }
+    if (k < cap) pnp_store_corr(corr + (size_t)k * PNP_CORR_WORDS, v, row, valid);
     total += __syncthreads_count(valid);
   }
   if (tid == 0) {
@@ -409,51 +402,19 @@ __global__ __launch_bounds__(64) void world_repair_kernel(const double* __restri
   const int n = (nf >= 0.0 && nf < 2147483647.0) ? (int)nf : 0;
   const bool lost = min(max(world_state[0], 0), map_cap) > 0 && world_state[1] == 0;
   bool fire = n >= 1 && n < capacity && status_in[0] == 0;
-  double Rw[9], C[3], tw[3];
+  double Rw[9], C[3];
   int flags = 0;
   double* row = table;
   if (fire) {
     row = table + (size_t)(n - 1) * POSE_ROW_WORDS;
     flags = (int)row[14];
-    bool fin = true;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      Rw[k] = rw_in[k];
-      fin = fin && isfinite(Rw[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      C[k] = c_in[k];
-      fin = fin && isfinite(C[k]);
-    }
-    fire = fin && ((flags & 3) || lost);
+    fire = pnp_load_pose(rw_in, c_in, Rw, C) && ((flags & 3) || lost);
   }
   if (!fire) {
     world_state[3] = 0;
     return;
   }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) tw[i] = -pose_dot(Rw[3 * i], Rw[3 * i + 1], Rw[3 * i + 2], C[0], C[1], C[2]);
-  double s = st[1];
-  int keep = flags & 2;
-  if (n >= 2) {
-    const double* prev = row - POSE_ROW_WORDS;
-    const double d0 = C[0] - prev[9], d1 = C[1] - prev[10], d2 = C[2] - prev[11];
-    const double len = sqrt(pose_dot(d0, d1, d2, d0, d1, d2));
-    if (isfinite(len) && len > PNP_SCALE_FRACTION * s) {
-      s = len;
-      keep = 0;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) row[k] = st[2 + k] = Rw[k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    row[9 + k] = C[k];
-    st[11 + k] = tw[k];
-  }
-  row[12] = st[1] = s;
-  row[14] = (double)(keep | PNP_FLAG_ABSOLUTE | WORLD_FLAG_WORLD);
+  pnp_rewrite_row(st, row, n, flags, Rw, C, PNP_FLAG_ABSOLUTE | WORLD_FLAG_WORLD);
   world_state[3] = world_state[3] + 1;
 }
 

@@ -109,38 +109,145 @@ class SspExportParams(C.Structure):
 
 _lib = None
 
-EXPORTS = ["ssp_last_error", "ssp_create", "ssp_destroy", "ssp_param_count", "ssp_bn_channel_count",
-           "ssp_bn_layer_count", "ssp_workspace_bytes", "ssp_bind", "ssp_forward", "ssp_backward", "ssp_zero_grad",
-           "ssp_pair_step", "ssp_adam_step", "ssp_sample_indices", "ssp_profile_enable", "ssp_profile_read", "ssp_profile_read_executed",
-           "ssp_op_conv", "ssp_op_conv_wgrad", "ssp_op_labels", "ssp_op_sparse_loss", "ssp_op_bn_bwd", "ssp_op_bn_bwd_strided",
-           "ssp_debug_buffer", "ssp_debug_conv_knobs", "ssp_set_conv_algo", "ssp_op_warp_image", "ssp_op_erode", "ssp_op_warp_labels",
-           "ssp_export_workspace_bytes", "ssp_export_max_points", "ssp_export_points", "ssp_op_homoadapt_views",
-           "ssp_op_flatten_detection", "ssp_op_combine_heatmap", "ssp_op_heatmap_points", "ssp_op_soft_argmax_points", "ssp_detector_heatmap", "ssp_op_heatmap_nms", "ssp_op_dense_loss",
-           "ssp_op_sample_homographies", "ssp_op_warp_labels_full", "ssp_op_sem_finalize", "ssp_adam_step_scaled",
-           "ssp_pair_step_phase", "ssp_grad_early_offset", "ssp_pair_step_graph", "ssp_handle_set_conv_algo",
-           "ssp_op_detector_loss", "ssp_debug_occupancy", "ssp_sample_indices_cell", "ssp_op_warp_labels_px",
-           "ssp_op_warp_labels_full_px", "ssp_profile_read_kernel", "ssp_op_label_quantize", "ssp_profile_pause", "ssp_op_conv_bf16", "ssp_op_conv_wgrad_bf16", "ssp_op_bn_bwd_bf16", "ssp_build_id",
-           "ssp_set_deterministic", "ssp_get_deterministic", "ssp_clock_probe", "ssp_op_sem_loss",
-           "ssp_describe_workspace_bytes", "ssp_describe_points", "ssp_op_sample_descriptors", "ssp_match_workspace_bytes",
-           "ssp_match_two_way", "ssp_debug_backward_taps", "ssp_debug_backward_tap_floats", "ssp_debug_backward_tap",
-           "ssp_eval_repeatability", "ssp_eval_ransac_workspace_bytes", "ssp_eval_ransac",
-           "ssp_op_photometric_draw", "ssp_op_photometric_apply",
-           "ssp_shapes_workspace_bytes", "ssp_op_shapes_draw", "ssp_op_shapes_render", "ssp_op_warp_points_scatter",
-           "ssp_op_sem_predict", "ssp_sem_predict",
-           "ssp_track_workspace_bytes", "ssp_op_track_update", "ssp_op_track_select", "ssp_op_track_points",
-           "ssp_op_point_classes", "ssp_point_classes", "ssp_filter_workspace_bytes", "ssp_op_filter_points",
-           "ssp_match_two_way_classes",
-           "ssp_det_eval_workspace_bytes", "ssp_op_det_tp_fp", "ssp_op_det_tp_fp_points", "ssp_det_pr_curve_workspace_bytes",
-           "ssp_op_det_pr_curve", "ssp_op_sparse_loss_path",
-           "ssp_eval_pixel_homographies", "ssp_eval_accumulate",
-           "ssp_epi_ransac_workspace_bytes", "ssp_epi_ransac", "ssp_op_filter_matches",
-           "ssp_pose_from_fundamental", "ssp_pose_chain",
-           "ssp_landmark_workspace_bytes", "ssp_map_window", "ssp_op_triangulate_tracks", "ssp_op_landmarks_select",
-           "ssp_pnp_workspace_bytes", "ssp_op_landmark_matches", "ssp_pnp_ransac", "ssp_pose_repair",
-           "ssp_ba_workspace_bytes", "ssp_bundle_adjust", "ssp_ba_apply",
-           "ssp_world_insert_workspace_bytes", "ssp_match_world_workspace_bytes", "ssp_op_world_insert", "ssp_match_world",
-           "ssp_op_world_correspondences", "ssp_world_repair",
-           "ssp_pose_graph_workspace_bytes", "ssp_op_loop_correspondences", "ssp_loop_edge", "ssp_pose_graph", "ssp_loop_apply"]
+
+def _signatures():
+    """{name: (argtypes, restype)} of every function declared in include/ssp_hip.h, in the header's order.  load_library applies
+    it; tests/test_boundary_cpu.py holds every argtypes list against the number of parameters of the declaration."""
+    vp, i, f, d, sz, u32, u64, i64, P = (C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int64,
+                                         C.POINTER)
+    return {
+        "ssp_last_error": ([], C.c_char_p),
+        "ssp_build_id": ([], C.c_char_p),
+        "ssp_set_deterministic": ([i], i),
+        "ssp_get_deterministic": ([], i),
+        "ssp_clock_probe": ([f, P(d), vp], i),
+        "ssp_create": ([P(SspConfig), P(vp)], i),
+        "ssp_destroy": ([vp], None),
+        "ssp_param_count": ([vp], sz),
+        "ssp_bn_channel_count": ([vp], sz),
+        "ssp_bn_layer_count": ([vp], i),
+        "ssp_workspace_bytes": ([vp], sz),
+        "ssp_bind": ([vp, P(SspBuffers), vp], i),
+        "ssp_forward": ([vp, i, vp, i, i, i, i, vp, vp, vp, vp], i),
+        "ssp_backward": ([vp, i, vp, vp, vp, vp], i),
+        "ssp_zero_grad": ([vp, vp], i),
+        "ssp_pair_step": ([vp, P(SspPairInputs), vp, vp], i),
+        "ssp_adam_step": ([vp, f, i, vp], i),
+        "ssp_adam_step_scaled": ([vp, f, i, f, vp], i),
+        "ssp_pair_step_phase": ([vp, P(SspPairInputs), vp, i, vp], i),
+        "ssp_grad_early_offset": ([vp], sz),
+        "ssp_pair_step_graph": ([vp, P(SspPairInputs), vp, i, i, vp], i),
+        "ssp_sample_indices": ([vp, vp, i, u64, vp, vp, vp, vp], i),
+        "ssp_sample_indices_cell": ([vp, vp, i, u64, vp, vp, vp, vp], i),
+        "ssp_profile_enable": ([vp, i], i),
+        "ssp_profile_read": ([vp, P(d), P(i64), P(d), P(d)], i),
+        "ssp_profile_pause": ([vp, i], i),
+        "ssp_profile_read_kernel": ([vp, i, P(d), P(i64), P(d), P(d), P(d)], i),
+        "ssp_profile_read_executed": ([vp, P(d)], i),
+        "ssp_op_conv": ([vp, vp, vp, vp] + [i] * 7 + [vp, vp, vp, i, vp, sz, vp], i),
+        "ssp_op_conv_wgrad": ([vp, vp, vp] + [i] * 7 + [vp, vp, vp, sz, vp], i),
+        "ssp_op_conv_bf16": ([vp, vp, vp, vp] + [i] * 7 + [vp, vp, vp, i, i, i, vp, vp, vp, sz, vp], i),
+        "ssp_op_conv_wgrad_bf16": ([vp, vp, vp] + [i] * 7 + [vp, vp, i, vp, sz, vp], i),
+        "ssp_op_bn_bwd_bf16": ([vp] * 9 + [i] * 7 + [vp], i),
+        "ssp_op_labels": ([vp, vp, vp, vp, i, i, i, vp], i),
+        "ssp_op_detector_loss": ([vp, i, vp, vp, i, i, i, vp, sz, vp, vp, vp], i),
+        "ssp_op_sem_loss": ([vp, i, vp] + [i] * 5 + [vp, sz, vp, vp, vp], i),
+        "ssp_op_sem_predict": ([vp, i, vp, i, i, i, i, vp, vp, vp], i),
+        "ssp_sem_predict": ([vp, i, vp, vp, vp, vp], i),
+        "ssp_op_warp_image": ([vp, vp, vp, i, i, i, i, vp], i),
+        "ssp_op_erode": ([vp, vp, i, i, i, i, vp], i),
+        "ssp_op_warp_labels": ([vp, vp, vp, i, i, i, vp], i),
+        "ssp_op_warp_labels_px": ([vp, vp, vp, i, i, i, vp], i),
+        "ssp_op_sample_homographies": ([u64, P(SspHomographyParams), i, vp, vp, vp], i),
+        "ssp_op_warp_labels_full": ([vp] * 5 + [i, i, i, vp], i),
+        "ssp_op_warp_labels_full_px": ([vp] * 5 + [i, i, i, vp], i),
+        "ssp_op_label_quantize": ([vp, vp, sz, vp], i),
+        "ssp_op_sem_finalize": ([vp, vp, vp, sz, i, vp], i),
+        "ssp_op_photometric_draw": ([u64, P(SspPhotometricParams), i, i, i, vp, vp], i),
+        "ssp_op_photometric_apply": ([vp, vp, vp, i, i, i, vp], i),
+        "ssp_shapes_workspace_bytes": ([P(SspShapesParams), i], sz),
+        "ssp_op_shapes_draw": ([u64, P(SspShapesParams), i, vp, vp], i),
+        "ssp_op_shapes_render": ([vp, P(SspShapesParams), i] + [vp] * 5, i),
+        "ssp_op_warp_points_scatter": ([vp, vp, vp, vp, i, i, i, i, vp], i),
+        "ssp_export_workspace_bytes": ([P(SspExportParams)], sz),
+        "ssp_export_max_points": ([P(SspExportParams)], i),
+        "ssp_export_points": ([vp, P(SspExportParams), i] + [P(vp)] * 7 + [vp], i),
+        "ssp_op_homoadapt_views": ([vp, vp, vp, vp, i, i, i, vp], i),
+        "ssp_op_flatten_detection": ([vp, vp, vp, i, i, i, vp], i),
+        "ssp_op_combine_heatmap": ([vp, vp, vp, vp, i, i, i, vp], i),
+        "ssp_op_heatmap_points": ([vp, P(SspExportParams), vp, vp, vp, vp], i),
+        "ssp_op_soft_argmax_points": ([vp, vp, vp, i, i, i, vp], i),
+        "ssp_detector_heatmap": ([vp, i, vp, vp], i),
+        "ssp_op_heatmap_nms": ([vp, P(SspExportParams), i] + [vp] * 5, i),
+        "ssp_describe_workspace_bytes": ([P(SspExportParams), i], sz),
+        "ssp_describe_points": ([vp, i, P(SspExportParams), i] + [vp] * 5, i),
+        "ssp_op_sample_descriptors": ([vp, i, i, i, vp, vp, i, vp, vp], i),
+        "ssp_match_workspace_bytes": ([i, i], sz),
+        "ssp_match_two_way": ([vp, vp, vp, vp, i, i, i, f, vp, vp, vp, vp], i),
+        "ssp_op_point_classes": ([vp] + [i] * 5 + [vp, i, vp, i, vp, vp], i),
+        "ssp_point_classes": ([vp, i, i, vp, i, vp, i, vp, vp], i),
+        "ssp_filter_workspace_bytes": ([i, i], sz),
+        "ssp_op_filter_points": ([vp, vp, vp, vp, P(u32), i, i] + [vp] * 6, i),
+        "ssp_match_two_way_classes": ([vp] * 6 + [i, i, i, f, vp, vp, vp, vp], i),
+        "ssp_eval_repeatability": ([vp, vp, vp, vp, i, i, i, vp, vp, i, i, i, d, vp, vp], i),
+        "ssp_eval_ransac_workspace_bytes": ([i, i], sz),
+        "ssp_eval_ransac": ([vp, vp, i, i, i] + [vp] * 10, i),
+        "ssp_epi_ransac_workspace_bytes": ([i, i], sz),
+        "ssp_epi_ransac": ([vp, vp, i, i, i, i, vp, vp, vp, d, i] + [vp] * 8, i),
+        "ssp_op_filter_matches": ([vp] * 5 + [i, i, i, vp, vp, vp], i),
+        "ssp_pose_from_fundamental": ([vp] * 6 + [i, i, i, i, vp, vp, vp, i] + [vp] * 11, i),
+        "ssp_pose_chain": ([vp] * 5 + [i] + [vp] * 7 + [i, i, vp, vp, i, vp], i),
+        "ssp_landmark_workspace_bytes": ([i, i], sz),
+        "ssp_map_window": ([vp, vp, i, vp, i, i, i, vp, vp], i),
+        "ssp_op_triangulate_tracks": ([vp, vp, vp, i, vp, i, i, i, i, d, d] + [vp] * 6, i),
+        "ssp_op_landmarks_select": ([vp] * 8 + [i, i, i, vp, vp, vp, vp], i),
+        "ssp_pnp_workspace_bytes": ([i], sz),
+        "ssp_op_landmark_matches": ([vp, vp, i, vp, vp, i, vp, i, i, vp, vp, vp], i),
+        "ssp_pnp_ransac": ([vp, vp, i, i, vp, i, vp, d, i, i] + [vp] * 9, i),
+        "ssp_pose_repair": ([vp, vp, vp, i, vp, vp, i, vp], i),
+        "ssp_ba_workspace_bytes": ([i, i], sz),
+        "ssp_bundle_adjust": ([vp, vp, vp, i, vp, i, i, i, vp, vp, i] + [vp] * 6, i),
+        "ssp_ba_apply": ([vp, vp, i, i, i, vp, vp, i, vp], i),
+        "ssp_world_insert_workspace_bytes": ([i], sz),
+        "ssp_match_world_workspace_bytes": ([i, i], sz),
+        "ssp_op_world_insert": ([vp, vp, i, vp, vp, i, vp] + [i] * 5 + [vp] * 11, i),
+        "ssp_match_world": ([vp, vp, i, vp, vp, i, f, vp, vp, vp, vp], i),
+        "ssp_op_world_correspondences": ([vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, vp], i),
+        "ssp_world_repair": ([vp] * 5 + [i, i, vp, vp], i),
+        "ssp_pose_graph_workspace_bytes": ([i], sz),
+        "ssp_op_loop_correspondences": ([vp, vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, i, i, i, vp, vp, vp, vp], i),
+        "ssp_loop_edge": ([vp] * 7 + [i, vp, i, vp, i, i, i, i, d, vp, vp, vp, vp], i),
+        "ssp_pose_graph": ([vp, i, vp, vp, i, i] + [vp] * 6, i),
+        "ssp_loop_apply": ([vp] * 5 + [i, vp, vp, i, vp, vp, vp, i, vp], i),
+        "ssp_eval_pixel_homographies": ([vp, i, i, i, vp, vp, vp], i),
+        "ssp_eval_accumulate": ([vp] * 6 + [i, vp, i, i, i, P(d), i64, vp, i64, vp, vp], i),
+        "ssp_det_eval_workspace_bytes": ([P(SspDetEvalParams), i, i], sz),
+        "ssp_op_det_tp_fp": ([vp, vp, i, P(SspDetEvalParams), i, vp, vp, i64, vp, vp], i),
+        "ssp_op_det_tp_fp_points": ([vp, vp, i, vp, i, P(SspDetEvalParams), i, vp, vp, i64, vp, vp], i),
+        "ssp_det_pr_curve_workspace_bytes": ([i64], sz),
+        "ssp_op_det_pr_curve": ([vp, i64] + [vp] * 8, i),
+        "ssp_track_workspace_bytes": ([i, i, i], sz),
+        "ssp_op_track_update": ([vp] * 8 + [i, i, i] + [vp] * 6, i),
+        "ssp_op_track_select": ([vp, vp, vp, vp, i, i, i, vp, vp, vp, vp], i),
+        "ssp_op_track_points": ([vp, vp, vp, vp, i, i, i, i, vp, vp], i),
+        "ssp_op_bn_bwd": ([vp] * 9 + [i] * 6 + [vp], i),
+        "ssp_op_bn_bwd_strided": ([vp] * 9 + [i] * 7 + [vp], i),
+        "ssp_set_conv_algo": ([i], i),
+        "ssp_handle_set_conv_algo": ([vp, i], i),
+        "ssp_debug_conv_knobs": ([i, i], i),
+        "ssp_debug_occupancy": ([i], i),
+        "ssp_debug_buffer": ([vp, i, C.c_char_p, P(vp), P(sz)], i),
+        "ssp_debug_backward_taps": ([vp, vp, sz, u32], i),
+        "ssp_debug_backward_tap_floats": ([vp, u32], sz),
+        "ssp_debug_backward_tap": ([vp, i, i, i, P(sz), P(sz), P(u32)], i),
+        "ssp_op_sparse_loss": ([vp] * 5 + [i] * 7 + [f, f, vp, vp, vp, vp], i),
+        "ssp_op_sparse_loss_path": ([vp] * 5 + [i] * 7 + [f, f, vp, vp, vp, i, vp, vp, vp, vp], i),
+        "ssp_op_dense_loss": ([vp, vp, vp, vp, i, i, i, f, f, i, f, vp, sz, vp, vp, vp, vp], i),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)
 
 MATCH_MAX_POINTS = 4096  # SSP_MATCH_MAX_POINTS (include/ssp_hip.h)
 TRACK_MAX_LENGTH = 16  # SSP_TRACK_MAX_LENGTH (include/ssp_hip.h)
@@ -189,243 +296,14 @@ def load_library(path=None):
         except OSError:  # read-only tree: verified, not stamped
             _build.verify_binary(path)
     lib = C.CDLL(path)
-    vp, i, f = C.c_void_p, C.c_int, C.c_float
-    lib.ssp_last_error.restype = C.c_char_p
-    try:
-        lib.ssp_build_id.restype = C.c_char_p
-        lib.ssp_set_deterministic.argtypes = [C.c_int]
-        lib.ssp_get_deterministic.restype = C.c_int
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    lib.ssp_create.argtypes = [C.POINTER(SspConfig), C.POINTER(vp)]
-    lib.ssp_destroy.argtypes = [vp]
-    lib.ssp_destroy.restype = None
-    for n in ("ssp_param_count", "ssp_bn_channel_count", "ssp_workspace_bytes"):
-        getattr(lib, n).argtypes = [vp]
-        getattr(lib, n).restype = C.c_size_t
-    lib.ssp_bn_layer_count.argtypes = [vp]
-    lib.ssp_bind.argtypes = [vp, C.POINTER(SspBuffers), vp]
-    lib.ssp_forward.argtypes = [vp, i, vp, i, i, i, i, vp, vp, vp, vp]
-    lib.ssp_backward.argtypes = [vp, i, vp, vp, vp, vp]
-    lib.ssp_zero_grad.argtypes = [vp, vp]
-    lib.ssp_pair_step.argtypes = [vp, C.POINTER(SspPairInputs), vp, vp]
-    lib.ssp_adam_step.argtypes = [vp, f, i, vp]
-    lib.ssp_adam_step_scaled.argtypes = [vp, f, i, f, vp]
-    lib.ssp_pair_step_phase.argtypes = [vp, C.POINTER(SspPairInputs), vp, i, vp]
-    lib.ssp_pair_step_graph.argtypes = [vp, C.POINTER(SspPairInputs), vp, i, i, vp]
-    lib.ssp_grad_early_offset.argtypes = [vp]
-    lib.ssp_grad_early_offset.restype = C.c_size_t
-    lib.ssp_handle_set_conv_algo.argtypes = [vp, i]
-    lib.ssp_op_detector_loss.argtypes = [vp, i, vp, vp, i, i, i, vp, C.c_size_t, vp, vp, vp]
-    try:  # (newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_op_sem_loss.argtypes = [vp, i, vp, i, i, i, i, i, vp, C.c_size_t, vp, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    lib.ssp_sample_indices.argtypes = [vp, vp, i, C.c_uint64, vp, vp, vp, vp]
-    lib.ssp_sample_indices_cell.argtypes = [vp, vp, i, C.c_uint64, vp, vp, vp, vp]
-    lib.ssp_op_warp_labels_px.argtypes = [vp, vp, vp, i, i, i, vp]
-    lib.ssp_op_warp_labels_full_px.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp]
-    lib.ssp_profile_enable.argtypes = [vp, i]
-    lib.ssp_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
-                                     C.POINTER(C.c_double)]
-    lib.ssp_profile_read_executed.argtypes = [vp, C.POINTER(C.c_double)]
-    try:
-        lib.ssp_profile_pause.argtypes = [vp, i]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:
-        lib.ssp_profile_read_kernel.argtypes = [vp, i, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
-                                                C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    lib.ssp_op_conv.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, i, vp, C.c_size_t, vp]
-    lib.ssp_op_conv_wgrad.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, C.c_size_t, vp]
-    try:  # (the bf16 operators are newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_op_conv_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, i, i, i, vp, vp, vp, C.c_size_t, vp]
-        lib.ssp_op_conv_wgrad_bf16.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, vp, vp, i, vp, C.c_size_t, vp]
-        lib.ssp_op_bn_bwd_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    lib.ssp_debug_buffer.argtypes = [vp, i, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    if hasattr(lib, "ssp_debug_backward_taps"):  # (an A/B library of an older revision, SSP_HIP_LIB, lacks the taps)
-        lib.ssp_debug_backward_taps.argtypes = [vp, vp, C.c_size_t, C.c_uint]
-        lib.ssp_debug_backward_tap_floats.argtypes = [vp, C.c_uint]
-        lib.ssp_debug_backward_tap_floats.restype = C.c_size_t
-        lib.ssp_debug_backward_tap.argtypes = [vp, i, i, i, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint)]
-    lib.ssp_debug_conv_knobs.argtypes = [i, i]
-    lib.ssp_debug_occupancy.argtypes = [i]
-    lib.ssp_set_conv_algo.argtypes = [i]
-    lib.ssp_op_warp_image.argtypes = [vp, vp, vp, i, i, i, i, vp]
-    lib.ssp_op_erode.argtypes = [vp, vp, i, i, i, i, vp]
-    lib.ssp_op_warp_labels.argtypes = [vp, vp, vp, i, i, i, vp]
-    lib.ssp_op_bn_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
-    lib.ssp_op_bn_bwd_strided.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp]
-    lib.ssp_op_labels.argtypes = [vp, vp, vp, vp, i, i, i, vp]
-    lib.ssp_op_sparse_loss.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, C.c_float, C.c_float, vp, vp, vp, vp]
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_op_sparse_loss_path.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, C.c_float, C.c_float, vp, vp, vp, i, vp, vp, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    ep = C.POINTER(SspExportParams)
-    lib.ssp_export_workspace_bytes.argtypes = [ep]
-    lib.ssp_export_workspace_bytes.restype = C.c_size_t
-    lib.ssp_export_max_points.argtypes = [ep]
-    lib.ssp_export_points.argtypes = [vp, ep, i] + [C.POINTER(vp)] * 7 + [vp]
-    lib.ssp_op_homoadapt_views.argtypes = [vp, vp, vp, vp, i, i, i, vp]
-    lib.ssp_op_flatten_detection.argtypes = [vp, vp, vp, i, i, i, vp]
-    lib.ssp_op_combine_heatmap.argtypes = [vp, vp, vp, vp, i, i, i, vp]
-    lib.ssp_op_heatmap_points.argtypes = [vp, ep, vp, vp, vp, vp]
-    lib.ssp_op_soft_argmax_points.argtypes = [vp, vp, vp, i, i, i, vp]
-    lib.ssp_detector_heatmap.argtypes = [vp, i, vp, vp]
-    lib.ssp_op_heatmap_nms.argtypes = [vp, ep, i, vp, vp, vp, vp, vp]
-    lib.ssp_op_sample_homographies.argtypes = [C.c_uint64, C.POINTER(SspHomographyParams), i, vp, vp, vp]
-    lib.ssp_op_warp_labels_full.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp]
-    lib.ssp_op_sem_finalize.argtypes = [vp, vp, vp, C.c_size_t, i, vp]
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_op_photometric_draw.argtypes = [C.c_uint64, C.POINTER(SspPhotometricParams), i, i, i, vp, vp]
-        lib.ssp_op_photometric_apply.argtypes = [vp, vp, vp, i, i, i, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        sp = C.POINTER(SspShapesParams)
-        lib.ssp_shapes_workspace_bytes.argtypes = [sp, i]
-        lib.ssp_shapes_workspace_bytes.restype = C.c_size_t
-        lib.ssp_op_shapes_draw.argtypes = [C.c_uint64, sp, i, vp, vp]
-        lib.ssp_op_shapes_render.argtypes = [vp, sp, i, vp, vp, vp, vp, vp]
-        lib.ssp_op_warp_points_scatter.argtypes = [vp, vp, vp, vp, i, i, i, i, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_op_label_quantize.argtypes = [vp, vp, C.c_size_t, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    lib.ssp_op_dense_loss.argtypes = [vp, vp, vp, vp, i, i, i, f, f, i, f, vp, C.c_size_t, vp, vp, vp, vp]
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_op_sem_predict.argtypes = [vp, i, vp, i, i, i, i, vp, vp, vp]
-        lib.ssp_sem_predict.argtypes = [vp, i, vp, vp, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_describe_workspace_bytes.argtypes = [ep, i]
-        lib.ssp_describe_workspace_bytes.restype = C.c_size_t
-        lib.ssp_describe_points.argtypes = [vp, i, ep, i, vp, vp, vp, vp, vp]
-        lib.ssp_op_sample_descriptors.argtypes = [vp, i, i, i, vp, vp, i, vp, vp]
-        lib.ssp_match_workspace_bytes.argtypes = [i, i]
-        lib.ssp_match_workspace_bytes.restype = C.c_size_t
-        lib.ssp_match_two_way.argtypes = [vp, vp, vp, vp, i, i, i, f, vp, vp, vp, vp]
-        lib.ssp_eval_repeatability.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, i, i, i, C.c_double, vp, vp]
-        lib.ssp_eval_ransac_workspace_bytes.argtypes = [i, i]
-        lib.ssp_eval_ransac_workspace_bytes.restype = C.c_size_t
-        lib.ssp_eval_ransac.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_track_workspace_bytes.argtypes = [i, i, i]
-        lib.ssp_track_workspace_bytes.restype = C.c_size_t
-        lib.ssp_op_track_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp]
-        lib.ssp_op_track_select.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]
-        lib.ssp_op_track_points.argtypes = [vp, vp, vp, vp, i, i, i, i, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_op_point_classes.argtypes = [vp, i, i, i, i, i, vp, i, vp, i, vp, vp]
-        lib.ssp_point_classes.argtypes = [vp, i, i, vp, i, vp, i, vp, vp]
-        lib.ssp_filter_workspace_bytes.argtypes = [i, i]
-        lib.ssp_filter_workspace_bytes.restype = C.c_size_t
-        lib.ssp_op_filter_points.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_uint32), i, i, vp, vp, vp, vp, vp, vp]
-        lib.ssp_match_two_way_classes.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, f, vp, vp, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        dp = C.POINTER(SspDetEvalParams)
-        lib.ssp_det_eval_workspace_bytes.argtypes = [dp, i, i]
-        lib.ssp_det_eval_workspace_bytes.restype = C.c_size_t
-        lib.ssp_op_det_tp_fp.argtypes = [vp, vp, i, dp, i, vp, vp, C.c_int64, vp, vp]
-        lib.ssp_op_det_tp_fp_points.argtypes = [vp, vp, i, vp, i, dp, i, vp, vp, C.c_int64, vp, vp]
-        lib.ssp_det_pr_curve_workspace_bytes.argtypes = [C.c_int64]
-        lib.ssp_det_pr_curve_workspace_bytes.restype = C.c_size_t
-        lib.ssp_op_det_pr_curve.argtypes = [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_epi_ransac_workspace_bytes.argtypes = [i, i]
-        lib.ssp_epi_ransac_workspace_bytes.restype = C.c_size_t
-        lib.ssp_epi_ransac.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, C.c_double, i, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.ssp_op_filter_matches.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_pose_from_fundamental.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, i] + [vp] * 11
-        lib.ssp_pose_chain.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp, i, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_landmark_workspace_bytes.argtypes = [i, i]
-        lib.ssp_landmark_workspace_bytes.restype = C.c_size_t
-        lib.ssp_map_window.argtypes = [vp, vp, i, vp, i, i, i, vp, vp]
-        lib.ssp_op_triangulate_tracks.argtypes = [vp, vp, vp, i, vp, i, i, i, i, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
-        lib.ssp_op_landmarks_select.argtypes = [vp] * 8 + [i, i, i, vp, vp, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_pnp_workspace_bytes.argtypes = [i]
-        lib.ssp_pnp_workspace_bytes.restype = C.c_size_t
-        lib.ssp_op_landmark_matches.argtypes = [vp, vp, i, vp, vp, i, vp, i, i, vp, vp, vp]
-        lib.ssp_pnp_ransac.argtypes = [vp, vp, i, i, vp, i, vp, C.c_double, i, i] + [vp] * 9
-        lib.ssp_pose_repair.argtypes = [vp, vp, vp, i, vp, vp, i, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_ba_workspace_bytes.argtypes = [i, i]
-        lib.ssp_ba_workspace_bytes.restype = C.c_size_t
-        lib.ssp_bundle_adjust.argtypes = [vp, vp, vp, i, vp, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp]
-        lib.ssp_ba_apply.argtypes = [vp, vp, i, i, i, vp, vp, i, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_world_insert_workspace_bytes.argtypes = [i]
-        lib.ssp_world_insert_workspace_bytes.restype = C.c_size_t
-        lib.ssp_match_world_workspace_bytes.argtypes = [i, i]
-        lib.ssp_match_world_workspace_bytes.restype = C.c_size_t
-        lib.ssp_op_world_insert.argtypes = [vp, vp, i, vp, vp, i, vp, i, i, i, i, i] + [vp] * 11
-        lib.ssp_match_world.argtypes = [vp, vp, i, vp, vp, i, C.c_float, vp, vp, vp, vp]
-        lib.ssp_op_world_correspondences.argtypes = [vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, vp]
-        lib.ssp_world_repair.argtypes = [vp, vp, vp, vp, vp, i, i, vp, vp]
-        lib.ssp_pose_graph_workspace_bytes.argtypes = [i]
-        lib.ssp_pose_graph_workspace_bytes.restype = C.c_size_t
-        lib.ssp_op_loop_correspondences.argtypes = [vp, vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, i, i, i, vp, vp, vp, vp]
-        lib.ssp_loop_edge.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, i, i, i, i, C.c_double, vp, vp, vp, vp]
-        lib.ssp_pose_graph.argtypes = [vp, i, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
-        lib.ssp_loop_apply.argtypes = [vp, vp, vp, vp, vp, i, vp, vp, i, vp, vp, vp, i, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
-    try:  # (entry points newer than an A/B library of an older revision, SSP_HIP_LIB)
-        lib.ssp_eval_pixel_homographies.argtypes = [vp, i, i, i, vp, vp, vp]
-        lib.ssp_eval_accumulate.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, i, i, C.POINTER(C.c_double), C.c_int64, vp,
-                                            C.c_int64, vp, vp]
-    except AttributeError:
-        if os.environ.get("SSP_HIP_LIB") is None:
-            raise
+    for name, (argtypes, restype) in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # (an A/B library of an older revision, SSP_HIP_LIB, may lack the newer entry points)
+            if os.environ.get("SSP_HIP_LIB") is None:
+                raise
+            continue
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = lib
     return lib
 
@@ -449,7 +327,6 @@ def clock_probe(ms=5.0):
     lib = load_library()
     if not hasattr(lib, "ssp_clock_probe"):
         return None
-    lib.ssp_clock_probe.argtypes = [C.c_float, C.POINTER(C.c_double), C.c_void_p]
     out = C.c_double(0.0)
     _check(lib.ssp_clock_probe(float(ms), C.byref(out), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return float(out.value)

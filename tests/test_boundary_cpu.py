@@ -28,6 +28,21 @@ def test_library_exports_every_declared_symbol():
     assert sorted(ssp.lib.EXPORTS) == declared
 
 
+def test_signatures_have_the_declared_number_of_parameters():
+    """lib.SIGNATURES against include/ssp_hip.h: one entry per declared function, as many argtypes as the declaration has
+    parameters ((void) counts as 0).  A call through ctypes with one argument too few or too many is not caught anywhere else."""
+    import semantic_superpoint_amd as ssp
+    hdr = open(os.path.join(ROOT, "include", "ssp_hip.h")).read()
+    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    declared = re.findall(r"\b(ssp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert len(declared) >= 120 and len({n for n, _ in declared}) == len(declared)
+    assert [n for n, _ in declared] == list(ssp.lib.SIGNATURES)
+    for name, params in declared:
+        want = 0 if params.strip() in ("void", "") else len(params.split(","))
+        assert len(ssp.lib.SIGNATURES[name][0]) == want, (name, len(ssp.lib.SIGNATURES[name][0]), want)
+    assert ssp.lib.EXPORTS == list(ssp.lib.SIGNATURES)
+
+
 def test_library_is_built_from_the_checked_out_sources():
     """The build id compiled into the in-tree library (sha256 over csrc/*.hip, csrc/*.hip.h, include/ssp_hip.h) equals the hash of
     the sources as checked out: the binary under test is HEAD's, by content (not by modification time)."""

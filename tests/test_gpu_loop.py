@@ -485,6 +485,67 @@ def test_trackers_loop_closure(through, which):
         print("apply: map X against the restated tracker %.3e" % float(np.abs(rows_dev[:, 1:4] - want_rows[:, 1:4]).max()))
 
 
+CHECK_POSE_KEYS = {"F", "mask", "n_inliers", "status", "winner", "err", "R", "t", "E", "cand", "counts", "n_front", "pose_status", "front",
+                   "depth", "X"}
+ABS_KEYS = {"abs_" + k for k in ("Rw", "C", "mask", "n_inliers", "winner", "rms", "status", "corr", "n_corr")}
+WORLD_KEYS = {"world_" + k for k in ("Rw", "C", "mask", "n_inliers", "winner", "rms", "status", "corr", "n_corr", "match", "n_match")}
+
+
+@pytest.mark.parametrize("through", ["PointTracker", "SequenceTracker"])
+def test_trackers_all_stages_together(through):
+    """One tracker with every stage over loop_ref's closed circuit: absolute_pose="repair", bundle_adjust="apply",
+    world_map="relocalise", loop_closure="observe".  This pins the order of a step: the kept landmarks (_abs_lm) and the inserted
+    landmarks (_world_lm) are both computed after the bundle adjustment's write-back, so each equals, bit for bit, what
+    landmarks_device gives after the update (the observing loop closure writes nothing in between).  The map rows seen in the
+    newest frame are copies of those rows, last_geometry() holds every stage's keys, and a step makes no host synchronisation."""
+    from semantic_superpoint_amd.export import PointTracker, SequenceTracker
+    from tests import world_ref as W
+    dev = _dev()
+    seq = G.circuit_sequence(G.CIRCUIT_DEVICE_SEED)
+    frames = len(seq["pts"])
+    kw = dict(geometric_check="fundamental", check_seed=G.CIRCUIT_SEED0, intrinsics=tuple(seq["intr"][0]), trajectory_rows=frames + 1,
+              absolute_pose="repair", bundle_adjust="apply", world_map="relocalise", world_cap=4096, loop_closure="observe",
+              loop_min_gap=G.CIRCUIT_GAP, loop_min_inliers=G.CIRCUIT_MIN_INLIERS, loop_cooldown=32)
+    if through == "PointTracker":
+        top = tr = PointTracker(G.CIRCUIT_L, W.NN_THRESH, dev, **kw)
+    else:
+        top = SequenceTracker(None, dev, 0.015, 4, False, W.NN_THRESH, G.CIRCUIT_L, **kw)             # fed through its tracker: no network
+        tr = top.tracker
+    seen = 0
+    for f in range(frames):
+        xy = seq["pts"][f]
+        frame = (_t(xy.reshape(-1, 2), dev), torch.tensor([xy.shape[0]], dtype=torch.int32, device=dev),
+                 _t(np.asarray(seq["desc"][f], dtype=np.float32).reshape(-1, 256), dev))
+        if f >= 2:                                                       # (the first frames allocate)
+            torch.cuda.set_sync_debug_mode("error")
+            try:
+                tr.update_device(*frame)
+            finally:
+                torch.cuda.set_sync_debug_mode("default")
+        else:
+            tr.update_device(*frame)
+        if f < 1:
+            continue
+        assert set(tr.last_geometry()) == CHECK_POSE_KEYS | ABS_KEYS | WORLD_KEYS | LOOP_KEYS | {"ba_info"}, f
+        lms, n_lms = top.landmarks_device(*tr.landmark_params)
+        n = int(n_lms)
+        for name, own in (("_abs_lm", tr._abs_lm), ("_world_lm", tr._world_lm)):
+            assert own["landmarks"] is not lms                          # the tracker's own buffers, not landmarks_device's
+            assert torch.equal(own["n_landmarks"], n_lms), (f, name)
+            assert torch.equal(own["landmarks"][:n], lms[:n]), (f, name)
+        # the rows seen in the newest frame are copies of the landmark rows the tracker kept for the insert
+        rows, _ = top.world_map()
+        by_tid = {int(r[0]): r for r in lms[:n].cpu().numpy()}
+        newest = rows[rows[:, 7] == f]
+        seen += len(newest)
+        for r in newest:
+            assert np.array_equal(r[1:4], by_tid[int(r[0])][1:4]) and r[5] == by_tid[int(r[0])][5] and r[4] == by_tid[int(r[0])][4]
+    ba = top.bundle_adjusted()
+    print("%s: %d landmarks at the end, %d map rows written in their frames, ba_info %s, flags %s, closures %s"
+          % (through, n, seen, ba[3].tolist(), tr.trajectory()[0][:frames, 14].tolist(), top.loop_closures().tolist()))
+    assert seen >= 12 and n >= 12 and ba is not None
+
+
 def test_trackers_refuse_a_loop_closure_without_a_map():
     from semantic_superpoint_amd.export import PointTracker, SequenceTracker
     dev = _dev()

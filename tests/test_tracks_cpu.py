@@ -163,3 +163,83 @@ def test_c_entry_points_refuse_bad_arguments():
     assert pts(first=5) != 0 and "first_slot" in err()
     assert pts(tracks=None) != 0 and "null pointer" in err()
     assert pts() != 0 and "null pointer" in err()
+
+
+# ---- the trackers' constructor: every refusal of the test_trackers_refuse_* GPU tests, with its message ---------------------------
+_A, _B = (300.0, 300.0, 160.0, 120.0), (310.0, 300.0, 160.0, 120.0)
+_FA = dict(geometric_check="fundamental", intrinsics=_A)
+_MAP = dict(_FA, world_map="observe")
+_ONE = " needs ONE camera: a fixed (previous, new) pair of different intrinsics cannot describe more than two views"
+_LANDMARKS_FROM = " needs intrinsics and geometric_check='fundamental': the landmarks come from the trajectory's cameras"
+_CAMERAS_FROM = " needs intrinsics and geometric_check='fundamental': the cameras come from the trajectory"
+_PARAMS = "landmark_params must be (min_views >= 2, min_parallax_deg, max_reproj)"
+_WORLD_P = "world_thresh must be finite and non-negative, world_min_inliers at least 4"
+_WORLD_C = "1 <= world_cap <= 65536 and world_patience >= 0 required"
+_BA = "1 <= bundle_iterations <= 16 and bundle_every >= 1 required"
+_ABS = "absolute_thresh must be finite and non-negative, absolute_min_inliers at least 4"
+_LOOP = "loop_min_gap must be at least 1, loop_min_inliers at least 4, loop_cooldown non-negative"
+
+
+def _needs(option, tail):
+    """The four cases every stage shares: no intrinsics (three ways), two different cameras."""
+    return [(dict({option: "observe"}, **kw), option + tail) for kw in (dict(), dict(geometric_check="fundamental"),
+                                                                         dict(geometric_check="homography"))] \
+        + [(dict(geometric_check="fundamental", intrinsics=(_A, _B), **{option: "observe"}), option + _ONE)]
+
+
+REFUSALS = _needs("world_map", _LANDMARKS_FROM) + [
+    (dict(_MAP, world_min_inliers=3), _WORLD_P), (dict(_MAP, world_thresh=-1.0), _WORLD_P), (dict(_MAP, world_cap=0), _WORLD_C),
+    (dict(_MAP, world_cap=65537), _WORLD_C), (dict(_MAP, world_patience=-1), _WORLD_C),
+    (dict(_FA, world_map="always"), "world_map must be None, 'observe' or 'relocalise' (got 'always')"),
+] + _needs("bundle_adjust", _CAMERAS_FROM) + [
+    (dict(_FA, bundle_adjust="observe", bundle_iterations=0), _BA), (dict(_FA, bundle_adjust="observe", bundle_iterations=17), _BA),
+    (dict(_FA, bundle_adjust="observe", bundle_every=0), _BA), (dict(_FA, bundle_adjust="observe", landmark_params=(1, 1.0, 2.0)), _PARAMS),
+    (dict(_FA, bundle_adjust="always"), "bundle_adjust must be None, 'observe' or 'apply' (got 'always')"),
+] + _needs("absolute_pose", _LANDMARKS_FROM) + [
+    (dict(_FA, absolute_pose="observe", absolute_min_inliers=3), _ABS), (dict(_FA, absolute_pose="observe", absolute_thresh=-1.0), _ABS),
+    (dict(_FA, absolute_pose="observe", landmark_params=(1, 1.0, 2.0)), _PARAMS),
+    (dict(_FA, absolute_pose="always"), "absolute_pose must be None, 'observe' or 'repair' (got 'always')"),
+    (dict(_FA, loop_closure="observe"), "loop_closure needs world_map: the closure is detected from the frame's matches against the map"),
+    (dict(_MAP, loop_closure="observe", loop_min_gap=0), _LOOP), (dict(_MAP, loop_closure="observe", loop_min_inliers=3), _LOOP),
+    (dict(_MAP, loop_closure="observe", loop_cooldown=-1), _LOOP),
+    (dict(_MAP, loop_closure="observe", loop_iterations=0), "1 <= loop_iterations <= 64 required"),
+    (dict(_MAP, loop_closure="observe", loop_weight=0.0), "loop_weight must be finite and positive"),
+    (dict(_MAP, loop_closure="observe", trajectory_rows=1), "loop_closure needs trajectory_rows >= 2"),
+    (dict(_MAP, loop_closure="always"), "loop_closure must be None, 'observe' or 'apply' (got 'always')"),
+    # the order of the checks: the map, the loop closure, the absolute pose, the bundle adjustment
+    (dict(world_map="always", loop_closure="always", absolute_pose="always", bundle_adjust="always"),
+     "world_map must be None, 'observe' or 'relocalise' (got 'always')"),
+    (dict(_FA, loop_closure="always", absolute_pose="always", bundle_adjust="always"),
+     "loop_closure must be None, 'observe' or 'apply' (got 'always')"),
+    (dict(absolute_pose="observe", bundle_adjust="observe"), "absolute_pose" + _LANDMARKS_FROM),
+    (dict(_MAP, world_min_inliers=3, landmark_params=(1, 1.0, 2.0)), _WORLD_P),
+]
+
+
+@pytest.mark.parametrize("through", ["PointTracker", "SequenceTracker"])
+@pytest.mark.parametrize("case", range(len(REFUSALS)))
+def test_trackers_refuse_with_the_same_messages(through, case):
+    """The constructor raises before any device work: the exception and its text for every refused combination."""
+    from semantic_superpoint_amd.export import PointTracker, SequenceTracker
+    kw, message = REFUSALS[case]
+    with pytest.raises(ValueError) as e:
+        PointTracker(3, 0.7, "cpu", **kw) if through == "PointTracker" else SequenceTracker(None, "cpu", 0.015, 4, False, 0.7, 3, **kw)
+    assert str(e.value) == message
+
+
+def test_landmark_calls_refuse_with_the_same_messages():
+    from semantic_superpoint_amd.export import PointTracker, SequenceTracker
+    need = "landmarks need intrinsics (and geometric_check='fundamental'): the cameras come from the trajectory"
+    one = ("landmarks need ONE camera: a fixed (previous, new) pair of different intrinsics cannot describe more than two views "
+           "(lib.op_map_window takes per-frame intrinsics)")
+    for make in (lambda **kw: PointTracker(3, 0.7, "cpu", **kw), lambda **kw: SequenceTracker(None, "cpu", 0.015, 4, False, 0.7, 3, **kw)):
+        for kw, message in ((dict(), need), (dict(geometric_check="fundamental"), need),
+                            (dict(geometric_check="fundamental", intrinsics=(_A, _B)), one),
+                            (dict(geometric_check="fundamental", intrinsics=(_A, _A), min_views=1), "min_views >= 2 required (got 1)")):
+            kw = dict(kw)
+            min_views = kw.pop("min_views", 2)
+            t = make(**kw)
+            for call in (t.landmarks, t.landmarks_device, t.landmark_rows_device):
+                with pytest.raises(ValueError) as e:
+                    call(min_views)
+                assert str(e.value) == message
