@@ -1,7 +1,7 @@
 // Windowed bundle adjustment: the cameras of the retained frames inside the newest consistent window and the
 // accepted rows of the N-view triangulation (section 26) refined together by Levenberg-Marquardt on the pixel reprojection error,
 // the points eliminated by the Schur complement.  The rules are restated in numpy by tests/ba_ref.py; everything here is fp64 with
-// contraction off, in the parenthesisation of that file, and every sum over the rows runs in one fixed order (eval_block_sum's
+// contraction off, in the parenthesisation of that file, and every sum over the rows runs in one fixed order (block_sum's
 // inside a tile of 256 rows, the tiles ascending), so a result does not depend on row_cap, on the order the workgroups run in or
 // on the run.  No floating-point atomics, no grid-wide barrier: every phase is a launch of its own, and what a phase decides
 // (accept / reject, done) the next one reads from device memory.
@@ -14,7 +14,7 @@
 //                        arithmetic and the butterfly.
 //   ba_solve_kernel      one workgroup: the tile partials summed in tile order into the 6L x (6L + 1) system in LDS, damping, the
 //                        gauge, Cholesky without pivoting (right-looking: every element's updates come in the order of k), the
-//                        step and the candidate cameras (section 27's Cayley update and renormalisation)
+//                        step and the candidate cameras (cayley_update: section 27's update and renormalisation)
 //   ba_backsub_kernel    per row dX = V^-1 (-g_r - sum W^T d_c), the candidate point, its cost and cheirality under the candidate
 //                        cameras, summed per tile
 //   ba_accept_kernel     every workgroup reads the same sums and takes the same decision; an accepted step copies the candidates;
@@ -22,6 +22,8 @@
 //                        one launch)
 //   ba_finish_kernel     rms_out and info
 //   ba_apply_kernel      a thread per sequence: the adjusted cameras written back into the trajectory table and the chain state
+// Needs: geom_blocks.hip.h, pose_kernels.hip.h (POSE_ROW_WORDS, POSE_STATE_WORDS), landmark_kernels.hip.h (the staged tile, LM_*),
+// pnp_kernels.hip.h (PNP_SCALE_FRACTION, PNP_THREADS).
 #pragma once
 
 namespace sspk {
@@ -132,19 +134,17 @@ __device__ __forceinline__ double2 ba_pixel(const BaStage& s, const double* __re
   return *reinterpret_cast<const double2*>(pts + ((size_t)((first_slot + c) % L) * point_cap + p) * 2);
 }
 
-// One view: y = Rw (X - C), the residual, the point Jacobians p0, p1 and the camera Jacobians j0, j1 over (w, dC).
+// One view: project's y = Rw (X - C) and residual, the point Jacobians p0, p1 and the camera Jacobians j0, j1 over (w, dC).
 struct BaView {
   double y2, r0, r1, p0[3], p1[3], j0[6], j1[6];
 };
 __device__ __forceinline__ void ba_view(const double* cam, double X0, double X1, double X2, double2 px, BaView& o) {
 #pragma clang fp contract(off)
-  const double q0 = X0 - cam[9], q1 = X1 - cam[10], q2 = X2 - cam[11];
-  const double y0 = pose_dot(cam[0], cam[1], cam[2], q0, q1, q2), y1 = pose_dot(cam[3], cam[4], cam[5], q0, q1, q2);
-  const double y2 = pose_dot(cam[6], cam[7], cam[8], q0, q1, q2);
-  const double un = y0 / y2, vn = y1 / y2, fa = cam[12] / y2, fb = cam[13] / y2;
+  const View w = project(cam, X0, X1, X2, px.x, px.y);
+  const double y0 = w.y0, y1 = w.y1, y2 = w.y2, un = w.u, vn = w.v, fa = cam[12] / y2, fb = cam[13] / y2;
   o.y2 = y2;
-  o.r0 = (cam[12] * un + cam[14]) - px.x;
-  o.r1 = (cam[13] * vn + cam[15]) - px.y;
+  o.r0 = w.r0;
+  o.r1 = w.r1;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     o.p0[k] = fa * (cam[k] - un * cam[6 + k]);
@@ -163,15 +163,16 @@ __device__ __forceinline__ void ba_view(const double* cam, double X0, double X1,
 // the residual alone: squared error and whether the point is in front
 __device__ __forceinline__ double ba_error(const double* cam, double X0, double X1, double X2, double2 px, bool& front) {
 #pragma clang fp contract(off)
-  const LmView w = lm_view(cam, X0, X1, X2, px.x, px.y);
+  const View w = project(cam, X0, X1, X2, px.x, px.y);
   front = isfinite(w.y2) && w.y2 > 0.0;
   return w.r0 * w.r0 + w.r1 * w.r1;
 }
 
 // The point block of a row under the cameras in s.cam: cofactors and determinant of the damped V_r, g_r, z = V_r^-1 g_r, the sum
-// of the squared residuals; ok by lm_solve3's refusal rule.
+// of the squared residuals; ok by cof3_solve's refusal rule.
 struct BaPoint {
-  double c00, c01, c02, c11, c12, c22, det, g0, g1, g2, z0, z1, z2, ss;
+  Cof3 c;
+  double g0, g1, g2, z0, z1, z2, ss;
   bool ok;
 };
 __device__ __forceinline__ void ba_point(const BaStage& s, const double* __restrict__ pts, int first_slot, int L, int point_cap,
@@ -195,25 +196,15 @@ __device__ __forceinline__ void ba_point(const BaStage& s, const double* __restr
     ss = ss + (v.r0 * v.r0 + v.r1 * v.r1);
   }
   const double damp = 1.0 + lambda;
-  const double a00 = h00 * damp, a01 = h01, a02 = h02, a11 = h11 * damp, a12 = h12, a22 = h22 * damp;
-  o.c00 = a11 * a22 - a12 * a12;
-  o.c01 = a02 * a12 - a01 * a22;
-  o.c02 = a01 * a12 - a02 * a11;
-  o.c11 = a00 * a22 - a02 * a02;
-  o.c12 = a01 * a02 - a00 * a12;
-  o.c22 = a00 * a11 - a01 * a01;
-  o.det = pose_dot(a00, a01, a02, o.c00, o.c01, o.c02);
+  o.c = cofactors3(h00 * damp, h01, h02, h11 * damp, h12, h22 * damp);
   o.g0 = g0;
   o.g1 = g1;
   o.g2 = g2;
-  o.z0 = pose_dot(o.c00, o.c01, o.c02, g0, g1, g2) / o.det;
-  o.z1 = pose_dot(o.c01, o.c11, o.c12, g0, g1, g2) / o.det;
-  o.z2 = pose_dot(o.c02, o.c12, o.c22, g0, g1, g2) / o.det;
+  o.ok = cof3_solve(o.c, LM_DET_EPS, g0, g1, g2, o.z0, o.z1, o.z2);
   o.ss = ss;
-  o.ok = isfinite(o.det) && o.det > LM_DET_EPS * ((a00 * a11) * a22) && isfinite(o.z0) && isfinite(o.z1) && isfinite(o.z2);
 }
 
-// N values summed over the workgroup in eval_block_sum's order (the xor butterfly inside each wave, the wave partials in wave
+// N values summed over the workgroup in block_sum's order (wave_sum inside each wave, the wave partials in wave
 // order) and stored by the first N threads.  `wave_has`: some lane of this wave contributes (else the wave's partial is the zero
 // its butterfly would give).  The caller has a barrier between two uses of `red`.
 template <int N>
@@ -221,9 +212,7 @@ __device__ __forceinline__ void ba_block_store(double (&v)[N], bool wave_has, do
 #pragma clang fp contract(off)
   if (wave_has) {
 #pragma unroll
-    for (int e = 0; e < N; ++e)
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) v[e] = v[e] + __shfl_xor(v[e], o);
+    for (int e = 0; e < N; ++e) v[e] = wave_sum(v[e]);
   }
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -337,10 +326,10 @@ __global__ __launch_bounds__(BA_THREADS) void ba_linearise_kernel(const int32_t*
           m[21 + a] = v.j0[a] * v.r0 + v.j1[a] * v.r1;
           const double w0 = v.j0[a] * v.p0[0] + v.j1[a] * v.p1[0], w1 = v.j0[a] * v.p0[1] + v.j1[a] * v.p1[1];
           const double w2 = v.j0[a] * v.p0[2] + v.j1[a] * v.p1[2];
-          m[27 + a] = pose_dot(w0, w1, w2, pt.z0, pt.z1, pt.z2);
-          Y[a][0] = pose_dot(w0, w1, w2, pt.c00, pt.c01, pt.c02) / pt.det;
-          Y[a][1] = pose_dot(w0, w1, w2, pt.c01, pt.c11, pt.c12) / pt.det;
-          Y[a][2] = pose_dot(w0, w1, w2, pt.c02, pt.c12, pt.c22) / pt.det;
+          m[27 + a] = dot3(w0, w1, w2, pt.z0, pt.z1, pt.z2);
+          Y[a][0] = dot3(w0, w1, w2, pt.c.c00, pt.c.c01, pt.c.c02) / pt.c.det;
+          Y[a][1] = dot3(w0, w1, w2, pt.c.c01, pt.c.c11, pt.c.c12) / pt.c.det;
+          Y[a][2] = dot3(w0, w1, w2, pt.c.c02, pt.c.c12, pt.c.c22) / pt.c.det;
         }
       }
       ba_block_store(m, wave_act, s.red, out_cam + 33 * c);
@@ -364,7 +353,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_linearise_kernel(const int32_t*
           const double w0 = v.j0[b] * v.p0[0] + v.j1[b] * v.p1[0], w1 = v.j0[b] * v.p0[1] + v.j1[b] * v.p1[1];
           const double w2 = v.j0[b] * v.p0[2] + v.j1[b] * v.p1[2];
 #pragma unroll
-          for (int a = 0; a < 6; ++a) E[6 * a + b] = pose_dot(Y[a][0], Y[a][1], Y[a][2], w0, w1, w2);
+          for (int a = 0; a < 6; ++a) E[6 * a + b] = dot3(Y[a][0], Y[a][1], Y[a][2], w0, w1, w2);
         }
       }
       ba_block_store(E, wave_both, s.red, out_pairs + 36 * c2);
@@ -489,7 +478,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_solve_kernel(const double* __re
     __syncthreads();
     bool fin = true;
     for (int i = tid; i < N; i += BA_THREADS) fin = fin && isfinite(ba_sys[i * ld + N]);
-    // the candidate cameras: a view held whole is copied, every other one takes section 27's Cayley update and renormalisation
+    // the candidate cameras: a view held whole is copied, every other one takes cayley_update
     if (tid < L) {
       const int c = tid;
       const double* cam = cams + c * LM_CAM_WORDS;
@@ -500,7 +489,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_solve_kernel(const double* __re
         const double delta[6] = {ba_sys[(6 * c) * ld + N], ba_sys[(6 * c + 1) * ld + N], ba_sys[(6 * c + 2) * ld + N], 0.0, 0.0, 0.0};
 #pragma unroll
         for (int e = 0; e < 9; ++e) R[e] = cam[e];
-        fin = pnp_cayley_update(R, t, delta) && fin;
+        fin = cayley_update(R, t, delta) && fin;
 #pragma unroll
         for (int e = 0; e < 9; ++e) o[e] = R[e];
 #pragma unroll
@@ -574,9 +563,9 @@ __global__ __launch_bounds__(BA_THREADS) void ba_backsub_kernel(const int32_t* _
         t2 = t2 + w[2];
       }
       const double b0 = (0.0 - pt.g0) - t0, b1 = (0.0 - pt.g1) - t1, b2 = (0.0 - pt.g2) - t2;
-      X0 = X0 + pose_dot(pt.c00, pt.c01, pt.c02, b0, b1, b2) / pt.det;
-      X1 = X1 + pose_dot(pt.c01, pt.c11, pt.c12, b0, b1, b2) / pt.det;
-      X2 = X2 + pose_dot(pt.c02, pt.c12, pt.c22, b0, b1, b2) / pt.det;
+      X0 = X0 + dot3(pt.c.c00, pt.c.c01, pt.c.c02, b0, b1, b2) / pt.c.det;
+      X1 = X1 + dot3(pt.c.c01, pt.c.c11, pt.c.c12, b0, b1, b2) / pt.c.det;
+      X2 = X2 + dot3(pt.c.c02, pt.c.c12, pt.c.c22, b0, b1, b2) / pt.c.det;
     }
     x_cand[(size_t)row * 3] = X0;
     x_cand[(size_t)row * 3 + 1] = X1;
@@ -730,7 +719,7 @@ __global__ __launch_bounds__(64) void ba_apply_kernel(const double* __restrict__
     const double* prev = cam - LM_CAM_WORDS;                 // (c >= 1: a valid view came before)
     if (prev[16] != 0.0) {
       const double d0 = cam[9] - prev[9], d1 = cam[10] - prev[10], d2 = cam[11] - prev[11];
-      const double len = sqrt(pose_dot(d0, d1, d2, d0, d1, d2));
+      const double len = sqrt(dot3(d0, d1, d2, d0, d1, d2));
       if (isfinite(len) && len > PNP_SCALE_FRACTION * row[12]) row[12] = len;
     }
     if (c == L - 1 && count == n && n < capacity) {
@@ -738,7 +727,7 @@ __global__ __launch_bounds__(64) void ba_apply_kernel(const double* __restrict__
 #pragma unroll
       for (int k = 0; k < 9; ++k) st[2 + k] = cam[k];
 #pragma unroll
-      for (int i = 0; i < 3; ++i) st[11 + i] = -pose_dot(cam[3 * i], cam[3 * i + 1], cam[3 * i + 2], cam[9], cam[10], cam[11]);
+      for (int i = 0; i < 3; ++i) st[11 + i] = -dot3(cam[3 * i], cam[3 * i + 1], cam[3 * i + 2], cam[9], cam[10], cam[11]);
     }
   }
 }

@@ -20,7 +20,8 @@
 //
 // The curve over the sorted keys is five launches: tp counts per tile, their scan, precision / recall per record (fp64,
 // contraction off) with the tile maxima, the suffix maxima of the tiles, and the right-to-left running maximum with the
-// per-tile mAP terms; one workgroup then sums the tile terms in a fixed order.
+// per-tile mAP terms; one workgroup then sums the tile terms in a fixed order (block_sum).
+// Needs: geom_blocks.hip.h.
 #pragma once
 
 namespace sspk {
@@ -42,29 +43,6 @@ struct DetParams {
 
 __device__ __forceinline__ bool det_label(const void* __restrict__ labels, int u8, size_t idx) {
   return u8 ? reinterpret_cast<const uint8_t*>(labels)[idx] != 0 : reinterpret_cast<const float*>(labels)[idx] != 0.f;
-}
-
-// Exclusive prefix of v over the workgroup's threads and the workgroup total (all DET_BLOCK threads call it); wsum: 16 ints.
-__device__ __forceinline__ int det_block_scan(int v, int* wsum, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o);
-    if (lane >= o) incl += t;
-  }
-  __syncthreads();
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < DET_BLOCK / 64; ++w) {
-    const int s = wsum[w];
-    off += w < wave ? s : 0;
-    tot += s;
-  }
-  total = tot;
-  return off + incl - v;
 }
 
 // Exclusive SUFFIX maximum of v >= 0 over the workgroup's threads (0 for the last) and the workgroup maximum; lds: DET_BLOCK doubles.
@@ -166,7 +144,7 @@ __global__ __launch_bounds__(DET_BLOCK) void det_match_kernel(const float* __res
   }
   if (e < total) gidx[e] = g;
   int tot;
-  det_block_scan(g != -2 ? 1 : 0, wsum, tot);
+  block_scan<DET_BLOCK>(g != -2 ? 1 : 0, wsum, tot);
   if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
 
@@ -178,7 +156,7 @@ __global__ __launch_bounds__(DET_BLOCK) void det_offsets_kernel(const int32_t* _
     const int k = k0 + threadIdx.x;
     const int v = k < nb ? sums[k] : 0;
     int tot;
-    const int ex = det_block_scan(v, wsum, tot);
+    const int ex = block_scan<DET_BLOCK>(v, wsum, tot);
     if (k < nb) offs[k] = carry + ex;
     carry += tot;
   }
@@ -197,7 +175,7 @@ __global__ __launch_bounds__(DET_BLOCK) void det_emit_kernel(const float* __rest
   const DetItem it = det_item<POINTS>(src, count, n_items, P, e, total);
   const int g = e < total ? gidx[e] : -2;
   int tot;
-  const int pos = block_offs[blockIdx.x] + det_block_scan(g != -2 ? 1 : 0, wsum, tot);
+  const int pos = block_offs[blockIdx.x] + block_scan<DET_BLOCK>(g != -2 ? 1 : 0, wsum, tot);
   if (g == -2) return;
   const long long rec = (long long)state[DET_STATE_RECORDS] + pos;  // (no kernel of this launch writes the word)
   if (rec >= capacity) {
@@ -219,7 +197,7 @@ __global__ __launch_bounds__(DET_BLOCK) void det_finish_kernel(const void* __res
   bool f = false;
   if (e < n_pix) f = P.simplified ? best[e] != 0ull : det_label(labels, P.labels_u8, (size_t)e);
   int tot;
-  det_block_scan(f ? 1 : 0, wsum, tot);
+  block_scan<DET_BLOCK>(f ? 1 : 0, wsum, tot);
   if (threadIdx.x == 0) {
     if (tot) atomicAdd(state + DET_STATE_NGT, (unsigned long long)tot);
     if (blockIdx.x == 0) state[DET_STATE_RECORDS] += (unsigned long long)block_offs[nb_items];
@@ -232,7 +210,7 @@ __global__ __launch_bounds__(DET_BLOCK) void det_curve_count_kernel(const unsign
   __shared__ int wsum[DET_BLOCK / 64];
   const long long e = (long long)blockIdx.x * DET_CURVE_TILE + threadIdx.x;
   int tot;
-  det_block_scan(e < n ? (int)(keys[e] & 1ull) : 0, wsum, tot);
+  block_scan<DET_BLOCK>(e < n ? (int)(keys[e] & 1ull) : 0, wsum, tot);
   if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
 
@@ -249,7 +227,7 @@ __global__ __launch_bounds__(DET_BLOCK) void det_curve_pr_kernel(const unsigned 
   const unsigned long long key = e < n ? keys[e] : 0ull;
   const int tp = (int)(key & 1ull);
   int tot;
-  const long long tp_cum = (long long)block_offs[blockIdx.x] + det_block_scan(tp, wsum, tot) + tp;
+  const long long tp_cum = (long long)block_offs[blockIdx.x] + block_scan<DET_BLOCK>(tp, wsum, tot) + tp;
   double raw = 0.0;
   if (e < n) {
     const long long n_gt = (long long)state[DET_STATE_NGT];
@@ -286,19 +264,6 @@ __global__ __launch_bounds__(DET_BLOCK) void det_suffix_blocks_kernel(const doub
   }
 }
 
-__device__ __forceinline__ double det_block_sum(double v, double* lds) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < DET_BLOCK / 64; ++w) s += lds[w];
-  return s;
-}
-
 // the right-to-left running maximum and the tile's share of sum(precision[1:] * (recall[1:] - recall[:-1]))
 __global__ __launch_bounds__(DET_BLOCK) void det_curve_final_kernel(long long n, const double* __restrict__ suffix,
                                                                     const double* __restrict__ recall, double* __restrict__ precision,
@@ -317,7 +282,7 @@ __global__ __launch_bounds__(DET_BLOCK) void det_curve_final_kernel(long long n,
     term = fin * (recall[e + 1] - recall[e]);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) precision[0] = fmax(tot, rest);
-  const double s = det_block_sum(term, lds);  // (the term of the padded last element is 0 * (1 - recall[n]) = 0)
+  const double s = block_sum<DET_BLOCK>(term, lds);  // (the term of the padded last element is 0 * (1 - recall[n]) = 0)
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -326,7 +291,7 @@ __global__ __launch_bounds__(DET_BLOCK) void det_sum_kernel(const double* __rest
   __shared__ double lds[DET_BLOCK / 64];
   double v = 0.0;
   for (int k = threadIdx.x; k < nb; k += DET_BLOCK) v += partial[k];
-  const double s = det_block_sum(v, lds);
+  const double s = block_sum<DET_BLOCK>(v, lds);
   if (threadIdx.x == 0) out[0] = s;
 }
 

@@ -7,8 +7,9 @@
 //   epi_finish_kernel      grid (pairs): the winner over the keys (a maximum: no order to depend on), its mask, the refit on
 //                          the inliers with fixed-order sums, the Jacobi rank-2 step, the outputs
 //   match_filter_kernel    grid (pairs): stable compaction of the match rows by the mask (wave ballots, no atomic ticket)
-// The 8x9 system of a hypothesis lives in registers: every swap of the complete pivoting is a compare-select with
-// constant indices, as in eval_solve8.
+// The 8x9 system of a hypothesis lives in registers: every swap of the complete pivoting (pivot_step, geom_blocks.hip.h) is a
+// compare-select with constant indices, as in eval_solve8.
+// Needs: geom_blocks.hip.h, track_kernels.hip.h (TRACK_BLOCK), eval_kernels.hip.h (EvalNorm, eval_solve8, EVAL_HYPOTHESES).
 #pragma once
 
 namespace sspk {
@@ -17,7 +18,6 @@ namespace sspk {
 #define EPI_MAX_GROUPS 64
 #define EPI_MIN_SCORE 8
 #define EPI_JACOBI_SWEEPS 8
-static_assert(EPI_THREADS == EVAL_THREADS, "eval_block_sum reduces EVAL_THREADS lanes");
 
 // Matches of pair p -> LDS rows (ax, ay, bx, by).  Indices are clamped to the arrays, as eval_gather_kernel does.
 __device__ __forceinline__ void epi_stage(const double* __restrict__ pts1, const double* __restrict__ pts2, int pt_stride,
@@ -77,57 +77,6 @@ __device__ __forceinline__ void epi_row(double ax, double ay, double bx, double 
   r[6] = ax; r[7] = ay; r[8] = 1.0;
 }
 
-// Step K of the complete pivoting (a template, not a loop: the eight steps together are beyond the size the compiler unrolls
-// a loop to, and a loop that stays rolled puts the matrix into scratch memory).
-template <int K>
-__device__ __forceinline__ void epi_pivot_step(double (&a)[8][9], int (&perm)[9], bool& ok) {
-#pragma clang fp contract(off)
-  double best = -1.0;
-  int pr = K, pc = K;
-#pragma unroll
-  for (int r = K; r < 8; ++r) {
-#pragma unroll
-    for (int c = K; c < 9; ++c) {
-      const double v = fabs(a[r][c]);
-      const bool g = v > best;
-      best = g ? v : best;
-      pr = g ? r : pr;
-      pc = g ? c : pc;
-    }
-  }
-#pragma unroll
-  for (int r = K + 1; r < 8; ++r) {
-    const bool sw = pr == r;
-#pragma unroll
-    for (int c = K; c < 9; ++c) {
-      const double t = a[K][c];
-      a[K][c] = sw ? a[r][c] : t;
-      a[r][c] = sw ? t : a[r][c];
-    }
-  }
-#pragma unroll
-  for (int c = K + 1; c < 9; ++c) {
-    const bool sw = pc == c;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const double t = a[r][K];
-      a[r][K] = sw ? a[r][c] : t;
-      a[r][c] = sw ? t : a[r][c];
-    }
-    const int tp = perm[K];
-    perm[K] = sw ? perm[c] : tp;
-    perm[c] = sw ? tp : perm[c];
-  }
-  ok = ok && fabs(a[K][K]) > 1e-12;
-  const double inv = 1.0 / a[K][K];
-#pragma unroll
-  for (int r = K + 1; r < 8; ++r) {
-    const double m = a[r][K] * inv;
-#pragma unroll
-    for (int c = K + 1; c < 9; ++c) a[r][c] = a[r][c] - m * a[K][c];
-  }
-}
-
 // Null vector of the 8x9 matrix a by Gaussian elimination with complete pivoting: at step k the pivot is the largest
 // |entry| of rows k..7, columns k..8 (row-major scan with a strict comparison: the lowest row, then the lowest column);
 // rows and columns are swapped; the unknown of the column left over is 1; back substitution; the column permutation is
@@ -139,14 +88,14 @@ __device__ __forceinline__ bool epi_null8x9(double (&a)[8][9], double (&f)[9]) {
   int perm[9];
 #pragma unroll
   for (int c = 0; c < 9; ++c) perm[c] = c;
-  epi_pivot_step<0>(a, perm, ok);
-  epi_pivot_step<1>(a, perm, ok);
-  epi_pivot_step<2>(a, perm, ok);
-  epi_pivot_step<3>(a, perm, ok);
-  epi_pivot_step<4>(a, perm, ok);
-  epi_pivot_step<5>(a, perm, ok);
-  epi_pivot_step<6>(a, perm, ok);
-  epi_pivot_step<7>(a, perm, ok);
+  pivot_step<0>(a, perm, ok, 1e-12);
+  pivot_step<1>(a, perm, ok, 1e-12);
+  pivot_step<2>(a, perm, ok, 1e-12);
+  pivot_step<3>(a, perm, ok, 1e-12);
+  pivot_step<4>(a, perm, ok, 1e-12);
+  pivot_step<5>(a, perm, ok, 1e-12);
+  pivot_step<6>(a, perm, ok, 1e-12);
+  pivot_step<7>(a, perm, ok, 1e-12);
   double x[9];
   x[8] = 1.0;
 #pragma unroll
@@ -166,29 +115,12 @@ __device__ __forceinline__ bool epi_null8x9(double (&a)[8][9], double (&f)[9]) {
   return ok;
 }
 
-// Hypothesis h of a pair: 8 distinct matches from the counter-based stream (the 4-point sampler's redraw rule), both
+// Hypothesis h of a pair: 8 distinct matches from the counter-based stream (sample_distinct), both
 // images normalised over the 8 points, the null vector of the 8x9 system, F in pixels.  false = invalid.
 __device__ __forceinline__ bool epi_hypothesis(const double4* M, int n, uint64_t seed, int h, double (&F)[9]) {
 #pragma clang fp contract(off)
   int id[8];
-  if (n == 8) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) id[k] = k;
-  } else {
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      int v;
-      bool dup;
-      do {
-        v = eval_draw(seed, h, c++, n);
-        dup = false;
-#pragma unroll
-        for (int j = 0; j < k; ++j) dup = dup || v == id[j];
-      } while (dup && c < EVAL_SAMPLE_DRAWS);
-      id[k] = v;
-    }
-  }
+  sample_distinct(seed, h, n, id, [](int) { return true; });
   bool distinct = true;
 #pragma unroll
   for (int k = 1; k < 8; ++k)
@@ -257,7 +189,7 @@ __device__ __forceinline__ bool epi_inlier(const double (&F)[9], double4 m, doub
 // Hypotheses tried for n matches: none below 8, the one direct solve at 8, EVAL_HYPOTHESES above.
 __device__ __forceinline__ int epi_total(int n) { return n < 8 ? 0 : (n == 8 ? 1 : EVAL_HYPOTHESES); }
 
-// grid (groups, pairs).  keys [pairs][groups]: ((score + 1) << 32) | (0xFFFFFFFF - h) of the best valid hypothesis of the
+// grid (groups, pairs).  keys [pairs][groups]: key_of(score, h) of the best valid hypothesis of the
 // slice [g * per, (g + 1) * per), per = ceil(EVAL_HYPOTHESES / groups); 0 = none.  Dynamic LDS: cap double4.
 __global__ __launch_bounds__(EPI_THREADS) void epi_hypotheses_kernel(const double* __restrict__ pts1,
                                                                      const double* __restrict__ pts2, int pt_stride, int cap,
@@ -288,6 +220,7 @@ __global__ __launch_bounds__(EPI_THREADS) void epi_hypotheses_kernel(const doubl
     if (!epi_hypothesis(M, n, seed, h, F)) continue;
     int sc = 0;
     for (int i = 0; i < n; ++i) sc += epi_inlier(F, M[i], t2);
+    // key_of and, below, publish_wave_keys / max_wave_key (geom_blocks.hip.h), written out: the same rules, keep them in step
     const uint64_t k = ((uint64_t)(sc + 1) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)h);
     key = k > key ? k : key;
   }
@@ -306,7 +239,7 @@ __global__ __launch_bounds__(EPI_THREADS) void epi_hypotheses_kernel(const doubl
   }
 }
 
-// Normalisation of the inliers of one image (dst = false: a, true: b); sums in eval_block_sum's fixed order.
+// Normalisation of the inliers of one image (dst = false: a, true: b); sums in block_sum's fixed order.
 __device__ __forceinline__ EvalNorm epi_norm_of(const double4* M, const uint8_t* mask, int n, double cnt, bool dst, double* red) {
 #pragma clang fp contract(off)
   double sx = 0.0, sy = 0.0;
@@ -317,15 +250,15 @@ __device__ __forceinline__ EvalNorm epi_norm_of(const double4* M, const uint8_t*
     sy = sy + (dst ? m.w : m.y);
   }
   EvalNorm t;
-  t.cx = eval_block_sum(sx, red) / cnt;
-  t.cy = eval_block_sum(sy, red) / cnt;
+  t.cx = block_sum<EPI_THREADS>(sx, red) / cnt;
+  t.cy = block_sum<EPI_THREADS>(sy, red) / cnt;
   double sa = 0.0;
   for (int i = threadIdx.x; i < n; i += EPI_THREADS) {
     if (!mask[i]) continue;
     const double4 m = M[i];
     sa = sa + (fabs((dst ? m.z : m.x) - t.cx) + fabs((dst ? m.w : m.y) - t.cy));
   }
-  t.s = cnt / eval_block_sum(sa, red);
+  t.s = cnt / block_sum<EPI_THREADS>(sa, red);
   return t;
 }
 
@@ -341,29 +274,9 @@ __device__ __forceinline__ void epi_rank2(double (&f)[9]) {
       V[i][j] = i == j ? 1.0 : 0.0;
     }
   for (int sweep = 0; sweep < EPI_JACOBI_SWEEPS; ++sweep) {
-#pragma unroll
-    for (int pq = 0; pq < 3; ++pq) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2, r = 3 - p - q;
-      const double gpq = G[p][q];
-      if (gpq == 0.0) continue;
-      const double theta = (G[q][q] - G[p][p]) / (2.0 * gpq);
-      double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-      if (theta < 0.0) t = -t;
-      const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-      const double gpp = G[p][p] - t * gpq, gqq = G[q][q] + t * gpq;
-      const double grp = c * G[r][p] - s * G[r][q], grq = s * G[r][p] + c * G[r][q];
-      G[p][p] = gpp;
-      G[q][q] = gqq;
-      G[p][q] = G[q][p] = 0.0;
-      G[r][p] = G[p][r] = grp;
-      G[r][q] = G[q][r] = grq;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const double vp = c * V[k][p] - s * V[k][q], vq = s * V[k][p] + c * V[k][q];
-        V[k][p] = vp;
-        V[k][q] = vq;
-      }
-    }
+    jacobi_rotate<0, 1>(G, V);
+    jacobi_rotate<0, 2>(G, V);
+    jacobi_rotate<1, 2>(G, V);
   }
   const bool k1 = G[1][1] < G[0][0];
   const double d01 = k1 ? G[1][1] : G[0][0];
@@ -413,13 +326,9 @@ __global__ __launch_bounds__(EPI_THREADS) void epi_finish_kernel(const double* _
   uint8_t* mo = mask_out + (size_t)p * cap;
   const uint64_t seed = seeds[p];
   const double t2 = thresh * thresh;
-  uint64_t key = 0;
-  for (int g = 0; g < groups; ++g) {
-    const uint64_t k = keys[(size_t)p * groups + g];
-    key = k > key ? k : key;
-  }
-  const int winner = (int)(0xFFFFFFFFu - (uint32_t)key);
-  bool valid = key != 0 && (int)(key >> 32) - 1 >= EPI_MIN_SCORE;  // (uniform over the workgroup)
+  const uint64_t key = max_group_key(keys, p, groups);
+  const int winner = hypothesis_of(key);
+  bool valid = key != 0 && score_of(key) >= EPI_MIN_SCORE;  // (uniform over the workgroup)
   double F[9], Fd[9];
   double cnt = 0.0, err = 0.0;
   if (valid) {
@@ -435,7 +344,7 @@ __global__ __launch_bounds__(EPI_THREADS) void epi_finish_kernel(const double* _
       mask[i] = in;
       c = c + (in ? 1.0 : 0.0);
     }
-    cnt = eval_block_sum(c, red);  // (the barriers inside also publish the mask)
+    cnt = block_sum<EPI_THREADS>(c, red);  // (the barriers inside also publish the mask)
     EvalNorm t1 = epi_norm_of(M, mask, n, cnt, false, red), tq = epi_norm_of(M, mask, n, cnt, true, red);
     if (!(isfinite(t1.s) && t1.s > 0.0 && isfinite(tq.s) && tq.s > 0.0)) {
       t1.s = tq.s = 1.0;
@@ -465,7 +374,7 @@ __global__ __launch_bounds__(EPI_THREADS) void epi_finish_kernel(const double* _
       for (int j = 0; j < 9; ++j)
 #pragma unroll
         for (int k = j; k < 9; ++k, ++e) {
-          const double s = eval_block_sum(mom[e], red);
+          const double s = block_sum<EPI_THREADS>(mom[e], red);
           if (tid == 0) s_mom[j][k] = s_mom[k][j] = s;
         }
     }
@@ -515,7 +424,7 @@ __global__ __launch_bounds__(EPI_THREADS) void epi_finish_kernel(const double* _
         const double d2 = epi_sampson2(Fd, M[i], usable);
         part = part + (usable ? d2 : 0.0);
       }
-      err = sqrt(eval_block_sum(part, red) / cnt);
+      err = sqrt(block_sum<EPI_THREADS>(part, red) / cnt);
     }
   }
   for (int i = tid; i < cap; i += EPI_THREADS) mo[i] = (valid && i < n) ? mask[i] : 0;
@@ -530,7 +439,7 @@ __global__ __launch_bounds__(EPI_THREADS) void epi_finish_kernel(const double* _
   }
 }
 
-// grid (pairs), TRACK_BLOCK threads.  Keeps the match rows whose mask byte is set, in order (track_block_scan: wave ballots
+// grid (pairs), TRACK_BLOCK threads.  Keeps the match rows whose mask byte is set, in order (block_scan_flag: wave ballots
 // and popcounts), and writes zero rows behind them.  status != 0 or n_inliers < min_inliers: every row passes.
 __global__ __launch_bounds__(TRACK_BLOCK) void match_filter_kernel(const float* __restrict__ match, const int32_t* __restrict__ n_match,
                                                                    const uint8_t* __restrict__ mask,
@@ -550,7 +459,7 @@ __global__ __launch_bounds__(TRACK_BLOCK) void match_filter_kernel(const float* 
     const int i = i0 + threadIdx.x;
     const bool keep = i < n && (pass || mk[i] != 0);
     int total;
-    const int pos = base + track_block_scan(keep, wsum, total);
+    const int pos = base + block_scan_flag<TRACK_BLOCK>(keep, wsum, total);
     if (keep) {
       dst[(size_t)pos * 3] = src[(size_t)i * 3];
       dst[(size_t)pos * 3 + 1] = src[(size_t)i * 3 + 1];

@@ -3,7 +3,9 @@
 // RANSAC homography (the cv2.findHomography step of evaluations/descriptor_evaluation.py:65-158 and evaluation.py:224-330)
 // with the average precision of evaluation.py:318-325 fused into its epilogue.  One workgroup per pair; fp64 throughout
 // except the matching-score count, which keeps the reference's float32 warp.  Every function here is compiled with
-// contraction off: the reference's numpy arithmetic rounds each product and each sum.
+// contraction off: the reference's numpy arithmetic rounds each product and each sum.  The sums over a workgroup or a wave
+// (block_sum, wave_sum), the RANSAC key and the sampler are those of geom_blocks.hip.h.
+// Needs: geom_blocks.hip.h.
 #pragma once
 
 namespace sspk {
@@ -11,23 +13,7 @@ namespace sspk {
 #define EVAL_THREADS 256
 #define EVAL_HYPOTHESES 2000
 #define EVAL_GN_STEPS 5
-#define EVAL_SAMPLE_DRAWS 64
 #define EVAL_FLT_EPS 1.1920928955078125e-07
-
-// Deterministic sum over the workgroup: xor butterfly inside each wave (every lane ends with the same value: each level
-// adds the same two operands), then the wave partials in wave order.  `red` holds EVAL_THREADS / 64 doubles.
-__device__ __forceinline__ double eval_block_sum(double v, double* red) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = red[0];
-#pragma unroll
-  for (int w = 1; w < EVAL_THREADS / 64; ++w) t = t + red[w];
-  return t;
-}
 
 // np.dot([x, y, 1], M^T) followed by [:, :2] / [:, 2:] (warp_keypoints, detector_evaluation.py:139-150)
 __device__ __forceinline__ void eval_warp(const double* M, double x, double y, double& u, double& v) {
@@ -151,7 +137,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_repeat_kernel(const double*
       }
     }
     atomicAdd(&s_count[s], c);
-    sum[s] = eval_block_sum(part, red);
+    sum[s] = block_sum<EVAL_THREADS>(part, red);
   }
   __syncthreads();
   if (tid == 0) {
@@ -168,18 +154,6 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_repeat_kernel(const double*
 }
 
 // ---- RANSAC homography ----
-__device__ __forceinline__ uint64_t eval_mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-// Draw c of hypothesis h: an index in [0, n) from the counter-based stream of the pair's seed.
-__device__ __forceinline__ int eval_draw(uint64_t seed, int h, int c, int n) {
-  const uint64_t r = eval_mix(seed ^ eval_mix(((uint64_t)h << 8) | (uint64_t)c));
-  return (int)(((r >> 32) * (uint64_t)n) >> 32);
-}
-
 __device__ __forceinline__ bool eval_collinear(double ax, double ay, double bx, double by, double cx, double cy) {
 #pragma clang fp contract(off)
   const double dx1 = bx - ax, dy1 = by - ay, dx2 = cx - ax, dy2 = cy - ay;
@@ -268,18 +242,8 @@ __device__ __forceinline__ double eval_resid2(const double (&H)[9], double4 m) {
 // either set, solves for h33 = 1.  Returns false for an invalid hypothesis.
 __device__ __forceinline__ bool eval_hypothesis(const double4* M, int n, uint64_t seed, int h, double (&H)[9]) {
 #pragma clang fp contract(off)
-  int c = 0;
   int id[4];
-  if (n == 4) {  // the direct solve of exactly 4 matches
-    id[0] = 0; id[1] = 1; id[2] = 2; id[3] = 3;
-  } else {
-  id[0] = eval_draw(seed, h, c++, n);
-  do { id[1] = eval_draw(seed, h, c++, n); } while (id[1] == id[0] && c < EVAL_SAMPLE_DRAWS);
-  do { id[2] = eval_draw(seed, h, c++, n); } while ((id[2] == id[0] || id[2] == id[1]) && c < EVAL_SAMPLE_DRAWS);
-  do {
-    id[3] = eval_draw(seed, h, c++, n);
-  } while ((id[3] == id[0] || id[3] == id[1] || id[3] == id[2]) && c < EVAL_SAMPLE_DRAWS);
-  }
+  sample_distinct(seed, h, n, id, [](int) { return true; });  // (n == 4: the direct solve of exactly 4 matches)
   if (id[1] == id[0] || id[2] == id[0] || id[2] == id[1] || id[3] == id[0] || id[3] == id[1] || id[3] == id[2])
     return false;
   double4 q[4];
@@ -365,15 +329,11 @@ __device__ __forceinline__ double eval_normal_eq(const double4* M, const uint8_t
       a[r][8] = a[r][8] - (j0[r] * r0 + j1[r] * r1);
     }
   }
+  cost = wave_sum(cost);
 #pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    cost = cost + __shfl_xor(cost, o);
+  for (int r = 0; r < 8; ++r)
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-#pragma unroll
-      for (int c = r; c < 9; ++c) a[r][c] = a[r][c] + __shfl_xor(a[r][c], o);
-    }
-  }
+    for (int c = r; c < 9; ++c) a[r][c] = wave_sum(a[r][c]);
 #pragma unroll
   for (int r = 1; r < 8; ++r)
 #pragma unroll
@@ -392,12 +352,9 @@ __device__ __forceinline__ EvalNorm eval_norm_of(const double4* M, const uint8_t
     sy = sy + (dst ? m.w : m.y);
     cnt = cnt + 1.0;
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    sx = sx + __shfl_xor(sx, o);
-    sy = sy + __shfl_xor(sy, o);
-    cnt = cnt + __shfl_xor(cnt, o);
-  }
+  sx = wave_sum(sx);
+  sy = wave_sum(sy);
+  cnt = wave_sum(cnt);
   EvalNorm t;
   t.cx = sx / cnt;
   t.cy = sy / cnt;
@@ -407,9 +364,7 @@ __device__ __forceinline__ EvalNorm eval_norm_of(const double4* M, const uint8_t
     const double4 m = M[i];
     sa = sa + (fabs((dst ? m.z : m.x) - t.cx) + fabs((dst ? m.w : m.y) - t.cy));
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) sa = sa + __shfl_xor(sa, o);
-  t.s = cnt / sa;
+  t.s = cnt / wave_sum(sa);
   return t;
 }
 
@@ -474,20 +429,12 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_ransac_kernel(const double4
       if (!eval_hypothesis(M, n, seed, h, Hh)) continue;
       int sc = 0;
       for (int i = 0; i < n; ++i) sc += eval_resid2(Hh, M[i]) <= 9.0;
-      const uint64_t k = ((uint64_t)(sc + 1) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)h);
+      const uint64_t k = key_of(sc, h);
       key = k > key ? k : key;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const uint64_t t = __shfl_xor((unsigned long long)key, o);
-      key = t > key ? t : key;
-    }
-    if (lane == 0) best_key[wave] = key;
-    __syncthreads();
-    key = best_key[0];
-#pragma unroll
-    for (int w = 1; w < EVAL_THREADS / 64; ++w) key = best_key[w] > key ? best_key[w] : key;
-    if (key != 0) valid = eval_hypothesis(M, n, seed, (int)(0xFFFFFFFFu - (uint32_t)key), H);
+    publish_wave_keys(key, best_key);
+    key = max_wave_key<EVAL_THREADS>(best_key);
+    if (key != 0) valid = eval_hypothesis(M, n, seed, hypothesis_of(key), H);
   }
   // the best hypothesis's inlier set (n == 4: all four)
   if (tid == 0) s_count = 0, s_refit = 0;
@@ -564,7 +511,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_ransac_kernel(const double4
         part = part + (double)tp / (double)all;
       }
     }
-    ap = eval_block_sum(part, red) / (double)(cnt > 0 ? cnt : 1);
+    ap = block_sum<EVAL_THREADS>(part, red) / (double)(cnt > 0 ? cnt : 1);
   }
   uint8_t* mo = mask_out + (size_t)p * cap;
   for (int i = tid; i < cap; i += EVAL_THREADS) mo[i] = i < n ? mask[i] : 0;
@@ -583,15 +530,6 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_ransac_kernel(const double4
 #define EVAL_ROW_WORDS 16
 #define EVAL_STATE_WORDS 16
 
-// c = a @ b for 3x3 row-major matrices: every element ((a0*b0 + a1*b1) + a2*b2), each product and each sum rounded.
-__device__ __forceinline__ void eval_mat3(const double (&a)[9], const double (&b)[9], double (&c)[9]) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) c[3 * r + k] = (a[3 * r] * b[k] + a[3 * r + 1] * b[3 + k]) + a[3 * r + 2] * b[6 + k];
-}
-
 // One lane per pair: the trainer's normalised homography hn (float32, image -> warped image in [-1, 1]^2) to pixels,
 // M = Tinv @ (Hn @ T) (utils/utils.py:291-294 homography_scaling in closed form, no division by h33), and its inverse
 // adj(M) / det(M).  The inverse is the adjugate, NOT np.linalg.inv's LU solve: the two differ in the last places.
@@ -606,8 +544,8 @@ __global__ __launch_bounds__(64) void eval_pixel_hom_kernel(const float* __restr
   double h[9], b[9], m[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) h[k] = (double)hn[(size_t)p * 9 + k];
-  eval_mat3(h, T, b);
-  eval_mat3(Ti, b, m);
+  mat3_mul(h, T, b);
+  mat3_mul(Ti, b, m);
   double a[9];
   a[0] = m[4] * m[8] - m[5] * m[7];
   a[1] = m[2] * m[7] - m[1] * m[8];

@@ -11,14 +11,15 @@
 //                              L2-resident) instead of holding a per-view private array.  The loop over the views is uniform
 //                              across the wavefront: the camera read is an LDS broadcast.
 //   landmark_count_kernel /    the stable compaction of the status-0 rows: the ballot / popcount / block-sum pattern of
-//   landmark_scatter_kernel    track_kernels.hip.h (track_block_scan, track_base_of), so the order is the table's and does not
+//   landmark_scatter_kernel    track_kernels.hip.h (block_scan_flag, block_base), so the order is the table's and does not
 //                              depend on the order the blocks run in
+// Needs: geom_blocks.hip.h, track_kernels.hip.h (TRACK_BLOCK), pose_kernels.hip.h (POSE_ROW_WORDS, POSE_THREADS).
 #pragma once
 
 namespace sspk {
 
 #define LM_THREADS 256
-#define LM_CAM_WORDS 20        // Rw [9], C [3], fx, fy, cx, cy, valid, 3 spare
+#define LM_CAM_WORDS 20        // Rw [9], C [3], fx, fy, cx, cy (project's camera record), valid, 3 spare
 #define LM_WORDS 8             // track id, X, Y, Z, n_views, rms, cos_parallax, index of the point in the newest frame (-1)
 #define LM_GN_STEPS 4
 #define LM_DET_EPS 1e-12
@@ -73,37 +74,6 @@ __global__ __launch_bounds__(64) void map_window_kernel(const double* __restrict
   o[17] = o[18] = o[19] = 0.0;
 }
 
-// x = A^-1 b of a symmetric 3x3 by cofactors.  false: the determinant is not finite or not above LM_DET_EPS times the product of
-// the diagonal, or the solution is not finite.
-__device__ __forceinline__ bool lm_solve3(double a00, double a01, double a02, double a11, double a12, double a22, double b0, double b1,
-                                          double b2, double& x0, double& x1, double& x2) {
-#pragma clang fp contract(off)
-  const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-  const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
-  const double det = pose_dot(a00, a01, a02, c00, c01, c02);
-  x0 = pose_dot(c00, c01, c02, b0, b1, b2) / det;
-  x1 = pose_dot(c01, c11, c12, b0, b1, b2) / det;
-  x2 = pose_dot(c02, c12, c22, b0, b1, b2) / det;
-  return isfinite(det) && det > LM_DET_EPS * ((a00 * a11) * a22) && isfinite(x0) && isfinite(x1) && isfinite(x2);
-}
-
-// The view of camera record `cam` (LDS) of the point X: y = Rw (X - C), u = y0 / y2, v = y1 / y2, the residual against the pixel.
-struct LmView {
-  double y2, u, v, r0, r1;
-};
-__device__ __forceinline__ LmView lm_view(const double* cam, double X0, double X1, double X2, double px, double py) {
-#pragma clang fp contract(off)
-  const double q0 = X0 - cam[9], q1 = X1 - cam[10], q2 = X2 - cam[11];
-  const double y0 = pose_dot(cam[0], cam[1], cam[2], q0, q1, q2), y1 = pose_dot(cam[3], cam[4], cam[5], q0, q1, q2);
-  LmView o;
-  o.y2 = pose_dot(cam[6], cam[7], cam[8], q0, q1, q2);
-  o.u = y0 / o.y2;
-  o.v = y1 / o.y2;
-  o.r0 = (cam[12] * o.u + cam[14]) - px;
-  o.r1 = (cam[13] * o.v + cam[15]) - py;
-  return o;
-}
-
 // grid (cdiv(row_cap, 256)), 256 threads, dynamic LDS lm_lds_bytes(L).  ids [row_cap][L], state [2 + L], pts [L][point_cap][2] (a
 // ring: retained frame c in slot (first_slot + c) % L), cams [L][LM_CAM_WORDS].  Per row < n_rows: x_out [3], n_views_out, rms_out,
 // cos_out, status_out.
@@ -155,9 +125,9 @@ __global__ __launch_bounds__(LM_THREADS) void triangulate_tracks_kernel(const in
     ++n_views;
     const double2 px = *reinterpret_cast<const double2*>(pts + ((size_t)((first_slot + c) % L) * point_cap + p) * 2);
     const double x0 = (px.x - cam[14]) / cam[12], x1 = (px.y - cam[15]) / cam[13];
-    const double e0 = pose_dot(cam[0], cam[3], cam[6], x0, x1, 1.0), e1 = pose_dot(cam[1], cam[4], cam[7], x0, x1, 1.0);
-    const double e2 = pose_dot(cam[2], cam[5], cam[8], x0, x1, 1.0);
-    const double nrm = sqrt(pose_dot(e0, e1, e2, e0, e1, e2));
+    const double e0 = dot3(cam[0], cam[3], cam[6], x0, x1, 1.0), e1 = dot3(cam[1], cam[4], cam[7], x0, x1, 1.0);
+    const double e2 = dot3(cam[2], cam[5], cam[8], x0, x1, 1.0);
+    const double nrm = sqrt(dot3(e0, e1, e2, e0, e1, e2));
     const double d0 = e0 / nrm, d1 = e1 / nrm, d2 = e2 / nrm;
     s_ray[(0 * L + c) * LM_THREADS + tid] = d0;
     s_ray[(1 * L + c) * LM_THREADS + tid] = d1;
@@ -170,9 +140,9 @@ __global__ __launch_bounds__(LM_THREADS) void triangulate_tracks_kernel(const in
     a11 = a11 + m11;
     a12 = a12 + m12;
     a22 = a22 + m22;
-    b0 = b0 + pose_dot(m00, m01, m02, cam[9], cam[10], cam[11]);
-    b1 = b1 + pose_dot(m01, m11, m12, cam[9], cam[10], cam[11]);
-    b2 = b2 + pose_dot(m02, m12, m22, cam[9], cam[10], cam[11]);
+    b0 = b0 + dot3(m00, m01, m02, cam[9], cam[10], cam[11]);
+    b1 = b1 + dot3(m01, m11, m12, cam[9], cam[10], cam[11]);
+    b2 = b2 + dot3(m02, m12, m22, cam[9], cam[10], cam[11]);
   }
   n_views_out[row] = n_views;
   double* xo = x_out + (size_t)row * 3;
@@ -192,7 +162,7 @@ __global__ __launch_bounds__(LM_THREADS) void triangulate_tracks_kernel(const in
     const double p2 = s_ray[(2 * L + i) * LM_THREADS + tid];
     for (int j = i + 1; j < L; ++j) {
       if (!((used >> j) & 1u)) continue;
-      const double v = pose_dot(p0, p1, p2, s_ray[(0 * L + j) * LM_THREADS + tid], s_ray[(1 * L + j) * LM_THREADS + tid],
+      const double v = dot3(p0, p1, p2, s_ray[(0 * L + j) * LM_THREADS + tid], s_ray[(1 * L + j) * LM_THREADS + tid],
                                 s_ray[(2 * L + j) * LM_THREADS + tid]);
       cosp = v < cosp ? v : cosp;
     }
@@ -201,12 +171,12 @@ __global__ __launch_bounds__(LM_THREADS) void triangulate_tracks_kernel(const in
 
   // the midpoint, its cheirality
   double X0, X1, X2;
-  degenerate |= !lm_solve3(a00, a01, a02, a11, a12, a22, b0, b1, b2, X0, X1, X2);
+  degenerate |= !cof3_solve(cofactors3(a00, a01, a02, a11, a12, a22), LM_DET_EPS, b0, b1, b2, X0, X1, X2);
   bool behind = false;
   for (int c = 0; c < L; ++c) {
     if (!((used >> c) & 1u)) continue;
     const double* cam = s_cam + c * LM_CAM_WORDS;
-    const double z = pose_dot(cam[6], cam[7], cam[8], X0 - cam[9], X1 - cam[10], X2 - cam[11]);
+    const double z = dot3(cam[6], cam[7], cam[8], X0 - cam[9], X1 - cam[10], X2 - cam[11]);
     behind |= !(isfinite(z) && z > 0.0);
   }
 
@@ -217,7 +187,7 @@ __global__ __launch_bounds__(LM_THREADS) void triangulate_tracks_kernel(const in
       if (!((used >> c) & 1u)) continue;
       const double* cam = s_cam + c * LM_CAM_WORDS;
       const double2 px = *reinterpret_cast<const double2*>(pts + ((size_t)((first_slot + c) % L) * point_cap + (my[c] - s_first[c])) * 2);
-      const LmView w = lm_view(cam, X0, X1, X2, px.x, px.y);
+      const View w = project(cam, X0, X1, X2, px.x, px.y);
       const double fa = cam[12] / w.y2, fb = cam[13] / w.y2;
       const double j00 = fa * (cam[0] - w.u * cam[6]), j01 = fa * (cam[1] - w.u * cam[7]), j02 = fa * (cam[2] - w.u * cam[8]);
       const double j10 = fb * (cam[3] - w.v * cam[6]), j11 = fb * (cam[4] - w.v * cam[7]), j12 = fb * (cam[5] - w.v * cam[8]);
@@ -232,7 +202,7 @@ __global__ __launch_bounds__(LM_THREADS) void triangulate_tracks_kernel(const in
       g2 = g2 + (j02 * w.r0 + j12 * w.r1);
     }
     double s0, s1, s2;
-    degenerate |= !lm_solve3(h00, h01, h02, h11, h12, h22, g0, g1, g2, s0, s1, s2);
+    degenerate |= !cof3_solve(cofactors3(h00, h01, h02, h11, h12, h22), LM_DET_EPS, g0, g1, g2, s0, s1, s2);
     X0 = X0 - s0;
     X1 = X1 - s1;
     X2 = X2 - s2;
@@ -244,7 +214,7 @@ __global__ __launch_bounds__(LM_THREADS) void triangulate_tracks_kernel(const in
     if (!((used >> c) & 1u)) continue;
     const double* cam = s_cam + c * LM_CAM_WORDS;
     const double2 px = *reinterpret_cast<const double2*>(pts + ((size_t)((first_slot + c) % L) * point_cap + (my[c] - s_first[c])) * 2);
-    const LmView w = lm_view(cam, X0, X1, X2, px.x, px.y);
+    const View w = project(cam, X0, X1, X2, px.x, px.y);
     behind |= !(isfinite(w.y2) && w.y2 > 0.0);
     ss = ss + (w.r0 * w.r0 + w.r1 * w.r1);
   }
@@ -267,7 +237,7 @@ __global__ __launch_bounds__(TRACK_BLOCK) void landmark_count_kernel(const int32
                                                                      int row_cap, int32_t* __restrict__ block_sums) {
   __shared__ int wsum[TRACK_BLOCK / 64];
   int total;
-  track_block_scan(landmark_keep(state, status, row_cap), wsum, total);
+  block_scan_flag<TRACK_BLOCK>(landmark_keep(state, status, row_cap), wsum, total);
   if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -281,10 +251,10 @@ __global__ __launch_bounds__(TRACK_BLOCK) void landmark_scatter_kernel(const int
   __shared__ int wsum[TRACK_BLOCK / 64];
   __shared__ int red[TRACK_BLOCK / 64];
   const int r = blockIdx.x * TRACK_BLOCK + threadIdx.x;
-  const int base = track_base_of(block_sums, blockIdx.x, red);
+  const int base = block_base<TRACK_BLOCK>(block_sums, blockIdx.x, red);
   const bool keep = landmark_keep(state, status, row_cap);
   int total;
-  const int pos = base + track_block_scan(keep, wsum, total);
+  const int pos = base + block_scan_flag<TRACK_BLOCK>(keep, wsum, total);
   if (keep) {
     int first = 0;
     for (int c = 0; c < L - 1; ++c) first += min(max(state[2 + c], 0), point_cap);

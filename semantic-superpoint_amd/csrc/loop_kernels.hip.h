@@ -1,10 +1,10 @@
 // Loop closure: a frame's map matches joined with the OLD rows of the world map and the frame's window
 // landmarks, the loop edge measured from the pose found against those rows, a Sim(3) pose graph over the trajectory rows since the
-// old place was last seen, and the write-back into the trajectory, the chain state and the map.  The rules are restated in numpy by
-// tests/loop_ref.py; everything here is fp64 with contraction off and every sum in the order of that file.
+// old place was last seen, and the write-back into the trajectory, the chain state and the map.  tests/loop_ref.py restates the
+// rules in numpy; everything here is fp64 with contraction off and every sum in the order of that file.
 //   loop_corr_kernel        one workgroup: "frame point -> lowest landmark row" in LDS (atomicMin: no order to depend on), then per
 //                           match row the correspondence of world_corr_kernel when the map row is old, and the point's landmark
-//   loop_edge_kernel        one workgroup: inlier count, anchor (a maximum) and the two depth sums in eval_block_sum's order, then
+//   loop_edge_kernel        one workgroup: inlier count, anchor (a maximum) and the two depth sums in block_sum's order, then
 //                           one thread: sigma, the acceptance rule, the edge row, the counters, the candidate record
 //   loop_graph_kernel       ONE persistent workgroup of 512 threads: Levenberg-Marquardt over the free nodes with every phase
 //                           (residuals and Jacobians per edge, normal blocks per node row, block cyclic reduction over the 7x7
@@ -13,6 +13,7 @@
 //                           all matrices live in the workspace, so no thread holds more than two 7-vectors
 //   loop_apply_map_kernel   a thread per map row: rows last seen in (a, f] keep their coordinates in their camera's frame
 //   loop_apply_rows_kernel  a thread per trajectory row: rows a + 1 .. f, the chain state
+// Needs: geom_blocks.hip.h, pose_kernels.hip.h (POSE_*), landmark_kernels.hip.h (LM_WORDS), pnp_kernels.hip.h (rows, pnp_owner_table).
 #pragma once
 
 namespace sspk {
@@ -33,8 +34,7 @@ namespace sspk {
 #define LOOP_LAMBDA_MAX 1e6
 #define LOOP_MAX_ITERATIONS 64
 
-// grid (1), 256 threads, dynamic LDS point_cap ints.  corr [cap][PNP_CORR_WORDS], xnew [cap][4], n_out [3] = rows, valid old rows,
-// valid old rows with a landmark.
+// grid (1), 256 threads, dynamic LDS point_cap ints.  corr [cap][PNP_CORR_WORDS], xnew [cap][4], n_out [3] = rows, valid old rows, those with a landmark.
 __global__ __launch_bounds__(256) void loop_corr_kernel(const double* __restrict__ map_x, const int32_t* __restrict__ map_last,
                                                         const int32_t* __restrict__ world_state, int map_cap,
                                                         const float* __restrict__ match, const int32_t* __restrict__ n_match, int cap,
@@ -138,16 +138,16 @@ __global__ __launch_bounds__(256) void loop_edge_kernel(const double* __restrict
         atomicMax(&s_anchor, map_last[row]);
         const double* q = xnew + (size_t)k * 4;
         if (q[3] != 0.0) {
-          sa = sa + pose_dot(Rl[6], Rl[7], Rl[8], o[0] - Cl[0], o[1] - Cl[1], o[2] - Cl[2]);
-          sb = sb + pose_dot(Rw[6], Rw[7], Rw[8], q[0] - C[0], q[1] - C[1], q[2] - C[2]);
+          sa = sa + dot3(Rl[6], Rl[7], Rl[8], o[0] - Cl[0], o[1] - Cl[1], o[2] - Cl[2]);
+          sb = sb + dot3(Rw[6], Rw[7], Rw[8], q[0] - C[0], q[1] - C[1], q[2] - C[2]);
           sc = sc + 1.0;
         }
       }
     }
     inliers += __syncthreads_count(inl);
   }
-  const double SA = eval_block_sum(sa, red), SB = eval_block_sum(sb, red);
-  const int shared = (int)eval_block_sum(sc, red);
+  const double SA = block_sum<256>(sa, red), SB = block_sum<256>(sb, red);
+  const int shared = (int)block_sum<256>(sc, red);
   if (tid != 0) return;
   const int a = s_anchor;
   bool fin = true;
@@ -184,14 +184,14 @@ __global__ __launch_bounds__(256) void loop_edge_kernel(const double* __restrict
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
-      for (int c = 0; c < 3; ++c) Rc[3 * r + c] = pose_dot(Rl[r], Rl[3 + r], Rl[6 + r], Rw[c], Rw[3 + c], Rw[6 + c]);
+      for (int c = 0; c < 3; ++c) Rc[3 * r + c] = dot3(Rl[r], Rl[3 + r], Rl[6 + r], Rw[c], Rw[3 + c], Rw[6 + c]);
 #pragma unroll
-    for (int r = 0; r < 3; ++r) tc[r] = Cl[r] - sigma * pose_dot(Rc[3 * r], Rc[3 * r + 1], Rc[3 * r + 2], C[0], C[1], C[2]);
+    for (int r = 0; r < 3; ++r) tc[r] = Cl[r] - sigma * dot3(Rc[3 * r], Rc[3 * r + 1], Rc[3 * r + 2], C[0], C[1], C[2]);
     const double tr = (Rc[0] + Rc[4]) + Rc[8];
     const double k0 = Rc[7] - Rc[5], k1 = Rc[2] - Rc[6], k2 = Rc[3] - Rc[1];
     cand[4] = sigma;
-    cand[5] = atan2(sqrt(pose_dot(k0, k1, k2, k0, k1, k2)), tr - 1.0);
-    cand[6] = sqrt(pose_dot(tc[0], tc[1], tc[2], tc[0], tc[1], tc[2]));
+    cand[5] = atan2(sqrt(dot3(k0, k1, k2, k0, k1, k2)), tr - 1.0);
+    cand[6] = sqrt(dot3(tc[0], tc[1], tc[2], tc[0], tc[1], tc[2]));
   }
   if (reason == 0) {
     const double* ra = table + (size_t)a * POSE_ROW_WORDS;
@@ -202,8 +202,8 @@ __global__ __launch_bounds__(256) void loop_edge_kernel(const double* __restrict
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) o[2 + 3 * r + c] = pose_dot(Rl[3 * r], Rl[3 * r + 1], Rl[3 * r + 2], ra[3 * c], ra[3 * c + 1], ra[3 * c + 2]);
-      o[11 + r] = pose_dot(ra[3 * r], ra[3 * r + 1], ra[3 * r + 2], d0, d1, d2);
+      for (int c = 0; c < 3; ++c) o[2 + 3 * r + c] = dot3(Rl[3 * r], Rl[3 * r + 1], Rl[3 * r + 2], ra[3 * c], ra[3 * c + 1], ra[3 * c + 2]);
+      o[11 + r] = dot3(ra[3 * r], ra[3 * r + 1], ra[3 * r + 2], d0, d1, d2);
     }
     o[14] = log(sigma);
     o[15] = weight;
@@ -285,16 +285,16 @@ __device__ __forceinline__ void loop_residual(const LoopEnds& n, const double* _
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j) Rr[3 * i + j] = pose_dot(n.Rj[3 * i], n.Rj[3 * i + 1], n.Rj[3 * i + 2], n.Ri[3 * j], n.Ri[3 * j + 1], n.Ri[3 * j + 2]);
+    for (int j = 0; j < 3; ++j) Rr[3 * i + j] = dot3(n.Rj[3 * i], n.Rj[3 * i + 1], n.Rj[3 * i + 2], n.Ri[3 * j], n.Ri[3 * j + 1], n.Ri[3 * j + 2]);
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j) E[3 * i + j] = pose_dot(z[i], z[3 + i], z[6 + i], Rr[j], Rr[3 + j], Rr[6 + j]);
+    for (int j = 0; j < 3; ++j) E[3 * i + j] = dot3(z[i], z[3 + i], z[6 + i], Rr[j], Rr[3 + j], Rr[6 + j]);
   const double bz = z[13], ei = exp(-n.li);
   const double d0 = n.Cj[0] - n.Ci[0], d1 = n.Cj[1] - n.Ci[1], d2 = n.Cj[2] - n.Ci[2];
   double tr[3];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) tr[i] = ei * pose_dot(n.Ri[3 * i], n.Ri[3 * i + 1], n.Ri[3 * i + 2], d0, d1, d2);
+  for (int i = 0; i < 3; ++i) tr[i] = ei * dot3(n.Ri[3 * i], n.Ri[3 * i + 1], n.Ri[3 * i + 2], d0, d1, d2);
   r[0] = 0.5 * (E[7] - E[5]);
   r[1] = 0.5 * (E[2] - E[6]);
   r[2] = 0.5 * (E[3] - E[1]);
@@ -318,7 +318,7 @@ __device__ __forceinline__ void loop_residual(const LoopEnds& n, const double* _
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       Ji[7 * i + j] = -0.5 * (trace * (i == j ? 1.0 : 0.0) - E[3 * j + i]);
-      Jj[7 * i + j] = 0.5 * pose_dot(TmE[3 * i], TmE[3 * i + 1], TmE[3 * i + 2], z[3 * j], z[3 * j + 1], z[3 * j + 2]);
+      Jj[7 * i + j] = 0.5 * dot3(TmE[3 * i], TmE[3 * i + 1], TmE[3 * i + 2], z[3 * j], z[3 * j + 1], z[3 * j + 2]);
     }
   const double ib = 1.0 / bz, eb = ei * ib;
   const double cr[9] = {0.0, -tr[2], tr[1], tr[2], 0.0, -tr[0], -tr[1], tr[0], 0.0};
@@ -440,8 +440,8 @@ __global__ __launch_bounds__(LOOP_THREADS) void loop_graph_kernel(const double* 
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) z[3 * r + c] = pose_dot(rj[3 * r], rj[3 * r + 1], rj[3 * r + 2], ri[3 * c], ri[3 * c + 1], ri[3 * c + 2]);
-        z[9 + r] = pose_dot(ri[3 * r], ri[3 * r + 1], ri[3 * r + 2], d0, d1, d2);
+        for (int c = 0; c < 3; ++c) z[3 * r + c] = dot3(rj[3 * r], rj[3 * r + 1], rj[3 * r + 2], ri[3 * c], ri[3 * c + 1], ri[3 * c + 2]);
+        z[9 + r] = dot3(ri[3 * r], ri[3 * r + 1], ri[3 * r + 2], d0, d1, d2);
       }
       z[12] = 0.0;
       z[14] = 1.0;
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(LOOP_THREADS) void loop_graph_kernel(const double* 
       for (int c = 0; c < 13; ++c) z[c] = o[2 + c];
       z[14] = o[15];
     }
-    const double b = sqrt(pose_dot(z[9], z[10], z[11], z[9], z[10], z[11]));
+    const double b = sqrt(dot3(z[9], z[10], z[11], z[9], z[10], z[11]));
     z[13] = (isfinite(b) && b > 0.0) ? b : 1.0;
     z[15] = 0.0;
   }
@@ -746,7 +746,7 @@ __global__ __launch_bounds__(LOOP_THREADS) void loop_graph_kernel(const double* 
       const double rot[6] = {delta[0], delta[1], delta[2], 0.0, 0.0, 0.0};
 #pragma unroll
       for (int c = 0; c < 9; ++c) R[c] = w.R[(size_t)(k + 1) * 9 + c];
-      bool fin = pnp_cayley_update(R, t, rot);
+      bool fin = cayley_update(R, t, rot);
 #pragma unroll
       for (int c = 0; c < 9; ++c) w.Rn[(size_t)(k + 1) * 9 + c] = R[c];
 #pragma unroll
@@ -847,10 +847,10 @@ __global__ __launch_bounds__(256) void loop_apply_map_kernel(const double* __res
       const double d0 = x[0] - ro[9], d1 = x[1] - ro[10], d2 = x[2] - ro[11];
       double y[3], xn[3];
 #pragma unroll
-      for (int r = 0; r < 3; ++r) y[r] = pose_dot(ro[3 * r], ro[3 * r + 1], ro[3 * r + 2], d0, d1, d2);
+      for (int r = 0; r < 3; ++r) y[r] = dot3(ro[3 * r], ro[3 * r + 1], ro[3 * r + 2], d0, d1, d2);
       const double sg = sigma[k];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) xn[c] = c1[c] + sg * pose_dot(r1[c], r1[3 + c], r1[6 + c], y[0], y[1], y[2]);
+      for (int c = 0; c < 3; ++c) xn[c] = c1[c] + sg * dot3(r1[c], r1[3 + c], r1[6 + c], y[0], y[1], y[2]);
       if (isfinite(xn[0]) && isfinite(xn[1]) && isfinite(xn[2])) {
         x[0] = xn[0];
         x[1] = xn[1];
@@ -882,7 +882,7 @@ __global__ __launch_bounds__(256) void loop_apply_rows_kernel(const double* __re
 #pragma unroll
   for (int c = 0; c < 3; ++c) row[9 + c] = c1[c];
   const double d0 = c1[0] - c1[-3], d1 = c1[1] - c1[-2], d2 = c1[2] - c1[-1];
-  const double len = sqrt(pose_dot(d0, d1, d2, d0, d1, d2));
+  const double len = sqrt(dot3(d0, d1, d2, d0, d1, d2));
   if (isfinite(len) && len > PNP_SCALE_FRACTION * row[12]) row[12] = len;
   row[14] = (double)((int)row[14] | LOOP_FLAG_LOOP);
   if (k == f) {
@@ -893,7 +893,7 @@ __global__ __launch_bounds__(256) void loop_apply_rows_kernel(const double* __re
 #pragma unroll
       for (int c = 0; c < 9; ++c) st[2 + c] = r1[c];
 #pragma unroll
-      for (int i = 0; i < 3; ++i) st[11 + i] = -pose_dot(r1[3 * i], r1[3 * i + 1], r1[3 * i + 2], c1[0], c1[1], c1[2]);
+      for (int i = 0; i < 3; ++i) st[11 + i] = -dot3(r1[3 * i], r1[3 * i + 1], r1[3 * i + 2], c1[0], c1[1], c1[2]);
     }
   }
 }

@@ -11,11 +11,12 @@
 //                          broadcast read served by the scalar cache / L2), not staged
 //   pnp_finish_kernel      grid (problems): the winner over the keys (a maximum: no order to depend on), its pose again, its mask,
 //                          PNP_GN_STEPS Gauss-Newton steps on (rotation, translation) with 27 moments reduced in
-//                          eval_block_sum's fixed order (pnp_block_sums: the same order, one pair of barriers for all 27) and a
+//                          block_sum's fixed order (block_sums: the same order, one pair of barriers for all 27) and a
 //                          6x6 solve by complete pivoting, the final mask, rms, status
 //   pose_repair_kernel     a thread per sequence: the newest trajectory row and the chain state rewritten from an absolute pose
 // The quartic's roots are bracketed by hand: the quadratic g'' by formula, three brackets of the cubic g', four of the quartic;
 // every coefficient index is a constant, so the polynomials and the 6x7 system live in registers.
+// Needs: geom_blocks.hip.h, pose_kernels.hip.h (POSE_ROW_WORDS), landmark_kernels.hip.h (LM_WORDS).
 #pragma once
 
 namespace sspk {
@@ -33,7 +34,6 @@ namespace sspk {
 #define PNP_SCALE_FRACTION (1.0 / 64.0)
 #define PNP_FLAG_ABSOLUTE 4
 #define PNP_NO_OWNER 0x7FFFFFFF
-static_assert(PNP_THREADS == EVAL_THREADS, "eval_block_sum reduces EVAL_THREADS lanes");
 
 struct PnpIntr {
   double fx, fy, cx, cy;
@@ -91,13 +91,13 @@ __device__ __forceinline__ void pnp_rewrite_row(double* __restrict__ st, double*
 #pragma clang fp contract(off)
   double tw[3];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) tw[i] = -pose_dot(Rw[3 * i], Rw[3 * i + 1], Rw[3 * i + 2], C[0], C[1], C[2]);
+  for (int i = 0; i < 3; ++i) tw[i] = -dot3(Rw[3 * i], Rw[3 * i + 1], Rw[3 * i + 2], C[0], C[1], C[2]);
   double s = st[1];
   int keep = flags & 2;
   if (n >= 2) {
     const double* prev = row - POSE_ROW_WORDS;
     const double d0 = C[0] - prev[9], d1 = C[1] - prev[10], d2 = C[2] - prev[11];
-    const double len = sqrt(pose_dot(d0, d1, d2, d0, d1, d2));
+    const double len = sqrt(dot3(d0, d1, d2, d0, d1, d2));
     if (isfinite(len) && len > PNP_SCALE_FRACTION * s) {
       s = len;
       keep = 0;
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(PNP_THREADS) void landmark_corr_kernel(const double
     pnp_store_corr(corr + (size_t)k * PNP_CORR_WORDS, v, r, valid);
     cnt = cnt + (valid ? 1.0 : 0.0);
   }
-  const double total = eval_block_sum(cnt, red);   // (a count: exact)
+  const double total = block_sum<PNP_THREADS>(cnt, red);   // (a count: exact)
   if (tid == 0) {
     n_out[0] = n;
     n_out[1] = (int)total;
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(PNP_THREADS) void landmark_corr_kernel(const double
 __device__ __forceinline__ void pnp_bearing(double px, double py, PnpIntr K, double (&f)[3]) {
 #pragma clang fp contract(off)
   const double x = (px - K.cx) / K.fx, y = (py - K.cy) / K.fy;
-  const double nrm = sqrt(pose_dot(x, y, 1.0, x, y, 1.0));
+  const double nrm = sqrt(dot3(x, y, 1.0, x, y, 1.0));
   f[0] = x / nrm;
   f[1] = y / nrm;
   f[2] = 1.0 / nrm;
@@ -197,26 +197,27 @@ __device__ __forceinline__ double pnp_clamp(double x) {
 __device__ __forceinline__ bool pnp_frame(const double (&e1)[3], const double (&e2)[3], double (&w1)[3], double (&w2)[3], double (&w3)[3]) {
 #pragma clang fp contract(off)
   double n[3];
-  pose_cross(e1, e2, n);
-  const double l1 = pose_dot(e1[0], e1[1], e1[2], e1[0], e1[1], e1[2]), l2 = pose_dot(e2[0], e2[1], e2[2], e2[0], e2[1], e2[2]);
-  const double ln = pose_dot(n[0], n[1], n[2], n[0], n[1], n[2]);
+  cross3(e1, e2, n);
+  const double l1 = dot3(e1[0], e1[1], e1[2], e1[0], e1[1], e1[2]), l2 = dot3(e2[0], e2[1], e2[2], e2[0], e2[1], e2[2]);
+  const double ln = dot3(n[0], n[1], n[2], n[0], n[1], n[2]);
   const double s1 = sqrt(l1), sn = sqrt(ln);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     w1[k] = e1[k] / s1;
     w3[k] = n[k] / sn;
   }
-  pose_cross(w3, w1, w2);
+  cross3(w3, w1, w2);
   return isfinite(ln) && ln > PNP_FRAME_EPS * (l1 * l2);
 }
 
-// Squared reprojection error of X against the pixel under (R, C); front = the depth is finite and positive.
+// Squared reprojection error of X against the pixel under (R, C); front = the depth is finite and positive.  The same arithmetic
+// as project (geom_blocks.hip.h), written out: keep the two in step.
 __device__ __forceinline__ double pnp_view(const double (&R)[9], const double (&C)[3], double X0, double X1, double X2, double px,
                                            double py, PnpIntr K, bool& front) {
 #pragma clang fp contract(off)
   const double q0 = X0 - C[0], q1 = X1 - C[1], q2 = X2 - C[2];
-  const double y0 = pose_dot(R[0], R[1], R[2], q0, q1, q2), y1 = pose_dot(R[3], R[4], R[5], q0, q1, q2);
-  const double y2 = pose_dot(R[6], R[7], R[8], q0, q1, q2);
+  const double y0 = dot3(R[0], R[1], R[2], q0, q1, q2), y1 = dot3(R[3], R[4], R[5], q0, q1, q2);
+  const double y2 = dot3(R[6], R[7], R[8], q0, q1, q2);
   const double r0 = (K.fx * (y0 / y2) + K.cx) - px, r1 = (K.fy * (y1 / y2) + K.cy) - py;
   front = isfinite(y2) && y2 > 0.0;
   return r0 * r0 + r1 * r1;
@@ -239,12 +240,12 @@ __device__ __forceinline__ bool pnp_p3p(const double (&q)[4][5], PnpIntr K, doub
     e1[c] = q[1][c] - q[0][c];
     e2[c] = q[2][c] - q[0][c];
   }
-  const double aa = pose_dot(d23[0], d23[1], d23[2], d23[0], d23[1], d23[2]);
-  const double bb = pose_dot(d13[0], d13[1], d13[2], d13[0], d13[1], d13[2]);
-  const double cc = pose_dot(d12[0], d12[1], d12[2], d12[0], d12[1], d12[2]);
-  const double ca = pose_dot(f1[0], f1[1], f1[2], f2[0], f2[1], f2[2]);
-  const double cb = pose_dot(f0[0], f0[1], f0[2], f2[0], f2[1], f2[2]);
-  const double cg = pose_dot(f0[0], f0[1], f0[2], f1[0], f1[1], f1[2]);
+  const double aa = dot3(d23[0], d23[1], d23[2], d23[0], d23[1], d23[2]);
+  const double bb = dot3(d13[0], d13[1], d13[2], d13[0], d13[1], d13[2]);
+  const double cc = dot3(d12[0], d12[1], d12[2], d12[0], d12[1], d12[2]);
+  const double ca = dot3(f1[0], f1[1], f1[2], f2[0], f2[1], f2[2]);
+  const double cb = dot3(f0[0], f0[1], f0[2], f2[0], f2[1], f2[2]);
+  const double cg = dot3(f0[0], f0[1], f0[2], f1[0], f1[1], f1[2]);
   // u = s2 / s1 = N(v) / M(v), v = s3 / s1; the quartic g(v) = N^2 - 2 cos(gamma) N M + Q M^2
   const double A = aa / bb, Cc = cc / bb;
   const double Kd = A - Cc;
@@ -317,7 +318,7 @@ __device__ __forceinline__ bool pnp_p3p(const double (&q)[4][5], PnpIntr K, doub
 #pragma unroll
       for (int j = 0; j < 3; ++j) R[3 * i + j] = (c1[i] * w1[j] + c2[i] * w2[j]) + c3[i] * w3[j];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) C[j] = q[0][j] - pose_dot(R[j], R[3 + j], R[6 + j], Y1[0], Y1[1], Y1[2]);
+    for (int j = 0; j < 3; ++j) C[j] = q[0][j] - dot3(R[j], R[3 + j], R[6 + j], Y1[0], Y1[1], Y1[2]);
     bool front;
     const double e4 = pnp_view(R, C, q[3][0], q[3][1], q[3][2], q[3][3], q[3][4], K, front);
     const bool take = ok && front && isfinite(e4) && e4 < best;
@@ -334,29 +335,12 @@ __device__ __forceinline__ bool pnp_p3p(const double (&q)[4][5], PnpIntr K, doub
 // Hypotheses tried for n rows: none below 4, the one direct solve at 4, PNP_HYPOTHESES above.
 __device__ __forceinline__ int pnp_total(int n) { return n < 4 ? 0 : (n == 4 ? 1 : PNP_HYPOTHESES); }
 
-// Hypothesis h of a problem: 4 distinct valid rows from the counter-based stream (section 22's redraw rule; a draw that hits an
+// Hypothesis h of a problem: 4 distinct valid rows from the counter-based stream (sample_distinct; a draw that hits an
 // invalid row is redrawn too), then the minimal solve.  rows [n][PNP_CORR_WORDS].  false = invalid.
 __device__ __forceinline__ bool pnp_hypothesis(const double* __restrict__ rows, int n, uint64_t seed, int h, PnpIntr K, double (&R)[9],
                                                double (&C)[3]) {
   int id[4];
-  if (n == 4) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) id[k] = k;
-  } else {
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      int v;
-      bool bad;
-      do {
-        v = eval_draw(seed, h, c++, n);
-        bad = rows[(size_t)v * PNP_CORR_WORDS + 6] == 0.0;
-#pragma unroll
-        for (int j = 0; j < k; ++j) bad = bad || v == id[j];
-      } while (bad && c < EVAL_SAMPLE_DRAWS);
-      id[k] = v;
-    }
-  }
+  sample_distinct(seed, h, n, id, [rows](int v) { return rows[(size_t)v * PNP_CORR_WORDS + 6] != 0.0; });
   bool usable = true;
   double q[4][5];
 #pragma unroll
@@ -378,7 +362,7 @@ __device__ __forceinline__ PnpIntr pnp_intr_of(const double* __restrict__ intr, 
 }
 
 // grid (groups, problems).  corr [problems][cap][PNP_CORR_WORDS], intr [n_intr][4] (n_intr = 1 or problems).  keys
-// [problems][groups]: ((score + 1) << 32) | (0xFFFFFFFF - h) of the best valid hypothesis of the slice [g * per, (g + 1) * per),
+// [problems][groups]: key_of(score, h) of the best valid hypothesis of the slice [g * per, (g + 1) * per),
 // per = ceil(PNP_HYPOTHESES / groups); 0 = none.
 __global__ __launch_bounds__(PNP_THREADS) void pnp_hypotheses_kernel(const double* __restrict__ corr, const int32_t* __restrict__ n_in,
                                                                      int cap, const double* __restrict__ intr, int n_intr,
@@ -411,6 +395,7 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_hypotheses_kernel(const doubl
       const double e = pnp_view(R, C, row[0], row[1], row[2], row[3], row[4], K, front);
       sc += (row[6] != 0.0 && front && e <= t2) ? 1 : 0;
     }
+    // key_of and, below, publish_wave_keys / max_wave_key (geom_blocks.hip.h), written out: the same rules, keep them in step
     const uint64_t k = ((uint64_t)(sc + 1) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)h);
     key = (ok && k > key) ? k : key;
   }
@@ -429,71 +414,20 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_hypotheses_kernel(const doubl
   }
 }
 
-// Step K of the complete pivoting of a 6x7 augmented system (the pattern of epi_pivot_step: a template, so that every index is a
-// constant and the matrix stays in registers).  The pivot is the largest |entry| of rows K..5, columns K..5 (row-major scan with
-// a strict comparison: the lowest row, then the lowest column).
-template <int K>
-__device__ __forceinline__ void pnp_pivot_step(double (&a)[6][7], int (&perm)[6], bool& ok) {
-#pragma clang fp contract(off)
-  double best = -1.0;
-  int pr = K, pc = K;
-#pragma unroll
-  for (int r = K; r < 6; ++r) {
-#pragma unroll
-    for (int c = K; c < 6; ++c) {
-      const double v = fabs(a[r][c]);
-      const bool g = v > best;
-      best = g ? v : best;
-      pr = g ? r : pr;
-      pc = g ? c : pc;
-    }
-  }
-#pragma unroll
-  for (int r = K + 1; r < 6; ++r) {
-    const bool sw = pr == r;
-#pragma unroll
-    for (int c = K; c < 7; ++c) {
-      const double t = a[K][c];
-      a[K][c] = sw ? a[r][c] : t;
-      a[r][c] = sw ? t : a[r][c];
-    }
-  }
-#pragma unroll
-  for (int c = K + 1; c < 6; ++c) {
-    const bool sw = pc == c;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      const double t = a[r][K];
-      a[r][K] = sw ? a[r][c] : t;
-      a[r][c] = sw ? t : a[r][c];
-    }
-    const int tp = perm[K];
-    perm[K] = sw ? perm[c] : tp;
-    perm[c] = sw ? tp : perm[c];
-  }
-  ok = ok && fabs(a[K][K]) > PNP_PIVOT_EPS;
-  const double inv = 1.0 / a[K][K];
-#pragma unroll
-  for (int r = K + 1; r < 6; ++r) {
-    const double m = a[r][K] * inv;
-#pragma unroll
-    for (int c = K + 1; c < 7; ++c) a[r][c] = a[r][c] - m * a[K][c];
-  }
-}
-
-// x of A x = b (A in a[r][0..5], b in a[r][6]).  false: a pivot is <= PNP_PIVOT_EPS in magnitude (or NaN) or x is not finite.
+// x of A x = b (A in a[r][0..5], b in a[r][6]) by complete pivoting over the columns 0..5 (pivot_step).  false: a pivot is <=
+// PNP_PIVOT_EPS in magnitude (or NaN) or x is not finite.
 __device__ __forceinline__ bool pnp_solve6(double (&a)[6][7], double (&x)[6]) {
 #pragma clang fp contract(off)
   bool ok = true;
   int perm[6];
 #pragma unroll
   for (int c = 0; c < 6; ++c) perm[c] = c;
-  pnp_pivot_step<0>(a, perm, ok);
-  pnp_pivot_step<1>(a, perm, ok);
-  pnp_pivot_step<2>(a, perm, ok);
-  pnp_pivot_step<3>(a, perm, ok);
-  pnp_pivot_step<4>(a, perm, ok);
-  pnp_pivot_step<5>(a, perm, ok);
+  pivot_step<0>(a, perm, ok, PNP_PIVOT_EPS);
+  pivot_step<1>(a, perm, ok, PNP_PIVOT_EPS);
+  pivot_step<2>(a, perm, ok, PNP_PIVOT_EPS);
+  pivot_step<3>(a, perm, ok, PNP_PIVOT_EPS);
+  pivot_step<4>(a, perm, ok, PNP_PIVOT_EPS);
+  pivot_step<5>(a, perm, ok, PNP_PIVOT_EPS);
   double y[6];
 #pragma unroll
   for (int k = 5; k >= 0; --k) {
@@ -513,69 +447,6 @@ __device__ __forceinline__ bool pnp_solve6(double (&a)[6][7], double (&x)[6]) {
   return ok;
 }
 
-// R <- orthonormalised(Cay(w) R), t <- Cay(w) t + dt, delta = (w, dt); Cay(w) = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a),
-// a = w / 2.  The renormalisation: row 0 scaled to unit length, row 1 made orthogonal to it and scaled, row 2 their cross
-// product.  false (nothing changed): the result is not finite.
-__device__ __forceinline__ bool pnp_cayley_update(double (&R)[9], double (&t)[3], const double (&delta)[6]) {
-#pragma clang fp contract(off)
-  const double a0 = 0.5 * delta[0], a1 = 0.5 * delta[1], a2 = 0.5 * delta[2];
-  const double aa = pose_dot(a0, a1, a2, a0, a1, a2);
-  const double den = 1.0 + aa, om = 1.0 - aa;
-  const double Q[9] = {(om + 2.0 * (a0 * a0)) / den,        (2.0 * (a0 * a1) - 2.0 * a2) / den, (2.0 * (a0 * a2) + 2.0 * a1) / den,
-                       (2.0 * (a0 * a1) + 2.0 * a2) / den, (om + 2.0 * (a1 * a1)) / den,        (2.0 * (a1 * a2) - 2.0 * a0) / den,
-                       (2.0 * (a0 * a2) - 2.0 * a1) / den, (2.0 * (a1 * a2) + 2.0 * a0) / den, (om + 2.0 * (a2 * a2)) / den};
-  double M[9], tn[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) M[3 * i + j] = pose_dot(Q[3 * i], Q[3 * i + 1], Q[3 * i + 2], R[j], R[3 + j], R[6 + j]);
-    tn[i] = pose_dot(Q[3 * i], Q[3 * i + 1], Q[3 * i + 2], t[0], t[1], t[2]) + delta[3 + i];
-  }
-  const double nr0 = sqrt(pose_dot(M[0], M[1], M[2], M[0], M[1], M[2]));
-  const double r0[3] = {M[0] / nr0, M[1] / nr0, M[2] / nr0};
-  const double pj = pose_dot(M[3], M[4], M[5], r0[0], r0[1], r0[2]);
-  const double w[3] = {M[3] - pj * r0[0], M[4] - pj * r0[1], M[5] - pj * r0[2]};
-  const double nr1 = sqrt(pose_dot(w[0], w[1], w[2], w[0], w[1], w[2]));
-  const double r1[3] = {w[0] / nr1, w[1] / nr1, w[2] / nr1};
-  double r2[3];
-  pose_cross(r0, r1, r2);
-  bool fin = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) fin = fin && isfinite(r0[k]) && isfinite(r1[k]) && isfinite(r2[k]) && isfinite(tn[k]);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    R[k] = fin ? r0[k] : R[k];
-    R[3 + k] = fin ? r1[k] : R[3 + k];
-    R[6 + k] = fin ? r2[k] : R[6 + k];
-    t[k] = fin ? tn[k] : t[k];
-  }
-  return fin;
-}
-
-// eval_block_sum for N values at once, in its order: the xor butterfly inside each wave, then the wave partials in wave order; one
-// pair of barriers for all of them.  `red` holds (PNP_THREADS / 64) * N doubles.
-template <int N>
-__device__ __forceinline__ void pnp_block_sums(double (&v)[N], double* red) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int e = 0; e < N; ++e)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v[e] = v[e] + __shfl_xor(v[e], o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int e = 0; e < N; ++e) red[(threadIdx.x >> 6) * N + e] = v[e];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int e = 0; e < N; ++e) {
-    double t = red[e];
-#pragma unroll
-    for (int w = 1; w < PNP_THREADS / 64; ++w) t = t + red[w * N + e];
-    v[e] = t;
-  }
-}
-
 // The mask of the rows under (R, C) into `mask`, the squared errors of the masked rows summed; returns the count.
 __device__ __forceinline__ double pnp_mask_of(const double* __restrict__ rows, int n, const double (&R)[9], const double (&C)[3], PnpIntr K,
                                               double t2, uint8_t* mask, double* red, double& ss) {
@@ -591,7 +462,7 @@ __device__ __forceinline__ double pnp_mask_of(const double* __restrict__ rows, i
     if (in) part = part + e;
   }
   double both[2] = {part, c};
-  pnp_block_sums(both, red);  // (the barriers inside also publish the mask)
+  block_sums<PNP_THREADS>(both, red);  // (the barriers inside also publish the mask)
   ss = both[0];
   return both[1];
 }
@@ -615,13 +486,9 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_finish_kernel(const double* _
   const PnpIntr K = pnp_intr_of(intr, n_intr, p);
   const double t2 = thresh * thresh;
   const int need = min_inliers > 4 ? min_inliers : 4;
-  uint64_t key = 0;
-  for (int g = 0; g < groups; ++g) {
-    const uint64_t k = keys[(size_t)p * groups + g];
-    key = k > key ? k : key;
-  }
-  const int winner = (int)(0xFFFFFFFFu - (uint32_t)key);
-  bool valid = key != 0 && (int)(key >> 32) - 1 >= need;   // (uniform over the workgroup, as everything below)
+  const uint64_t key = max_group_key(keys, p, groups);
+  const int winner = hypothesis_of(key);
+  bool valid = key != 0 && score_of(key) >= need;   // (uniform over the workgroup, as everything below)
   double R0[9], C0[3], R[9], C[3], t[3];
   double k0 = 0.0, k1 = 0.0, ss0 = 0.0, ss1 = 0.0;
   bool refined = false;
@@ -634,7 +501,7 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_finish_kernel(const double* _
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = R0[k];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) t[i] = -pose_dot(R0[3 * i], R0[3 * i + 1], R0[3 * i + 2], C0[0], C0[1], C0[2]);
+    for (int i = 0; i < 3; ++i) t[i] = -dot3(R0[3 * i], R0[3 * i + 1], R0[3 * i + 2], C0[0], C0[1], C0[2]);
 #pragma unroll 1
     for (int step = 0; step < PNP_GN_STEPS; ++step) {
       // the 21 + 6 moments of y <- Cay(w) y + dt over the winner's inliers
@@ -644,9 +511,9 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_finish_kernel(const double* _
       for (int i = tid; i < n; i += PNP_THREADS) {
         if (!s_mask0[i]) continue;
         const double* row = rows + (size_t)i * PNP_CORR_WORDS;
-        const double y0 = pose_dot(R[0], R[1], R[2], row[0], row[1], row[2]) + t[0];
-        const double y1 = pose_dot(R[3], R[4], R[5], row[0], row[1], row[2]) + t[1];
-        const double y2 = pose_dot(R[6], R[7], R[8], row[0], row[1], row[2]) + t[2];
+        const double y0 = dot3(R[0], R[1], R[2], row[0], row[1], row[2]) + t[0];
+        const double y1 = dot3(R[3], R[4], R[5], row[0], row[1], row[2]) + t[1];
+        const double y2 = dot3(R[6], R[7], R[8], row[0], row[1], row[2]) + t[2];
         const double un = y0 / y2, vn = y1 / y2;
         const double r0 = (K.fx * un + K.cx) - row[3], r1 = (K.fy * vn + K.cy) - row[4];
         const double fa = K.fx / y2, fb = K.fy / y2;
@@ -660,7 +527,7 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_finish_kernel(const double* _
 #pragma unroll
         for (int a = 0; a < 6; ++a) mom[21 + a] = mom[21 + a] + (j0[a] * r0 + j1[a] * r1);
       }
-      pnp_block_sums(mom, red);
+      block_sums<PNP_THREADS>(mom, red);
       double a[6][7], delta[6];
       {
         int e = 0;
@@ -671,10 +538,10 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_finish_kernel(const double* _
 #pragma unroll
         for (int r = 0; r < 6; ++r) a[r][6] = -mom[21 + r];
       }
-      if (pnp_solve6(a, delta)) pnp_cayley_update(R, t, delta);
+      if (pnp_solve6(a, delta)) cayley_update(R, t, delta);
     }
 #pragma unroll
-    for (int j = 0; j < 3; ++j) C[j] = -pose_dot(R[j], R[3 + j], R[6 + j], t[0], t[1], t[2]);
+    for (int j = 0; j < 3; ++j) C[j] = -dot3(R[j], R[3 + j], R[6 + j], t[0], t[1], t[2]);
     k1 = pnp_mask_of(rows, n, R, C, K, t2, s_mask1, red, ss1);
     bool fin = true;
 #pragma unroll

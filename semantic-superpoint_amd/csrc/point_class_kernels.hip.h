@@ -7,15 +7,13 @@
 //                          H x W x C for the class map.
 //   filter_count_kernel    keep flags (row < count and bit cls of the 256-bit mask) counted per 1024-row block
 //   filter_scatter_kernel  every block sums the block counts before it and writes its surviving rows in order: the STABLE
-//                          cross-workgroup compaction of track_kernels.hip.h (track_block_scan / track_base_of), so the
+//                          cross-workgroup compaction of track_kernels.hip.h (block_scan_flag / block_base), so the
 //                          result does not depend on the order the blocks run in and needs no atomic ticket.  The 1 KiB
 //                          descriptor rows are moved by whole waves (16 bytes per lane), not by the thread that owns the row.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
+#include "geom_blocks.hip.h"
 #include "sem_eval_kernels.hip.h"
-#include "track_kernels.hip.h"
+#include "track_kernels.hip.h"  // TRACK_BLOCK
 
 namespace sspk {
 
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(TRACK_BLOCK) void filter_count_kernel(const int32_t
   const int img = blockIdx.y, r = blockIdx.x * TRACK_BLOCK + threadIdx.x;
   const int n = min(max(count[img], 0), cap);
   int total;
-  track_block_scan(filter_keep(mask, cls + (size_t)img * cap, r, n), wsum, total);
+  block_scan_flag<TRACK_BLOCK>(filter_keep(mask, cls + (size_t)img * cap, r, n), wsum, total);
   if (threadIdx.x == 0) block_sums[img * gridDim.x + blockIdx.x] = total;
 }
 
@@ -98,10 +96,10 @@ __global__ __launch_bounds__(TRACK_BLOCK) void filter_scatter_kernel(const float
   const int img = blockIdx.y, b = blockIdx.x, r = b * TRACK_BLOCK + threadIdx.x;
   const int n = min(max(count[img], 0), cap);
   const size_t row0 = (size_t)img * cap;
-  const int base = track_base_of(block_sums + img * gridDim.x, b, red);
+  const int base = block_base<TRACK_BLOCK>(block_sums + img * gridDim.x, b, red);
   const bool keep = filter_keep(mask, cls + row0, r, n);
   int total;
-  const int pos = base + track_block_scan(keep, wsum, total);  // pos <= r < cap
+  const int pos = base + block_scan_flag<TRACK_BLOCK>(keep, wsum, total);  // pos <= r < cap
   dst[threadIdx.x] = keep ? pos : -1;
   if (keep) {
     const float* s = pts + (row0 + r) * 5;

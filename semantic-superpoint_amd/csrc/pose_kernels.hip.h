@@ -3,11 +3,12 @@
 // in numpy by tests/pose_ref.py; everything here is fp64 with contraction off, in the parenthesisation of that file.
 //   pose_kernel        grid (pairs), 256 threads: E0 = K2^T F K1, the Jacobi sweeps on E0^T E0, U and V without a 3x3 SVD,
 //                      the four (R, t) candidates (all redundantly per thread), the in-front counts of the inliers in
-//                      eval_block_sum's fixed order, then the per-row outputs under the winner
+//                      block_sum's fixed order, then the per-row outputs under the winner
 //   pose_chain_kernel  grid (sequences), 256 threads: depth of frame f's points under pair A in LDS ("the lowest row wins"
 //                      by an LDS minimum: no order to depend on), the two sums over the shared points, the state update and
 //                      the trajectory row
 // The 3x3 work lives in registers: every index is a constant after unrolling, a data-dependent column is a select.
+// Needs: geom_blocks.hip.h, epipolar_kernels.hip.h (EPI_JACOBI_SWEEPS).
 #pragma once
 
 namespace sspk {
@@ -17,46 +18,6 @@ namespace sspk {
 #define POSE_DET_EPS 1e-12
 #define POSE_ROW_WORDS 16
 #define POSE_STATE_WORDS 16
-static_assert(POSE_THREADS == EVAL_THREADS, "eval_block_sum reduces EVAL_THREADS lanes");
-
-__device__ __forceinline__ double pose_dot(double p0, double p1, double p2, double q0, double q1, double q2) {
-#pragma clang fp contract(off)
-  return (p0 * q0 + p1 * q1) + p2 * q2;
-}
-
-__device__ __forceinline__ void pose_cross(const double (&a)[3], const double (&b)[3], double (&c)[3]) {
-#pragma clang fp contract(off)
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// One rotation of the cyclic Jacobi of section 22 on the pair (P, Q) of a symmetric 3x3 (the rule of epi_rank2, which keeps
-// its eigenvectors to itself: it returns the rank-2 matrix only).  A template: P, Q and the third index are constants.
-template <int P, int Q>
-__device__ __forceinline__ void pose_jacobi_rotate(double (&G)[3][3], double (&V)[3][3]) {
-#pragma clang fp contract(off)
-  constexpr int R = 3 - P - Q;
-  const double gpq = G[P][Q];
-  if (gpq == 0.0) return;
-  const double theta = (G[Q][Q] - G[P][P]) / (2.0 * gpq);
-  double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-  if (theta < 0.0) t = -t;
-  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-  const double gpp = G[P][P] - t * gpq, gqq = G[Q][Q] + t * gpq;
-  const double grp = c * G[R][P] - s * G[R][Q], grq = s * G[R][P] + c * G[R][Q];
-  G[P][P] = gpp;
-  G[Q][Q] = gqq;
-  G[P][Q] = G[Q][P] = 0.0;
-  G[R][P] = G[P][R] = grp;
-  G[R][Q] = G[Q][R] = grq;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double vp = c * V[k][P] - s * V[k][Q], vq = s * V[k][P] + c * V[k][Q];
-    V[k][P] = vp;
-    V[k][Q] = vq;
-  }
-}
 
 // (fx, fy, cx, cy) of the two views of a pair
 struct PoseIntr {
@@ -92,13 +53,13 @@ __device__ __forceinline__ bool pose_candidates(const double* __restrict__ F, Po
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-      G[i][j] = pose_dot(E0[i], E0[3 + i], E0[6 + i], E0[j], E0[3 + j], E0[6 + j]);
+      G[i][j] = dot3(E0[i], E0[3 + i], E0[6 + i], E0[j], E0[3 + j], E0[6 + j]);
       V[i][j] = i == j ? 1.0 : 0.0;
     }
   for (int sweep = 0; sweep < EPI_JACOBI_SWEEPS; ++sweep) {
-    pose_jacobi_rotate<0, 1>(G, V);
-    pose_jacobi_rotate<0, 2>(G, V);
-    pose_jacobi_rotate<1, 2>(G, V);
+    jacobi_rotate<0, 1>(G, V);
+    jacobi_rotate<0, 2>(G, V);
+    jacobi_rotate<1, 2>(G, V);
   }
   // the columns of the largest and the second-largest diagonal entry, the lowest index on ties
   const double d0 = G[0][0], d1 = G[1][1], d2 = G[2][2];
@@ -112,24 +73,24 @@ __device__ __forceinline__ bool pose_candidates(const double* __restrict__ F, Po
     v0[k] = k0 == 0 ? V[k][0] : (k0 == 1 ? V[k][1] : V[k][2]);
     v1[k] = k1 == 0 ? V[k][0] : (k1 == 1 ? V[k][1] : V[k][2]);
   }
-  pose_cross(v0, v1, v2);
+  cross3(v0, v1, v2);
   double w[3], u0[3], u1[3];
 #pragma unroll
-  for (int r = 0; r < 3; ++r) w[r] = pose_dot(E0[3 * r], E0[3 * r + 1], E0[3 * r + 2], v0[0], v0[1], v0[2]);
-  const double n0 = sqrt(pose_dot(w[0], w[1], w[2], w[0], w[1], w[2]));
+  for (int r = 0; r < 3; ++r) w[r] = dot3(E0[3 * r], E0[3 * r + 1], E0[3 * r + 2], v0[0], v0[1], v0[2]);
+  const double n0 = sqrt(dot3(w[0], w[1], w[2], w[0], w[1], w[2]));
   ok = ok && isfinite(n0) && n0 > 0.0;
 #pragma unroll
   for (int r = 0; r < 3; ++r) u0[r] = w[r] / n0;
 #pragma unroll
-  for (int r = 0; r < 3; ++r) w[r] = pose_dot(E0[3 * r], E0[3 * r + 1], E0[3 * r + 2], v1[0], v1[1], v1[2]);
-  const double pw = pose_dot(w[0], w[1], w[2], u0[0], u0[1], u0[2]);
+  for (int r = 0; r < 3; ++r) w[r] = dot3(E0[3 * r], E0[3 * r + 1], E0[3 * r + 2], v1[0], v1[1], v1[2]);
+  const double pw = dot3(w[0], w[1], w[2], u0[0], u0[1], u0[2]);
 #pragma unroll
   for (int r = 0; r < 3; ++r) w[r] = w[r] - pw * u0[r];
-  const double n1 = sqrt(pose_dot(w[0], w[1], w[2], w[0], w[1], w[2]));
+  const double n1 = sqrt(dot3(w[0], w[1], w[2], w[0], w[1], w[2]));
   ok = ok && isfinite(n1) && n1 > 0.0;
 #pragma unroll
   for (int r = 0; r < 3; ++r) u1[r] = w[r] / n1;
-  pose_cross(u0, u1, u2);
+  cross3(u0, u1, u2);
 #pragma unroll
   for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -146,12 +107,12 @@ __device__ __forceinline__ bool pose_candidates(const double* __restrict__ F, Po
 __device__ __forceinline__ bool pose_depths(const double (&R)[9], double t0, double t1, double t2, double x1x, double x1y,
                                             double x2x, double x2y, double& z1, double& z2) {
 #pragma clang fp contract(off)
-  const double a0 = pose_dot(R[0], R[1], R[2], x1x, x1y, 1.0);
-  const double a1 = pose_dot(R[3], R[4], R[5], x1x, x1y, 1.0);
-  const double a2 = pose_dot(R[6], R[7], R[8], x1x, x1y, 1.0);
-  const double A11 = pose_dot(a0, a1, a2, a0, a1, a2), A22 = pose_dot(x2x, x2y, 1.0, x2x, x2y, 1.0);
-  const double A12 = pose_dot(a0, a1, a2, x2x, x2y, 1.0);
-  const double b1 = -pose_dot(a0, a1, a2, t0, t1, t2), b2 = pose_dot(x2x, x2y, 1.0, t0, t1, t2);
+  const double a0 = dot3(R[0], R[1], R[2], x1x, x1y, 1.0);
+  const double a1 = dot3(R[3], R[4], R[5], x1x, x1y, 1.0);
+  const double a2 = dot3(R[6], R[7], R[8], x1x, x1y, 1.0);
+  const double A11 = dot3(a0, a1, a2, a0, a1, a2), A22 = dot3(x2x, x2y, 1.0, x2x, x2y, 1.0);
+  const double A12 = dot3(a0, a1, a2, x2x, x2y, 1.0);
+  const double b1 = -dot3(a0, a1, a2, t0, t1, t2), b2 = dot3(x2x, x2y, 1.0, t0, t1, t2);
   const double det = A11 * A22 - A12 * A12;
   z1 = (b1 * A22 + A12 * b2) / det;
   z2 = (A11 * b2 + A12 * b1) / det;
@@ -216,10 +177,10 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_kernel(const double* __rest
       c2 = c2 + (pose_depths(Rb, u2[0], u2[1], u2[2], x1x, x1y, x2x, x2y, z1, z2) ? 1.0 : 0.0);
       c3 = c3 + (pose_depths(Rb, -u2[0], -u2[1], -u2[2], x1x, x1y, x2x, x2y, z1, z2) ? 1.0 : 0.0);
     }
-    cnt[0] = (int)eval_block_sum(c0, red);  // (counts: exact in fp64, and the order is fixed anyway)
-    cnt[1] = (int)eval_block_sum(c1, red);
-    cnt[2] = (int)eval_block_sum(c2, red);
-    cnt[3] = (int)eval_block_sum(c3, red);
+    cnt[0] = (int)block_sum<POSE_THREADS>(c0, red);  // (counts: exact in fp64, and the order is fixed anyway)
+    cnt[1] = (int)block_sum<POSE_THREADS>(c1, red);
+    cnt[2] = (int)block_sum<POSE_THREADS>(c2, red);
+    cnt[3] = (int)block_sum<POSE_THREADS>(c3, red);
     win = 0;
     int best = cnt[0];
 #pragma unroll
@@ -315,8 +276,8 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_chain_kernel(const uint8_t*
     sb = sb + db[(size_t)k * 2];
     sc = sc + 1.0;
   }
-  const double SA = eval_block_sum(sa, red), SB = eval_block_sum(sb, red);
-  const int n_shared = (int)eval_block_sum(sc, red);
+  const double SA = block_sum<POSE_THREADS>(sa, red), SB = block_sum<POSE_THREADS>(sb, red);
+  const int n_shared = (int)block_sum<POSE_THREADS>(sc, red);
   if (tid != 0) return;
   double* st = state + (size_t)q * POSE_STATE_WORDS;
   const double ratio = n_shared > 0 ? SA / SB : 0.0;
@@ -337,11 +298,11 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_chain_kernel(const uint8_t*
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) Rw[3 * r + c] = pose_dot(R[3 * r], R[3 * r + 1], R[3 * r + 2], Rw0[c], Rw0[3 + c], Rw0[6 + c]);
-    tw[r] = pose_dot(R[3 * r], R[3 * r + 1], R[3 * r + 2], tw0[0], tw0[1], tw0[2]) + s * t[r];
+    for (int c = 0; c < 3; ++c) Rw[3 * r + c] = dot3(R[3 * r], R[3 * r + 1], R[3 * r + 2], Rw0[c], Rw0[3 + c], Rw0[6 + c]);
+    tw[r] = dot3(R[3 * r], R[3 * r + 1], R[3 * r + 2], tw0[0], tw0[1], tw0[2]) + s * t[r];
   }
 #pragma unroll
-  for (int c = 0; c < 3; ++c) C[c] = -pose_dot(Rw[c], Rw[3 + c], Rw[6 + c], tw[0], tw[1], tw[2]);
+  for (int c = 0; c < 3; ++c) C[c] = -dot3(Rw[c], Rw[3 + c], Rw[6 + c], tw[0], tw[1], tw[2]);
   const int flags = (posed ? 0 : 1) | (ok ? 0 : 2);
   const int row = (int)st[0];
   if (row >= 0 && row < capacity) {

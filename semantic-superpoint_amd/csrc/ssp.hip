@@ -31,6 +31,7 @@
 #include "photo_kernels.hip.h"
 #include "shapes_kernels.hip.h"
 #include "export_kernels.hip.h"
+#include "geom_blocks.hip.h"
 #include "describe_kernels.hip.h"
 #include "track_kernels.hip.h"
 #include "eval_kernels.hip.h"
@@ -4231,7 +4232,7 @@ int ssp_world_repair(const double* rw_dev, const double* c_dev, const int32_t* s
 // ---- loop closure: the join against old rows, the loop edge, the pose graph, the write-back ----
 static_assert(LOOP_MAX_EDGES == SSP_LOOP_MAX_EDGES && LOOP_EDGE_WORDS == SSP_LOOP_EDGE_WORDS && LOOP_STATE_WORDS == SSP_LOOP_STATE_WORDS &&
               LOOP_CAND_WORDS == SSP_LOOP_CAND_WORDS && LOOP_MAX_INNER == SSP_LOOP_MAX_INNER && LOOP_INFO_WORDS == SSP_LOOP_INFO_WORDS &&
-              LOOP_FLAG_LOOP == SSP_POSE_FLAG_LOOP && LOOP_MAX_ITERATIONS == SSP_LOOP_MAX_ITERATIONS && EVAL_THREADS == 256,
+              LOOP_FLAG_LOOP == SSP_POSE_FLAG_LOOP && LOOP_MAX_ITERATIONS == SSP_LOOP_MAX_ITERATIONS,
               "include/ssp_hip.h and loop_kernels.hip.h disagree");
 size_t ssp_pose_graph_workspace_bytes(int capacity) {
   if (capacity < 2 || capacity > (1 << 20)) {

@@ -14,6 +14,8 @@
 //                          ballots and writes the surviving rows in order: a STABLE compaction across workgroups whose
 //                          result does not depend on the order the blocks run in.  The last block writes the state.
 // get_tracks is the same count / scatter pair with another predicate; it writes the public fp64 [M][2+L] matrix.
+// The in-block scan and the sum of the earlier blocks are block_scan_flag and block_base of geom_blocks.hip.h.
+// Needs: geom_blocks.hip.h.
 #pragma once
 
 namespace sspk {
@@ -107,40 +109,6 @@ __device__ __forceinline__ bool track_row_selected(const int32_t* __restrict__ i
   return n >= min_length && ids[L - 1] != -1;
 }
 
-// Exclusive position of this thread's flag inside its block and the block's total (all threads of the block call it).
-__device__ __forceinline__ int track_block_scan(bool keep, int* wsum, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(keep);
-  const int before = __popcll(bal & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (lane == 0) wsum[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < TRACK_BLOCK / 64; ++w) {
-    const int s = wsum[w];
-    off += w < wave ? s : 0;
-    tot += s;
-  }
-  total = tot;
-  return off + before;
-}
-
-// Sum of the block counts before block b (every thread returns it); `red` holds 16 ints.
-__device__ __forceinline__ int track_base_of(const int32_t* __restrict__ block_sums, int b, int* red) {
-  int v = 0;
-  for (int k = threadIdx.x; k < b; k += TRACK_BLOCK) v += block_sums[k];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < TRACK_BLOCK / 64; ++w) t += red[w];
-  return t;
-}
-
 // Blocks [0, nb_old) cover the old rows, blocks [nb_old, nb_old + nb_new) the points of the new frame.
 __device__ __forceinline__ bool track_update_flag(int b, int nb_old, int n_rows, int n_new, const int32_t* __restrict__ ids_tmp,
                                                   const int32_t* __restrict__ matched, int L) {
@@ -159,7 +127,7 @@ __global__ __launch_bounds__(TRACK_BLOCK) void track_count_kernel(const int32_t*
   __shared__ int wsum[TRACK_BLOCK / 64];
   const int n_rows = min(max(state_in[0], 0), row_cap), n_new = min(max(n_points[0], 0), point_cap);
   int total;
-  track_block_scan(track_update_flag(blockIdx.x, nb_old, n_rows, n_new, ids_tmp, matched, L), wsum, total);
+  block_scan_flag<TRACK_BLOCK>(track_update_flag(blockIdx.x, nb_old, n_rows, n_new, ids_tmp, matched, L), wsum, total);
   if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -176,11 +144,11 @@ __global__ __launch_bounds__(TRACK_BLOCK) void track_scatter_kernel(const int32_
   const TrackCounts t = track_counts(state_in, L, point_cap, row_cap);
   const int n_new = min(max(n_points[0], 0), point_cap);
   const int b = blockIdx.x, nb = gridDim.x;
-  const int base = track_base_of(block_sums, b, red);
-  const int kept_old = b < nb_old ? 0 : track_base_of(block_sums, nb_old, red);  // (uniform per block)
+  const int base = block_base<TRACK_BLOCK>(block_sums, b, red);
+  const int kept_old = b < nb_old ? 0 : block_base<TRACK_BLOCK>(block_sums, nb_old, red);  // (uniform per block)
   const bool keep = track_update_flag(b, nb_old, t.n_rows, n_new, ids_tmp, matched, L);
   int total;
-  const int pos = base + track_block_scan(keep, wsum, total);
+  const int pos = base + block_scan_flag<TRACK_BLOCK>(keep, wsum, total);
   if (keep && pos < row_cap) {
     int32_t* dst = ids_out + (size_t)pos * L;
     if (b < nb_old) {
@@ -213,7 +181,7 @@ __global__ __launch_bounds__(TRACK_BLOCK) void track_select_count_kernel(const i
   const int n_rows = min(max(state[0], 0), row_cap);
   const int r = blockIdx.x * TRACK_BLOCK + threadIdx.x;
   int total;
-  track_block_scan(r < n_rows && track_row_selected(ids + (size_t)r * L, L, min_length), wsum, total);
+  block_scan_flag<TRACK_BLOCK>(r < n_rows && track_row_selected(ids + (size_t)r * L, L, min_length), wsum, total);
   if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -228,10 +196,10 @@ __global__ __launch_bounds__(TRACK_BLOCK) void track_select_scatter_kernel(const
   __shared__ int red[TRACK_BLOCK / 64];
   const int n_rows = min(max(state[0], 0), row_cap);
   const int r = blockIdx.x * TRACK_BLOCK + threadIdx.x;
-  const int base = track_base_of(block_sums, blockIdx.x, red);
+  const int base = block_base<TRACK_BLOCK>(block_sums, blockIdx.x, red);
   const bool keep = r < n_rows && track_row_selected(ids + (size_t)r * L, L, min_length);
   int total;
-  const int pos = base + track_block_scan(keep, wsum, total);
+  const int pos = base + block_scan_flag<TRACK_BLOCK>(keep, wsum, total);
   if (keep) {
     double* o = out + (size_t)pos * (2 + L);
     o[0] = (double)tid[r];

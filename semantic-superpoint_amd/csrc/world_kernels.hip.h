@@ -21,6 +21,8 @@
 //                          descriptor copy; block 0 writes the map's counters
 //   world_corr_kernel      one workgroup: a correspondence row (X, Y, Z, px, py, map row, valid, 0) per match row
 //   world_repair_kernel    one thread: section 27's repair with the world's firing condition, the streak of repaired frames
+// Needs: geom_blocks.hip.h, describe_kernels.hip.h (min_u64, shfl_xor_u64), pose_kernels.hip.h (POSE_ROW_WORDS),
+// landmark_kernels.hip.h (LM_WORDS), pnp_kernels.hip.h (the correspondence rows, pnp_load_pose, pnp_rewrite_row).
 #pragma once
 
 namespace sspk {
@@ -137,30 +139,6 @@ __global__ __launch_bounds__(256, 2) void world_match_kernel(const float* __rest
   }
 }
 
-// block-wide exclusive scan of one int per thread (WORLD_BLOCK threads); wsum: 16 ints of LDS.  Returns the exclusive prefix and
-// leaves the total in *total.  Two barriers; safe to call again after the second.
-__device__ __forceinline__ int world_block_scan(int v, int* wsum, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int up = __shfl_up(inc, o);
-    if (lane >= o) inc += up;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < WORLD_BLOCK / 64; ++w) {
-    const int s = wsum[w];
-    off += w < wave ? s : 0;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return off + inc - v;
-}
-
 __global__ __launch_bounds__(WORLD_BLOCK) void world_compact_kernel(const uint64_t* __restrict__ rowmin, const uint64_t* __restrict__ colmin,
                                                                     const int32_t* __restrict__ world_state, int map_cap,
                                                                     const int32_t* __restrict__ count2, int cap, float thresh,
@@ -182,7 +160,7 @@ __global__ __launch_bounds__(WORLD_BLOCK) void world_compact_kernel(const uint64
     cnt += (dd < thresh && j < (uint32_t)n2 && (uint32_t)colmin[j] == (uint32_t)i) ? 1 : 0;
   }
   int total;
-  int off = world_block_scan(cnt, wsum, &total);
+  int off = block_scan<WORLD_BLOCK>(cnt, wsum, total);
   for (int i = lo; i < hi; ++i) {
     const uint64_t k = rowmin[i];
     const uint32_t j = (uint32_t)k;
@@ -302,7 +280,7 @@ __global__ __launch_bounds__(WORLD_BLOCK) void world_scatter_kernel(const int32_
   for (int b = 0; b < (int)blockIdx.x; ++b) base += bcount[b];
   const int code = r < row_cap ? cls[r] : WORLD_CLS_SKIP;
   int total;
-  const int rank = world_block_scan(code == WORLD_CLS_NEW ? 1 : 0, wsum, &total);
+  const int rank = block_scan<WORLD_BLOCK>(code == WORLD_CLS_NEW ? 1 : 0, wsum, total);
   int slot = -1, p = 0;
   if (code != WORLD_CLS_SKIP) {
     const double* lm = landmarks + (size_t)r * LM_WORDS;

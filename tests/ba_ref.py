@@ -5,7 +5,7 @@ the trajectory (`apply`).  There is no reference counterpart, so this file is th
 Everything is fp64 in the parenthesisation written here, vectorised over the rows (the loops over the views and the pairs of
 views are the kernel's); every function also runs in pose_ref.WAY2 (numpy.longdouble where that is wider than float64), which is
 how the tolerance of the continuous outputs is measured (`way_difference`).  Sums over the rows run in the device's order:
-eval_block_sum's inside a tile of 256 rows (`tile_sum`), the tiles ascending.  Also the fixtures: landmarks_ref's tables under
+block_sum's (csrc/geom_blocks.hip.h) inside a tile of 256 rows (`tile_sum`), the tiles ascending.  Also the fixtures: landmarks_ref's tables under
 perturbed true cameras, two of its window scenarios, six noisy chains of pnp_ref.run_sequence."""
 import functools
 import math
@@ -36,7 +36,7 @@ def _dot(p, q, rev=False):
 # ---- sums in the device's order ------------------------------------------------------------------------------------------------
 def tile_sum(vals):
     """Sum over axis 0 (the rows; a row that takes no part holds zeros): per tile of 256 rows the xor butterfly inside each wave
-    of 64 and the four wave partials in wave order (eval_block_sum), then the tiles in ascending order."""
+    of 64 and the four wave partials in wave order (block_sum), then the tiles in ascending order."""
     vals = np.asarray(vals)
     n = vals.shape[0]
     tiles = max(1, -(-n // TILE))

@@ -4,7 +4,7 @@ the depth ratio, roots by bracketing between the derivative's roots and bisectio
 point picks the solution), the Gauss-Newton refit with the Cayley update (`refit`) and the repair of a flagged trajectory row
 (`repair`).  There is no reference counterpart and no OpenCV here, so this file is the specification the kernels are tested
 against.  Camera model of section 26: y = Rw (X - C), u = fx * y0 / y2 + cx.  Everything is fp64 in the parenthesisation written
-here, vectorised over the hypotheses or over the rows; the sums over the rows repeat eval_block_sum's order (`block_sum`), so the
+here, vectorised over the hypotheses or over the rows; the sums over the rows repeat block_sum's order (`block_sum`), so the
 device agrees to the last bit wherever its sqrt and division are correctly rounded.  Every function also runs in another "way"
 (pose_ref.WAY2: numpy.longdouble where that is wider than float64, else the dot products in the reverse order), which is how the
 tolerance of the continuous outputs is measured (`way_difference`).  Also the fixtures."""
@@ -258,7 +258,7 @@ def inliers(R, C, corr, n, k, thresh, way=WAY1):
         return (corr[None, :, 6] != 0.0) & front & (e <= t2), e
 
 
-# ---- sums in eval_block_sum's order --------------------------------------------------------------------------------------------
+# ---- sums in block_sum's order (csrc/geom_blocks.hip.h) --------------------------------------------------------------------------------------------
 def block_sum(vals, active):
     """Sum over the rows of vals [n, M] where active [n]: thread t adds rows t, t + 256, ... in order, the xor butterfly inside each
     wave of 64, the four wave partials in wave order."""

@@ -566,3 +566,44 @@ def test_shipped_binary_keeps_the_accumulation_register_contract():
     wrong = {"conv_wino4_kernel": dict(hipbuild.FIXED_AGPR_KERNELS["conv_wino4_kernel"], v_accvgpr_read_b32=511)}
     with pytest.raises(RuntimeError, match="differ from the inline-asm contract"):
         hipbuild.verify_binary(lib, expected=wrong)
+
+
+GEOMETRY_HEADERS = ("describe", "track", "eval", "epipolar", "pose", "landmark", "pnp", "ba", "world", "loop", "detector_eval",
+                    "point_class")
+
+
+def test_geometry_headers_stand_on_the_shared_blocks(tmp_path):
+    """csrc/geom_blocks.hip.h holds the one copy of the device routines the geometry headers share.  ssp.hip includes it ahead
+    of every one of them, and each header compiles for gfx950 when a unit includes nothing but the shared blocks, the headers
+    its `// Needs:` line names (and theirs) and the header itself: no header borrows a helper from a sibling it does not
+    declare."""
+    import shutil
+    import subprocess
+    csrc = os.path.join(ROOT, "semantic-superpoint_amd", "csrc")
+    order = re.findall(r'^#include "(\w+)\.hip\.h"', open(os.path.join(csrc, "ssp.hip")).read(), re.M)
+    assert "geom_blocks" in order
+    assert all(order.index("geom_blocks") < order.index(h + "_kernels") for h in GEOMETRY_HEADERS)
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    assert os.path.exists(hipcc), "hipcc is needed to compile the headers alone"
+
+    def needs(name, seen):
+        text = open(os.path.join(csrc, name)).read()
+        m = re.search(r"^// Needs:(.*?)^#pragma once", text, re.S | re.M)
+        for dep in re.findall(r"(\w+\.hip\.h)", m.group(1) if m else ""):
+            if dep not in seen:
+                needs(dep, seen)
+        if name not in seen:
+            seen.append(name)
+        return seen
+
+    failed = {}
+    for h in GEOMETRY_HEADERS:
+        units = needs(h + "_kernels.hip.h", ["geom_blocks.hip.h"])
+        assert set(units) <= {"geom_blocks.hip.h"} | {g + "_kernels.hip.h" for g in GEOMETRY_HEADERS}, units
+        tu = tmp_path / (h + ".hip")
+        tu.write_text("#include <hip/hip_runtime.h>\n#include <stdint.h>\n" + "".join('#include "%s"\n' % u for u in units))
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-fsyntax-only", "-I", csrc, str(tu)],
+                           capture_output=True, text=True, timeout=600)
+        if r.returncode != 0:
+            failed[h] = r.stderr[-2000:]
+    assert not failed, failed
