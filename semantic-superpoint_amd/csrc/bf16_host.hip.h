@@ -1,5 +1,5 @@
 // Host side of the bf16 path (conv algorithm 12): launchers of conv_bf16.hip.h / wgrad_bf16.hip.h and their operator-level
-// entry points.  Included by ssp.hip after its helpers (fail, CHK, HIPCHK, cdiv, AttrOnce, device_cu_count).
+// entry points.  Included by ssp.hip after its helpers (the environment accessors, fail, CHK, HIPCHK, launch_lds, TraceSite, cdiv, device_cu_count).
 #pragma once
 
 struct ConvBCall {
@@ -23,35 +23,17 @@ static inline size_t convb_image_bytes(int ks, int cin, int cout) {
   return (size_t)convb_ncob(cout) * convb_nchunks(cin) * ks * ks * 4096;
 }
 
-template <int KS, int IN_MODE, bool IN_F32, bool OUT_F32>
-static int launch_conv_bf16_t(const ConvBArgs& a, int nblocks, hipStream_t st) {
-  using G = ConvBGeom<KS>;
-  static AttrOnce attr_once;
-  auto kern = conv_bf16_kernel<KS, IN_MODE, IN_F32, OUT_F32>;
-  if (attr_once.need())
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), G::LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <int IN_MODE, bool NC2>
-static int launch_conv_bf16_ws_t(const ConvBArgs& a, int nblocks, hipStream_t st) {
-  static AttrOnce attr_once;
-  auto kern = conv_bf16_ws_kernel<IN_MODE, NC2>;
-  if (attr_once.need())
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ConvWsGeom::LDS_BYTES));
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(conv_ws_threads<IN_MODE>()), ConvWsGeom::LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// whether launch_conv_bf16 runs this call on the wave-specialised kernel (the form that can carry the fused BatchNorm-backward sums)
-static bool launch_conv_bf16_is_ws(const ConvBCall& c) {
-  static const int ws_env = getenv("SSP_CONVB_WS") ? atoi(getenv("SSP_CONVB_WS")) : 1;
+// can this call run on the wave-specialised kernel (3x3, bf16 tensors at both ends, whole pairs of 32-channel chunks; the staging-free
+// form is the data gradient: no bias path)?  launch_conv_bf16 runs every such call there.
+static bool convb_ws_ok(const ConvBCall& c) {
   const int nchunks = convb_nchunks(c.cin);
-  return ws_env != 0 && c.ks == 3 && !c.in_f32 && !c.out_f32 && nchunks >= 2 && nchunks % 2 == 0 && c.cin % CB_KC == 0 &&
-         c.in_mode == 0 && c.bias == nullptr && c.out_co == 0 && c.out_cs == c.cout && !c.stats[0];
+  return convb_ws_env() && c.ks == 3 && !c.in_f32 && !c.out_f32 && nchunks >= 2 && nchunks % 2 == 0 && c.cin % CB_KC == 0 &&
+         !(c.in_mode == 0 && c.bias != nullptr);
+}
+// whether launch_conv_bf16 runs this call on the wave-specialised kernel in the form that can carry the fused BatchNorm-backward sums:
+// the data gradient with a dense output and no forward statistics
+static bool launch_conv_bf16_is_ws(const ConvBCall& c) {
+  return convb_ws_ok(c) && c.in_mode == 0 && c.out_co == 0 && c.out_cs == c.cout && !c.stats[0];
 }
 
 static int launch_conv_bf16(const ConvBCall& c, int n_cu, hipStream_t st) {
@@ -70,18 +52,10 @@ static int launch_conv_bf16(const ConvBCall& c, int n_cu, hipStream_t st) {
   const double img = (double)c.H * c.W * c.in_cs * (c.in_f32 ? 4.0 : 2.0);
   if (img > 2147483647.0) return fail(-3, "bf16 conv: one input image [%d,%d,%d] exceeds 2 GiB", c.H, c.W, c.in_cs);
   a.in_img_bytes = (unsigned)img;
-  static const int ablate_env = getenv("SSP_CONVB_ABLATE") ? atoi(getenv("SSP_CONVB_ABLATE")) : 0;  // (perf-debug)
-  a.ablate = ablate_env;
-  a.trace = nullptr;
-  static const int trace_env = getenv("SSP_CONVB_TRACE") ? atoi(getenv("SSP_CONVB_TRACE")) : 0;  // (perf-debug: blocking, prints per launch)
-  static unsigned long long* trace_buf = nullptr;
-  static int trace_count = 0;
-  const bool trace_now = trace_env > 0 && c.ks == 3 && !c.in_f32 && !c.out_f32 && (++trace_count % trace_env) == 0;   // every N-th launch
-  if (trace_now) {
-    if (!trace_buf) HIPCHK(hipMalloc(&trace_buf, (64 + 1024) * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(trace_buf, 0, (64 + 1024) * sizeof(unsigned long long), st));
-    a.trace = trace_buf;
-  }
+  a.ablate = convb_ablate_env();
+  // (perf-debug: blocking, prints per launch) every SSP_CONVB_TRACE-th launch of a 3x3 layer with bf16 tensors at both ends
+  static TraceSite<64 + 1024> tr;
+  CHK(tr.begin(c.ks == 3 && !c.in_f32 && !c.out_f32 ? convb_trace_env() : 0, st, &a.trace));
   if (!c.out_f32 && (c.cout % 8 || c.out_cs % 8 || c.out_co % 8)) return fail(-3, "bf16 conv: bf16 output needs channel counts / offsets that are multiples of 8");
   if (!c.in_f32 && (c.in_cs % 8 || c.in_co % 8)) return fail(-3, "bf16 conv: bf16 input needs channel stride / offset that are multiples of 8");
   if (c.in_f32 && (c.in_cs % 4 || c.in_co % 4)) return fail(-3, "bf16 conv: fp32 input needs channel stride / offset that are multiples of 4");
@@ -91,12 +65,8 @@ static int launch_conv_bf16(const ConvBCall& c, int n_cu, hipStream_t st) {
   const long units = (long)c.nviews * a.ncob * c.N * a.tiles_x * a.tiles_y;
   int nblocks = (int)std::min<long>(2L * n_cu, cdiv(units, 8) * 8L) / 8 * 8;
   nblocks = std::max(nblocks, 8);
-  static const int grid_env = getenv("SSP_CONVB_GRID") ? atoi(getenv("SSP_CONVB_GRID")) : 0;  // (perf-debug)
-  if (grid_env > 0) nblocks = grid_env;
   // the 3x3 layers with bf16 tensors at both ends: wave-specialised kernel, one 8-wave workgroup per CU (SSP_CONVB_WS=0: perf-debug A/B)
-  static const int ws_env = getenv("SSP_CONVB_WS") ? atoi(getenv("SSP_CONVB_WS")) : 1;
-  const bool ws_ok = ws_env != 0 && c.ks == 3 && !c.in_f32 && !c.out_f32 && a.nchunks >= 2 && a.nchunks % 2 == 0 && c.cin % CB_KC == 0 &&
-                     !(c.in_mode == 0 && c.bias != nullptr);   // (the staging-free form is the data gradient: no bias path)
+  const bool ws_ok = convb_ws_ok(c);
   // fused BatchNorm-backward sums: the wave-specialised data-gradient form with a dense output, or the generic kernel with a bf16 output
   // (there the tensor of the layer below has the geometry of the output: out_cs, out_co) - never beside forward statistics
   if (c.bnr_t[0] != nullptr && (c.stats[0] || c.out_f32 || (ws_ok && !(c.in_mode == 0 && c.out_co == 0 && c.out_cs == c.cout))))
@@ -104,14 +74,16 @@ static int launch_conv_bf16(const ConvBCall& c, int n_cu, hipStream_t st) {
   if (ws_ok) {
     int nb = (int)std::min<long>((long)n_cu, cdiv(units, 8) * 8L) / 8 * 8;
     nb = std::max(nb, 8);
-    if (grid_env > 0) nb = grid_env;
     const bool nc2 = a.nchunks == 2;   // a layer of 64 input channels: its affine stays in registers
-    const int rc = c.in_mode == 1 ? (nc2 ? launch_conv_bf16_ws_t<1, true>(a, nb, st) : launch_conv_bf16_ws_t<1, false>(a, nb, st))
-                                  : (nc2 ? launch_conv_bf16_ws_t<0, true>(a, nb, st) : launch_conv_bf16_ws_t<0, false>(a, nb, st));
-    if (trace_now && rc == 0) {
-      static unsigned long long h[64 + 1024];
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipMemcpy(h, trace_buf, sizeof(h), hipMemcpyDeviceToHost));
+    constexpr size_t lds = ConvWsGeom::LDS_BYTES;
+    const dim3 grid(nb);
+    if (c.in_mode == 1) CHK((nc2 ? launch_lds<conv_bf16_ws_kernel<1, true>>(lds, grid, dim3(conv_ws_threads<1>()), lds, st, a)
+                                 : launch_lds<conv_bf16_ws_kernel<1, false>>(lds, grid, dim3(conv_ws_threads<1>()), lds, st, a)));
+    else CHK((nc2 ? launch_lds<conv_bf16_ws_kernel<0, true>>(lds, grid, dim3(conv_ws_threads<0>()), lds, st, a)
+                  : launch_lds<conv_bf16_ws_kernel<0, false>>(lds, grid, dim3(conv_ws_threads<0>()), lds, st, a)));
+    if (a.trace) {
+      CHK(tr.fetch(st));
+      const unsigned long long* h = tr.host;
       fprintf(stderr, "[convb trace] %dx%d cin %d cout %d mode %d: %llu stages of workgroup 0; cycles per stage\n", c.H, c.W, c.cin, c.cout, c.in_mode, h[7]);
       const double ns = (double)std::max<unsigned long long>(h[7], 1);
       {
@@ -129,10 +101,11 @@ static int launch_conv_bf16(const ConvBCall& c, int n_cu, hipStream_t st) {
       for (int w = 0; w < 4; ++w) fprintf(stderr, "  consumer %d: mfma %.0f  rest %.0f  barrier %.0f\n", w, h[w * 8] / ns, h[w * 8 + 1] / ns, h[w * 8 + 2] / ns);
       for (int w = 4; w < 8; ++w) fprintf(stderr, "  producer %d: copy-out %.0f  load wait %.0f  staging %.0f  advance %.0f  issue %.0f  barrier %.0f\n", w - 4, h[w * 8] / ns, h[w * 8 + 4] / ns, h[w * 8 + 1] / ns, h[w * 8 + 5] / ns, h[w * 8 + 2] / ns, h[w * 8 + 3] / ns);
     }
-    return rc;
+    return 0;
   }
-#define CONVB_CASE(KS_, M_, I_, O_) \
-  if (c.ks == KS_ && c.in_mode == M_ && c.in_f32 == I_ && c.out_f32 == O_) return launch_conv_bf16_t<KS_, M_, I_, O_>(a, nblocks, st);
+#define CONVB_CASE(KS_, M_, I_, O_)                                                \
+  if (c.ks == KS_ && c.in_mode == M_ && c.in_f32 == I_ && c.out_f32 == O_)         \
+    return launch_lds<conv_bf16_kernel<KS_, M_, I_, O_>>(ConvBGeom<KS_>::LDS_BYTES, dim3(nblocks), dim3(256), ConvBGeom<KS_>::LDS_BYTES, st, a);
   CONVB_CASE(3, 1, false, false) CONVB_CASE(3, 0, false, false) CONVB_CASE(1, 1, false, true) CONVB_CASE(1, 0, true, false)
 #undef CONVB_CASE
   return fail(-3, "bf16 conv: unsupported variant ks=%d in_mode=%d in_f32=%d out_f32=%d", c.ks, c.in_mode, (int)c.in_f32, (int)c.out_f32);
@@ -174,6 +147,8 @@ struct PackBQueue {
   }
 };
 
+constexpr int WGB_SLABS_PER_CU = 2;   // partial slabs (= workgroups) of a weight gradient per CU
+
 struct WgradBCall {
   const void* x[2] = {nullptr, nullptr}; int x_cs = 0, x_co = 0, cin = 0;
   const void* dy[2] = {nullptr, nullptr}; int dy_cs = 0, dy_co = 0, cout = 0;
@@ -189,20 +164,6 @@ struct WgradBCall {
   const float* f_invstd[2] = {nullptr, nullptr}; const float* f_k12[2] = {nullptr, nullptr}; const float* f_gamma = nullptr;
   int f_dcs = 0, f_dco = 0;
 };
-
-template <int KS, int IN_MODE, bool DY_F32, int FUSE = 0>
-static int launch_wgrad_bf16_t(const WgradBArgs& a, int nblocks, hipStream_t st) {
-  using G = WgradBGeom<KS>;
-  static AttrOnce attr_once;
-  auto kern = wgrad_bf16_kernel<KS, IN_MODE, DY_F32, FUSE>;
-  constexpr int lds = G::LDS_BYTES + (FUSE != 0 ? G::P_BYTES : 0);
-  static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");
-  if (attr_once.need())
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), lds, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
 
 // Deferred slab reductions of a backward pass (the engine's launches): every weight gradient keeps its own slice of the partial
 // buffer until flush() sums them all in ONE launch (wgrad_reduce_multi_kernel).  Two jobs never write the same gradient.
@@ -239,8 +200,7 @@ static int launch_wgrad_bf16(const WgradBCall& c, float* partial, size_t partial
   if (c.in_mode == 1 && (!c.x_scale[0] || !c.x_shift[0])) return fail(-1, "bf16 wgrad: in_mode 1 needs scale / shift");
   const int pairs = a.ncib * a.ncob, taps = c.ks * c.ks;
   const long ntiles = (long)c.nviews * c.N * a.tiles_x * a.tiles_y;
-  static const int wg_per_cu = getenv("SSP_WGB_PER_CU") ? std::max(1, atoi(getenv("SSP_WGB_PER_CU"))) : 2;  // (perf-debug: slabs per CU)
-  long nsplit = std::max(1L, std::min<long>(ntiles, ((long)wg_per_cu * n_cu) / pairs));
+  long nsplit = std::max(1L, std::min<long>(ntiles, ((long)WGB_SLABS_PER_CU * n_cu) / pairs));
   while (nsplit > 1 && (size_t)pairs * nsplit * taps * 4096 > partial_floats) --nsplit;
   if ((size_t)pairs * nsplit * taps * 4096 > partial_floats) return fail(-4, "bf16 wgrad: scratch too small");
   a.nsplit = (int)nsplit;
@@ -267,15 +227,23 @@ static int launch_wgrad_bf16(const WgradBCall& c, float* partial, size_t partial
     }
     a.f_gamma = c.f_gamma; a.f_dcs = c.f_dcs; a.f_dco = c.f_dco;
   }
+  // dynamic LDS: the staging buffers, with a fused APPLY the P tile as well
+#define WGB_LAUNCH(KS_, M_, F_, FU_)                                                                          \
+  {                                                                                                           \
+    constexpr size_t lds = WgradBGeom<KS_>::LDS_BYTES + (FU_ != 0 ? WgradBGeom<KS_>::P_BYTES : 0);            \
+    static_assert(2 * lds <= 160 * 1024, "two workgroups per CU");                                            \
+    CHK((launch_lds<wgrad_bf16_kernel<KS_, M_, F_, FU_>>(lds, dim3(nblocks), dim3(256), lds, st, a)));        \
+  }
 #define WGB_CASE(KS_, M_, F_) \
-  if (c.ks == KS_ && c.in_mode == M_ && c.dy_f32 == F_ && c.fuse == 0) { CHK((launch_wgrad_bf16_t<KS_, M_, F_>(a, nblocks, st))); } else
+  if (c.ks == KS_ && c.in_mode == M_ && c.dy_f32 == F_ && c.fuse == 0) WGB_LAUNCH(KS_, M_, F_, 0) else
 #define WGB_FCASE(M_, FU_) \
-  if (c.ks == 3 && c.in_mode == M_ && !c.dy_f32 && c.fuse == FU_) { CHK((launch_wgrad_bf16_t<3, M_, false, FU_>(a, nblocks, st))); } else
+  if (c.ks == 3 && c.in_mode == M_ && !c.dy_f32 && c.fuse == FU_) WGB_LAUNCH(3, M_, false, FU_) else
   WGB_FCASE(1, 1) WGB_FCASE(1, 2) WGB_FCASE(0, 1) WGB_FCASE(0, 2)
   WGB_CASE(3, 1, false) WGB_CASE(3, 0, false) WGB_CASE(1, 1, true)
   return fail(-3, "bf16 wgrad: unsupported variant ks=%d in_mode=%d dy_f32=%d", c.ks, c.in_mode, (int)c.dy_f32);
 #undef WGB_CASE
 #undef WGB_FCASE
+#undef WGB_LAUNCH
   if (queue != nullptr) return 0;
   const int total = c.cout * c.cin * taps;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total, 64)), dim3(256), 0, st, partial, c.dw, c.cin, c.cout, c.ks, a.ncob, a.nsplit);

@@ -103,6 +103,37 @@ static int check_conv_algo(int algo) {
     if (r_ != 0) return r_; \
   } while (0)
 
+// ------------------------------------------------------------------------------------------------
+// Environment switches: every SSP_* variable the library reads, one accessor each.  An accessor reads its variable at its own
+// first call and keeps the value for the process, except the two marked "every call".
+// ------------------------------------------------------------------------------------------------
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+// 1: bit-reproducible accumulation (det.hip.h).  Every call: det_mode() asks until it or ssp_set_deterministic has fixed the mode.
+static bool deterministic_env() { return env_int("SSP_DETERMINISTIC", 0) != 0; }
+// 0 (same-box A/B, fallback): the match term of the sparse descriptor loss scatters with atomics.  Read at ssp_create.
+static bool desc_gather_env() { static const int v = env_int("SSP_DESC_GATHER", 1); return v != 0; }
+// 0: the APPLY pass of the bf16 path's BatchNorm backward as a pass of its own.  Every call: run_backward asks once per pass
+// (tests switch it between two steps of one process).
+static bool bf16_fuse_apply_env() { return env_int("SSP_BF16_FUSE_APPLY", 1) != 0; }
+// 0 (perf-debug A/B): the 3x3 bf16 layers on the generic kernel instead of the wave-specialised one
+static bool convb_ws_env() { static const int v = env_int("SSP_CONVB_WS", 1); return v != 0; }
+// bf16 path, activated copy of a 30x40 layer's input (perf-debug A/B): 0 off, 1 heads only, 2 also layers 6, 7
+static int act7_env() { static const int v = env_int("SSP_ACT7", 1); return v; }
+// 0 (perf-debug): pass 1 of the bf16 path's BatchNorm backward as a pass of its own
+static bool bf16_bnr_env() { static const int v = env_int("SSP_BF16_BNR", 1); return v != 0; }
+// 0 (same-box A/B): the pixels-then-classes form of the segmentation loss everywhere
+static int sem_xc_env() { static const int v = env_int("SSP_SEM_XC", 1); return v; }
+// perf-debug ablation mask of the bf16 conv kernels (ConvBArgs::ablate)
+static int convb_ablate_env() { static const int v = env_int("SSP_CONVB_ABLATE", 0); return v; }
+// n > 0 (perf-debug: blocking): every n-th wave-specialised bf16 conv launch is traced and printed
+static int convb_trace_env() { static const int v = env_int("SSP_CONVB_TRACE", 0); return v; }
+// the same for conv_wino4_kernel in a -DW4_TRACE=1 build and for wgrad_wino_fused_kernel in a -DWGF_TRACE=1 build
+static int w4_trace_env() { static const int v = env_int("SSP_W4_TRACE", 0); return v; }
+static int wgf_trace_env() { static const int v = env_int("SSP_WGF_TRACE", 0); return v; }
+
 // hipFuncSetAttribute is per device: one flag per (kernel instantiation, device)
 struct AttrOnce {
   bool done[64] = {};
@@ -112,6 +143,39 @@ struct AttrOnce {
     if (done[dev]) return false;
     done[dev] = true;
     return true;
+  }
+};
+// Launch of a kernel whose dynamic LDS may exceed the 64 KiB a kernel gets without asking: raises the kernel's limit to lds_max
+// once per (instantiation, device), launches with `lds` bytes, checks the launch.
+template <auto Kern, class... A>
+static int launch_lds(size_t lds_max, dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  static AttrOnce attr_once;
+  if (attr_once.need())
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+  hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// Perf-debug traces: every n-th launch of a site carries a device buffer of WORDS 64-bit counters (allocated once, cleared on the
+// launch's stream); after the launch fetch() waits for it and copies the counters to host[].  Each site prints its own.
+template <int WORDS>
+struct TraceSite {
+  unsigned long long* dev = nullptr;
+  int count = 0;
+  unsigned long long host[WORDS];
+  int begin(int every, hipStream_t st, unsigned long long** trace) {   // *trace: the buffer for this launch, or nullptr
+    *trace = nullptr;
+    if (every <= 0 || (++count % every) != 0) return 0;
+    if (!dev) HIPCHK(hipMalloc(&dev, sizeof(host)));
+    HIPCHK(hipMemsetAsync(dev, 0, sizeof(host), st));
+    *trace = dev;
+    return 0;
+  }
+  int fetch(hipStream_t st) {
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(host, dev, sizeof(host), hipMemcpyDeviceToHost));
+    return 0;
   }
 };
 
@@ -502,19 +566,6 @@ static int dev_zero2(void* p0, void* p1, size_t bytes, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // launch helpers
 // ------------------------------------------------------------------------------------------------
-template <int KS, int IN_MODE, int SH, int SW>
-static int launch_conv_t(const ConvArgs& a, int nblocks, hipStream_t st) {
-  using G = ConvGeom<KS, SH, SW>;
-  static AttrOnce attr_once;
-  auto kern = conv_mfma_kernel<KS, IN_MODE, SH, SW>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), G::LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 struct ConvCall {
   const float* in; int in_cs, in_co, cin;
   const float* wpk; const float* bias;
@@ -545,69 +596,6 @@ static bool can_fuse_bnr(const ConvCall& c) {
   return c.wino && c.in_mode == 0 && c.cout % 4 == 0 && c.out_co % 4 == 0 && c.out_cs % 4 == 0;
 }
 
-template <int IN_MODE, bool WIDE>
-static int launch_wino_pipe_t(const ConvArgs& a, int nblocks, hipStream_t st) {
-  static AttrOnce attr_once;
-  auto kern = conv_wino_pipe_kernel<IN_MODE, WIDE>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PIPE_LDS_BYTES));
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(WINO_THREADS), PIPE_LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <int IN_MODE, bool WIDE>
-static int launch_wino_p2_t(const ConvArgs& a, int nblocks, hipStream_t st) {
-  static AttrOnce attr_once;
-  auto kern = conv_wino_p2_kernel<IN_MODE, WIDE>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, P2_LDS_BYTES));
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(P2_THREADS), P2_LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <int IN_MODE, bool WIDE>
-static int launch_wino4_t(const ConvArgs& a_in, int nblocks, hipStream_t st) {
-  static AttrOnce attr_once;
-  auto kern = conv_wino4_kernel<IN_MODE, WIDE>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS_BYTES));
-  }
-#if W4_TRACE
-  // perf-debug build only: every SSP_W4_TRACE-th launch carries a trace buffer, is waited for and printed (cycles per stage)
-  ConvArgs a = a_in;
-  static const int trace_env = getenv("SSP_W4_TRACE") ? atoi(getenv("SSP_W4_TRACE")) : 0;
-  static unsigned long long* trace_buf = nullptr;
-  static int trace_count = 0;
-  const bool trace_now = trace_env > 0 && (++trace_count % trace_env) == 0;
-  if (trace_now) {
-    if (!trace_buf) HIPCHK(hipMalloc(&trace_buf, 64 * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(trace_buf, 0, 64 * sizeof(unsigned long long), st));
-    a.trace = trace_buf;
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(W4_THREADS), W4_LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  if (trace_now) {
-    unsigned long long hbuf[64];
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(hbuf, trace_buf, sizeof(hbuf), hipMemcpyDeviceToHost));
-    const double ns = (double)std::max<unsigned long long>(hbuf[6], 1);
-    fprintf(stderr, "[w4 trace] %dx%d cin %d cout %d mode %d bnr %d nprob %d: %llu stages of workgroup 0; cycles per stage (MFMA floor 4608)\n",
-            a.H, a.W, a.Cin, a.Cout, IN_MODE, a.bnr_mode, a.nprob, hbuf[6]);
-    for (int w = 0; w < 4; ++w)
-      fprintf(stderr, "  wave %d: first half %.0f  barrier A %.0f  second half %.0f  barrier B %.0f  epilogue %.0f  | loop %.0f\n", w,
-              hbuf[w * 8] / ns, hbuf[w * 8 + 1] / ns, hbuf[w * 8 + 2] / ns, hbuf[w * 8 + 3] / ns, hbuf[w * 8 + 4] / ns, hbuf[w * 8 + 5] / ns);
-  }
-#else
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(W4_THREADS), W4_LDS_BYTES, st, a_in);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
-}
-
 // default algorithm (1): maps with few first-generation work items per CU (the 30x40 layers: 640 items on 256 CUs =
 // 2.5 rounds) run on the finer-grained second-generation kernel (measured 10-15 % faster there, 1-4 % slower on the
 // large maps: tools/archive/conv_probe.py)
@@ -621,6 +609,8 @@ static void w4_geometry(int H, int W, bool& wide, int& tiles_y, int& tiles_x) {
 // same predicate (launch_pack / pack_all).  Default algorithm: maps of >= 60x80 pixels with >= 4 tile blocks per CU
 // (measured 1.2x / 1.15x faster than F(2x2,3x3) on the 64 -> 64 layers at 240x320 / 120x160; the 60x80 layers of a
 // 32-pair step gain 0.7 % of the step, the 30x40 ones nothing).
+constexpr long W4_MIN_PIXELS = 60L * 80L;
+constexpr long W4_MIN_ITEMS_X4 = 16L;   // (quarter tile blocks per CU)
 static bool w4_eligible(const ssp_handle* h, int nprob, int N, int H, int W, int cin, int cout) {
   if (g_conv_algo != 1 && g_conv_algo != 10 && g_conv_algo != 11) return false;
   if (cin % 8 != 0 || cin > W4_MAX_CIN) return false;   // (the producer's BatchNorm scale | shift of <= W4_MAX_CIN channels sit in LDS)
@@ -628,9 +618,7 @@ static bool w4_eligible(const ssp_handle* h, int nprob, int N, int H, int W, int
   bool wide; int ty, tx;
   w4_geometry(H, W, wide, ty, tx);
   const long items = (long)nprob * N * ty * tx * cdiv(cout, NB);
-  static const long min_px = getenv("SSP_W4_MIN_PIXELS") ? atol(getenv("SSP_W4_MIN_PIXELS")) : 60L * 80L;  // (perf-debug override)
-  static const long min_items_x4 = getenv("SSP_W4_MIN_ITEMS_X4") ? atol(getenv("SSP_W4_MIN_ITEMS_X4")) : 16L;  // (quarter blocks per CU)
-  return (long)H * W >= min_px && 4L * items >= min_items_x4 * (h ? h->n_cu : 256);
+  return (long)H * W >= W4_MIN_PIXELS && 4L * items >= W4_MIN_ITEMS_X4 * (h ? h->n_cu : 256);
 }
 static bool conv_uses_w4(const ssp_handle* h, const ConvCall& c) {
   if (!(c.wino && c.allow_w4 && c.ks == 3 && c.in_mode != 2)) return false;
@@ -652,12 +640,8 @@ static bool conv_writes_pool(const ssp_handle* h, const ConvCall& c) {
 }
 
 // will this launch run a kernel whose prologue can derive its input layer's BatchNorm affine from the raw statistics (BnLazy:
-// conv_wino4 / conv_wino_p2 / conv_wino_pipe reading under BatchNorm + ReLU)?  SSP_BN_LAZY=0 (perf-debug): bn_finalize_kernel everywhere.
-static bool bn_lazy_env() {
-  static const int v = getenv("SSP_BN_LAZY") ? atoi(getenv("SSP_BN_LAZY")) : 1;
-  return v != 0;
-}
-static bool conv_has_bn_lazy(const ConvCall& c) { return bn_lazy_env() && c.wino && c.in_mode == 1; }
+// conv_wino4 / conv_wino_p2 / conv_wino_pipe reading under BatchNorm + ReLU)?
+static bool conv_has_bn_lazy(const ConvCall& c) { return c.wino && c.in_mode == 1; }
 
 static int launch_conv(ssp_handle* h, const ConvCall& c, hipStream_t st, int prof_family = 0) {
   ConvArgs a;
@@ -730,21 +714,51 @@ static int launch_conv(ssp_handle* h, const ConvCall& c, hipStream_t st, int pro
   // multiplies executed on the matrix cores: 36 per 16 outputs x 9 taps (F(4x4,3x3)), 16 per 4 x 9 (F(2x2,3x3))
   const int pkern = w4 ? SSP_PROF_K_CONV_WINO4 : p2 ? SSP_PROF_K_CONV_WINO_P2 : c.wino ? SSP_PROF_K_CONV_WINO_PIPE : SSP_PROF_K_OTHER;
   ProfScope ps(h, fam, st, flops, bytes, flops * (w4 ? 0.25 : c.wino ? 16.0 / 36.0 : 1.0), pkern);
+  const dim3 grid(nblocks);
   if (w4) {  // Winograd F(4x4,3x3), one 8-wave workgroup per CU
-    if (c.in_mode == 0) return wide4 ? launch_wino4_t<0, true>(a, nblocks, st) : launch_wino4_t<0, false>(a, nblocks, st);
-    return wide4 ? launch_wino4_t<1, true>(a, nblocks, st) : launch_wino4_t<1, false>(a, nblocks, st);
+    const dim3 block(W4_THREADS);
+#if W4_TRACE
+    // perf-debug build only: every SSP_W4_TRACE-th launch carries a trace buffer, is waited for and printed (cycles per stage)
+    static TraceSite<64> tr;
+    CHK(tr.begin(w4_trace_env(), st, &a.trace));
+#endif
+    if (c.in_mode == 0) CHK((wide4 ? launch_lds<conv_wino4_kernel<0, true>>(W4_LDS_BYTES, grid, block, W4_LDS_BYTES, st, a)
+                                   : launch_lds<conv_wino4_kernel<0, false>>(W4_LDS_BYTES, grid, block, W4_LDS_BYTES, st, a)));
+    else CHK((wide4 ? launch_lds<conv_wino4_kernel<1, true>>(W4_LDS_BYTES, grid, block, W4_LDS_BYTES, st, a)
+                    : launch_lds<conv_wino4_kernel<1, false>>(W4_LDS_BYTES, grid, block, W4_LDS_BYTES, st, a)));
+#if W4_TRACE
+    if (a.trace) {
+      CHK(tr.fetch(st));
+      const unsigned long long* hbuf = tr.host;
+      const double ns = (double)std::max<unsigned long long>(hbuf[6], 1);
+      fprintf(stderr, "[w4 trace] %dx%d cin %d cout %d mode %d bnr %d nprob %d: %llu stages of workgroup 0; cycles per stage (MFMA floor 4608)\n",
+              a.H, a.W, a.Cin, a.Cout, c.in_mode, a.bnr_mode, a.nprob, hbuf[6]);
+      for (int w = 0; w < 4; ++w)
+        fprintf(stderr, "  wave %d: first half %.0f  barrier A %.0f  second half %.0f  barrier B %.0f  epilogue %.0f  | loop %.0f\n", w,
+                hbuf[w * 8] / ns, hbuf[w * 8 + 1] / ns, hbuf[w * 8 + 2] / ns, hbuf[w * 8 + 3] / ns, hbuf[w * 8 + 4] / ns, hbuf[w * 8 + 5] / ns);
+    }
+#endif
+    return 0;
   }
   if (p2) {  // second-generation pipelined Winograd: two independent 4-wave workgroups per CU
-    if (c.in_mode == 0) return wide ? launch_wino_p2_t<0, true>(a, nblocks, st) : launch_wino_p2_t<0, false>(a, nblocks, st);
-    return wide ? launch_wino_p2_t<1, true>(a, nblocks, st) : launch_wino_p2_t<1, false>(a, nblocks, st);
+    const dim3 block(P2_THREADS);
+    if (c.in_mode == 0) return wide ? launch_lds<conv_wino_p2_kernel<0, true>>(P2_LDS_BYTES, grid, block, P2_LDS_BYTES, st, a)
+                                    : launch_lds<conv_wino_p2_kernel<0, false>>(P2_LDS_BYTES, grid, block, P2_LDS_BYTES, st, a);
+    return wide ? launch_lds<conv_wino_p2_kernel<1, true>>(P2_LDS_BYTES, grid, block, P2_LDS_BYTES, st, a)
+                : launch_lds<conv_wino_p2_kernel<1, false>>(P2_LDS_BYTES, grid, block, P2_LDS_BYTES, st, a);
   }
   if (c.wino) {  // first-generation pipelined Winograd, weight fragments straight from L2
-    if (c.in_mode == 0) return wide ? launch_wino_pipe_t<0, true>(a, nblocks, st) : launch_wino_pipe_t<0, false>(a, nblocks, st);
-    return wide ? launch_wino_pipe_t<1, true>(a, nblocks, st) : launch_wino_pipe_t<1, false>(a, nblocks, st);
+    const dim3 block(WINO_THREADS);
+    if (c.in_mode == 0) return wide ? launch_lds<conv_wino_pipe_kernel<0, true>>(PIPE_LDS_BYTES, grid, block, PIPE_LDS_BYTES, st, a)
+                                    : launch_lds<conv_wino_pipe_kernel<0, false>>(PIPE_LDS_BYTES, grid, block, PIPE_LDS_BYTES, st, a);
+    return wide ? launch_lds<conv_wino_pipe_kernel<1, true>>(PIPE_LDS_BYTES, grid, block, PIPE_LDS_BYTES, st, a)
+                : launch_lds<conv_wino_pipe_kernel<1, false>>(PIPE_LDS_BYTES, grid, block, PIPE_LDS_BYTES, st, a);
   }
-#define CONV_CASE(KS_, M_)                                                          \
-  if (c.ks == KS_ && c.in_mode == M_) {                                             \
-    return wide ? launch_conv_t<KS_, M_, 1, 32>(a, nblocks, st) : launch_conv_t<KS_, M_, 4, 8>(a, nblocks, st); \
+#define CONV_CASE(KS_, M_)                                                                                                       \
+  if (c.ks == KS_ && c.in_mode == M_) {                                                                                          \
+    constexpr size_t lw = ConvGeom<KS_, 1, 32>::LDS_BYTES, ln = ConvGeom<KS_, 4, 8>::LDS_BYTES;                                  \
+    return wide ? launch_lds<conv_mfma_kernel<KS_, M_, 1, 32>>(lw, grid, dim3(256), lw, st, a)                                   \
+                : launch_lds<conv_mfma_kernel<KS_, M_, 4, 8>>(ln, grid, dim3(256), ln, st, a);                                   \
   }
   CONV_CASE(3, 0) CONV_CASE(3, 1) CONV_CASE(3, 2) CONV_CASE(1, 0) CONV_CASE(1, 1)
 #undef CONV_CASE
@@ -766,11 +780,12 @@ struct G1Layer {
   int K = 0, N = 0;
 };
 static inline size_t g1_image_floats(int K, int N) { return (size_t)cdiv(K, G1_KC) * cdiv(N, 32) * G1_TILE_FLOATS; }
-// SSP_G1=0 (perf-debug) and the direct algorithm 0 keep the pointwise layers on conv_mfma_kernel<1, ...>
-static bool g1_enabled() {
-  static const int env = getenv("SSP_G1") ? atoi(getenv("SSP_G1")) : 1;
-  return env != 0 && g_conv_algo != 0;
-}
+// the direct algorithm 0 keeps the pointwise layers on conv_mfma_kernel<1, ...>
+static bool g1_enabled() { return g_conv_algo != 0; }
+// cycles of a wave per 32-pixel tile (every problem of a launch has the same pixels): 4 MFMAs of 64 cycles per k-quad and
+// n-tile, plus the epilogue of an n-tile (16 stores and the channel sums; with the BatchNorm-backward sums 16 loads and the
+// gates as well) - without that term the 65-channel data gradient (9 k-quads) got half the CUs it needed
+constexpr long G1_ECOST = 2000, G1_ECOST_BNR = 5000;
 static inline int g1_ntmax(int K) { return std::min(G1_NT, 32 / cdiv(K, G1_KC)); }  // n-tiles whose weight image fits the 128 KB of LDS
 static bool g1_fits(int K, int N, long npx, int in_cs, int out_cs, int nviews) {
   if (K < 1 || K > G1_KMAX || N < 1 || npx <= 0) return false;
@@ -803,12 +818,7 @@ static int launch_g1(const G1Layer* L, int nl, int nviews, long npx, int in_mode
         q.bnr_scale = bnr ? y.bnr_scale[k] + 32 * t0 : nullptr; q.bnr_shift = bnr ? y.bnr_shift[k] + 32 * t0 : nullptr;
         q.bnr_mean = bnr ? y.bnr_mean[k] + 32 * t0 : nullptr; q.bnr_invstd = bnr ? y.bnr_invstd[k] + 32 * t0 : nullptr;
         if (in_mode != 0 && (!q.in_scale || !q.in_shift)) return fail(-1, "pointwise conv: in_mode 1 needs scale / shift");
-        // cycles of a wave per 32-pixel tile (every problem of a launch has the same pixels): 4 MFMAs of 64 cycles per k-quad and
-        // n-tile, plus the epilogue of an n-tile (16 stores and the channel sums; with the BatchNorm-backward sums 16 loads and the
-        // gates as well) - without that term the 65-channel data gradient (9 k-quads) got half the CUs it needed
-        static const long e_plain = getenv("SSP_G1_ECOST") ? atol(getenv("SSP_G1_ECOST")) : 2000;      // (perf-debug knobs)
-        static const long e_bnr = getenv("SSP_G1_ECOST_BNR") ? atol(getenv("SSP_G1_ECOST_BNR")) : 5000;
-        cost[a.nprob] = (long)size * (256L * cdiv(y.K, 4) + (bnr ? e_bnr : e_plain));
+        cost[a.nprob] = (long)size * (256L * cdiv(y.K, 4) + (bnr ? G1_ECOST_BNR : G1_ECOST));
         total += cost[a.nprob];
         ++a.nprob;
       }
@@ -844,19 +854,10 @@ static int launch_g1(const G1Layer* L, int nl, int nviews, long npx, int in_mode
   }
   int wg = 0;
   for (int i = 0; i < a.nprob; ++i) { a.p[i].wg0 = wg; wg += a.p[i].nwg; }
-  static AttrOnce attr0, attr1, attr2;
-#define SSP_G1_LAUNCH(M_, B_, ATTR_)                                                                                                  \
-  {                                                                                                                                   \
-    auto kern = conv1x1_group_kernel<M_, B_>;                                                                                         \
-    if (ATTR_.need()) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G1_LDS_BYTES)); \
-    hipLaunchKernelGGL(kern, dim3(wg), dim3(64 * G1_WAVES), G1_LDS_BYTES, st, a);                                                     \
-  }
-  if (in_mode != 0) SSP_G1_LAUNCH(1, false, attr1)
-  else if (bnr) SSP_G1_LAUNCH(0, true, attr2)
-  else SSP_G1_LAUNCH(0, false, attr0)
-#undef SSP_G1_LAUNCH
-  HIPCHK(hipGetLastError());
-  return 0;
+  const dim3 grid_dim(wg), block(64 * G1_WAVES);
+  if (in_mode != 0) return launch_lds<conv1x1_group_kernel<1, false>>(G1_LDS_BYTES, grid_dim, block, G1_LDS_BYTES, st, a);
+  if (bnr) return launch_lds<conv1x1_group_kernel<0, true>>(G1_LDS_BYTES, grid_dim, block, G1_LDS_BYTES, st, a);
+  return launch_lds<conv1x1_group_kernel<0, false>>(G1_LDS_BYTES, grid_dim, block, G1_LDS_BYTES, st, a);
 }
 // grouped weight gradient of pointwise layers with 256 input channels (wgrad1x1_group_kernel + wgrad1x1_reduce_kernel)
 struct G1WLayer {
@@ -925,86 +926,6 @@ static void g1_add_pack(G1PackJobs& J, int& nblocks, const float* w, float* dst,
   nblocks += cdiv((long)q.nchunks * q.nt_total * G1_TILE_FLOATS, 256);
 }
 
-template <int KS, int IN_MODE, int SH, int SW>
-static int launch_wgrad_t(const WgradArgs& a, int nblocks, hipStream_t st) {
-  using G = WgradGeom<KS, SH, SW>;
-  static AttrOnce attr_once;
-  auto kern = wgrad_mfma_kernel<KS, IN_MODE, SH, SW>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(256), G::LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <int IN_MODE, bool WIDE>
-static int launch_wgrad_wino_t(const WgradArgs& a, int nblocks, hipStream_t st) {
-  using G = WgradWinoGeom<WIDE>;
-  static AttrOnce attr_once;
-  auto kern = wgrad_wino_kernel<IN_MODE, WIDE>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(512), G::LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <int IN_MODE, bool WIDE, bool POOL>
-static int launch_wgrad_wino_fused_t(const WgradArgs& a_in, int nblocks, hipStream_t st) {
-  using GF = WgradFusedGeom<WIDE>;
-  static AttrOnce attr_once;
-  auto kern = wgrad_wino_fused_kernel<IN_MODE, WIDE, POOL>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, GF::LDS_BYTES));
-  }
-#if WGF_TRACE
-  // perf-debug build only: every SSP_WGF_TRACE-th launch carries a trace buffer, is waited for and printed (cycles per tile)
-  WgradArgs a = a_in;
-  static const int trace_env = getenv("SSP_WGF_TRACE") ? atoi(getenv("SSP_WGF_TRACE")) : 0;
-  static unsigned long long* trace_buf = nullptr;
-  static int trace_count = 0;
-  const bool trace_now = trace_env > 0 && (++trace_count % trace_env) == 0;
-  if (trace_now) {
-    if (!trace_buf) HIPCHK(hipMalloc(&trace_buf, 64 * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(trace_buf, 0, 64 * sizeof(unsigned long long), st));
-    a.trace = trace_buf;
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(512), GF::LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  if (trace_now) {
-    unsigned long long hbuf[64];
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipMemcpy(hbuf, trace_buf, sizeof(hbuf), hipMemcpyDeviceToHost));
-    const double nt = (double)std::max<unsigned long long>(hbuf[6], 1);
-    fprintf(stderr, "[wgf trace] %dx%d cin %d cout %d mode %d pool %d nprob %d: %llu tiles of workgroup 0 at %.0f MHz; cycles per tile (MFMA floor 2 x 8192 per SIMD)\n",
-            a.H, a.W, a.Cin, a.Cout, IN_MODE, (int)POOL, a.nprob, hbuf[6], 100.0 * (double)hbuf[5] / (double)std::max<unsigned long long>(hbuf[7], 1));
-    for (int w = 0; w < 8; ++w)
-      fprintf(stderr, "  wave %d: top barrier %.0f  staging %.0f  barrier %.0f  issue %.0f  mfma %.0f  | loop %.0f\n", w, hbuf[w * 8] / nt,
-              hbuf[w * 8 + 1] / nt, hbuf[w * 8 + 2] / nt, hbuf[w * 8 + 3] / nt, hbuf[w * 8 + 4] / nt, hbuf[w * 8 + 5] / nt);
-  }
-#else
-  const WgradArgs& a = a_in;
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(512), GF::LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-#endif
-  return 0;
-}
-
-template <int IN_MODE, bool WIDE>
-static int launch_wgrad_wino4_t(const WgradArgs& a, int nblocks, hipStream_t st) {
-  using G = Wgrad4Geom<WIDE>;
-  static AttrOnce attr_once;
-  auto kern = wgrad_wino4_kernel<IN_MODE, WIDE>;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-  }
-  hipLaunchKernelGGL(kern, dim3(nblocks), dim3(WG4_THREADS), G::LDS_BYTES, st, a);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 struct WgradCall {
   const float* in; int in_cs, in_co, cin;
   const float* dout; int dout_cs, dout_co, cout;
@@ -1032,19 +953,12 @@ struct WgradCall {
 // Can the weight gradient of a layer whose output feeds BatchNorm + ReLU + MaxPool2d(2) take that layer's APPLY pass along
 // (wgrad_wino_fused_kernel)?  fp32 Winograd F(3x3,2x2) weight gradient, even map, whole 4-channel quads, dense y / dY.
 static bool wgrad_can_fuse_apply(int ks, int in_mode, int H, int W, int cout) {
-  static const int env = getenv("SSP_FUSE_APPLY") ? atoi(getenv("SSP_FUSE_APPLY")) : 1;  // (perf-debug A/B)
-  static const int f4 = getenv("SSP_WGRAD_F4") ? atoi(getenv("SSP_WGRAD_F4")) : 0;        // (forces wgrad_wino4_kernel)
   const bool algo_ok = g_conv_algo == 1 || g_conv_algo == 9 || g_conv_algo == 10;
-  return env != 0 && f4 == 0 && algo_ok && ks == 3 && in_mode != 2 && H % 2 == 0 && W % 2 == 0 && cout % 4 == 0;
+  return algo_ok && ks == 3 && in_mode != 2 && H % 2 == 0 && W % 2 == 0 && cout % 4 == 0;
 }
 
 // sums the pending partial slabs of the deferred Winograd weight-gradient launches into the OIHW gradients
 static int flush_wgrad_reduce_bf16(ssp_handle* h, hipStream_t st);
-// SSP_TAIL_MERGE=0 (perf-debug A/B): the pointwise slab reduction and the column sums as launches of their own
-static bool tail_merge_env() {
-  static const int v = getenv("SSP_TAIL_MERGE") ? atoi(getenv("SSP_TAIL_MERGE")) : 1;
-  return v != 0;
-}
 static int flush_wgrad_reduce(ssp_handle* h, hipStream_t st) {
   if (h != nullptr) CHK(flush_wgrad_reduce_bf16(h, st));
   if (h == nullptr) return 0;
@@ -1083,11 +997,10 @@ static int launch_wgrad(ssp_handle* h, const WgradCall& c, float* partial, size_
   const bool wide = (c.W % 32) == 0;
   // Winograd F(3x3,2x2): 3x3 filters on even-sized maps with a prefetchable (non-pooled) input
   // Winograd F(3x3,4x4) (wgrad_wino4_kernel: 1/4 of the direct multiplies), OPT-IN: conv algorithm 11 (= algorithm 1 with this
-  // weight gradient) or SSP_WGRAD_F4=1 under algorithms 1 / 10.  Correct on every 3x3 layer with a prefetchable input and any
+  // weight gradient).  Correct on every 3x3 layer with a prefetchable input and any
   // map size (dY is zero-filled outside the map); 64 ci x 32 co slabs over the same 128-pixel block tiles as F(3x3,2x2).
   // Not the default: measured equal at 240x320 and 10-50 % slower below (profiles/r03_kernel_experiments.txt, DESIGN.md s. 12).
-  static const int wg4_env = getenv("SSP_WGRAD_F4") ? atoi(getenv("SSP_WGRAD_F4")) : 0;
-  const bool wino4 = (g_conv_algo == 11 || (wg4_env != 0 && (g_conv_algo == 1 || g_conv_algo == 10))) && c.ks == 3 && c.in_mode != 2;
+  const bool wino4 = g_conv_algo == 11 && c.ks == 3 && c.in_mode != 2;
   const bool wino = wino4 || (g_conv_algo != 0 && c.ks == 3 && c.in_mode != 2 && c.H % 2 == 0 && c.W % 2 == 0);
   if (wino && ((double)c.H * c.W * std::max(c.in_cs, c.dout_cs) * 4.0 > 2147483647.0))
     return fail(-3, "wgrad: one image [%d,%d,%d] exceeds 2 GiB", c.H, c.W, std::max(c.in_cs, c.dout_cs));
@@ -1130,18 +1043,46 @@ static int launch_wgrad(ssp_handle* h, const WgradCall& c, float* partial, size_
                                                             (c.fuse_apply ? (2.0 + (c.fuse_pool ? 0.25 : 1.0)) * c.cout : (double)c.cout));
     ProfScope ps(h, c.ks == 3 ? SSP_PROF_CONV3X3_WGRAD : -1, st, flops, bytes, flops * (wino4 ? 0.25 : wino ? 16.0 / 36.0 : 1.0),
                  wino4 ? SSP_PROF_K_WGRAD_WINO4 : wino ? SSP_PROF_K_WGRAD_WINO : SSP_PROF_K_OTHER);
+    const dim3 grid(nblocks);
     if (c.fuse_apply) {
       if (!wino || wino4) return fail(-3, "fused BatchNorm apply needs the fp32 F(3x3,2x2) weight gradient");
-#define WGF_CASE(M_, P_) \
-      if (c.in_mode == M_ && c.fuse_pool == P_) CHK((wide ? launch_wgrad_wino_fused_t<M_, true, P_>(a, nblocks, st) : launch_wgrad_wino_fused_t<M_, false, P_>(a, nblocks, st)));
+      constexpr size_t lw = WgradFusedGeom<true>::LDS_BYTES, ln = WgradFusedGeom<false>::LDS_BYTES;
+#if WGF_TRACE
+      // perf-debug build only: every SSP_WGF_TRACE-th launch carries a trace buffer, is waited for and printed (cycles per tile)
+      static TraceSite<64> tr;
+      CHK(tr.begin(wgf_trace_env(), st, &a.trace));
+#endif
+#define WGF_CASE(M_, P_)                                                                                           \
+      if (c.in_mode == M_ && c.fuse_pool == P_)                                                                    \
+        CHK((wide ? launch_lds<wgrad_wino_fused_kernel<M_, true, P_>>(lw, grid, dim3(512), lw, st, a)              \
+                  : launch_lds<wgrad_wino_fused_kernel<M_, false, P_>>(ln, grid, dim3(512), ln, st, a)));
       WGF_CASE(0, false) WGF_CASE(0, true) WGF_CASE(1, false) WGF_CASE(1, true)
 #undef WGF_CASE
+#if WGF_TRACE
+      if (a.trace) {
+        CHK(tr.fetch(st));
+        const unsigned long long* hbuf = tr.host;
+        const double nt = (double)std::max<unsigned long long>(hbuf[6], 1);
+        fprintf(stderr, "[wgf trace] %dx%d cin %d cout %d mode %d pool %d nprob %d: %llu tiles of workgroup 0 at %.0f MHz; cycles per tile (MFMA floor 2 x 8192 per SIMD)\n",
+                a.H, a.W, a.Cin, a.Cout, c.in_mode, (int)c.fuse_pool, a.nprob, hbuf[6], 100.0 * (double)hbuf[5] / (double)std::max<unsigned long long>(hbuf[7], 1));
+        for (int w = 0; w < 8; ++w)
+          fprintf(stderr, "  wave %d: top barrier %.0f  staging %.0f  barrier %.0f  issue %.0f  mfma %.0f  | loop %.0f\n", w, hbuf[w * 8] / nt,
+                  hbuf[w * 8 + 1] / nt, hbuf[w * 8 + 2] / nt, hbuf[w * 8 + 3] / nt, hbuf[w * 8 + 4] / nt, hbuf[w * 8 + 5] / nt);
+      }
+#endif
     } else if (wino4) {
-      if (c.in_mode == 0) CHK((wide ? launch_wgrad_wino4_t<0, true>(a, nblocks, st) : launch_wgrad_wino4_t<0, false>(a, nblocks, st)));
-      else CHK((wide ? launch_wgrad_wino4_t<1, true>(a, nblocks, st) : launch_wgrad_wino4_t<1, false>(a, nblocks, st)));
+      constexpr size_t lw = Wgrad4Geom<true>::LDS_BYTES, ln = Wgrad4Geom<false>::LDS_BYTES;
+      const dim3 block(WG4_THREADS);
+      if (c.in_mode == 0) CHK((wide ? launch_lds<wgrad_wino4_kernel<0, true>>(lw, grid, block, lw, st, a)
+                                    : launch_lds<wgrad_wino4_kernel<0, false>>(ln, grid, block, ln, st, a)));
+      else CHK((wide ? launch_lds<wgrad_wino4_kernel<1, true>>(lw, grid, block, lw, st, a)
+                     : launch_lds<wgrad_wino4_kernel<1, false>>(ln, grid, block, ln, st, a)));
     } else if (wino) {
-      if (c.in_mode == 0) CHK((wide ? launch_wgrad_wino_t<0, true>(a, nblocks, st) : launch_wgrad_wino_t<0, false>(a, nblocks, st)));
-      else CHK((wide ? launch_wgrad_wino_t<1, true>(a, nblocks, st) : launch_wgrad_wino_t<1, false>(a, nblocks, st)));
+      constexpr size_t lw = WgradWinoGeom<true>::LDS_BYTES, ln = WgradWinoGeom<false>::LDS_BYTES;
+      if (c.in_mode == 0) CHK((wide ? launch_lds<wgrad_wino_kernel<0, true>>(lw, grid, dim3(512), lw, st, a)
+                                    : launch_lds<wgrad_wino_kernel<0, false>>(ln, grid, dim3(512), ln, st, a)));
+      else CHK((wide ? launch_lds<wgrad_wino_kernel<1, true>>(lw, grid, dim3(512), lw, st, a)
+                     : launch_lds<wgrad_wino_kernel<1, false>>(ln, grid, dim3(512), ln, st, a)));
     }
     if (wino) {
       if (!deferred && wino4)
@@ -1156,9 +1097,11 @@ static int launch_wgrad(ssp_handle* h, const WgradCall& c, float* partial, size_
       HIPCHK(hipGetLastError());
       return 0;
     }
-#define WG_CASE(KS_, M_)                                                              \
-  if (c.ks == KS_ && c.in_mode == M_) {                                               \
-    CHK((wide ? launch_wgrad_t<KS_, M_, 1, 32>(a, nblocks, st) : launch_wgrad_t<KS_, M_, 4, 8>(a, nblocks, st))); \
+#define WG_CASE(KS_, M_)                                                                                    \
+  if (c.ks == KS_ && c.in_mode == M_) {                                                                     \
+    constexpr size_t lw = WgradGeom<KS_, 1, 32>::LDS_BYTES, ln = WgradGeom<KS_, 4, 8>::LDS_BYTES;           \
+    CHK((wide ? launch_lds<wgrad_mfma_kernel<KS_, M_, 1, 32>>(lw, grid, dim3(256), lw, st, a)               \
+              : launch_lds<wgrad_mfma_kernel<KS_, M_, 4, 8>>(ln, grid, dim3(256), ln, st, a)));             \
   } else
     WG_CASE(3, 0) WG_CASE(3, 1) WG_CASE(3, 2) WG_CASE(1, 0) WG_CASE(1, 1)
     return fail(-3, "unsupported wgrad variant ks=%d in_mode=%d", c.ks, c.in_mode);
@@ -1263,7 +1206,6 @@ static int l0_resident_grid(K kern, const ssp_handle* h, int nviews, long rows, 
 static int flush_wgrad_reduce_bf16(ssp_handle* h, hipStream_t st) { return h->rq_bf16 != nullptr ? h->rq_bf16->flush(st) : 0; }
 
 static int ensure_aux_stream(ssp_handle* h);
-static bool desc_gather_env();
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -1274,7 +1216,7 @@ static std::vector<DetHostRegion> g_det_regions;
 static int g_det_mode = -1;   // -1: not read yet (SSP_DETERMINISTIC), 0 / 1
 static int g_det_device = -1; // device of the registered regions
 static bool det_mode() {
-  if (g_det_mode < 0) { const char* e = getenv("SSP_DETERMINISTIC"); g_det_mode = (e != nullptr && atoi(e) != 0) ? 1 : 0; }
+  if (g_det_mode < 0) g_det_mode = deterministic_env() ? 1 : 0;
   return g_det_mode == 1;
 }
 static int det_upload() {
@@ -1389,14 +1331,6 @@ int ssp_clock_probe(float ms, double* mhz_out, void* stream_) {
   if (e != hipSuccess || h[1] == 0) return fail(-2, "ssp_clock_probe: %s", hipGetErrorString(e));
   *mhz_out = 100.0 * (double)h[0] / (double)h[1];
   return 0;
-}
-
-// perf-debug (SSP_DBG_IDLE_US=n): one wave that sleeps for n microseconds of the constant 100 MHz counter - an idle stretch in front of
-// the loss phase of the pair step, to see how much of it the power / clock management gives back to the kernels around it
-// (PERF_LOG round 6 section 9).
-__global__ void idle_kernel(unsigned long long ticks) {
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(127);
 }
 
 int ssp_set_deterministic(int on) {
@@ -1827,7 +1761,7 @@ static int conv_layer_fwd_bf16(ssp_handle* h, const SlotSet& SS, int l, int src,
   const bool pool_out = l < 8 && SS.s[0]->Apool[l] != nullptr && d.bn;
   // 3x3 layers on the 30x40 maps (layers 6, 7 and the three heads): the input is activated once into act[src]
   // (bn_relu_bf16_kernel: 20 MB, 9 us) and read without staging arithmetic by every unit and by the weight gradient
-  static const int act_env = getenv("SSP_ACT7") ? atoi(getenv("SSP_ACT7")) : 1;   // (perf-debug A/B: 0 off, 1 heads only, 2 also layers 6, 7)
+  const int act_env = act7_env();
   const bool from_act = d.ks == 3 && d.cin == 128 && src >= 5 && src <= 7 && (src == 7 ? act_env != 0 : act_env >= 2) &&
                         SS.s[0]->act[src] != nullptr && (pooled ? SS.s[0]->pool_raw[src] : (SS.s[0]->y_cs[src] == 128 && SS.s[0]->y_co[src] == 0));
   if (from_act && !SS.s[0]->act_valid[src]) {
@@ -1931,7 +1865,7 @@ static int conv_layer_fwd(ssp_handle* h, const SlotSet& SS, int l, int src, int 
   }
   CHK(launch_conv(h, c, st, d.ks == 3 ? SSP_PROF_CONV3X3_FWD : 0));
   if (d.bn && deferred != nullptr && deferred->n < 3) deferred->layers[deferred->n++] = l;
-  else if (d.bn && train && l < 8 && bn_lazy_env()) {   // encoder layers: the next convolution finalizes (or bn_finalize_pending)
+  else if (d.bn && train && l < 8) {   // encoder layers: the next convolution finalizes (or bn_finalize_pending)
     h->fin_pending[l] = true;
     h->fin_count[l] = (double)N * H * W;
   }
@@ -1952,16 +1886,10 @@ static int run_forward(ssp_handle* h, const SlotSet& SS, const float* const* xs,
   else for (int k = 0; k < SS.n; ++k) CHK(dev_zero(SS.s[k]->stats_region, SS.s[k]->stats_bytes, st));
   // The Winograd weight images (a ~95 us latency-bound launch over 2.6 M floats) are packed on the side stream beside the
   // HBM-bound first-layer convolution, which needs none of them; layer 1 waits for the join.
-  static const int pack_stream_env = getenv("SSP_PACK_STREAM") ? atoi(getenv("SSP_PACK_STREAM")) : 1;  // (perf-debug: 0 = in line)
-  const bool pack_forked = pack_stream_env != 0;
   SideFork pack_fork;
-  if (pack_forked) {
-    CHK(ensure_aux_stream(h));
-    CHK(pack_fork.fork(st, h->aux_stream, h->ev_pack_fork, h->ev_pack_join));
-    CHK(pack_all(h, for_backward, SS.n, N, H, W, h->aux_stream));
-  } else {
-    CHK(pack_all(h, for_backward, SS.n, N, H, W, st));
-  }
+  CHK(ensure_aux_stream(h));
+  CHK(pack_fork.fork(st, h->aux_stream, h->ev_pack_fork, h->ev_pack_join));
+  CHK(pack_all(h, for_backward, SS.n, N, H, W, h->aux_stream));
   // layer 0: direct 1->64 conv (HBM-bound; the views ride one launch, blockIdx.y)
   {
     const LayerDesc& d = h->L[0];
@@ -1975,7 +1903,7 @@ static int run_forward(ssp_handle* h, const SlotSet& SS, const float* const* xs,
                        P(h, d.b_off), S0.Y[0], S1.Y[0], train ? S0.bn[0].stats : nullptr, train ? S1.bn[0].stats : nullptr,
                        N, H, W);
     HIPCHK(hipGetLastError());
-    if (train && bn_lazy_env() && !bf16_path()) { h->fin_pending[0] = true; h->fin_count[0] = (double)N * H * W; }   // layer 1 finalizes
+    if (train && !bf16_path()) { h->fin_pending[0] = true; h->fin_count[0] = (double)N * H * W; }   // layer 1 finalizes
     else CHK(bn_finalize(h, SS.s, SS.n, 0, (double)N * H * W, train, st));
   }
   CHK(pack_fork.join());
@@ -2111,7 +2039,7 @@ static int bn_layer_backward(ssp_handle* h, const SlotSet& SS, int l, const floa
     h->apply_fused[l] = defer;
     // pass 1 came from the data gradient above, pass 2 goes into the weight gradient: what is left is the replica reduction, and
     // the fused weight gradient can do that in its prologue (WgradArgs::f_lazy) - no launch at all
-    if (fused && defer && bn_lazy_env()) h->sums_lazy[l] = true;
+    if (fused && defer) h->sums_lazy[l] = true;
     else CHK((launch_bn_bwd<true, false>(a, SS.n, dg, db, st, fused, defer, queue)));
   }
   else if (collect != nullptr) {   // BatchNorm without ReLU (the pointwise heads): the caller launches two layers together
@@ -2235,6 +2163,17 @@ static int conv_layer_backward(ssp_handle* h, const SlotSet& SS, int l, int src,
   return 0;
 }
 
+// bf16 path: ask the data-gradient launch `c` (output = dOut of layer src) to accumulate pass 1 of layer src's BatchNorm backward in
+// its copy-out (ConvBArgs::bnr_*); the tensor read beside the output is src's raw output, or its raw pooled copy
+static void set_bnr_bf16(ConvBCall& c, const SlotSet& SS, int src, bool pooled) {
+  for (int k = 0; k < SS.n; ++k) {
+    Slot& S = *SS.s[k];
+    c.bnr_t[k] = reinterpret_cast<const uint16_t*>(pooled ? S.Apool[src] : S.Y[src]);
+    c.bnr_scale[k] = S.bn[src].scale; c.bnr_shift[k] = S.bn[src].shift; c.bnr_mean[k] = S.bn[src].mean;
+    c.bnr_invstd[k] = S.bn[src].invstd; c.bnr_sums[k] = S.bn[src].bsums;
+  }
+}
+
 // bf16 path (conv algorithm 12): encoder layers l_hi .. l_lo.  gP holds dOut of layer l_hi (bf16, grad wrt its (pooled) activation);
 // per layer: BatchNorm + ReLU (+ pool) backward in fp32 arithmetic on the bf16 tensors (sums, then apply: dY -> gQ, bf16), weight
 // gradient and data gradient on the bf16 matrix cores (-> gP, bf16).
@@ -2342,16 +2281,8 @@ static int encoder_backward_bf16(ssp_handle* h, const SlotSet& SS, int l_hi, int
       for (int k = 0; k < SS.n; ++k) { c.in[k] = SS.s[k]->gQ; c.out[k] = SS.s[k]->gP; }
       // pass 1 of layer src's BatchNorm backward in this launch's copy-out: its output IS dOut of layer src, at the resolution of
       // src's (pooled) raw output - the tensor the separate pass would read beside it (Apool for the pooled layers, see above)
-      static const int bnr_env = getenv("SSP_BF16_BNR") ? atoi(getenv("SSP_BF16_BNR")) : 1;   // (perf-debug: 0 = separate pass 1)
-      const bool bnr = bnr_env != 0 && launch_conv_bf16_is_ws(c);
-      if (bnr) {
-        for (int k = 0; k < SS.n; ++k) {
-          Slot& S = *SS.s[k];
-          c.bnr_t[k] = reinterpret_cast<const uint16_t*>(pooled_in ? S.Apool[src] : S.Y[src]);
-          c.bnr_scale[k] = S.bn[src].scale; c.bnr_shift[k] = S.bn[src].shift; c.bnr_mean[k] = S.bn[src].mean;
-          c.bnr_invstd[k] = S.bn[src].invstd; c.bnr_sums[k] = S.bn[src].bsums;
-        }
-      }
+      const bool bnr = bf16_bnr_env() && launch_conv_bf16_is_ws(c);
+      if (bnr) set_bnr_bf16(c, SS, src, pooled_in);
       const double flops = 2.0 * SS.n * N * lh * lw * (double)d.cin * C * 9;
       // (bytes: dY in, dOut of the layer below out, + the layer-below raw (pooled) output the fused BatchNorm-backward sums read)
       ProfScope ps(h, SSP_PROF_CONV3X3_DGRAD, st, flops, 2.0 * SS.n * N * lh * lw * ((double)d.cin * (bnr ? 2.0 : 1.0) + C), flops, SSP_PROF_K_CONV_BF16);
@@ -2386,20 +2317,15 @@ static int heads_backward_bf16(ssp_handle* h, const SlotSet& SS, const float* co
     c.out_cs = hcs; c.out_co = co; c.cout = 256;
     // pass 1 of the 3x3 head's BatchNorm backward in this data gradient's copy-out (its output is dOut of that head; the head's raw
     // output has the output's geometry: its 256-channel slice of [cells][256 heads])
-    static const int bnr_env = getenv("SSP_BF16_BNR") ? atoi(getenv("SSP_BF16_BNR")) : 1;
     // (the same geometry predicate as the fp32 path's add_dgrad: the generic kernel reads S.Y[src] with the OUTPUT's stride / offset /
     // channel count - a layer table in which the head's raw output sits elsewhere falls back to the separate pass 1)
-    const bool bnr = bnr_env != 0 && h->L[src].bn && S0.y_cs[src] == hcs && S0.y_co[src] == co && h->L[src].cout == c.cout;
+    const bool bnr = bf16_bnr_env() && h->L[src].bn && S0.y_cs[src] == hcs && S0.y_co[src] == co && h->L[src].cout == c.cout;
     for (int k = 0; k < SS.n; ++k) {
       Slot& S = *SS.s[k];
       w.x[k] = S.Y[src]; w.dy[k] = dy[k]; w.x_scale[k] = S.bn[src].scale; w.x_shift[k] = S.bn[src].shift;
       c.in[k] = dy[k]; c.out[k] = S.gP;
-      if (bnr) {
-        c.bnr_t[k] = reinterpret_cast<const uint16_t*>(S.Y[src]);
-        c.bnr_scale[k] = S.bn[src].scale; c.bnr_shift[k] = S.bn[src].shift; c.bnr_mean[k] = S.bn[src].mean;
-        c.bnr_invstd[k] = S.bn[src].invstd; c.bnr_sums[k] = S.bn[src].bsums;
-      }
     }
+    if (bnr) set_bnr_bf16(c, SS, src, false);
     CHK(launch_wgrad_bf16(w, h->partial, h->partial_floats, h->n_cu, st, h->rq_bf16));
     CHK(launch_conv_bf16(c, h->n_cu, st));
     if (bnr) h->bsums_fused[src] = true;
@@ -2501,16 +2427,8 @@ static int heads_backward_bf16(ssp_handle* h, const SlotSet& SS, const float* co
   c.out_cs = 128; c.out_co = 0; c.cout = 128;
   for (int k = 0; k < SS.n; ++k) { c.in[k] = SS.s[k]->gQ; c.out[k] = SS.s[k]->gP; }
   // pass 1 of layer 7's BatchNorm backward in this launch's copy-out (its output IS dOut of layer 7), as between the encoder layers
-  static const int bnr_env = getenv("SSP_BF16_BNR") ? atoi(getenv("SSP_BF16_BNR")) : 1;
-  const bool bnr = bnr_env != 0 && launch_conv_bf16_is_ws(c);
-  if (bnr) {
-    for (int k = 0; k < SS.n; ++k) {
-      Slot& S = *SS.s[k];
-      c.bnr_t[k] = reinterpret_cast<const uint16_t*>(S.Y[7]);
-      c.bnr_scale[k] = S.bn[7].scale; c.bnr_shift[k] = S.bn[7].shift; c.bnr_mean[k] = S.bn[7].mean;
-      c.bnr_invstd[k] = S.bn[7].invstd; c.bnr_sums[k] = S.bn[7].bsums;
-    }
-  }
+  const bool bnr = bf16_bnr_env() && launch_conv_bf16_is_ws(c);
+  if (bnr) set_bnr_bf16(c, SS, 7, false);
   const double flops = 2.0 * SS.n * ncells * (double)hcs * 128 * 9;
   ProfScope ps(h, SSP_PROF_CONV3X3_DGRAD, st, flops, 2.0 * SS.n * ncells * (hcs + 128.0), flops, SSP_PROF_K_CONV_BF16);
   CHK(launch_conv_bf16(c, h->n_cu, st));
@@ -2529,10 +2447,6 @@ static int heads_backward_bf16(ssp_handle* h, const SlotSet& SS, const float* co
 enum { EARLY_SPLIT_LAYER = 2 };
 static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* const* dsemi, const float* const* draw_desc,
                              float* const* dsout, hipStream_t st, int part);
-static bool bf16_fuse_apply_env() {
-  const char* const e = getenv("SSP_BF16_FUSE_APPLY");
-  return e ? atoi(e) != 0 : true;
-}
 static int run_backward(ssp_handle* h, const SlotSet& SS, const float* const* dsemi, const float* const* draw_desc,
                         float* const* dsout, hipStream_t st, int part = 0) {
   if (part != 2) h->bf16_fuse_apply = bf16_fuse_apply_env();   // (one value for the heads and the encoder of a step, both phases)
@@ -2602,9 +2516,8 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
     for (int k = 0; k < SS.n; ++k) gQd[k] = gQ[k] + ncells_all * 80;
   G1Layer Lg[3];
   int ng = 0;
-  // ... and so do the three weight gradients (wgrad1x1_group_kernel; SSP_G1_WGRAD=0, perf-debug: wgrad_mfma_kernel per layer)
-  static const int g1_wgrad_env = getenv("SSP_G1_WGRAD") ? atoi(getenv("SSP_G1_WGRAD")) : 1;
-  const bool gw = grouped && g1_wgrad_env != 0 && g1w_fits(256, 65, (long)ncells_all, hcs, std::max(256, h->sout_cs));
+  // ... and so do the three weight gradients (wgrad1x1_group_kernel)
+  const bool gw = grouped && g1w_fits(256, 65, (long)ncells_all, hcs, std::max(256, h->sout_cs));
   G1WLayer Lw[3];
   int nw = 0;
   auto add_wgrad = [&](int l, float* const* dy, int dy_cs) {
@@ -2619,13 +2532,12 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
   };
   // ... and accumulates pass 1 of the BatchNorm backward of the 3x3 head below (Pa, Da, DS: dact has the geometry of their
   // raw outputs, [cells][hcs] at channel 256 k) on the way: bn_layer_backward of those layers then skips its reduction pass
-  static const int g1_bnr_env = getenv("SSP_G1_BNR") ? atoi(getenv("SSP_G1_BNR")) : 1;  // (perf-debug: 0 = separate pass)
   auto add_dgrad = [&](int l, float* const* dy, int dy_cs, int co) {
     const LayerDesc& d = h->L[l];
     const int src = l - 1;
     G1Layer& y = Lg[ng++];
     y.in_cs = dy_cs; y.in_co = 0; y.out_cs = hcs; y.out_co = co; y.wpk = h->wpk_g1_bwd[l]; y.K = d.cout; y.N = d.cin;
-    const bool bnr = g1_bnr_env != 0 && h->L[src].bn && S0.y_cs[src] == hcs && S0.y_co[src] == co && h->L[src].cout == d.cin;
+    const bool bnr = h->L[src].bn && S0.y_cs[src] == hcs && S0.y_co[src] == co && h->L[src].cout == d.cin;
     for (int k = 0; k < SS.n; ++k) {
       Slot& S = *SS.s[k];
       y.in[k] = dy[k]; y.out[k] = dact[k];
@@ -2664,21 +2576,14 @@ static int run_backward_impl(ssp_handle* h, const SlotSet& SS, const float* cons
     const LayerDesc& d = h->L[L_SOUT];
     const int ncells = N * Hc * Wc;
     if (h->sout_cs > 256) return fail(-3, "segmentation head: more than 256 classes are not supported by colsum_kernel");
-    if (tail_merge_env()) {   // dsout outlives the pass: the column sums join the tail launch
-      TailJobs& T = h->tail;
-      T.cs_m[0] = dsout[0]; T.cs_m[1] = dsout[SS.n - 1]; T.cs_out = Gd(h, d.b_off);
-      T.cs_rows = ncells; T.cs_C = d.cout; T.cs_cs = h->sout_cs; T.cs_blocks = cdiv(ncells, COLSUM_ROWS); T.cs_views = SS.n;
-    } else {
-      hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(ncells, COLSUM_ROWS), SS.n), dim3(256), 0, st, dsout[0], Gd(h, d.b_off), ncells, d.cout,
-                         h->sout_cs, dsout[SS.n - 1]);
-      HIPCHK(hipGetLastError());
-    }
+    TailJobs& T = h->tail;   // dsout outlives the pass: the column sums join the tail launch
+    T.cs_m[0] = dsout[0]; T.cs_m[1] = dsout[SS.n - 1]; T.cs_out = Gd(h, d.b_off);
+    T.cs_rows = ncells; T.cs_C = d.cout; T.cs_cs = h->sout_cs; T.cs_blocks = cdiv(ncells, COLSUM_ROWS); T.cs_views = SS.n;
     CHK(conv_layer_backward(h, SS, L_SOUT, L_DS, dsout, h->sout_cs, 0, dact, hcs, 512, N, Hc, Wc, 1, st, grouped, gw));
     if (grouped) add_dgrad(L_SOUT, dsout, h->sout_cs, 512);
     if (gw) add_wgrad(L_SOUT, dsout, h->sout_cs);
   }
-  if (gw && nw > 0) CHK(launch_g1_wgrad(Lw, nw, SS.n, (long)ncells_all, h->g1_partial, h->g1_partial_slabs, h->n_cu, st,
-                                        tail_merge_env() ? &h->tail : nullptr));
+  if (gw && nw > 0) CHK(launch_g1_wgrad(Lw, nw, SS.n, (long)ncells_all, h->g1_partial, h->g1_partial_slabs, h->n_cu, st, &h->tail));
   if (grouped && ng > 0) CHK(launch_g1(Lg, ng, SS.n, (long)ncells_all, 0, h->n_cu, st));
   for (int l : {L_PB, L_DB, L_SOUT}) {
     const bool ran = l == L_PB ? has_semi : l == L_DB ? has_desc : has_sem;
@@ -2836,15 +2741,7 @@ int ssp_adam_step(ssp_handle* h, float lr, int step, void* stream) {
 // Segmentation loss of one view.  algo 0: the step's choice - the (x, class) lane form (sem_ce_xc_kernel) when the label map is exactly
 // 8x the logit map and the classes fit its 9 x 16 slots, the pixels-then-classes form (sem_ce_kernel) otherwise; SSP_SEM_XC=0 keeps
 // the latter everywhere (same-box A/B).  1 / 2 force a form (2 fails on shapes it does not cover).
-// SSP_DESC_GATHER=0 (same-box A/B, fallback): the match term of the sparse descriptor loss scatters with atomics
-static bool desc_gather_env() {
-  static const int v = getenv("SSP_DESC_GATHER") ? atoi(getenv("SSP_DESC_GATHER")) : 1;
-  return v != 0;
-}
-static int sem_xc_env() {
-  static const int v = [] { const char* e = getenv("SSP_SEM_XC"); return e ? atoi(e) : 1; }();
-  return v;
-}
+constexpr int SEM_XC_WGS_PER_CU = 2;   // two 4-wave workgroups per CU and view, all resident
 static int launch_sem_ce(int algo, bool train, const float* sout, const int64_t* labels, float* dsout, StepAccum* acc, int view, int B,
                          int Hc, int Wc, int H, int W, int C, int cs, hipStream_t st, const float* sout1 = nullptr,
                          const int64_t* labels1 = nullptr, float* dsout1 = nullptr) {
@@ -2856,8 +2753,7 @@ static int launch_sem_ce(int algo, bool train, const float* sout, const int64_t*
   const long ntile = (long)B * (Hc + 1) * (Wc + 1);
   const int nviews = sout1 != nullptr ? 2 : 1;
   if (xc) {
-    static const int wgs_per_cu = [] { const char* e = getenv("SSP_SEM_XC_WGS"); return e ? atoi(e) : 2; }();
-    const SemXcGeom geom = sem_xc_geom(B, Hc, Wc, wgs_per_cu * device_cu_count());   // two 4-wave workgroups per CU and view, all resident
+    const SemXcGeom geom = sem_xc_geom(B, Hc, Wc, SEM_XC_WGS_PER_CU * device_cu_count());
     const int grid = B * geom.row_groups * geom.x_splits * nviews;
 #define SSP_SEM_XC(MODE, NB) \
   hipLaunchKernelGGL((sem_ce_xc_kernel<MODE, NB>), dim3(grid), dim3(256), 0, st, sout, labels, dsout, acc, view, B, Hc, Wc, C, cs, geom, sout1, \
@@ -2882,12 +2778,7 @@ static int launch_desc_csr(const int32_t* match_a, const int32_t* match_b, int32
   const size_t lds = desc_csr_lds_bytes(Hc * Wc, n_match);
   constexpr size_t lds_max = 128 * 1024;
   if (lds > lds_max) return fail(-1, "desc_csr: %d cells x %d matches need %zu B of LDS (> %zu)", Hc * Wc, n_match, lds, lds_max);
-  static AttrOnce attr_once;
-  if (attr_once.need())
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(desc_csr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-  hipLaunchKernelGGL(desc_csr_kernel, dim3(B, 2), dim3(DESC_CSR_THREADS), lds, st, match_a, match_b, off, em, ew, Hc, Wc, n_match, dflags);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_lds<desc_csr_kernel>(lds_max, dim3(B, 2), dim3(DESC_CSR_THREADS), lds, st, match_a, match_b, off, em, ew, Hc, Wc, n_match, dflags);
 }
 
 static int pair_step_impl(ssp_handle* h, const ssp_pair_inputs* in, float* scalars_dev, int phase, hipStream_t st_in) {
@@ -2931,16 +2822,18 @@ static int pair_step_impl(ssp_handle* h, const ssp_pair_inputs* in, float* scala
   // stream beside the first-layer convolution and the weight packing (both leave the chip room; a launch beside the later,
   // CU-filling convolutions would delay their workgroups), and the scatter targets are zeroed by kernels that run anyway:
   // d(convSout) by the label count, d(desc) by the descriptor normalisation at the end of the forward pass.  ~0.15 ms of small
-  // memory-bound launches off the serial part of the step.  SSP_EARLY_LABELS=0: in place, in front of the loss kernels.
-  static const int early_env = getenv("SSP_EARLY_LABELS") ? atoi(getenv("SSP_EARLY_LABELS")) : 1;
-  const bool early = early_env != 0;
+  // memory-bound launches off the serial part of the step.
   const float* masks[2] = {in->valid_mask_dev, in->warped_valid_mask_dev};
   const int64_t* sems[2] = {in->semantic_dev, in->warped_semantic_dev};
   const bool zero_dsout = semantic && in->train;
   // the corner lists of the match term need the index arrays only: beside the forward pass as well
   const bool gather = h->desc_gather && in->train && use_desc && !dense;
   const int dflags = (in->sparse_method != 0 ? DESC_METHOD_1D : 0) | (in->sparse_dist != 0 ? DESC_EUCLIDEAN : 0);
-  auto label_kernels = [&](hipStream_t se) -> int {
+  {
+    CHK(ensure_aux_stream(h));
+    hipStream_t se = h->aux2_stream;
+    HIPCHK(hipEventRecord(h->ev_early_fork, st));   // (behind step_begin_kernel: the accumulators are zero, the last step is done)
+    HIPCHK(hipStreamWaitEvent(se, h->ev_early_fork, 0));
     if (gather)
       CHK(launch_desc_csr(in->match_a_dev, in->match_b_dev, h->csr_off, h->csr_match, h->csr_weight, B, Hc, Wc, h->cfg.n_match, dflags, se));
     hipLaunchKernelGGL(cell_mask_kernel, dim3(std::min(cdiv(ncells, 4), 512), nv), dim3(256), 0, se, masks[0], h->slot[0].cellmask,
@@ -2950,29 +2843,16 @@ static int pair_step_impl(ssp_handle* h, const ssp_pair_inputs* in, float* scala
                          zero_dsout ? h->slot[0].dsout : (float*)nullptr, zero_dsout && nv == 2 ? h->slot[1].dsout : (float*)nullptr,
                          (long)ncells * h->sout_cs);
     HIPCHK(hipGetLastError());
-    return 0;
-  };
-  if (early) {
-    CHK(ensure_aux_stream(h));
-    HIPCHK(hipEventRecord(h->ev_early_fork, st));   // (behind step_begin_kernel: the accumulators are zero, the last step is done)
-    HIPCHK(hipStreamWaitEvent(h->aux2_stream, h->ev_early_fork, 0));
-    CHK(label_kernels(h->aux2_stream));
-    HIPCHK(hipEventRecord(h->ev_early_join, h->aux2_stream));
+    HIPCHK(hipEventRecord(h->ev_early_join, se));
   }
   {
     const float* xs[2] = {in->image_dev, in->warped_image_dev};
-    CHK(run_forward(h, SS, xs, B, H, W, 1, in->train != 0, st, false, early && in->train && use_desc && !dense));
+    CHK(run_forward(h, SS, xs, B, H, W, 1, in->train != 0, st, false, in->train && use_desc && !dense));
   }
-  if (early) HIPCHK(hipStreamWaitEvent(st, h->ev_early_join, 0));
-  else CHK(label_kernels(st));
-  {
-    static const int idle_us = getenv("SSP_DBG_IDLE_US") ? atoi(getenv("SSP_DBG_IDLE_US")) : 0;
-    if (idle_us > 0) hipLaunchKernelGGL(idle_kernel, dim3(1), dim3(64), 0, st, (unsigned long long)idle_us * 100ull);
-  }
+  HIPCHK(hipStreamWaitEvent(st, h->ev_early_join, 0));
   // ---- descriptor loss on the side stream (fork) ----
-  static const int loss_stream_env = getenv("SSP_LOSS_STREAM") ? atoi(getenv("SSP_LOSS_STREAM")) : 1;  // (perf-debug: 0 = one stream)
   hipStream_t sd = st;
-  const bool forked = loss_stream_env != 0 && use_desc && !dense;  // (the dense loss reads the cell mask of the main stream's kernels)
+  const bool forked = use_desc && !dense;  // (the dense loss reads the cell mask of the main stream's kernels)
   SideFork loss_fork;
   if (forked) {
     CHK(ensure_aux_stream(h));
@@ -3016,10 +2896,7 @@ static int pair_step_impl(ssp_handle* h, const ssp_pair_inputs* in, float* scala
     SSP_DESC(desc_nonmatch_fwd_kernel, A.desc, Bs.desc, in->match_a_dev, in->nonmatch_b_dev, in->train ? h->dots : (float*)nullptr, h->accum,
              B, Hc, Wc, h->cfg.n_match, h->cfg.n_non, dflags)
     if (in->train) {
-      if (!early) {   // (early: zeroed by the descriptor normalisation of the forward pass; the non-match atomics need a zeroed target either way)
-        CHK(dev_zero(A.ddesc, (size_t)ncells * 256 * sizeof(float), sd));
-        CHK(dev_zero(Bs.ddesc, (size_t)ncells * 256 * sizeof(float), sd));
-      }
+      // (d(desc) was zeroed by the descriptor normalisation of the forward pass: the non-match atomics need a zeroed target)
       if (gather) {   // two gradient rows per match instead of the scatter; desc_normalize_bwd_kernel below gathers them per cell
         if (euc) hipLaunchKernelGGL((desc_match_kernel<true, true, true>), dgrid, dim3(256), 0, sd, A.desc, Bs.desc, in->match_a_dev, in->match_b_dev,
                                     (float*)nullptr, (float*)nullptr, h->accum, B, Hc, Wc, h->cfg.n_match, dflags, h->g_rows);
@@ -3081,13 +2958,8 @@ static int sample_indices_impl(ssp_handle* h, const float* homographies_dev, con
   if (h->cfg.n_match > SAMPLER_MAX_CELLS) return fail(-1, "n_match too large for the device sampler");
   int cap = 2048;  // power of two >= cells and >= n_match (2048 for every reference configuration)
   while (cap < Hc * Wc || cap < h->cfg.n_match) cap <<= 1;
-  static AttrOnce attr_once;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(sample_matches_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               SAMPLER_MAX_CELLS * 12));
-  }
-  hipLaunchKernelGGL(sample_matches_kernel, dim3(batch), dim3(1024), (size_t)cap * 12, st, homographies_dev, hcell_dev, seed,
-                     seed_dev, match_a_dev, match_b_dev, Hc, Wc, h->cfg.n_match, cap);
+  CHK(launch_lds<sample_matches_kernel>(SAMPLER_MAX_CELLS * 12, dim3(batch), dim3(1024), (size_t)cap * 12, st, homographies_dev, hcell_dev,
+                                        seed, seed_dev, match_a_dev, match_b_dev, Hc, Wc, h->cfg.n_match, cap));
   const long tot = (long)batch * h->cfg.n_match * h->cfg.n_non;
   hipLaunchKernelGGL(sample_nonmatches_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, st, seed, seed_dev, nonmatch_b_dev, tot, Hc,
                      Wc);
@@ -3785,14 +3657,8 @@ int ssp_eval_repeatability(const double* pts1_dev, const int32_t* n1_dev, const 
                 EVAL_KEEP_MAX);
   const int kk = std::min(keep_k, cap);
   const size_t lds = (size_t)((cap + 1) & ~1) * sizeof(double) + (size_t)2 * kk * 2 * sizeof(double);
-  static AttrOnce attr_once;
-  if (attr_once.need())
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_repeat_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               EVAL_LDS_MAX));
-  hipLaunchKernelGGL(eval_repeat_kernel, dim3(n_pairs), dim3(EVAL_THREADS), lds, (hipStream_t)stream, pts1_dev, n1_dev,
-                     pts2_dev, n2_dev, cap, pair_stride, hom_dev, hom_inv_dev, height, width, kk, dist_thresh, out_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_lds<eval_repeat_kernel>(EVAL_LDS_MAX, dim3(n_pairs), dim3(EVAL_THREADS), lds, (hipStream_t)stream, pts1_dev, n1_dev,
+                                        pts2_dev, n2_dev, cap, pair_stride, hom_dev, hom_inv_dev, height, width, kk, dist_thresh, out_dev);
 }
 
 size_t ssp_eval_ransac_workspace_bytes(int cap, int n_pairs) {
@@ -3812,17 +3678,11 @@ int ssp_eval_ransac(const double* pts1_dev, const double* pts2_dev, int cap, int
   double4* xy = reinterpret_cast<double4*>(workspace_dev);
   const size_t small = (size_t)cap * (sizeof(float) + 1);
   const bool use_lds = (size_t)cap * sizeof(double4) + small <= EVAL_LDS_MAX;
-  static AttrOnce attr_once;
-  if (attr_once.need())
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_ransac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               EVAL_LDS_MAX));
   hipLaunchKernelGGL(eval_gather_kernel, dim3(cdiv(cap, 256), n_pairs), dim3(256), 0, st, pts1_dev, pts2_dev, cap, pair_stride,
                      match_dev, n_match_dev, xy);
-  hipLaunchKernelGGL(eval_ransac_kernel, dim3(n_pairs), dim3(EVAL_THREADS), use_lds ? (size_t)cap * sizeof(double4) + small : small,
-                     st, (const double4*)xy, match_dev, n_match_dev, cap, seeds_dev, (int)use_lds, h_dev, mask_dev,
-                     n_inlier_dev, status_dev, ap_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_lds<eval_ransac_kernel>(EVAL_LDS_MAX, dim3(n_pairs), dim3(EVAL_THREADS), use_lds ? (size_t)cap * sizeof(double4) + small : small,
+                                        st, (const double4*)xy, match_dev, n_match_dev, cap, seeds_dev, (int)use_lds, h_dev, mask_dev,
+                                        n_inlier_dev, status_dev, ap_dev);
 }
 
 // ---- epipolar check of matches: fundamental-matrix RANSAC over several workgroups per pair ----
@@ -3860,20 +3720,11 @@ int ssp_epi_ransac(const double* pts1_dev, const double* pts2_dev, int pt_stride
   if (groups == 0) groups = n_pairs * EPI_GROUPS_FEW_PAIRS <= EPI_CU_COUNT ? EPI_GROUPS_FEW_PAIRS : EPI_GROUPS_MANY_PAIRS;
   hipStream_t st = (hipStream_t)stream;
   uint64_t* keys = reinterpret_cast<uint64_t*>(workspace_dev);
-  static AttrOnce attr_once;
-  if (attr_once.need()) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(epi_hypotheses_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)EPI_LDS_MAX));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(epi_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)EPI_LDS_MAX));
-  }
-  hipLaunchKernelGGL(epi_hypotheses_kernel, dim3(groups, n_pairs), dim3(EPI_THREADS), (size_t)cap * sizeof(double4), st, pts1_dev,
-                     pts2_dev, pt_stride, cap, pair_stride, match_dev, n_match_dev, seeds_dev, thresh, keys);
-  hipLaunchKernelGGL(epi_finish_kernel, dim3(n_pairs), dim3(EPI_THREADS), (size_t)cap * (sizeof(double4) + 1), st, pts1_dev,
-                     pts2_dev, pt_stride, cap, pair_stride, match_dev, n_match_dev, seeds_dev, thresh, groups,
-                     (const uint64_t*)keys, f_dev, mask_dev, n_inlier_dev, status_dev, winner_dev, err_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
+  CHK(launch_lds<epi_hypotheses_kernel>(EPI_LDS_MAX, dim3(groups, n_pairs), dim3(EPI_THREADS), (size_t)cap * sizeof(double4), st, pts1_dev,
+                                        pts2_dev, pt_stride, cap, pair_stride, match_dev, n_match_dev, seeds_dev, thresh, keys));
+  return launch_lds<epi_finish_kernel>(EPI_LDS_MAX, dim3(n_pairs), dim3(EPI_THREADS), (size_t)cap * (sizeof(double4) + 1), st, pts1_dev,
+                                       pts2_dev, pt_stride, cap, pair_stride, match_dev, n_match_dev, seeds_dev, thresh, groups,
+                                       (const uint64_t*)keys, f_dev, mask_dev, n_inlier_dev, status_dev, winner_dev, err_dev);
 }
 
 int ssp_op_filter_matches(const float* match_dev, const int32_t* n_match_dev, const uint8_t* mask_dev, const int32_t* status_dev,
@@ -3969,15 +3820,10 @@ int ssp_op_triangulate_tracks(const int32_t* ids_dev, const int32_t* state_dev, 
     return fail(-1, "triangulate_tracks: -1 <= cos_min_parallax <= 1 and max_reproj >= 0 required");
   if (!ids_dev || !state_dev || !pts_dev || !cams_dev || !x_dev || !n_views_dev || !rms_dev || !cos_parallax_dev || !status_dev)
     return fail(-1, "triangulate_tracks: null pointer");
-  static AttrOnce attr_once;
-  if (attr_once.need())
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(triangulate_tracks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lm_lds_bytes(SSP_TRACK_MAX_LENGTH)));
-  hipLaunchKernelGGL(triangulate_tracks_kernel, dim3(cdiv(row_cap, LM_THREADS)), dim3(LM_THREADS), lm_lds_bytes(max_length),
-                     (hipStream_t)stream, ids_dev, state_dev, pts_dev, first_slot, cams_dev, max_length, point_cap, row_cap, min_views,
-                     cos_min_parallax, max_reproj, x_dev, n_views_dev, rms_dev, cos_parallax_dev, status_dev);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launch_lds<triangulate_tracks_kernel>(lm_lds_bytes(SSP_TRACK_MAX_LENGTH), dim3(cdiv(row_cap, LM_THREADS)), dim3(LM_THREADS),
+                                               lm_lds_bytes(max_length), (hipStream_t)stream, ids_dev, state_dev, pts_dev, first_slot, cams_dev,
+                                               max_length, point_cap, row_cap, min_views, cos_min_parallax, max_reproj, x_dev, n_views_dev,
+                                               rms_dev, cos_parallax_dev, status_dev);
 }
 
 int ssp_op_landmarks_select(const int32_t* ids_dev, const int32_t* tid_dev, const int32_t* state_dev, const int32_t* status_dev,
@@ -4091,10 +3937,6 @@ int ssp_bundle_adjust(const int32_t* ids_dev, const int32_t* state_dev, const do
       !info_dev || !workspace_dev)
     return fail(-1, "bundle_adjust: null pointer");
   if (cams_out_dev == cams_dev || x_out_dev == x_dev) return fail(-1, "bundle_adjust: the outputs must not alias the inputs");
-  static AttrOnce attr_once;
-  if (attr_once.need())
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(ba_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)ba_solve_lds_bytes(SSP_TRACK_MAX_LENGTH)));
   hipStream_t st = (hipStream_t)stream;
   const int L = max_length, tiles = cdiv(row_cap, BA_THREADS);
   const BaWs w = ba_ws_of(reinterpret_cast<double*>(workspace_dev), L, row_cap);
@@ -4104,8 +3946,8 @@ int ssp_bundle_adjust(const int32_t* ids_dev, const int32_t* state_dev, const do
     const double* ctl = w.ctl + (size_t)it * BA_CTL_WORDS;
     hipLaunchKernelGGL(ba_linearise_kernel, dim3(tiles), dim3(BA_THREADS), stage, st, ids_dev, state_dev, pts_dev, first_slot,
                        (const double*)cams_out_dev, (const double*)x_out_dev, status_dev, L, point_cap, row_cap, ctl, w.part);
-    hipLaunchKernelGGL(ba_solve_kernel, dim3(1), dim3(BA_THREADS), ba_solve_lds_bytes(L), st, (const double*)w.part, tiles,
-                       (const double*)cams_out_dev, L, ctl, w.sol, w.cand_cams);
+    CHK(launch_lds<ba_solve_kernel>(ba_solve_lds_bytes(SSP_TRACK_MAX_LENGTH), dim3(1), dim3(BA_THREADS), ba_solve_lds_bytes(L), st,
+                                    (const double*)w.part, tiles, (const double*)cams_out_dev, L, ctl, w.sol, w.cand_cams));
     hipLaunchKernelGGL(ba_backsub_kernel, dim3(tiles), dim3(BA_THREADS), stage, st, ids_dev, state_dev, pts_dev, first_slot,
                        (const double*)cams_out_dev, (const double*)x_out_dev, status_dev, L, point_cap, row_cap, ctl,
                        (const double*)w.sol, (const double*)w.cand_cams, w.x_cand, w.cpart);

@@ -607,3 +607,39 @@ def test_geometry_headers_stand_on_the_shared_blocks(tmp_path):
         if r.returncode != 0:
             failed[h] = r.stderr[-2000:]
     assert not failed, failed
+
+
+KEPT_SWITCHES = ("SSP_DETERMINISTIC", "SSP_DESC_GATHER", "SSP_BF16_FUSE_APPLY", "SSP_CONVB_WS", "SSP_ACT7", "SSP_BF16_BNR", "SSP_SEM_XC",
+                 "SSP_CONVB_ABLATE", "SSP_CONVB_TRACE", "SSP_W4_TRACE", "SSP_WGF_TRACE")
+RETIRED_SWITCHES = ("SSP_BN_LAZY", "SSP_FUSE_APPLY", "SSP_TAIL_MERGE", "SSP_PACK_STREAM", "SSP_LOSS_STREAM", "SSP_EARLY_LABELS",
+                    "SSP_G1", "SSP_G1_WGRAD", "SSP_G1_BNR", "SSP_G1_ECOST", "SSP_G1_ECOST_BNR",
+                    "SSP_WGRAD_F4", "SSP_W4_MIN_PIXELS", "SSP_W4_MIN_ITEMS_X4", "SSP_WGB_PER_CU", "SSP_SEM_XC_WGS",
+                    "SSP_CONVB_GRID", "SSP_DBG_IDLE_US")
+
+
+def test_host_layer_reads_only_the_kept_switches_and_launches_lds_kernels_one_way():
+    """The host launch layer (csrc/ssp.hip, csrc/bf16_host.hip.h) reads exactly the kept SSP_* environment switches, each through
+    its one accessor on top of env_int (the only getenv of the library); no retired A/B switch is named anywhere in csrc/; and the
+    per-(kernel, device) dynamic-LDS attribute flag AttrOnce is used by launch_lds alone."""
+    csrc = os.path.join(ROOT, "semantic-superpoint_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hip.h"))}
+    code = {f: re.sub(r"//[^\n]*", "", t) for f, t in text.items()}   # (no /* */ comment in csrc holds code words)
+    whole = "\n".join(code.values())
+    # one getenv, inside env_int; every switch is a string literal handed to env_int (or, as on older trees, to getenv) exactly once
+    assert len(re.findall(r"\bgetenv\s*\(", whole)) == 1
+    assert re.search(r"static int env_int\(const char\* name, int dflt\) \{[^}]*\bgetenv\(name\)[^}]*\}", code["ssp.hip"])
+    reads = re.findall(r'\b(?:getenv|env_int)\s*\(\s*"(SSP_\w+)"', whole)
+    assert sorted(reads) == sorted(KEPT_SWITCHES), reads
+    literals = set(re.findall(r'"(SSP_\w+)"', whole))
+    assert literals == set(KEPT_SWITCHES), literals   # (no name assembled elsewhere and read through a variable)
+    for name in RETIRED_SWITCHES:
+        hits = [f for f, t in text.items() if re.search(r"\b%s\b" % name, t)]
+        assert not hits, (name, hits)
+    # AttrOnce: its definition and the one static flag inside launch_lds
+    uses = [(f, m.start()) for f, t in code.items() for m in re.finditer(r"\bAttrOnce\b", t)]
+    assert [f for f, _ in uses] == ["ssp.hip", "ssp.hip"], uses
+    src = code["ssp.hip"]
+    assert src[uses[0][1] - 7:uses[0][1]] == "struct "
+    m = re.search(r"static int launch_lds\(.*?\n\}\n", src, re.S)
+    assert m and m.start() < uses[1][1] < m.end()
+    assert len(re.findall(r"\.need\(\)", whole)) == 1
