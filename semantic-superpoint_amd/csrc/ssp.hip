@@ -1000,7 +1000,11 @@ static int launch_wgrad(ssp_handle* h, const WgradCall& c, float* partial, size_
   // weight gradient).  Correct on every 3x3 layer with a prefetchable input and any
   // map size (dY is zero-filled outside the map); 64 ci x 32 co slabs over the same 128-pixel block tiles as F(3x3,2x2).
   // Not the default: measured equal at 240x320 and 10-50 % slower below (profiles/r03_kernel_experiments.txt, DESIGN.md s. 12).
-  const bool wino4 = g_conv_algo == 11 && c.ks == 3 && c.in_mode != 2;
+  // A map that fits into ONE 128-pixel block tile (2x3, 4x6, 3x32 ...) stays on the weight gradient of algorithm 1: over so few
+  // 4x4 tiles the rounding of F(3x3,4x4) (transform constants up to 8) is not small beside a single tap's own sum - gradients that
+  // are exactly 0 came out as 1e-7 beside max |dW| 0.45, errors up to 2e-2 of |A| (*) |dY|.
+  const bool one_tile = c.H <= (wide ? 4 : 16) && c.W <= (wide ? 32 : 8);
+  const bool wino4 = g_conv_algo == 11 && c.ks == 3 && c.in_mode != 2 && !one_tile;
   const bool wino = wino4 || (g_conv_algo != 0 && c.ks == 3 && c.in_mode != 2 && c.H % 2 == 0 && c.W % 2 == 0);
   if (wino && ((double)c.H * c.W * std::max(c.in_cs, c.dout_cs) * 4.0 > 2147483647.0))
     return fail(-3, "wgrad: one image [%d,%d,%d] exceeds 2 GiB", c.H, c.W, std::max(c.in_cs, c.dout_cs));

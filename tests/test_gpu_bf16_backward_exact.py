@@ -44,6 +44,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import cpu_ref as C
+from tests.exact_sweep_cases import SWEEP_CASES
 from tests.test_gpu_backward_exact import L_DA, L_DB, L_DS, L_PA, L_PB, L_SOUT, POOLED, TAP_LAYERS, _Back, _edit_gammas, _nchw, _res
 from tests.test_gpu_bf16_path import _engine
 from tests.test_gpu_layer_exact import _inputs, _sd_tensor
@@ -380,7 +381,13 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("tag,B,H,W,fuse", CASES, ids=["%s-B%d-%dx%d-fuse%d" % c for c in CASES])
+# the tile-edge sweep (tests/exact_sweep_cases.py; what each case adds: its table): fused APPLY on; 88x72 (the only map with interior
+# 16x16 tiles among the small ones) also with the separate pass
+SWEEP_BACK_CASES = [c + (1,) for c in SWEEP_CASES] + [c + (0,) for c in SWEEP_CASES if c[2:] == (88, 72)]
+ALL_CASES = CASES + SWEEP_BACK_CASES
+
+
+@pytest.mark.parametrize("tag,B,H,W,fuse", ALL_CASES, ids=["%s-B%d-%dx%d-fuse%d" % c for c in ALL_CASES])
 def test_bf16_backward_chain_teacher_forced(tag, B, H, W, fuse, monkeypatch):
     torch.set_num_threads(min(int(os.environ.get("OMP_NUM_THREADS", "16")), 16))
     monkeypatch.setenv("SSP_BF16_FUSE_APPLY", str(fuse))   # (read once per backward pass)
@@ -393,6 +400,15 @@ def test_bf16_backward_chain_teacher_forced(tag, B, H, W, fuse, monkeypatch):
     e.zero_grad()
     e.pair_step(sample, indices=None, seed=7, train=True)
     torch.cuda.synchronize()
+    _check_backward(e, arch, sd, tag, B, H, W, fuse, sample, t0)
+    del e
+    torch.cuda.empty_cache()
+    _transparency(arch, sd, B, H, W, sample)
+
+
+def _check_backward(e, arch, sd, tag, B, H, W, fuse, sample, t0):
+    """Every stage of the bf16 backward of the engine's last pair step (B pairs of HxW, taps on) against fp64, and its route
+    record against the mirror of the dispatch."""
     want = _predict_routes(arch, B, H, W, bool(fuse))
     got = {l: _decode(e.backward_route(l)) for l in want}
     print("%s B=%d %dx%d fuse %d routes: %s" % (tag, B, H, W, fuse, {l: got[l] for l in sorted(got)}))
@@ -410,6 +426,4 @@ def test_bf16_backward_chain_teacher_forced(tag, B, H, W, fuse, monkeypatch):
     assert not bk.fails, bk.fails
     if B < 32:
         assert sum(bk.ties.values()) > 0, "no tied pooling window: the routing rule is not exercised"
-    del bk, e
-    torch.cuda.empty_cache()
-    _transparency(arch, sd, B, H, W, sample)
+    return bk.worst

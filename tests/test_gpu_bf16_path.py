@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import cpu_ref as C
+from tests.exact_sweep_cases import SWEEP_CASES
 
 pytestmark = pytest.mark.gpu
 ARCHS = ("SuperPointNet_gauss2", "SuperPointNet_gauss2_ssmall")
@@ -87,18 +88,41 @@ def _ulp_bad(stored_bf16, exact_f64, noise):
     return int((err > exact_f64.abs() * 2.0 ** -7 + noise).sum())
 
 
-@pytest.mark.parametrize("arch,H,W,B", [(ARCHS[1], 64, 96, 2), (ARCHS[1], 120, 160, 2), (ARCHS[0], 240, 320, 2)])
+SWEEP_ARCH = {"sp": ARCHS[0], "ssp": ARCHS[1]}
+# the tile-edge sweep (tests/exact_sweep_cases.py; what each case adds: its table), with negative BatchNorm scales on every third
+# channel below B = 32 (the min branch of the raw pooled copies); B >= 32: the convolutions on the images [0, 1, B/2, B-2, B-1]
+SWEEP_FORWARD_CASES = [(SWEEP_ARCH[tag], H, W, B) for tag, B, H, W in SWEEP_CASES]
+FORWARD_CASES = [(ARCHS[1], 64, 96, 2), (ARCHS[1], 120, 160, 2), (ARCHS[0], 240, 320, 2)]
+
+
+def _flip_gammas(arch, sd):
+    for _, bn, _, _, _ in C.layer_table(arch):
+        if bn is not None:
+            g = np.array(sd[bn + ".weight"], copy=True)
+            g[::3] = -g[::3]
+            sd[bn + ".weight"] = g
+
+
+@pytest.mark.parametrize("arch,H,W,B", FORWARD_CASES + SWEEP_FORWARD_CASES)
 def test_bf16_forward_chain_teacher_forced(arch, H, W, B):
     """Every layer of the HIP bf16 forward, re-evaluated from the HIP path's OWN stored input of that layer: operand =
     bf16(relu(fma(y_prev, scale, shift))) (2x2 max-pooled where the reference pools), exact fp64 products and sums of bf16(weights),
     + bias -> the stored bf16 (fp32 for the pointwise heads) output must be the correctly rounded value up to one ulp; the
     BatchNorm affine the engine derived from the stored tensor must be that tensor's batch statistics."""
+    import os
+    import time
+    torch.set_num_threads(min(int(os.environ.get("OMP_NUM_THREADS", "16")), 16))
+    t0 = time.perf_counter()
+    sweep = (arch, H, W, B) in SWEEP_FORWARD_CASES
     sd = C.init_state_dict(arch, seed=5)
+    if sweep and B < 32:
+        _flip_gammas(arch, sd)
     x = torch.rand(B, 1, H, W, generator=torch.Generator().manual_seed(3))
     e = _engine(arch, B, H, W, sd, with_grad=False)
     e.forward(x.to(_dev()), slot=0, train=True, want=())
     torch.cuda.synchronize()
-    _forward_chain(e, arch, sd, x, 0, list(range(B)))
+    _forward_chain(e, arch, sd, x, 0, [0, 1, B // 2, B - 2, B - 1] if B >= 32 else list(range(B)))
+    print("bf16 forward chain %s B=%d %dx%d: %.1f s" % (arch, B, H, W, time.perf_counter() - t0))
 
 
 def test_bf16_forward_chain_teacher_forced_at_the_benchmark_size():
