@@ -2,7 +2,8 @@
 hypothesis stream, degeneracy test, normalised 4-point DLT, scoring, refit and Gauss-Newton steps.  It is the reference
 of the kernel, which cannot be checked against OpenCV here ("parity unpinned").  The hypothesis
 solves repeat the kernel's operation order, so they agree with it to the last bit; the refit's sums run in another order
-(agreement to rounding)."""
+(agreement to rounding), and a second time in the kernel's own (lane_sum: lane-strided by 64, then the butterfly of
+wave_sum).  The spread between the two refits is this restatement's own floor."""
 import numpy as np
 
 HYPOTHESES = 2000
@@ -148,13 +149,34 @@ def hypotheses(m, seed, hs):
     return H, valid
 
 
-def _norm_of(pts):
-    c = pts.mean(axis=0)
-    sa = np.sum(np.abs(pts[:, 0] - c[0]) + np.abs(pts[:, 1] - c[1]))
-    return pts.shape[0] / sa, c[0], c[1]
+def lane_sum(terms, index):
+    """The sum of terms [k, ...] as wave 0 forms it: lane l adds its terms (those whose match index is l mod 64) in
+    index order from 0.0, then the 64 partials meet in the xor butterfly of wave_sum (offsets 32, 16, .., 1)."""
+    terms = np.asarray(terms, dtype=np.float64)
+    part = np.zeros((64,) + terms.shape[1:])
+    for lane in range(64):
+        t = terms[index % 64 == lane]
+        if t.shape[0]:
+            part[lane] = np.add.accumulate(t, axis=0)[-1]
+    o = 32
+    while o >= 1:
+        part = part + part[np.arange(64) ^ o]
+        o >>= 1
+    return part[0]
 
 
-def _normal_eq(m, tp, tq, geometric, h):
+def _norm_of(pts, index=None):
+    """index None: numpy's own summation; else the match indices of the rows, for the kernel's lane order."""
+    if index is None:
+        c = pts.mean(axis=0)
+        sa = np.sum(np.abs(pts[:, 0] - c[0]) + np.abs(pts[:, 1] - c[1]))
+        return pts.shape[0] / sa, c[0], c[1]
+    s = lane_sum(np.concatenate([pts, np.ones((pts.shape[0], 1))], axis=1), index)
+    cx, cy = s[0] / s[2], s[1] / s[2]
+    return s[2] / lane_sum(np.abs(pts[:, 0] - cx) + np.abs(pts[:, 1] - cy), index), cx, cy
+
+
+def _normal_eq(m, tp, tq, geometric, h, index=None):
     x, y = (m[:, 0] - tp[1]) * tp[0], (m[:, 1] - tp[2]) * tp[0]
     u, v = (m[:, 2] - tq[1]) * tq[0], (m[:, 3] - tq[2]) * tq[0]
     z, o = np.zeros_like(x), np.ones_like(x)
@@ -170,14 +192,47 @@ def _normal_eq(m, tp, tq, geometric, h):
         j1 = np.stack([z, z, z, x, y, o, -(x * v), -(y * v)], 1)
         r0, r1 = -u, -v
     a = np.zeros((8, 9))
-    a[:, :8] = j0.T @ j0 + j1.T @ j1
-    a[:, 8] = -(j0.T @ r0 + j1.T @ r1)
-    return float(np.sum(r0 * r0 + r1 * r1)), a
+    if index is None:
+        a[:, :8] = j0.T @ j0 + j1.T @ j1
+        a[:, 8] = -(j0.T @ r0 + j1.T @ r1)
+        return float(np.sum(r0 * r0 + r1 * r1)), a
+    # the kernel's terms: a[r][c] += j0[r] j0[c] + j1[r] j1[c] (c >= r, mirrored), a[r][8] -= j0[r] r0 + j1[r] r1
+    a[:, :8] = lane_sum(j0[:, :, None] * j0[:, None, :] + j1[:, :, None] * j1[:, None, :], index)
+    a[:, 8] = -lane_sum(j0 * r0[:, None] + j1 * r1[:, None], index)
+    return float(lane_sum(r0 * r0 + r1 * r1, index)), a
+
+
+def refit(m, mask, lanes=False):
+    """The refit of the winner's inliers: algebraic least squares, then Gauss-Newton steps kept while the cost falls.
+    lanes: the sums in wave 0's order (lane_sum) instead of numpy's.  -> H [9], or None when the refit gives none."""
+    idx = np.nonzero(mask)[0] if lanes else None
+    mi = m[mask]
+    tp, tq = _norm_of(mi[:, :2], idx), _norm_of(mi[:, 2:], idx)
+    if not all(np.isfinite(t[0]) and t[0] > 0 for t in (tp, tq)):
+        return None
+    _, a = _normal_eq(mi, tp, tq, False, np.zeros(8), idx)
+    h, ok = solve8(a[None])
+    if not ok[0]:
+        return None
+    h = h[0]
+    cost, a = _normal_eq(mi, tp, tq, True, h, idx)
+    for _ in range(GN_STEPS):
+        d, ok = solve8(a[None])
+        if not ok[0]:
+            break
+        hn = h + d[0]
+        cn, an = _normal_eq(mi, tp, tq, True, hn, idx)
+        if not cn < cost:
+            break
+        cost, h, a = cn, hn, an
+    Hr = denorm(h[None], np.array(tp)[:, None], np.array(tq)[:, None])[0]
+    return Hr if np.all(np.isfinite(Hr)) else None
 
 
 def ransac(m, seed, scores=None):
     """m: [n,4] float64 matches (x1, y1, x2, y2).  Returns dict(H [3,3], mask [n] bool, status 0 / 1, best hypothesis,
-    ap when scores (the match distances) are given)."""
+    H_best [3,3] (the winner before the refit), H_lanes [3,3] (the refit with its sums in wave 0's order: the spread
+    between H and H_lanes is this restatement's own floor), ap when scores (the match distances) are given)."""
     m = np.asarray(m, dtype=np.float64).reshape(-1, 4)
     n = m.shape[0]
     out = {"H": np.eye(3), "mask": np.zeros(n, dtype=bool), "status": 1, "best": -1}
@@ -189,7 +244,8 @@ def ransac(m, seed, scores=None):
         H, valid = hypotheses(m, seed, [0])
         if not valid[0]:
             return out
-        out.update(H=H[0].reshape(3, 3), mask=np.ones(4, dtype=bool), status=0, best=0)
+        out.update(H=H[0].reshape(3, 3), mask=np.ones(4, dtype=bool), status=0, best=0, H_best=H[0].reshape(3, 3),
+                   H_lanes=H[0].reshape(3, 3))
     else:
         best, best_sc, best_H = -1, -1, None
         for h0 in range(0, HYPOTHESES, 250):
@@ -202,32 +258,28 @@ def ransac(m, seed, scores=None):
         if best < 0:
             return out
         mask = resid2(best_H[None], m)[0] <= 9.0
-        Hf = best_H
+        Hf = Hl = best_H
         if mask.sum() >= 4:
-            mi = m[mask]
-            tp, tq = _norm_of(mi[:, :2]), _norm_of(mi[:, 2:])
-            if all(np.isfinite(t[0]) and t[0] > 0 for t in (tp, tq)):
-                _, a = _normal_eq(mi, tp, tq, False, np.zeros(8))
-                h, ok = solve8(a[None])
-                if ok[0]:
-                    h = h[0]
-                    cost, a = _normal_eq(mi, tp, tq, True, h)
-                    for _ in range(GN_STEPS):
-                        d, ok = solve8(a[None])
-                        if not ok[0]:
-                            break
-                        hn = h + d[0]
-                        cn, an = _normal_eq(mi, tp, tq, True, hn)
-                        if not cn < cost:
-                            break
-                        cost, h, a = cn, hn, an
-                    Hr = denorm(h[None], np.array(tp)[:, None], np.array(tq)[:, None])[0]
-                    if np.all(np.isfinite(Hr)):
-                        Hf = Hr
-        out.update(H=Hf.reshape(3, 3), mask=mask, status=0, best=best)
+            Hr, Hq = refit(m, mask), refit(m, mask, lanes=True)
+            Hf = best_H if Hr is None else Hr
+            Hl = best_H if Hq is None else Hq
+        out.update(H=Hf.reshape(3, 3), mask=mask, status=0, best=best, H_best=best_H.reshape(3, 3), H_lanes=Hl.reshape(3, 3))
     if scores is not None:
         out["ap"] = average_precision(out["mask"], -np.asarray(scores, dtype=np.float64))
     return out
+
+
+def average_precision_counting(mask, dist):
+    """The same AP in the kernel's form: the sum over the inliers i of tp(d <= d_i) / n(d <= d_i) in index order, over
+    the inlier count (float32 distances compared as they are)."""
+    mask, dist = np.asarray(mask, dtype=bool), np.asarray(dist, dtype=np.float32)
+    if not mask.any():
+        return 0.0
+    s = np.float64(0.0)
+    for i in np.nonzero(mask)[0]:
+        le = dist <= dist[i]
+        s = s + np.float64(np.sum(le & mask)) / np.float64(np.sum(le))
+    return float(s / np.float64(mask.sum()))
 
 
 def average_precision(labels, scores):
