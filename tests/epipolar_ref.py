@@ -3,8 +3,10 @@ reference counterpart and no OpenCV here, so this file is the specification the 
 counter-based draws (tests/eval_restatement.py's stream), the normalised 8-point solve by complete pivoting, the Sampson
 score, the refit on the inliers, the Jacobi rank-2 step and the output scaling.  The hypothesis solves and the scores
 repeat the kernel's operation order (equal to the last bit); the refit's sums over the inliers run in another order than
-the kernel's (agreement to rounding, see `ransac(..., pairwise=)` and tests/test_gpu_epipolar.py for the measured bound).
-Also the synthetic two-view scenes and the fixtures the tests use."""
+the kernel's (agreement to rounding, see `ransac(..., pairwise=)` and tests/test_gpu_epipolar.py for the measured bound), and
+a third time in the kernel's own (`order="block"`: block_sum<256>, see `block_sum`).  `decisions` reports how far every
+comparison of a problem is from going the other way.  Also the synthetic two-view scenes and the
+fixtures the tests use."""
 import functools
 
 import numpy as np
@@ -16,11 +18,14 @@ SAMPLE_DRAWS = ER.SAMPLE_DRAWS
 PIVOT_EPS = 1e-12
 JACOBI_SWEEPS = 8
 MIN_SCORE = 8
+DIRECT_N = 8          # this many matches: the one direct solve of matches 0..7
+BLOCK_THREADS = 256   # EPI_THREADS
+WINDOW = 1e-6         # decisions(): a squared distance within WINDOW * thresh^2 of thresh^2 is ambiguous
 
 
 def sample8(seed, h, n):
     """The 8 match indices of hypothesis h (None when the draws do not give 8 distinct ones)."""
-    if n == 8:
+    if n == DIRECT_N:
         return list(range(8))
     c = 0
     ids = []
@@ -34,9 +39,10 @@ def sample8(seed, h, n):
     return ids if len(set(ids)) == 8 else None
 
 
-def null_vector(A, trace=None):
+def null_vector(A, trace=None, pivots=None):
     """Null vectors of B 8x9 matrices A [B,8,9] by Gaussian elimination with complete pivoting.  Returns (f [B,9], ok [B]).
-    trace: a list that receives the (row, column) of every pivot of matrix 0."""
+    trace: a list that receives the (row, column) of every pivot of matrix 0; pivots: a list that receives the pivot
+    magnitudes [B] of every step."""
     a = np.array(A, dtype=np.float64)
     B = a.shape[0]
     ar = np.arange(B)
@@ -61,6 +67,8 @@ def null_vector(A, trace=None):
             perm[ar, pc] = t
             piv = a[:, k, k]
             ok &= np.abs(piv) > PIVOT_EPS
+            if pivots is not None:
+                pivots.append(np.abs(piv))
             inv = 1.0 / piv
             for r in range(k + 1, 8):
                 f = a[:, r, k] * inv
@@ -144,8 +152,9 @@ def inliers(F, m, thresh):
         return usable & (d2 <= thresh * thresh)
 
 
-def hypotheses(m, seed, hs):
-    """(F [len(hs),9], valid [len(hs)]) of the hypotheses hs of matches m [n,4]."""
+def hypotheses(m, seed, hs, pivots=None):
+    """(F [len(hs),9], valid [len(hs)]) of the hypotheses hs of matches m [n,4].  pivots: a list that receives (sampled
+    [len(hs)] = the hypothesis reached the elimination, pivot magnitudes [8, len(hs)])."""
     n = m.shape[0]
     B = len(hs)
     q = np.zeros((B, 8, 4))
@@ -168,15 +177,34 @@ def hypotheses(m, seed, hs):
         s1, s2 = 8.0 / sp, 8.0 / sq
         ax, ay = (q[:, :, 0] - c[:, None, 0]) * s1[:, None], (q[:, :, 1] - c[:, None, 1]) * s1[:, None]
         bx, by = (q[:, :, 2] - c[:, None, 2]) * s2[:, None], (q[:, :, 3] - c[:, None, 3]) * s2[:, None]
-        fn, ok = null_vector(rows_of(ax, ay, bx, by))
+        piv = [] if pivots is not None else None
+        fn, ok = null_vector(rows_of(ax, ay, bx, by), pivots=piv)
+        if pivots is not None:
+            pivots.append((valid.copy(), np.stack(piv)))
         F = denorm(fn, (s1, c[:, 0], c[:, 1]), (s2, c[:, 2], c[:, 3]))
     valid &= ok & np.all(np.isfinite(F), axis=1)
     return F, valid
 
 
-def _total(v, pairwise):
-    """Sum over axis 0: ascending (one accumulator) or pairwise (halves folded onto each other)."""
+def block_sum(terms, index, threads=BLOCK_THREADS):
+    """The sum of terms [k, ...] as block_sum<threads> (csrc/geom_blocks.hip.h) forms it in epi_finish_kernel: term i goes to
+    thread index[i] mod threads; each thread adds its terms in index order from 0.0; the 64 partials of each wave meet in the
+    xor butterfly of wave_sum (offsets 32 .. 1); the wave partials are added in wave order.  index: the match rows of the
+    terms (not their positions among the inliers), ascending."""
+    part = ER.strided_partials(terms, index, threads)
+    total = ER.butterfly(part[:64])
+    for w in range(1, threads // 64):
+        total = total + ER.butterfly(part[64 * w:64 * (w + 1)])
+    return total
+
+
+def _total(v, pairwise, index=None):
+    """Sum over axis 0: ascending (one accumulator), pairwise (halves folded onto each other) or, with pairwise = "block",
+    in the kernel's order (block_sum over the match rows `index`)."""
     v = np.asarray(v, dtype=np.float64)
+    if isinstance(pairwise, str):
+        assert pairwise == "block" and index is not None
+        return block_sum(v, index)
     if not pairwise:
         acc = np.zeros(v.shape[1:])
         for k in range(v.shape[0]):
@@ -193,12 +221,12 @@ def _total(v, pairwise):
     return w[0]
 
 
-def norm_of(pts, pairwise=False):
+def norm_of(pts, pairwise=False, index=None):
     """EvalNorm of a point set [k,2]: (s, cx, cy), s = k / sum(|x - cx| + |y - cy|)."""
-    k = float(pts.shape[0])
+    k = float(_total(np.ones(pts.shape[0]), pairwise, index))      # the kernel's count is a sum too (exact in every order)
     with np.errstate(all="ignore"):
-        cx, cy = _total(pts[:, 0], pairwise) / k, _total(pts[:, 1], pairwise) / k
-        sa = _total(np.abs(pts[:, 0] - cx) + np.abs(pts[:, 1] - cy), pairwise)
+        cx, cy = _total(pts[:, 0], pairwise, index) / k, _total(pts[:, 1], pairwise, index) / k
+        sa = _total(np.abs(pts[:, 0] - cx) + np.abs(pts[:, 1] - cy), pairwise, index)
         return k / sa, cx, cy
 
 
@@ -261,10 +289,25 @@ def _argmax_abs(v):
     return k
 
 
-def refit(F, mi, pairwise=False):
-    """The final F [9] from the winner's F [9] and its inliers mi [k,4] (None: no usable norm), and err."""
+def sign_rule(Fd):
+    """The output's sign: the largest |entry| (the lowest index on ties) is positive."""
+    return -Fd if Fd[_argmax_abs(Fd)] < 0.0 else Fd
+
+
+def _gap(v):
+    """Relative gap between the two largest |entries| of v: what the argmax hangs on."""
+    a = np.sort(np.abs(np.asarray(v, dtype=np.float64)))
+    return float((a[-1] - a[-2]) / a[-1]) if a[-1] > 0.0 else 0.0
+
+
+def refit(F, mi, pairwise=False, index=None, report=None):
+    """The final F [9] from the winner's F [9] and its inliers mi [k,4] (None: no usable norm), and err.  pairwise: False
+    (ascending sums), True (pairwise) or "block" (the kernel's order; index = the match rows of mi).  report: a dict that
+    receives norm_usable, gap_G, gap_Fd (see _gap), solved (the 8x8 system was accepted) and pivots [8]."""
     with np.errstate(all="ignore"):
-        t1, t2 = norm_of(mi[:, :2], pairwise), norm_of(mi[:, 2:], pairwise)
+        t1, t2 = norm_of(mi[:, :2], pairwise, index), norm_of(mi[:, 2:], pairwise, index)
+        if report is not None:
+            report["norm_usable"] = all(np.isfinite(t[0]) and t[0] > 0.0 for t in (t1, t2))
         if not all(np.isfinite(t[0]) and t[0] > 0.0 for t in (t1, t2)):
             t1 = t2 = (1.0, 0.0, 0.0)
         G = carry(F, t1, t2)
@@ -274,14 +317,17 @@ def refit(F, mi, pairwise=False):
         Mom = np.zeros((9, 9))
         for j in range(9):
             for k in range(j, 9):
-                Mom[j, k] = Mom[k, j] = _total(A[:, j] * A[:, k], pairwise)
+                Mom[j, k] = Mom[k, j] = _total(A[:, j] * A[:, k], pairwise, index)
         idx = [j for j in range(9) if j != ks]
         a = np.zeros((8, 9))
         for r in range(8):
             for c in range(8):
                 a[r, c] = Mom[idx[r], idx[c]]
             a[r, 8] = -Mom[idx[r], ks]
-        g, ok = ER.solve8(a[None])
+        piv = []
+        g, ok = ER.solve8(a[None], pivots=piv)
+        if report is not None:
+            report.update(gap_G=_gap(G), solved=bool(ok[0] and np.all(np.isfinite(g[0]))), pivots=np.array([v[0] for v in piv]))
         fn = G
         if ok[0] and np.all(np.isfinite(g[0])):
             fn = np.zeros(9)
@@ -297,10 +343,11 @@ def refit(F, mi, pairwise=False):
         if not (np.isfinite(nrm) and nrm > 0.0):
             return None, 0.0
         Fd = Fd / nrm
-        if Fd[_argmax_abs(Fd)] < 0.0:
-            Fd = -Fd
+        if report is not None:
+            report["gap_Fd"] = _gap(Fd)
+        Fd = sign_rule(Fd)
         d2, usable = sampson2(Fd[None], mi)
-        err = np.sqrt(_total(np.where(usable[0], d2[0], 0.0), pairwise) / float(mi.shape[0]))
+        err = np.sqrt(_total(np.where(usable[0], d2[0], 0.0), pairwise, index) / float(mi.shape[0]))
     return Fd, float(err)
 
 
@@ -310,7 +357,7 @@ def winner_of(m, seed, thresh=1.0):
     best, best_sc, best_F = -1, -1, None
     if n < 8:
         return best, best_sc, best_F
-    total = 1 if n == 8 else HYPOTHESES
+    total = 1 if n == DIRECT_N else HYPOTHESES
     for h0 in range(0, total, 250):
         hs = list(range(h0, min(h0 + 250, total)))
         F, valid = hypotheses(m, seed, hs)
@@ -321,10 +368,10 @@ def winner_of(m, seed, thresh=1.0):
     return best, best_sc, best_F
 
 
-def ransac(m, seed, thresh=1.0, pairwise=False, winner=None):
+def ransac(m, seed, thresh=1.0, pairwise=False, winner=None, report=None):
     """m: [n,4] float64 matches (ax, ay, bx, by).  Returns dict(F [3,3], mask [n] bool, n_inliers, status 0 / 1, winner,
-    err, F_winner [3,3] = the unrefitted winner).  pairwise: the summation order of the refit; winner: a winner_of() result
-    to reuse."""
+    err, F_winner [3,3] = the unrefitted winner).  pairwise: the summation order of the refit (False: ascending, True:
+    pairwise, "block": the kernel's); winner: a winner_of() result to reuse; report: see refit()."""
     m = np.asarray(m, dtype=np.float64).reshape(-1, 4)
     n = m.shape[0]
     out = {"F": np.zeros((3, 3)), "mask": np.zeros(n, dtype=bool), "n_inliers": 0, "status": 1, "winner": -1, "err": 0.0,
@@ -333,11 +380,73 @@ def ransac(m, seed, thresh=1.0, pairwise=False, winner=None):
     if best < 0 or best_sc < MIN_SCORE:
         return out
     mask = inliers(best_F[None], m, thresh)[0]
-    Fd, err = refit(best_F, m[mask], pairwise)
+    Fd, err = refit(best_F, m[mask], pairwise, np.nonzero(mask)[0], report)
     if Fd is None:
         return out
     out.update(F=Fd.reshape(3, 3), mask=mask, n_inliers=int(mask.sum()), status=0, winner=best, err=err,
                F_winner=best_F.reshape(3, 3))
+    return out
+
+
+def decisions(m, seed, thresh=1.0):
+    """How far the problem is from every comparison going the other way.  Returns dict(
+      score [H], ambiguous [H]: per hypothesis, the inliers and the matches with |d2 - t2| <= WINDOW * t2 (0 where invalid),
+      valid [H],
+      pivot_least_accepted: the least pivot magnitude of any hypothesis whose eight pivots are all accepted (inf: none),
+      pivot_largest_refused: over the refused hypotheses, the largest of their smallest pivots, the one that holds the
+          refusal (0: none; a NaN pivot is refused in every order and is not counted),
+      pivot_log_margin: the least |log10(pivot / PIVOT_EPS)| of those two,
+      winner, best (its score), winner_F [9],
+      decided: the winner has no ambiguous match, every lower hypothesis has score + ambiguous < best and every higher one
+          score + ambiguous <= best (without a valid hypothesis: True, the refusals are judged by the pivots),
+      slack: how many more matches the nearest rival would need: min(best - 1 - max(score + ambiguous) below the winner,
+          best - max(score + ambiguous) above it); >= 0 when decided, None without a rival).
+    The refit's margins (argmax and sign gaps, its own pivots) come from ransac(..., report=)."""
+    m = np.asarray(m, dtype=np.float64).reshape(-1, 4)
+    n = m.shape[0]
+    total = 0 if n < 8 else (1 if n == DIRECT_N else HYPOTHESES)
+    score, amb, valid = (np.zeros(total, dtype=np.int64) for _ in range(3))
+    valid = valid.astype(bool)
+    Fs = np.zeros((total, 9))
+    t2 = thresh * thresh
+    least_ok, largest_bad, log_margin = np.inf, 0.0, np.inf
+    for h0 in range(0, total, 250):
+        hs = list(range(h0, min(h0 + 250, total)))
+        piv = []
+        F, v = hypotheses(m, seed, hs, pivots=piv)
+        sampled, pv = piv[0]
+        with np.errstate(all="ignore"):
+            low = np.min(np.where(np.isnan(pv), np.inf, pv), axis=0)     # [B] the smallest pivot of each hypothesis
+            accepted = sampled & np.all(pv > PIVOT_EPS, axis=0)
+            acc, ref = low[accepted], low[sampled & ~accepted & (low <= PIVOT_EPS)]
+            if acc.size:
+                least_ok = min(least_ok, float(acc.min()))
+            if ref.size:
+                largest_bad = max(largest_bad, float(ref.max()))
+            d2, usable = sampson2(F, m)
+            inl = usable & (d2 <= t2)
+            near = usable & (np.abs(d2 - t2) <= WINDOW * t2)
+        sl = slice(h0, h0 + len(hs))
+        valid[sl], Fs[sl] = v, F
+        score[sl], amb[sl] = np.where(v, inl.sum(axis=1), 0), np.where(v, near.sum(axis=1), 0)
+    with np.errstate(all="ignore"):
+        if np.isfinite(least_ok):
+            log_margin = min(log_margin, abs(np.log10(least_ok / PIVOT_EPS)))
+        if largest_bad > 0.0:
+            log_margin = min(log_margin, abs(np.log10(largest_bad / PIVOT_EPS)))
+    out = {"score": score, "ambiguous": amb, "valid": valid, "pivot_log_margin": float(log_margin),
+           "pivot_least_accepted": least_ok, "pivot_largest_refused": largest_bad, "winner": -1, "best": -1, "winner_F": None,
+           "decided": True, "slack": None}
+    if not valid.any():
+        return out
+    sv = np.where(valid, score, -1)
+    w = int(np.argmax(sv))                                               # the first maximum: the lowest hypothesis
+    best = int(sv[w])
+    reach = np.where(valid, score + amb, -1)
+    lower, higher = reach[:w], reach[w + 1:]
+    decided = amb[w] == 0 and (lower.size == 0 or lower.max() < best) and (higher.size == 0 or higher.max() <= best)
+    gaps = ([best - 1 - int(lower.max())] if lower.size else []) + ([best - int(higher.max())] if higher.size else [])
+    out.update(winner=w, best=best, winner_F=Fs[w], decided=bool(decided), slack=min(gaps) if gaps else None)
     return out
 
 
@@ -447,8 +556,9 @@ CASES = {
     "planar": (4, 48, 0, 0.0, True, 104),
 }
 NOISE_FREE = ("mixed48", "eight", "n257", "n4096")
-# The fixtures whose F and err are compared: a planar scene does not determine F (its refit is ill-conditioned by
-# construction: the two summation orders differ by 1e-8 there), so only its status, mask, count and winner are.
+# The fixtures whose F and err are compared.  The planar scene has none: each of its 2000 systems has rank 6 and is refused
+# by the pivot rule (largest smallest-pivot 5.2e-16 against PIVOT_EPS = 1e-12), so its answer is status 1, winner -1, an
+# empty mask (decisions() reports the margin; tests/test_epipolar_exact_cpu.py asserts it).
 F_COMPARED = ("mixed48", "eight", "n257", "n4096", "noisy")
 # The largest difference of F and err between the ascending and the pairwise refit over F_COMPARED, as
 # order_difference(F_COMPARED) returned it when the fixtures were fixed (the err of "eight"), and the tolerance of the device

@@ -46,8 +46,9 @@ def _collinear(a, b, c):
     return abs(dx2 * dy1 - dy2 * dx1) <= FLT_EPS * (((abs(dx1) + abs(dy1)) + abs(dx2)) + abs(dy2))
 
 
-def solve8(a):
-    """Batched [B,8,9] elimination in the kernel's order (eval_solve8).  Returns (h [B,8], ok [B])."""
+def solve8(a, pivots=None):
+    """Batched [B,8,9] elimination in the kernel's order (eval_solve8).  Returns (h [B,8], ok [B]).  pivots: a list that
+    receives the pivot magnitudes [B] of every step."""
     a = np.array(a, dtype=np.float64)
     B = a.shape[0]
     ok = np.ones(B, dtype=bool)
@@ -59,6 +60,8 @@ def solve8(a):
                 a[sw, k, k:] = a[sw, r, k:]
                 a[sw, r, k:] = t
             ok &= np.abs(a[:, k, k]) > 1e-12
+            if pivots is not None:
+                pivots.append(np.abs(a[:, k, k]))
             inv = 1.0 / a[:, k, k]
             for r in range(k + 1, 8):
                 f = a[:, r, k] * inv
@@ -149,20 +152,32 @@ def hypotheses(m, seed, hs):
     return H, valid
 
 
-def lane_sum(terms, index):
-    """The sum of terms [k, ...] as wave 0 forms it: lane l adds its terms (those whose match index is l mod 64) in
-    index order from 0.0, then the 64 partials meet in the xor butterfly of wave_sum (offsets 32, 16, .., 1)."""
+def strided_partials(terms, index, threads):
+    """Partial sums [threads, ...] of terms [k, ...]: thread t adds the terms whose index is t mod threads, in index order
+    (index ascending) from 0.0."""
     terms = np.asarray(terms, dtype=np.float64)
-    part = np.zeros((64,) + terms.shape[1:])
-    for lane in range(64):
-        t = terms[index % 64 == lane]
-        if t.shape[0]:
-            part[lane] = np.add.accumulate(t, axis=0)[-1]
+    index = np.asarray(index, dtype=np.int64)
+    part = np.zeros((threads,) + terms.shape[1:])
+    rnd = index // threads
+    for r in np.unique(rnd):
+        sel = rnd == r                      # one term per thread at most: the indexed addition adds each once
+        part[index[sel] % threads] = part[index[sel] % threads] + terms[sel]
+    return part
+
+
+def butterfly(part):
+    """wave_sum over axis 0 (64 lanes): the xor butterfly with offsets 32, 16, .., 1; every lane ends with the same value."""
     o = 32
     while o >= 1:
         part = part + part[np.arange(64) ^ o]
         o >>= 1
     return part[0]
+
+
+def lane_sum(terms, index):
+    """The sum of terms [k, ...] as wave 0 forms it: lane l adds its terms (those whose match index is l mod 64) in
+    index order from 0.0, then the 64 partials meet in the xor butterfly of wave_sum (offsets 32, 16, .., 1)."""
+    return butterfly(strided_partials(terms, index, 64))
 
 
 def _norm_of(pts, index=None):

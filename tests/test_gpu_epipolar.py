@@ -5,8 +5,10 @@ ssp_op_filter_matches against torch boolean indexing, and the geometric check of
 Tolerance of F and err (E.TOLERANCE = 2.94e-11): measured, not chosen.  The restatement's refit was evaluated with two
 summation orders (ascending and pairwise) on the compared fixtures below; the largest difference of any entry of F or of err
 was 1.837e-12 (the err of the 8-match fixture) and the tolerance is 16 times that.  tests/test_epipolar_cpu.py repeats the
-measurement.  mask, n_inliers, status and winner are compared for equality.  The planar fixture does not determine F (the two
-orders differ by 1e-8 there), so its F and err are not compared."""
+measurement.  mask, n_inliers, status and winner are compared for equality.  The planar fixture has no F to compare: every one
+of its 2000 systems has rank 6 and is refused by the pivot rule (largest smallest-pivot 5.2e-16 against 1e-12), so the answer
+is status 1 (tests/test_epipolar_exact_cpu.py prints the margin).  tests/test_gpu_epipolar_exact.py holds the same kernels
+to the restatement in their own summation order, where F and err agree to the last bit."""
 import functools
 
 import numpy as np
