@@ -634,6 +634,49 @@ int ssp_pose_chain(const uint8_t* front_prev_dev, const double* depth_prev_dev, 
                    const float* match_dev, const int32_t* n_match_dev, int cap, int n_seq, double* state_dev, double* table_dev,
                    int capacity, void* stream);
 
+/* ---- homography pose and model selection ---------------------------------------------------------
+ * The camera motion of a calibrated pair from ssp_eval_ransac's H (view 1 pixels to view 2 pixels), mask, n_inlier and status,
+ * for the pairs a fundamental matrix does not describe: a plane N . X1 = d seen twice (K2^-1 H K1 ~ R + (t/d) N^T) and a camera
+ * that only rotates.  Camera model as above.  fp64 without contraction; restated in numpy by tests/pose_h_ref.py.  No call
+ * synchronises with the host or allocates.
+ * ssp_pose_from_homography: pts / match / n_match / pt_stride / cap / pair_stride / intr_dev / n_intr and the outputs r_dev ..
+ *   x_dev as for ssp_pose_from_fundamental (there is no e_dev).  prior_dev: fp64 [n_pairs][2][3] or NULL, the normals2 of the
+ *   pair before (a zero vector is no prior); not the array normals2_dev.  use_h_dev: int32 [n_pairs] or NULL; when given, a pair
+ *   whose entry is 0 keeps all its outputs as they are, except model 0 and zero normals.  Valid: status_in == 0 and n_inlier >= 8,
+ *   else status 1 with the outputs of ssp_pose_from_fundamental's "no pose" and model 0.  Hn = K2^-1 H K1, negated when fewer
+ *   than half of n_inlier mask rows have b~^T Hn a~ > 0.  8 sweeps of cyclic Jacobi on Hn^T Hn, eigenvalues w1 >= w2 >= w3 (the
+ *   lowest index on ties) with v1, v2, v3, v3 flipped so that det V = +1; Hn / sqrt(w2), w1 / w2, w3 / w2 (a negative w3 counts
+ *   as 0); a non-finite value or w2 <= 0 gives status 1.  sqrt(w1) - sqrt(w3) <= rotation_eps: model 2, R = Hn made orthonormal
+ *   (row 0 normalised, row 1 made orthogonal to it and normalised, row 2 their cross product), t = 0, per-row outputs and counts
+ *   0, cand -1, status 0, normal 0, normals2 = R prior (the priors travel with the camera).  Otherwise model 1: u_a, u_b =
+ *   (sqrt(1 - w3) v1 +- sqrt(w1 - 1) v3) / sqrt(w1 - w3); per u: U = [v2, u, v2 x u], W = [Hn v2, Hn u, Hn v2 x Hn u], R = W U^T,
+ *   N = v2 x u, T = (Hn - R) N; candidates 0..3 = (R_a, N_a, T_a), (R_a, -N_a, -T_a), (R_b, N_b, T_b), (R_b, -N_b, -T_b).  A mask
+ *   row counts for a candidate when N . a~ > 0 and it is in front under (R, T / |T|) by ssp_pose_from_fundamental's rule.  A
+ *   candidate is alive with count >= 8 and 2 count >= n_inlier.  None alive: the highest count wins (ties to the lowest index),
+ *   status 2.  One alive: it wins, status 0.  More: each is scored by max_k (N . prior_k) over the non-zero priors; the best wins
+ *   with status 0 when it leads the next by at least normal_margin; without a prior or with a smaller lead the largest N_z wins
+ *   (ties to the lowest index), status 2.  t = T / |T|; model_dev [n_pairs] (0 = none, 1 = plane, 2 = rotation), normal_dev
+ *   [n_pairs][3] = the winner's N, normals2_dev [n_pairs][2][3] = R_c N_c of the candidates alive in index order (two at most),
+ *   zeros behind them.  Per-row outputs under the winner (front also needs N . a~ > 0).
+ * ssp_model_select: F / H with the mask, n_inlier and status of ssp_epi_ransac / ssp_eval_ransac; the unfiltered matches and the
+ *   points as above.  S_H = sum over the match rows of rho(d12^2; 5.99) + rho(d21^2; 5.99), the squared transfer distances under
+ *   H and under its inverse (by cofactors; a zero or non-finite determinant gives S_H = 0); S_F the same with the squared
+ *   distances to the epipolar lines in both images and 3.84; rho(d2; T) = 5.99 - d2 when d2 < T, else 0; sums in a fixed order.
+ *   use_h = status_H == 0 and (status_F != 0 or S_H >= model_ratio (S_H + S_F)).  scores_dev [n_pairs][2] = (S_H, S_F), use_h_dev
+ *   [n_pairs]; mask_dev [n_pairs][cap], n_inlier_dev, status_dev [n_pairs]: the selected model's, copied (arrays of their own). */
+int ssp_pose_from_homography(const double* h_dev, const uint8_t* mask_dev, const int32_t* n_inlier_dev, const int32_t* status_in_dev,
+                             const double* pts1_dev, const double* pts2_dev, int pt_stride, int cap, int n_pairs, int pair_stride,
+                             const float* match_dev, const int32_t* n_match_dev, const double* intr_dev, int n_intr,
+                             const double* prior_dev, const int32_t* use_h_dev, double rotation_eps, double normal_margin, double* r_dev,
+                             double* t_dev, int32_t* cand_dev, int32_t* counts_dev, int32_t* n_front_dev, int32_t* status_dev,
+                             uint8_t* front_dev, double* depth_dev, double* x_dev, int32_t* model_dev, double* normal_dev,
+                             double* normals2_dev, void* stream);
+int ssp_model_select(const double* f_dev, const uint8_t* f_mask_dev, const int32_t* f_n_inlier_dev, const int32_t* f_status_dev,
+                     const double* h_dev, const uint8_t* h_mask_dev, const int32_t* h_n_inlier_dev, const int32_t* h_status_dev,
+                     const double* pts1_dev, const double* pts2_dev, int pt_stride, int cap, int n_pairs, int pair_stride,
+                     const float* match_dev, const int32_t* n_match_dev, double model_ratio, double* scores_dev, int32_t* use_h_dev,
+                     uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev, void* stream);
+
 /* ---- landmarks from tracks ---------------------------------------------------------------------
  * One point in the world frame per track row: the row's observations in the L retained frames (the track table and the ring
  * of point sets of ssp_op_track_update / ssp_op_track_points) under the cameras of the trajectory (ssp_pose_chain).  World =

@@ -37,6 +37,7 @@
 #include "eval_kernels.hip.h"
 #include "epipolar_kernels.hip.h"
 #include "pose_kernels.hip.h"
+#include "pose_h_kernels.hip.h"
 #include "landmark_kernels.hip.h"
 #include "pnp_kernels.hip.h"
 #include "ba_kernels.hip.h"
@@ -3788,6 +3789,51 @@ int ssp_pose_chain(const uint8_t* front_prev_dev, const double* depth_prev_dev, 
   hipLaunchKernelGGL(pose_chain_kernel, dim3(n_seq), dim3(POSE_THREADS), lds, (hipStream_t)stream, front_prev_dev, depth_prev_dev,
                      status_prev_dev, match_prev_dev, n_match_prev_dev, cap_prev, front_dev, depth_dev, status_dev, r_dev, t_dev,
                      match_dev, n_match_dev, cap, state_dev, table_dev, capacity);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- homography pose and model selection ----
+int ssp_pose_from_homography(const double* h_dev, const uint8_t* mask_dev, const int32_t* n_inlier_dev, const int32_t* status_in_dev,
+                             const double* pts1_dev, const double* pts2_dev, int pt_stride, int cap, int n_pairs, int pair_stride,
+                             const float* match_dev, const int32_t* n_match_dev, const double* intr_dev, int n_intr,
+                             const double* prior_dev, const int32_t* use_h_dev, double rotation_eps, double normal_margin, double* r_dev,
+                             double* t_dev, int32_t* cand_dev, int32_t* counts_dev, int32_t* n_front_dev, int32_t* status_dev,
+                             uint8_t* front_dev, double* depth_dev, double* x_dev, int32_t* model_dev, double* normal_dev,
+                             double* normals2_dev, void* stream) {
+  CHK(epi_check("pose_from_homography", cap, n_pairs, pair_stride, pt_stride));
+  if (!h_dev || !mask_dev || !n_inlier_dev || !status_in_dev || !pts1_dev || !pts2_dev || !match_dev || !n_match_dev || !intr_dev ||
+      !r_dev || !t_dev || !cand_dev || !counts_dev || !n_front_dev || !status_dev || !front_dev || !depth_dev || !x_dev || !model_dev ||
+      !normal_dev || !normals2_dev)
+    return fail(-1, "pose_from_homography: null pointer");
+  if (n_intr != 1 && n_intr != n_pairs)
+    return fail(-1, "pose_from_homography: n_intr must be 1 or n_pairs (got %d for %d pairs)", n_intr, n_pairs);
+  if (!(rotation_eps >= 0.0) || !std::isfinite(rotation_eps) || !(normal_margin >= 0.0) || !std::isfinite(normal_margin))
+    return fail(-1, "pose_from_homography: finite rotation_eps >= 0 and normal_margin >= 0 required");
+  if (prior_dev == normals2_dev) return fail(-1, "pose_from_homography: the priors are not updated in place (pass a second array)");
+  hipLaunchKernelGGL(pose_h_kernel, dim3(n_pairs), dim3(POSE_THREADS), 0, (hipStream_t)stream, h_dev, mask_dev, n_inlier_dev,
+                     status_in_dev, pts1_dev, pts2_dev, pt_stride, cap, pair_stride, match_dev, n_match_dev, intr_dev, n_intr, prior_dev,
+                     use_h_dev, rotation_eps, normal_margin, r_dev, t_dev, cand_dev, counts_dev, n_front_dev, status_dev, front_dev,
+                     depth_dev, x_dev, model_dev, normal_dev, normals2_dev);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ssp_model_select(const double* f_dev, const uint8_t* f_mask_dev, const int32_t* f_n_inlier_dev, const int32_t* f_status_dev,
+                     const double* h_dev, const uint8_t* h_mask_dev, const int32_t* h_n_inlier_dev, const int32_t* h_status_dev,
+                     const double* pts1_dev, const double* pts2_dev, int pt_stride, int cap, int n_pairs, int pair_stride,
+                     const float* match_dev, const int32_t* n_match_dev, double model_ratio, double* scores_dev, int32_t* use_h_dev,
+                     uint8_t* mask_dev, int32_t* n_inlier_dev, int32_t* status_dev, void* stream) {
+  CHK(epi_check("model_select", cap, n_pairs, pair_stride, pt_stride));
+  if (!f_dev || !f_mask_dev || !f_n_inlier_dev || !f_status_dev || !h_dev || !h_mask_dev || !h_n_inlier_dev || !h_status_dev ||
+      !pts1_dev || !pts2_dev || !match_dev || !n_match_dev || !scores_dev || !use_h_dev || !mask_dev || !n_inlier_dev || !status_dev)
+    return fail(-1, "model_select: null pointer");
+  if (!(model_ratio >= 0.0) || !(model_ratio <= 1.0)) return fail(-1, "model_select: 0 <= model_ratio <= 1 required");
+  if (mask_dev == f_mask_dev || mask_dev == h_mask_dev)
+    return fail(-1, "model_select: the selected mask is a copy (pass an array of its own)");
+  hipLaunchKernelGGL(model_select_kernel, dim3(n_pairs), dim3(POSE_THREADS), 0, (hipStream_t)stream, f_dev, f_mask_dev, f_n_inlier_dev,
+                     f_status_dev, h_dev, h_mask_dev, h_n_inlier_dev, h_status_dev, pts1_dev, pts2_dev, pt_stride, cap, pair_stride,
+                     match_dev, n_match_dev, model_ratio, scores_dev, use_h_dev, mask_dev, n_inlier_dev, status_dev);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -197,6 +197,8 @@ def _signatures():
         "ssp_op_filter_matches": ([vp] * 5 + [i, i, i, vp, vp, vp], i),
         "ssp_pose_from_fundamental": ([vp] * 6 + [i, i, i, i, vp, vp, vp, i] + [vp] * 11, i),
         "ssp_pose_chain": ([vp] * 5 + [i] + [vp] * 7 + [i, i, vp, vp, i, vp], i),
+        "ssp_pose_from_homography": ([vp] * 6 + [i] * 4 + [vp, vp, vp, i, vp, vp, d, d] + [vp] * 13, i),
+        "ssp_model_select": ([vp] * 10 + [i] * 4 + [vp, vp, d] + [vp] * 6, i),
         "ssp_landmark_workspace_bytes": ([i, i], sz),
         "ssp_map_window": ([vp, vp, i, vp, i, i, i, vp, vp], i),
         "ssp_op_triangulate_tracks": ([vp, vp, vp, i, vp, i, i, i, i, d, d] + [vp] * 6, i),
@@ -1968,6 +1970,127 @@ def op_pose_chain(prev, cur, match_prev, match_cur, n_match_prev, n_match_cur, s
                                   _ptr(cur["status"]), _ptr(cur["R"]), _ptr(cur["t"]), _ptr(match_cur), _ptr(n_match_cur), cap, S,
                                   _ptr(state), _ptr(table), int(table.shape[-2]), _stream()))
     return state, table
+
+
+# ---- homography pose and model selection ----
+HOMOGRAPHY_POSE_KEYS = ("R", "t", "cand", "counts", "n_front", "status", "front", "depth", "X", "model", "normal", "normals2")
+
+
+def _pair_inputs(pts1, pts2, match, n_match, pair_stride):
+    """The checks the pair operators share; returns (P, cap)."""
+    for t, nm in ((pts1, "pts1"), (pts2, "pts2"), (match, "match"), (n_match, "n_match")):
+        _need_gpu(t, nm)
+    if match.dtype != torch.float32 or match.dim() != 3 or match.shape[2] != 3 or not match.is_contiguous():
+        raise ValueError("match must be contiguous float32 [P, cap, 3]")
+    P, cap = match.shape[0], match.shape[1]
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
+    if pts1.dim() != 3 or pts1.shape[2] < 2 or pts2.dim() != 3 or pts2.shape[2] != pts1.shape[2]:
+        raise ValueError("pts1 and pts2 must be float64 [., cap, pt_stride >= 2] with one pt_stride")
+    for t, nm in ((pts1, "pts1"), (pts2, "pts2")):
+        if t.dtype != torch.float64 or t.shape[1] != cap or t.shape[0] < (P - 1) * pair_stride + 1 or not t.is_contiguous():
+            raise ValueError("%s must be contiguous float64 [P*pair_stride, %d, pt_stride]" % (nm, cap))
+    if n_match.dtype != torch.int32 or n_match.numel() != P:
+        raise ValueError("n_match must be int32 [%d]" % P)
+    return P, cap
+
+
+def _model_inputs(geometry, key, what, P, cap):
+    """(matrix, mask, n_inliers, status) of a RANSAC dict, checked."""
+    for k in (key, "mask", "n_inliers", "status"):
+        if k not in geometry:
+            raise ValueError("%s must be the dict of a RANSAC operator (no %r)" % (what, k))
+        _need_gpu(geometry[k], "%s[%r]" % (what, k))
+    M, mask, n_inl, status = (geometry[k] for k in (key, "mask", "n_inliers", "status"))
+    if M.dtype != torch.float64 or M.numel() != P * 9 or not M.is_contiguous():
+        raise ValueError("%s[%r] must be contiguous float64 [%d, 3, 3]" % (what, key, P))
+    if mask.dtype != torch.uint8 or mask.numel() != P * cap or not mask.is_contiguous():
+        raise ValueError("%s['mask'] must be contiguous uint8 [%d, %d]" % (what, P, cap))
+    for t, nm in ((n_inl, "n_inliers"), (status, "status")):
+        if t.dtype != torch.int32 or t.numel() != P:
+            raise ValueError("%s[%r] must be int32 [%d]" % (what, nm, P))
+    return M, mask, n_inl, status
+
+
+def op_homography_pose(geometry_h, pts1, pts2, match, n_match, intrinsics, prior=None, rotation_eps=0.02, normal_margin=0.01,
+                       pair_stride=1, use_h=None, out=None):
+    """The camera motion of P calibrated pairs from their homography (ssp_pose_from_homography): a plane
+    seen twice or a camera that only rotates, the pairs a fundamental matrix does not describe.  geometry_h: the dict of
+    op_eval_ransac ("H", "mask", "n_inliers", "status"); pts1, pts2, match, n_match, intrinsics, pair_stride as for
+    op_two_view_pose (any pt_stride >= 2).  prior: float64 [P, 2, 3], the "normals2" of the pair before, or None.  rotation_eps:
+    the spread sqrt(w1) - sqrt(w3) of the normalised homography up to which the pair is a rotation; normal_margin: the lead in
+    N . prior that decides between the two poses of a plane.  use_h: int32 [P] of op_model_select or None; pairs whose entry is 0
+    keep what `out` holds.  out: the dict of op_two_view_pose to write over (its "E" stays), or None for new tensors.  Returns
+    `out` (or a new dict) with op_two_view_pose's keys but "E", and "model": int32 [P] (0 none, 1 plane, 2 rotation), "normal":
+    float64 [P,3], "normals2": float64 [P,2,3] (the next pair's prior).  status 2 = the two poses of the plane could not be
+    told apart (the one whose normal points more along the optical axis is written).  No host synchronisation."""
+    lib = load_library()
+    P, cap = _pair_inputs(pts1, pts2, match, n_match, pair_stride)
+    H, mask, n_inl, status = _model_inputs(geometry_h, "H", "geometry_h", P, cap)
+    _need_gpu(intrinsics, "intrinsics")
+    if (intrinsics.dtype != torch.float64 or intrinsics.dim() != 3 or tuple(intrinsics.shape[1:]) != (2, 4)
+            or intrinsics.shape[0] not in (1, P) or not intrinsics.is_contiguous()):
+        raise ValueError("intrinsics must be contiguous float64 [1, 2, 4] or [%d, 2, 4] rows (fx, fy, cx, cy)" % P)
+    if prior is not None:
+        _need_gpu(prior, "prior")
+        if prior.dtype != torch.float64 or tuple(prior.shape) != (P, 2, 3) or not prior.is_contiguous():
+            raise ValueError("prior must be contiguous float64 [%d, 2, 3]" % P)
+    if use_h is not None:
+        _need_gpu(use_h, "use_h")
+        if use_h.dtype != torch.int32 or use_h.numel() != P:
+            raise ValueError("use_h must be int32 [%d]" % P)
+    if not (rotation_eps >= 0.0 and normal_margin >= 0.0):
+        raise ValueError("rotation_eps and normal_margin must be non-negative")
+    dev = match.device
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    if out is None:
+        if use_h is not None:
+            raise ValueError("use_h needs out: the pairs that keep the fundamental matrix keep its pose")
+        o = {"R": torch.empty(P, 3, 3, **f64), "t": torch.empty(P, 3, **f64), "cand": torch.empty(P, **i32),
+             "counts": torch.empty(P, 4, **i32), "n_front": torch.empty(P, **i32), "status": torch.empty(P, **i32),
+             "front": torch.empty(P, cap, dtype=torch.uint8, device=dev), "depth": torch.empty(P, cap, 2, **f64),
+             "X": torch.empty(P, cap, 3, **f64)}
+    else:
+        o = out
+        shapes = {"R": (P, 3, 3), "t": (P, 3), "cand": (P,), "counts": (P, 4), "n_front": (P,), "status": (P,), "front": (P, cap),
+                  "depth": (P, cap, 2), "X": (P, cap, 3)}
+        for k, shp in shapes.items():
+            if k not in o or tuple(o[k].shape) != shp or not o[k].is_contiguous():
+                raise ValueError("out[%r] must be the contiguous tensor of op_two_view_pose for these pairs" % k)
+            _need_gpu(o[k], "out[%r]" % k)
+    o["model"], o["normal"], o["normals2"] = torch.empty(P, **i32), torch.empty(P, 3, **f64), torch.empty(P, 2, 3, **f64)
+    with torch.cuda.device(dev):
+        _check(lib.ssp_pose_from_homography(_ptr(H), _ptr(mask), _ptr(n_inl), _ptr(status), _ptr(pts1), _ptr(pts2),
+                                            int(pts1.shape[2]), cap, P, int(pair_stride), _ptr(match), _ptr(n_match),
+                                            _ptr(intrinsics), int(intrinsics.shape[0]), _ptr(prior), _ptr(use_h), float(rotation_eps),
+                                            float(normal_margin), *[_ptr(o[k]) for k in HOMOGRAPHY_POSE_KEYS], _stream()))
+    return o
+
+
+def op_model_select(geometry_f, geometry_h, pts1, pts2, match, n_match, model_ratio=0.40, pair_stride=1):
+    """Whether P pairs obey their fundamental matrix or their homography (ssp_model_select).  geometry_f: the
+    dict of op_epipolar_ransac, geometry_h: the dict of op_eval_ransac; pts1, pts2, match, n_match, pair_stride: what those calls
+    were given (any pt_stride >= 2).  Each model is scored over the unfiltered matches by its truncated squared distances in both
+    images (5.99 - d^2 below the chi-square threshold of one pixel, 5.99 for the transfer and 3.84 for the epipolar line); the
+    homography is used when it has a model and the fundamental matrix has none or S_H >= model_ratio (S_H + S_F).  Returns device
+    tensors {"scores": float64 [P,2] = (S_H, S_F), "use_h": int32 [P], "mask": uint8 [P,cap], "n_inliers": int32 [P], "status":
+    int32 [P]}, the last three copied from the selected model.  No host synchronisation."""
+    lib = load_library()
+    P, cap = _pair_inputs(pts1, pts2, match, n_match, pair_stride)
+    F, f_mask, f_n, f_status = _model_inputs(geometry_f, "F", "geometry_f", P, cap)
+    H, h_mask, h_n, h_status = _model_inputs(geometry_h, "H", "geometry_h", P, cap)
+    if not 0.0 <= model_ratio <= 1.0:
+        raise ValueError("0 <= model_ratio <= 1 required")
+    dev = match.device
+    o = {"scores": torch.empty(P, 2, dtype=torch.float64, device=dev), "use_h": torch.empty(P, dtype=torch.int32, device=dev),
+         "mask": torch.empty(P, cap, dtype=torch.uint8, device=dev), "n_inliers": torch.empty(P, dtype=torch.int32, device=dev),
+         "status": torch.empty(P, dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev):
+        _check(lib.ssp_model_select(_ptr(F), _ptr(f_mask), _ptr(f_n), _ptr(f_status), _ptr(H), _ptr(h_mask), _ptr(h_n), _ptr(h_status),
+                                    _ptr(pts1), _ptr(pts2), int(pts1.shape[2]), cap, P, int(pair_stride), _ptr(match), _ptr(n_match),
+                                    float(model_ratio), _ptr(o["scores"]), _ptr(o["use_h"]), _ptr(o["mask"]), _ptr(o["n_inliers"]),
+                                    _ptr(o["status"]), _stream()))
+    return o
 
 
 # ---- landmarks from tracks (DESIGN.md section 26) ----

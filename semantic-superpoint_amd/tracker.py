@@ -23,10 +23,11 @@ def _check_one_camera(intrinsics, message):
 
 
 def _check_stage(option, source, intrinsics, geometric_check, landmark_params, *own):
-    """What every stage that works on the window's landmarks needs, in this order: intrinsics with the fundamental check, ONE
+    """What every stage that works on the window's landmarks needs, in this order: intrinsics with the fundamental or auto check
+    (the stages read the trajectory, the matches and front / depth, never F), ONE
     camera, the stage's own options (`own`: pairs of a test that returns True when refused, and its message), landmark_params."""
-    if intrinsics is None or geometric_check != "fundamental":
-        raise ValueError("%s needs intrinsics and geometric_check='fundamental': %s" % (option, source))
+    if intrinsics is None or geometric_check not in ("fundamental", "auto"):
+        raise ValueError("%s needs intrinsics and geometric_check='fundamental': %s" % (option, source))   # (or 'auto': section 36)
     _check_one_camera(intrinsics, "%s needs ONE camera: a fixed (previous, new) pair of different intrinsics cannot describe "
                                   "more than two views" % option)
     for refused, message in own:
@@ -73,8 +74,12 @@ class PointTracker(object):
     distance) and "homography" a homography (lib.op_eval_ransac with its own 3 px rule); only the inliers continue tracks and
     are reported by get_matches / get_mscores.  A frame with no model or fewer than min_inliers inliers keeps all its
     matches; that is decided on the device.  Frame f (0-based) uses seed check_seed + f.  last_geometry() is the newest
-    frame's result.
-    intrinsics (needs geometric_check="fundamental"): (fx, fy, cx, cy) of the camera, or a pair of such
+    frame's result.  "auto" (needs intrinsics) runs both with the frame's seed, decides per frame which model
+    the frame obeys (lib.op_model_select, model_ratio) and takes the pose from that model (lib.op_homography_pose with rotation_eps,
+    normal_margin and the previous frame's normals2 as the prior): planar scenes and a camera that only rotates get a pose and a
+    trajectory row.  last_geometry() gains "model" (0 fundamental, 1 plane, 2 rotation), "scores", "H", "h_mask", "h_n_inliers",
+    "h_status", "normal", "normals2"; "mask", "n_inliers", "status" are the selected model's, "F", "winner", "err" the F fit's.
+    intrinsics (needs geometric_check="fundamental" or "auto"): (fx, fy, cx, cy) of the camera, or a pair of such
     tuples (the camera of the previous frame, the camera of the new frame).  Every frame's fundamental matrix then gives the
     camera motion from the previous frame (lib.op_two_view_pose: last_geometry() gains its keys, "status" as "pose_status")
     and one row of the trajectory (lib.op_pose_chain), read with trajectory(); trajectory_rows sizes that table.  All of it is
@@ -119,9 +124,15 @@ class PointTracker(object):
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
                  absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1,
                  world_map=None, world_cap=65536, world_patience=30, world_thresh=2.0, world_min_inliers=6,
-                 loop_closure=None, loop_min_gap=32, loop_min_inliers=12, loop_cooldown=32, loop_iterations=10, loop_weight=1.0):
+                 loop_closure=None, loop_min_gap=32, loop_min_inliers=12, loop_cooldown=32, loop_iterations=10, loop_weight=1.0,
+                 model_ratio=0.40, rotation_eps=0.02, normal_margin=0.01):
         stage = (intrinsics, geometric_check, landmark_params)
-        _check_mode("geometric_check", geometric_check, "fundamental", "homography")
+        _check_mode("geometric_check", geometric_check, "fundamental", "homography", "auto")
+        if geometric_check == "auto":
+            if intrinsics is None:
+                raise ValueError("geometric_check='auto' needs intrinsics: it chooses between two poses, not two filters")
+            if not (0.0 <= model_ratio <= 1.0 and rotation_eps >= 0.0 and normal_margin >= 0.0):
+                raise ValueError("0 <= model_ratio <= 1 and non-negative rotation_eps and normal_margin required")
         _check_mode("world_map", world_map, "observe", "relocalise")
         if world_map is not None:
             _check_stage("world_map", "the landmarks come from the trajectory's cameras", *stage, (
@@ -152,8 +163,9 @@ class PointTracker(object):
                 lambda: not 1 <= int(bundle_iterations) <= L.BA_MAX_ITERATIONS or int(bundle_every) < 1,
                 "1 <= bundle_iterations <= %d and bundle_every >= 1 required" % L.BA_MAX_ITERATIONS))
         if intrinsics is not None:
-            if geometric_check != "fundamental":
-                raise ValueError("intrinsics need geometric_check='fundamental': the pose is read off its fundamental matrix")
+            if geometric_check not in ("fundamental", "auto"):
+                raise ValueError("intrinsics need geometric_check='fundamental' or 'auto': the pose is read off the fundamental "
+                                 "matrix (or, with 'auto', the homography where the frame obeys that)")
             k = np.asarray(intrinsics, dtype=np.float64)
             if k.shape == (4,):
                 k = np.stack([k, k])
@@ -197,6 +209,8 @@ class PointTracker(object):
         self._intr = None         # float64 [1, 2, 4] on the device
         self._traj_state = self._traj_table = None
         self._pose_prev = None    # (pose dict, unfiltered match [1, cap, 3], n_match) of the previous frame's pair
+        self.model_ratio, self.rotation_eps, self.normal_margin = float(model_ratio), float(rotation_eps), float(normal_margin)
+        self._normals_prev = None # float64 [1, 2, 3]: the previous frame's normals2 ("auto": the next frame's prior)
         self._lm = None           # lib.landmark_buffers of the table's row_cap (landmarks_device; allocated on first use)
         self.absolute_pose = absolute_pose
         self.absolute_thresh, self.absolute_min_inliers = float(absolute_thresh), int(absolute_min_inliers)
@@ -308,15 +322,18 @@ class PointTracker(object):
         slot, _ = self._slots()
         pslot = (slot - 1) % self.maxl
         p1, p2 = self._pts[pslot:pslot + 1], self._pts[slot:slot + 1]
-        if self.geometric_check == "fundamental":
+        gh = None
+        if self.geometric_check in ("fundamental", "auto"):
             g = L.op_epipolar_ransac(p1, p2, m[None], nm, self._seed, thresh=self.check_thresh)
-        else:
+        if self.geometric_check in ("homography", "auto"):
             pad = torch.zeros(2, self._cap, 1, dtype=torch.float64, device=self.device)
             p12 = torch.cat([torch.cat([p1, p2]), pad], dim=2)
-            g = L.op_eval_ransac(p12[0:1], p12[1:2], m[None], nm, self._seed)
+            gh = L.op_eval_ransac(p12[0:1], p12[1:2], m[None], nm, self._seed)
+            if self.geometric_check == "homography":
+                g, gh = gh, None
         seed, self._seed = self._seed, self._seed + 1
         if self.intrinsics is not None:
-            g = self._pose_device(g, p1, p2, m[None], nm)
+            g = self._pose_device(g, p1, p2, m[None], nm, gh)
         if self.absolute_pose is not None:
             g = self._absolute_device(g, m, nm, p2[0], seed)
         if self.world_map_mode is not None:
@@ -324,13 +341,22 @@ class PointTracker(object):
         self._geometry = g
         return L.op_filter_matches(m, nm, g["mask"], g["status"], g["n_inliers"], self.min_inliers)
 
-    def _pose_device(self, g, p1, p2, m, nm):
-        """The pose of the newest frame against the previous one and its trajectory row; returns g with the pose keys."""
+    def _pose_device(self, g, p1, p2, m, nm, gh=None):
+        """The pose of the newest frame against the previous one and its trajectory row; returns g with the pose keys.  gh: the
+        homography RANSAC of the frame ("auto"): the model is selected, a frame that obeys the homography gets its pose written
+        over the fundamental matrix's, and mask / n_inliers / status become the selected model's."""
         if self._intr is None:
             self._intr = torch.from_numpy(self.intrinsics[None].copy()).to(self.device)
             self._traj_state = L.pose_state(self.device)
             self._traj_table = L.pose_table(self.trajectory_rows, self.device)
         pose = L.op_two_view_pose(g, p1, p2, m, nm, self._intr)
+        if gh is not None:
+            sel = L.op_model_select(g, gh, p1, p2, m, nm, model_ratio=self.model_ratio)
+            L.op_homography_pose(gh, p1, p2, m, nm, self._intr, prior=self._normals_prev, rotation_eps=self.rotation_eps,
+                                 normal_margin=self.normal_margin, use_h=sel["use_h"], out=pose)
+            self._normals_prev = pose["normals2"]
+            g = dict(g, mask=sel["mask"], n_inliers=sel["n_inliers"], status=sel["status"], scores=sel["scores"], H=gh["H"],
+                     h_mask=gh["mask"], h_n_inliers=gh["n_inliers"], h_status=gh["status"])
         prev, m_prev, nm_prev = self._pose_prev if self._pose_prev is not None else (None, None, None)
         L.op_pose_chain(prev, pose, m_prev, m, nm_prev, nm, self._traj_state, self._traj_table)
         self._pose_prev = (pose, m, nm)
@@ -790,7 +816,7 @@ class SequenceTracker:
     geometric_check / check_thresh / min_inliers / check_seed: PointTracker's epipolar or homography check of every frame's
     matches, also without a host copy or a synchronisation.
     intrinsics / trajectory_rows: PointTracker's two-view pose and trajectory of a calibrated camera (DESIGN.md section 24;
-    needs geometric_check="fundamental"); read them with tracker.last_geometry() and trajectory().
+    needs geometric_check="fundamental" or "auto"); read them with tracker.last_geometry() and trajectory().
     landmarks / landmarks_device / landmark_rows_device: PointTracker's, on demand.
     absolute_pose / absolute_thresh / absolute_min_inliers / landmark_params: PointTracker's absolute pose of every frame from the
     landmarks of the window before it, and with "repair" the repair of the trajectory; read it with
