@@ -365,6 +365,125 @@ def _need_gpu(t, name):
         raise RuntimeError("%s must be contiguous" % name)
 
 
+# ---- argument checks of the operator wrappers (one copy of each) ----
+def _shape_text(shape):
+    return "[%s]" % ", ".join("." if w is None else str(w) if not isinstance(w, tuple) else
+                              (">= %d" % w[0] if w[1] is None else "%d..%d" % w) for w in shape)
+
+
+def _tensor(t, name, dtype, shape, hint=None):
+    """One device tensor argument.  _need_gpu first: a CPU or strided tensor is its RuntimeError.  Anything else that is wrong is
+    a ValueError naming the argument, the dtype and the shape.  shape: one entry per dimension, an int, None (any) or a (lo, hi)
+    range (hi None: open); dtype None: any.  hint: where the sizes come from, for the message.  Returns t."""
+    _need_gpu(t, name)
+    if t.shape == shape and t.dtype == dtype:  # an exact spec: one compare
+        return t
+    ok = (dtype is None or t.dtype == dtype) and t.dim() == len(shape)
+    if ok:
+        for n, w in zip(t.shape, shape):
+            if w is None or n == w:
+                continue
+            if w.__class__ is not tuple or n < w[0] or (w[1] is not None and n > w[1]):
+                ok = False
+                break
+    if not ok:
+        raise ValueError("%s must be %s %s%s (got %s %s)" % (name, "a tensor" if dtype is None else str(dtype)[6:], _shape_text(shape),
+                                                            " (%s)" % hint if hint else "", str(t.dtype)[6:], list(t.shape)))
+    return t
+
+
+def _count(t, name, n, dtype=torch.int32, like=None, hint=None):
+    """A tensor held by its length, not its shape: a per-pair vector may be [P] or [P, 1], a matrix per pair [P, 3, 3] or [P, 9]
+    (`like`: the shape the message shows).  Device and contiguity as in _tensor.  Returns t."""
+    _need_gpu(t, name)
+    if t.dtype != dtype or t.numel() != n:
+        raise ValueError("%s must be %s %s%s (got %s %s)" % (name, str(dtype)[6:], list(like or (n,)), " (%s)" % hint if hint else "",
+                                                            str(t.dtype)[6:], list(t.shape)))
+    return t
+
+
+def _pair_inputs(pts1, pts2, match, n_match, pair_stride=1, pt_stride=(2, None), what="", S=None, single=False, points=True):
+    """The matches of P pairs, as every pair operator takes them; returns (P, cap, match as [P, cap, 3]).  match float32 [P, cap, 3]
+    with 1 <= cap <= MATCH_MAX_POINTS, n_match int32 of P entries and, with `points`, pts1 / pts2 float64 [>= (P-1)*pair_stride+1,
+    cap, pt_stride] with one pt_stride (an int or a range).  what: the suffix of both names ("_cur"); S: the P the caller already
+    holds, as (P, where it comes from); single: a [cap, 3] match is one pair."""
+    name, m = "match" + what, match
+    if single:
+        _need_gpu(match, name)
+        m = match[None] if match.dim() == 2 else match
+    S, hint = S or (None, "[cap, 3] for one pair" if single else None)
+    _tensor(m, name, torch.float32, (S, None, 3), hint)
+    P, cap = m.shape[0], m.shape[1]
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
+    if points:
+        rows = ((P - 1) * pair_stride + 1, None)
+        _tensor(pts1, "pts1", torch.float64, (rows, cap, pt_stride), "(P-1)*pair_stride+1 rows or more, P and cap from match")
+        _tensor(pts2, "pts2", torch.float64, (rows, cap, pts1.shape[2]), "as pts1; P and cap from match, at pair_stride")
+    _count(n_match, "n_match" + what, P, hint="one per pair of " + name)
+    return P, cap, m
+
+
+def _model_inputs(geometry, key, what, P, cap):
+    """(matrix, mask, n_inliers, status) of a RANSAC dict, checked: all four are held by their lengths."""
+    for k in (key, "mask", "n_inliers", "status"):
+        if k not in geometry:
+            raise ValueError("%s must be the dict of a RANSAC operator (no %r)" % (what, k))
+    return (_count(geometry[key], "%s[%r]" % (what, key), P * 9, torch.float64, (P, 3, 3)),
+            _count(geometry["mask"], "%s['mask']" % what, P * cap, torch.uint8, (P, cap)),
+            _count(geometry["n_inliers"], "%s['n_inliers']" % what, P), _count(geometry["status"], "%s['status']" % what, P))
+
+
+def _intrinsics(t, name, rows, n):
+    """Camera intrinsics float64 [1, *rows] (shared) or [n, *rows], rows = (2, 4) or (4,) of (fx, fy, cx, cy); returns the count."""
+    _tensor(t, name, torch.float64, (None,) + rows, "rows (fx, fy, cx, cy)")
+    if t.shape[0] not in (1, n):
+        raise ValueError("%s must be float64 %s or %s rows (fx, fy, cx, cy)" % (name, [1] + list(rows), [n] + list(rows)))
+    return int(t.shape[0])
+
+
+def _chain_arrays(state, table, S):
+    """The pose chain of S sequences: state float64 [S, POSE_STATE_WORDS] held by its length (one sequence may be flat), table
+    float64 [S, capacity, POSE_ROW_WORDS] or [capacity, .] for one sequence; returns capacity."""
+    _count(state, "state", S * POSE_STATE_WORDS, torch.float64, (S, POSE_STATE_WORDS))
+    _need_gpu(table, "table")
+    if (table.dtype != torch.float64 or table.dim() not in (2, 3) or table.shape[-1] != POSE_ROW_WORDS
+            or table.numel() != S * table.shape[-2] * POSE_ROW_WORDS):
+        raise ValueError("table must be float64 [%d, capacity, %d] (pose_table)" % (S, POSE_ROW_WORDS))
+    return int(table.shape[-2])
+
+
+_SHAPES = {}
+
+
+def _shapes(spec, dims):
+    """{key: shape} of a buffer family at sizes `dims`.  spec: (symbols, {key: (dtype, shape in those symbols or constants)}), the one
+    statement of the family's layout; dims: a size per symbol, in their order.  A process meets a handful of sizes: each is built once."""
+    shapes = _SHAPES.get((id(spec), dims))
+    if shapes is None:
+        if len(_SHAPES) >= 256:
+            _SHAPES.clear()
+        size = dict(zip(spec[0], dims))
+        shapes = _SHAPES[id(spec), dims] = {k: tuple(size.get(n, n) for n in shape) for k, (_, shape) in spec[1].items()}
+    return shapes
+
+
+def _alloc(spec, dims, device, keys=None, zero=True):
+    """The tensors `keys` (default: all) of a buffer family at sizes `dims`, zeroed unless told otherwise."""
+    new, shapes = torch.zeros if zero else torch.empty, _shapes(spec, dims)
+    return {k: new(*shapes[k], dtype=spec[1][k][0], device=device) for k in (keys or spec[1])}
+
+
+def _check_family(d, what, spec, dims, keys, source):
+    """The members `keys` of the dict argument `what` against the family that its allocator `source` allocates from."""
+    shapes = _shapes(spec, dims)
+    for k in keys:
+        if k not in d:
+            raise ValueError("%s must be the dict of %s (no %r)" % (what, source, k))
+        _tensor(d[k], "%s[%r]" % (what, k), spec[1][k][0], shapes[k], source)
+    return d
+
+
 def scaled_homographies(hn, height, width):
     """T^-1 @ H @ T with T = [[2/width, 0, -1], [0, 2/height, -1], [0, 0, 1]] for a batch of normalised homographies,
     computed on the HOST with the reference's own fp32 op sequence (`torch.inverse(trans) @ H @ trans`, per matrix:
@@ -1468,10 +1587,8 @@ def op_match_two_way(desc1, count1, desc2, count2, nn_thresh, pair_stride=1, n_p
     match = torch.empty(P, cap, 3, dtype=torch.float32, device=desc1.device)
     n_match = torch.empty(P, dtype=torch.int32, device=desc1.device)
     if cls1 is not None:
-        for t, d, nm in ((cls1, desc1, "cls1"), (cls2, desc2, "cls2")):
-            _need_gpu(t, nm)
-            if t.dtype != torch.uint8 or tuple(t.shape) != (d.shape[0], cap):
-                raise ValueError("%s must be uint8 %s beside its descriptors" % (nm, (d.shape[0], cap)))
+        _tensor(cls1, "cls1", torch.uint8, (desc1.shape[0], cap), "a class beside each row of desc1")
+        _tensor(cls2, "cls2", torch.uint8, (desc2.shape[0], cap), "a class beside each row of desc2")
     with torch.cuda.device(desc1.device):
         if cls1 is not None:
             _check(lib.ssp_match_two_way_classes(_ptr(desc1), _ptr(count1), _ptr(desc2), _ptr(count2), _ptr(cls1), _ptr(cls2),
@@ -1522,12 +1639,11 @@ def op_track_update(table, match, n_match, n_points, match_score64=None, out=Non
     arrays); the input table is left as it was.  No host synchronisation."""
     lib = load_library()
     L, point_cap, row_cap = table["L"], table["point_cap"], table["row_cap"]
-    for t, nm in ((match, "match"), (n_match, "n_match"), (n_points, "n_points")):
+    _tensor(match, "match", torch.float32, ((point_cap, None), 3), "rows (i, j, distance)")
+    for t, nm in ((n_match, "n_match"), (n_points, "n_points")):
         _need_gpu(t, nm)
-    if match.dtype != torch.float32 or match.dim() != 2 or match.shape[1] != 3 or match.shape[0] < point_cap:
-        raise ValueError("match must be float32 [>= %d, 3] rows (i, j, distance)" % point_cap)
-    if n_match.dtype != torch.int32 or n_points.dtype != torch.int32:
-        raise ValueError("n_match and n_points must be int32 device scalars")
+        if t.dtype != torch.int32:
+            raise ValueError("%s must be an int32 device scalar" % nm)
     if match_score64 is not None:
         _need_gpu(match_score64, "match_score64")
         if match_score64.dtype != torch.float64 or match_score64.numel() < point_cap:
@@ -1570,13 +1686,14 @@ def op_track_points(tracks, n_tracks, pts, state, first_slot=0):
     int32 [1] rows; pts: float64 [L, point_cap, 2] (x, y), retained frame c in slot (first_slot + c) % L; state: the table's
     state vector.  Returns float64 [track_cap, L, 2], NaN where the id is -1 (rows >= n_tracks are undefined)."""
     lib = load_library()
-    for t, nm in ((tracks, "tracks"), (n_tracks, "n_tracks"), (pts, "pts"), (state, "state")):
-        _need_gpu(t, nm)
+    _need_gpu(tracks, "tracks")
     L = tracks.shape[1] - 2
-    if tracks.dtype != torch.float64 or pts.dtype != torch.float64 or pts.dim() != 3 or pts.shape[0] != L or pts.shape[2] != 2:
-        raise ValueError("tracks must be float64 [M, 2+L] and pts float64 [L, point_cap, 2]")
-    if state.dtype != torch.int32 or state.numel() != 2 + L or n_tracks.dtype != torch.int32:
-        raise ValueError("state must be int32 [2+L] and n_tracks an int32 device scalar")
+    _tensor(tracks, "tracks", torch.float64, (None, 2 + L), "rows (track id, score, L ids)")
+    _tensor(pts, "pts", torch.float64, (L, None, 2), "L from tracks [M, 2+L]")
+    _count(state, "state", 2 + L, hint="2+L, L from tracks")
+    _need_gpu(n_tracks, "n_tracks")
+    if n_tracks.dtype != torch.int32:
+        raise ValueError("n_tracks must be an int32 device scalar")
     xy = torch.empty(tracks.shape[0], L, 2, dtype=torch.float64, device=tracks.device)
     if tracks.shape[0] == 0:
         return xy
@@ -1609,18 +1726,15 @@ def detector_eval_state(device):
 
 
 def _det_eval_args(labels, keys, state, remove_zero, r2, prob_thresh, simplified):
-    for t, nm in ((labels, "labels"), (keys, "keys"), (state, "state")):
-        _need_gpu(t, nm)
+    _need_gpu(labels, "labels")
     if labels.dtype not in (torch.float32, torch.uint8):
         raise ValueError("labels must be float32 or uint8 (nonzero = ground truth)")
     if labels.dim() == 4 and labels.shape[1] == 1:
         labels = labels[:, 0]
     if labels.dim() != 3:
         raise ValueError("labels must be [B,H,W] (or [B,1,H,W])")
-    if keys.dtype != torch.int64 or keys.dim() != 1 or keys.numel() < 1:
-        raise ValueError("keys must be a non-empty int64 vector (its length is the record capacity)")
-    if state.dtype != torch.int64 or state.numel() != DET_EVAL_STATE_WORDS:
-        raise ValueError("state must be int64 [%d] (detector_eval_state)" % DET_EVAL_STATE_WORDS)
+    _tensor(keys, "keys", torch.int64, ((1, None),), "its length is the record capacity")
+    _count(state, "state", DET_EVAL_STATE_WORDS, torch.int64)
     B, H, W = labels.shape
     p = SspDetEvalParams(H, W, float(np.float32(remove_zero)), int(r2), float(np.float32(prob_thresh)), int(bool(simplified)))
     return labels, p
@@ -1659,14 +1773,10 @@ def op_detector_tp_fp_points(pts, count, labels, keys, state, remove_zero=1e-4, 
     int32 [B], as Engine.describe_points / op_heatmap_points produce them.  The rows < count with confidence > remove_zero are
     the candidates, in list order; rows outside the image are skipped and counted in state word DET_EVAL_OUTSIDE."""
     lib = load_library()
-    _need_gpu(pts, "pts")
-    _need_gpu(count, "count")
     labels, p = _det_eval_args(labels, keys, state, remove_zero, r2, prob_thresh, simplified)
     B = labels.shape[0]
-    if pts.dtype != torch.float32 or pts.dim() != 3 or pts.shape[0] != B or pts.shape[2] != 5 or pts.shape[1] < 1:
-        raise ValueError("pts must be float32 [%d, cap >= 1, 5] rows (x, y, confidence, sx, sy)" % B)
-    if count.dtype != torch.int32 or count.numel() != B:
-        raise ValueError("count must be int32 [%d]" % B)
+    _tensor(pts, "pts", torch.float32, (B, (1, None), 5), "cap >= 1 rows (x, y, confidence, sx, sy) per image of labels")
+    _count(count, "count", B)
     cap = pts.shape[1]
     ws = _det_eval_ws(lib, p, B, cap, ws, pts.device)
     with torch.cuda.device(pts.device):
@@ -1680,12 +1790,8 @@ def op_detector_pr_curve(sorted_keys, state):
     is the sort: the keys are unique).  Returns device tensors {"prob": float32 [n], "tp": uint8 [n], "precision", "recall":
     float64 [n+2], "mAP": float64 [1]}."""
     lib = load_library()
-    _need_gpu(sorted_keys, "sorted_keys")
-    _need_gpu(state, "state")
-    if sorted_keys.dtype != torch.int64 or sorted_keys.dim() != 1:
-        raise ValueError("sorted_keys must be an int64 vector")
-    if state.dtype != torch.int64 or state.numel() != DET_EVAL_STATE_WORDS:
-        raise ValueError("state must be int64 [%d] (detector_eval_state)" % DET_EVAL_STATE_WORDS)
+    _tensor(sorted_keys, "sorted_keys", torch.int64, (None,))
+    _count(state, "state", DET_EVAL_STATE_WORDS, torch.int64)
     n, dev = sorted_keys.numel(), sorted_keys.device
     wsb = lib.ssp_det_pr_curve_workspace_bytes(n)
     if wsb == 0:
@@ -1701,13 +1807,9 @@ def op_detector_pr_curve(sorted_keys, state):
     return out
 
 
-def _eval_points(pts, counts, name):
-    _need_gpu(pts, name)
-    _need_gpu(counts, name + " counts")
-    if pts.dtype != torch.float64 or pts.dim() != 3 or pts.shape[2] != 3:
-        raise ValueError("%s must be float64 [n, cap, 3] rows (x, y, confidence)" % name)
-    if counts.dtype != torch.int32 or counts.numel() != pts.shape[0]:
-        raise ValueError("%s counts must be int32 [%d]" % (name, pts.shape[0]))
+def _eval_points(pts, counts, name, count_name):
+    _tensor(pts, name, torch.float64, (None, None, 3), "rows (x, y, confidence)")
+    _count(counts, count_name, pts.shape[0], hint="one per image of " + name)
     if not 1 <= pts.shape[1] <= MATCH_MAX_POINTS:
         raise ValueError("%s: 1 <= cap <= %d points per image (got %d)" % (name, MATCH_MAX_POINTS, pts.shape[1]))
 
@@ -1719,18 +1821,16 @@ def op_eval_repeatability(pts1, n1, pts2, n2, hom, hom_inv, height, width, keep_
     n1, n2: int32 counts (pair p uses entry p*pair_stride), hom / hom_inv: float64 [P,3,3] (hom_inv from np.linalg.inv).
     Returns float64 [P,8] = N1, N2, count1, count2, sum1, sum2, n_unwarped, 0 (device tensor)."""
     lib = load_library()
-    _eval_points(pts1, n1, "pts1")
-    _eval_points(pts2, n2, "pts2")
+    _eval_points(pts1, n1, "pts1", "n1")
+    _eval_points(pts2, n2, "pts2", "n2")
     cap = pts1.shape[1]
     if pts2.shape[1] != cap:
         raise ValueError("pts1 and pts2 need the same cap")
     P = n_pairs if n_pairs is not None else pts1.shape[0] // pair_stride
     if P < 1 or (P - 1) * pair_stride >= min(pts1.shape[0], pts2.shape[0]):
         raise ValueError("%d pairs at stride %d do not fit the point arrays" % (P, pair_stride))
-    for t, nm in ((hom, "hom"), (hom_inv, "hom_inv")):
-        _need_gpu(t, nm)
-        if t.dtype != torch.float64 or tuple(t.shape) != (P, 3, 3):
-            raise ValueError("%s must be float64 [%d,3,3]" % (nm, P))
+    _tensor(hom, "hom", torch.float64, (P, 3, 3), "P from pts1, pair_stride and n_pairs")
+    _tensor(hom_inv, "hom_inv", torch.float64, (P, 3, 3), "P from pts1, pair_stride and n_pairs")
     out = torch.empty(P, 8, dtype=torch.float64, device=pts1.device)
     with torch.cuda.device(pts1.device):
         _check(lib.ssp_eval_repeatability(_ptr(pts1), _ptr(n1), _ptr(pts2), _ptr(n2), cap, P, int(pair_stride), _ptr(hom),
@@ -1746,21 +1846,8 @@ def op_eval_ransac(pts1, pts2, match, n_match, seeds, pair_stride=1, want_ap=Fal
     Returns device tensors {"H": float64 [P,3,3], "mask": uint8 [P,cap], "n_inliers": int32 [P], "status": int32 [P]
     (1 = no model), "ap": float64 [P] when want_ap}."""
     lib = load_library()
-    for t, nm in ((pts1, "pts1"), (pts2, "pts2"), (match, "match"), (n_match, "n_match"), (seeds, "seeds")):
-        _need_gpu(t, nm)
-    cap = match.shape[1]
-    P = match.shape[0]
-    if not 1 <= cap <= MATCH_MAX_POINTS:
-        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
-    if match.dtype != torch.float32 or match.dim() != 3 or match.shape[2] != 3:
-        raise ValueError("match must be float32 [P, cap, 3]")
-    for t, nm in ((pts1, "pts1"), (pts2, "pts2")):
-        if t.dtype != torch.float64 or t.dim() != 3 or t.shape[1:] != (cap, 3) or t.shape[0] < (P - 1) * pair_stride + 1:
-            raise ValueError("%s must be float64 [P*pair_stride, %d, 3]" % (nm, cap))
-    if n_match.dtype != torch.int32 or n_match.numel() != P:
-        raise ValueError("n_match must be int32 [%d]" % P)
-    if seeds.dtype != torch.int64 or seeds.numel() != P:
-        raise ValueError("seeds must be int64 [%d]" % P)
+    P, cap, _ = _pair_inputs(pts1, pts2, match, n_match, pair_stride, pt_stride=3)
+    _count(seeds, "seeds", P, torch.int64)
     wsb = lib.ssp_eval_ransac_workspace_bytes(cap, P)
     if wsb == 0:
         _check(-1)
@@ -1789,22 +1876,8 @@ def op_epipolar_ransac(pts1, pts2, match, n_match, seeds, thresh=1.0, pair_strid
     "status": int32 [P] (1 = no model), "winner": int32 [P] (the hypothesis, -1), "err": float64 [P] (RMS Sampson distance
     of the inliers)}.  No host synchronisation."""
     lib = load_library()
-    for t, nm in ((pts1, "pts1"), (pts2, "pts2"), (match, "match"), (n_match, "n_match"), (seeds, "seeds")):
-        _need_gpu(t, nm)
-    if match.dtype != torch.float32 or match.dim() != 3 or match.shape[2] != 3 or not match.is_contiguous():
-        raise ValueError("match must be contiguous float32 [P, cap, 3]")
-    P, cap = match.shape[0], match.shape[1]
-    if not 1 <= cap <= MATCH_MAX_POINTS:
-        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
-    if pts1.dim() != 3 or pts1.shape[2] < 2 or pts2.shape[2] != pts1.shape[2]:
-        raise ValueError("pts1 and pts2 must be float64 [., cap, pt_stride >= 2] with one pt_stride")
-    for t, nm in ((pts1, "pts1"), (pts2, "pts2")):
-        if t.dtype != torch.float64 or t.shape[1] != cap or t.shape[0] < (P - 1) * pair_stride + 1 or not t.is_contiguous():
-            raise ValueError("%s must be contiguous float64 [P*pair_stride, %d, pt_stride]" % (nm, cap))
-    if n_match.dtype != torch.int32 or n_match.numel() != P:
-        raise ValueError("n_match must be int32 [%d]" % P)
-    if seeds.dtype != torch.int64 or seeds.numel() != P:
-        raise ValueError("seeds must be int64 [%d]" % P)
+    P, cap, _ = _pair_inputs(pts1, pts2, match, n_match, pair_stride)
+    _count(seeds, "seeds", P, torch.int64)
     wsb = lib.ssp_epi_ransac_workspace_bytes(cap, P)
     if wsb == 0:
         _check(-1)
@@ -1831,19 +1904,10 @@ def op_filter_matches(match, n_match, mask, status, n_inliers, min_inliers):
     pair with status != 0 or fewer than min_inliers inliers passes through unchanged.  That decision is taken on the device:
     no host synchronisation."""
     lib = load_library()
-    for t, nm in ((match, "match"), (n_match, "n_match"), (mask, "mask"), (status, "status"), (n_inliers, "n_inliers")):
-        _need_gpu(t, nm)
-    m3 = match if match.dim() == 3 else match[None]
-    if m3.dtype != torch.float32 or m3.dim() != 3 or m3.shape[2] != 3 or not m3.is_contiguous():
-        raise ValueError("match must be contiguous float32 [P, cap, 3] or [cap, 3]")
-    P, cap = m3.shape[0], m3.shape[1]
-    if not 1 <= cap <= MATCH_MAX_POINTS:
-        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
-    if mask.dtype != torch.uint8 or mask.numel() != P * cap or not mask.is_contiguous():
-        raise ValueError("mask must be contiguous uint8 [%d, %d]" % (P, cap))
-    for t, nm in ((n_match, "n_match"), (status, "status"), (n_inliers, "n_inliers")):
-        if t.dtype != torch.int32 or t.numel() != P:
-            raise ValueError("%s must be int32 [%d]" % (nm, P))
+    P, cap, m3 = _pair_inputs(None, None, match, n_match, single=True, points=False)
+    _count(mask, "mask", P * cap, torch.uint8, (P, cap), "P and cap from match")
+    _count(status, "status", P, hint="P from match")
+    _count(n_inliers, "n_inliers", P, hint="P from match")
     out = torch.empty_like(m3)
     n_out = torch.empty(P, dtype=torch.int32, device=m3.device)
     with torch.cuda.device(m3.device):
@@ -1853,6 +1917,12 @@ def op_filter_matches(match, n_match, mask, status, n_inliers, min_inliers):
 
 
 POSE_KEYS = ("R", "t", "E", "cand", "counts", "n_front", "status", "front", "depth", "X")
+# the outputs of op_two_view_pose and op_homography_pose for P pairs of cap matches
+POSE_SPEC = (("P", "cap"), {"R": (torch.float64, ("P", 3, 3)), "t": (torch.float64, ("P", 3)), "E": (torch.float64, ("P", 3, 3)),
+             "cand": (torch.int32, ("P",)), "counts": (torch.int32, ("P", 4)), "n_front": (torch.int32, ("P",)),
+             "status": (torch.int32, ("P",)), "front": (torch.uint8, ("P", "cap")), "depth": (torch.float64, ("P", "cap", 2)),
+             "X": (torch.float64, ("P", "cap", 3)), "model": (torch.int32, ("P",)), "normal": (torch.float64, ("P", 3)),
+             "normals2": (torch.float64, ("P", 2, 3))})
 
 
 def op_two_view_pose(geometry, pts1, pts2, match, n_match, intrinsics, pair_stride=1):
@@ -1865,43 +1935,15 @@ def op_two_view_pose(geometry, pts1, pts2, match, n_match, intrinsics, pair_stri
     "X": float64 [P,cap,3] (the point in camera 1's frame, the baseline as the unit)}; the per-row outputs are aligned with
     the UNFILTERED match rows, as the mask is.  No host synchronisation."""
     lib = load_library()
-    for k in ("F", "mask", "n_inliers", "status"):
-        if k not in geometry:
-            raise ValueError("geometry must be the dict of op_epipolar_ransac (no %r)" % k)
-    F, mask, n_inl, status = (geometry[k] for k in ("F", "mask", "n_inliers", "status"))
-    for t, nm in ((F, "F"), (mask, "mask"), (n_inl, "n_inliers"), (status, "status"), (pts1, "pts1"), (pts2, "pts2"), (match, "match"),
-                  (n_match, "n_match"), (intrinsics, "intrinsics")):
-        _need_gpu(t, nm)
-    if match.dtype != torch.float32 or match.dim() != 3 or match.shape[2] != 3 or not match.is_contiguous():
-        raise ValueError("match must be contiguous float32 [P, cap, 3]")
-    P, cap = match.shape[0], match.shape[1]
-    if not 1 <= cap <= MATCH_MAX_POINTS:
-        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
-    if pts1.dim() != 3 or pts1.shape[2] < 2 or pts2.shape[2] != pts1.shape[2]:
-        raise ValueError("pts1 and pts2 must be float64 [., cap, pt_stride >= 2] with one pt_stride")
-    for t, nm in ((pts1, "pts1"), (pts2, "pts2")):
-        if t.dtype != torch.float64 or t.shape[1] != cap or t.shape[0] < (P - 1) * pair_stride + 1 or not t.is_contiguous():
-            raise ValueError("%s must be contiguous float64 [P*pair_stride, %d, pt_stride]" % (nm, cap))
-    if F.dtype != torch.float64 or F.numel() != P * 9 or not F.is_contiguous():
-        raise ValueError("geometry['F'] must be contiguous float64 [%d, 3, 3]" % P)
-    if mask.dtype != torch.uint8 or mask.numel() != P * cap or not mask.is_contiguous():
-        raise ValueError("geometry['mask'] must be contiguous uint8 [%d, %d]" % (P, cap))
-    for t, nm in ((n_match, "n_match"), (n_inl, "geometry['n_inliers']"), (status, "geometry['status']")):
-        if t.dtype != torch.int32 or t.numel() != P:
-            raise ValueError("%s must be int32 [%d]" % (nm, P))
-    if (intrinsics.dtype != torch.float64 or intrinsics.dim() != 3 or tuple(intrinsics.shape[1:]) != (2, 4)
-            or intrinsics.shape[0] not in (1, P) or not intrinsics.is_contiguous()):
-        raise ValueError("intrinsics must be contiguous float64 [1, 2, 4] or [%d, 2, 4] rows (fx, fy, cx, cy)" % P)
+    P, cap, _ = _pair_inputs(pts1, pts2, match, n_match, pair_stride)
+    F, mask, n_inl, status = _model_inputs(geometry, "F", "geometry", P, cap)
+    n_intr = _intrinsics(intrinsics, "intrinsics", (2, 4), P)
     dev = match.device
-    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
-    o = {"R": torch.empty(P, 3, 3, **f64), "t": torch.empty(P, 3, **f64), "E": torch.empty(P, 3, 3, **f64),
-         "cand": torch.empty(P, **i32), "counts": torch.empty(P, 4, **i32), "n_front": torch.empty(P, **i32),
-         "status": torch.empty(P, **i32), "front": torch.empty(P, cap, dtype=torch.uint8, device=dev),
-         "depth": torch.empty(P, cap, 2, **f64), "X": torch.empty(P, cap, 3, **f64)}
+    o = _alloc(POSE_SPEC, (P, cap), dev, POSE_KEYS, zero=False)
     with torch.cuda.device(dev):
         _check(lib.ssp_pose_from_fundamental(_ptr(F), _ptr(mask), _ptr(n_inl), _ptr(status), _ptr(pts1), _ptr(pts2),
                                              int(pts1.shape[2]), cap, P, int(pair_stride), _ptr(match), _ptr(n_match),
-                                             _ptr(intrinsics), int(intrinsics.shape[0]), *[_ptr(o[k]) for k in POSE_KEYS], _stream()))
+                                             _ptr(intrinsics), n_intr, *[_ptr(o[k]) for k in POSE_KEYS], _stream()))
     return o
 
 
@@ -1930,86 +1972,30 @@ def op_pose_chain(prev, cur, match_prev, match_cur, n_match_prev, n_match_cur, s
     lib = load_library()
     S = cur["front"].shape[0]
 
-    def pair(d, m, nm, what):
-        for k in ("front", "depth", "status"):
-            _need_gpu(d[k], "%s[%r]" % (what, k))
-        _need_gpu(m, "match_" + what)
-        _need_gpu(nm, "n_match_" + what)
-        if m.dtype != torch.float32 or m.dim() != 3 or m.shape[0] != S or m.shape[2] != 3 or not m.is_contiguous():
-            raise ValueError("match_%s must be contiguous float32 [%d, cap, 3]" % (what, S))
-        cap = m.shape[1]
-        if not 1 <= cap <= MATCH_MAX_POINTS:
-            raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
-        if d["front"].dtype != torch.uint8 or tuple(d["front"].shape) != (S, cap) or not d["front"].is_contiguous():
-            raise ValueError("%s['front'] must be contiguous uint8 [%d, %d]" % (what, S, cap))
-        if d["depth"].dtype != torch.float64 or tuple(d["depth"].shape) != (S, cap, 2) or not d["depth"].is_contiguous():
-            raise ValueError("%s['depth'] must be contiguous float64 [%d, %d, 2]" % (what, S, cap))
-        for t, n in ((nm, "n_match_" + what), (d["status"], "%s['status']" % what)):
-            if t.dtype != torch.int32 or t.numel() != S:
-                raise ValueError("%s must be int32 [%d]" % (n, S))
+    def pair(d, m, nm, what):  # the two pairs may have different caps
+        _, cap, _ = _pair_inputs(None, None, m, nm, what="_" + what, S=(S, "S sequences from cur['front']"), points=False)
+        _tensor(d["front"], "%s['front']" % what, torch.uint8, (S, cap), "cap from match_" + what)
+        _tensor(d["depth"], "%s['depth']" % what, torch.float64, (S, cap, 2), "S from cur['front'], cap from match_" + what)
+        _count(d["status"], "%s['status']" % what, S, hint="S from cur['front']")
         return cap
 
     cap = pair(cur, match_cur, n_match_cur, "cur")
     cap_prev = pair(prev, match_prev, n_match_prev, "prev") if prev is not None else 0
-    for k in ("R", "t"):
-        _need_gpu(cur[k], "cur[%r]" % k)
-        if cur[k].dtype != torch.float64 or cur[k].numel() != S * (9 if k == "R" else 3) or not cur[k].is_contiguous():
-            raise ValueError("cur[%r] must be the contiguous float64 tensor of op_two_view_pose" % k)
-    _need_gpu(state, "state")
-    _need_gpu(table, "table")
-    if state.dtype != torch.float64 or state.numel() != S * POSE_STATE_WORDS or not state.is_contiguous():
-        raise ValueError("state must be contiguous float64 [%d, %d] (pose_state)" % (S, POSE_STATE_WORDS))
-    if (table.dtype != torch.float64 or table.dim() not in (2, 3) or table.shape[-1] != POSE_ROW_WORDS or not table.is_contiguous()
-            or table.numel() != S * table.shape[-2] * POSE_ROW_WORDS):
-        raise ValueError("table must be contiguous float64 [%d, capacity, %d] (pose_table)" % (S, POSE_ROW_WORDS))
+    _count(cur["R"], "cur['R']", S * 9, torch.float64, (S, 3, 3), "S from cur['front']")
+    _count(cur["t"], "cur['t']", S * 3, torch.float64, (S, 3), "S from cur['front']")
+    capacity = _chain_arrays(state, table, S)
     have = prev is not None
     with torch.cuda.device(state.device):
         _check(lib.ssp_pose_chain(_ptr(prev["front"]) if have else None, _ptr(prev["depth"]) if have else None,
                                   _ptr(prev["status"]) if have else None, _ptr(match_prev) if have else None,
                                   _ptr(n_match_prev) if have else None, cap_prev, _ptr(cur["front"]), _ptr(cur["depth"]),
                                   _ptr(cur["status"]), _ptr(cur["R"]), _ptr(cur["t"]), _ptr(match_cur), _ptr(n_match_cur), cap, S,
-                                  _ptr(state), _ptr(table), int(table.shape[-2]), _stream()))
+                                  _ptr(state), _ptr(table), capacity, _stream()))
     return state, table
 
 
 # ---- homography pose and model selection ----
 HOMOGRAPHY_POSE_KEYS = ("R", "t", "cand", "counts", "n_front", "status", "front", "depth", "X", "model", "normal", "normals2")
-
-
-def _pair_inputs(pts1, pts2, match, n_match, pair_stride):
-    """The checks the pair operators share; returns (P, cap)."""
-    for t, nm in ((pts1, "pts1"), (pts2, "pts2"), (match, "match"), (n_match, "n_match")):
-        _need_gpu(t, nm)
-    if match.dtype != torch.float32 or match.dim() != 3 or match.shape[2] != 3 or not match.is_contiguous():
-        raise ValueError("match must be contiguous float32 [P, cap, 3]")
-    P, cap = match.shape[0], match.shape[1]
-    if not 1 <= cap <= MATCH_MAX_POINTS:
-        raise ValueError("1 <= cap <= %d matches per pair (got %d)" % (MATCH_MAX_POINTS, cap))
-    if pts1.dim() != 3 or pts1.shape[2] < 2 or pts2.dim() != 3 or pts2.shape[2] != pts1.shape[2]:
-        raise ValueError("pts1 and pts2 must be float64 [., cap, pt_stride >= 2] with one pt_stride")
-    for t, nm in ((pts1, "pts1"), (pts2, "pts2")):
-        if t.dtype != torch.float64 or t.shape[1] != cap or t.shape[0] < (P - 1) * pair_stride + 1 or not t.is_contiguous():
-            raise ValueError("%s must be contiguous float64 [P*pair_stride, %d, pt_stride]" % (nm, cap))
-    if n_match.dtype != torch.int32 or n_match.numel() != P:
-        raise ValueError("n_match must be int32 [%d]" % P)
-    return P, cap
-
-
-def _model_inputs(geometry, key, what, P, cap):
-    """(matrix, mask, n_inliers, status) of a RANSAC dict, checked."""
-    for k in (key, "mask", "n_inliers", "status"):
-        if k not in geometry:
-            raise ValueError("%s must be the dict of a RANSAC operator (no %r)" % (what, k))
-        _need_gpu(geometry[k], "%s[%r]" % (what, k))
-    M, mask, n_inl, status = (geometry[k] for k in (key, "mask", "n_inliers", "status"))
-    if M.dtype != torch.float64 or M.numel() != P * 9 or not M.is_contiguous():
-        raise ValueError("%s[%r] must be contiguous float64 [%d, 3, 3]" % (what, key, P))
-    if mask.dtype != torch.uint8 or mask.numel() != P * cap or not mask.is_contiguous():
-        raise ValueError("%s['mask'] must be contiguous uint8 [%d, %d]" % (what, P, cap))
-    for t, nm in ((n_inl, "n_inliers"), (status, "status")):
-        if t.dtype != torch.int32 or t.numel() != P:
-            raise ValueError("%s[%r] must be int32 [%d]" % (what, nm, P))
-    return M, mask, n_inl, status
 
 
 def op_homography_pose(geometry_h, pts1, pts2, match, n_match, intrinsics, prior=None, rotation_eps=0.02, normal_margin=0.01,
@@ -2025,44 +2011,32 @@ def op_homography_pose(geometry_h, pts1, pts2, match, n_match, intrinsics, prior
     float64 [P,3], "normals2": float64 [P,2,3] (the next pair's prior).  status 2 = the two poses of the plane could not be
     told apart (the one whose normal points more along the optical axis is written).  No host synchronisation."""
     lib = load_library()
-    P, cap = _pair_inputs(pts1, pts2, match, n_match, pair_stride)
+    P, cap, _ = _pair_inputs(pts1, pts2, match, n_match, pair_stride)
     H, mask, n_inl, status = _model_inputs(geometry_h, "H", "geometry_h", P, cap)
-    _need_gpu(intrinsics, "intrinsics")
-    if (intrinsics.dtype != torch.float64 or intrinsics.dim() != 3 or tuple(intrinsics.shape[1:]) != (2, 4)
-            or intrinsics.shape[0] not in (1, P) or not intrinsics.is_contiguous()):
-        raise ValueError("intrinsics must be contiguous float64 [1, 2, 4] or [%d, 2, 4] rows (fx, fy, cx, cy)" % P)
+    n_intr = _intrinsics(intrinsics, "intrinsics", (2, 4), P)
     if prior is not None:
-        _need_gpu(prior, "prior")
-        if prior.dtype != torch.float64 or tuple(prior.shape) != (P, 2, 3) or not prior.is_contiguous():
-            raise ValueError("prior must be contiguous float64 [%d, 2, 3]" % P)
+        _tensor(prior, "prior", torch.float64, (P, 2, 3), "the normals2 of the pair before")
     if use_h is not None:
-        _need_gpu(use_h, "use_h")
-        if use_h.dtype != torch.int32 or use_h.numel() != P:
-            raise ValueError("use_h must be int32 [%d]" % P)
+        _count(use_h, "use_h", P)
     if not (rotation_eps >= 0.0 and normal_margin >= 0.0):
         raise ValueError("rotation_eps and normal_margin must be non-negative")
-    dev = match.device
-    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    dev, dims = match.device, (P, cap)
+    kept, new = HOMOGRAPHY_POSE_KEYS[:9], HOMOGRAPHY_POSE_KEYS[9:]  # what op_two_view_pose wrote ("E" aside), what only this call writes
     if out is None:
         if use_h is not None:
             raise ValueError("use_h needs out: the pairs that keep the fundamental matrix keep its pose")
-        o = {"R": torch.empty(P, 3, 3, **f64), "t": torch.empty(P, 3, **f64), "cand": torch.empty(P, **i32),
-             "counts": torch.empty(P, 4, **i32), "n_front": torch.empty(P, **i32), "status": torch.empty(P, **i32),
-             "front": torch.empty(P, cap, dtype=torch.uint8, device=dev), "depth": torch.empty(P, cap, 2, **f64),
-             "X": torch.empty(P, cap, 3, **f64)}
+        o = _alloc(POSE_SPEC, dims, dev, kept, zero=False)
     else:
-        o = out
-        shapes = {"R": (P, 3, 3), "t": (P, 3), "cand": (P,), "counts": (P, 4), "n_front": (P,), "status": (P,), "front": (P, cap),
-                  "depth": (P, cap, 2), "X": (P, cap, 3)}
-        for k, shp in shapes.items():
-            if k not in o or tuple(o[k].shape) != shp or not o[k].is_contiguous():
+        o, shapes = out, _shapes(POSE_SPEC, dims)
+        for k in kept:  # held by shape alone, and a strided tensor is refused with the others: a ValueError
+            if k not in o or o[k].shape != shapes[k] or not o[k].is_contiguous():
                 raise ValueError("out[%r] must be the contiguous tensor of op_two_view_pose for these pairs" % k)
             _need_gpu(o[k], "out[%r]" % k)
-    o["model"], o["normal"], o["normals2"] = torch.empty(P, **i32), torch.empty(P, 3, **f64), torch.empty(P, 2, 3, **f64)
+    o.update(_alloc(POSE_SPEC, dims, dev, new, zero=False))
     with torch.cuda.device(dev):
         _check(lib.ssp_pose_from_homography(_ptr(H), _ptr(mask), _ptr(n_inl), _ptr(status), _ptr(pts1), _ptr(pts2),
                                             int(pts1.shape[2]), cap, P, int(pair_stride), _ptr(match), _ptr(n_match),
-                                            _ptr(intrinsics), int(intrinsics.shape[0]), _ptr(prior), _ptr(use_h), float(rotation_eps),
+                                            _ptr(intrinsics), n_intr, _ptr(prior), _ptr(use_h), float(rotation_eps),
                                             float(normal_margin), *[_ptr(o[k]) for k in HOMOGRAPHY_POSE_KEYS], _stream()))
     return o
 
@@ -2076,7 +2050,7 @@ def op_model_select(geometry_f, geometry_h, pts1, pts2, match, n_match, model_ra
     tensors {"scores": float64 [P,2] = (S_H, S_F), "use_h": int32 [P], "mask": uint8 [P,cap], "n_inliers": int32 [P], "status":
     int32 [P]}, the last three copied from the selected model.  No host synchronisation."""
     lib = load_library()
-    P, cap = _pair_inputs(pts1, pts2, match, n_match, pair_stride)
+    P, cap, _ = _pair_inputs(pts1, pts2, match, n_match, pair_stride)
     F, f_mask, f_n, f_status = _model_inputs(geometry_f, "F", "geometry_f", P, cap)
     H, h_mask, h_n, h_status = _model_inputs(geometry_h, "H", "geometry_h", P, cap)
     if not 0.0 <= model_ratio <= 1.0:
@@ -2095,6 +2069,10 @@ def op_model_select(geometry_f, geometry_h, pts1, pts2, match, n_match, model_ra
 
 # ---- landmarks from tracks ----
 LANDMARK_ROW_KEYS = ("X", "n_views", "rms", "cos_parallax", "status")
+LANDMARK_SPEC = (("L", "row_cap"), {"cams": (torch.float64, ("L", CAM_WORDS)), "X": (torch.float64, ("row_cap", 3)),
+                 "n_views": (torch.int32, ("row_cap",)), "rms": (torch.float64, ("row_cap",)),
+                 "cos_parallax": (torch.float64, ("row_cap",)), "status": (torch.int32, ("row_cap",)),
+                 "landmarks": (torch.float64, ("row_cap", LANDMARK_WORDS)), "n_landmarks": (torch.int32, (1,))})
 
 
 def landmark_buffers(max_length, row_cap, device):
@@ -2110,26 +2088,15 @@ def landmark_buffers(max_length, row_cap, device):
     wsb = lib.ssp_landmark_workspace_bytes(L, row_cap)
     if wsb == 0:
         _check(-1)
-    f64, i32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int32, device=device)
-    return {"cams": torch.zeros(L, CAM_WORDS, **f64), "X": torch.zeros(row_cap, 3, **f64), "n_views": torch.zeros(row_cap, **i32),
-            "rms": torch.zeros(row_cap, **f64), "cos_parallax": torch.zeros(row_cap, **f64), "status": torch.zeros(row_cap, **i32),
-            "landmarks": torch.zeros(row_cap, LANDMARK_WORDS, **f64), "n_landmarks": torch.zeros(1, **i32),
-            "ws": torch.empty(wsb, dtype=torch.uint8, device=device)}
+    out = _alloc(LANDMARK_SPEC, (L, row_cap), device)
+    out["ws"] = torch.empty(wsb, dtype=torch.uint8, device=device)
+    return out
 
 
-def _landmark_out(out, keys, L, row_cap, device):
+def _landmark_out(out, what, keys, L, row_cap, device):
     if out is None:
         return landmark_buffers(L, row_cap, device)
-    shapes = {"cams": (L, CAM_WORDS), "X": (row_cap, 3), "n_views": (row_cap,), "rms": (row_cap,), "cos_parallax": (row_cap,),
-              "status": (row_cap,), "landmarks": (row_cap, LANDMARK_WORDS), "n_landmarks": (1,)}
-    for k in keys:
-        if k not in out:
-            raise ValueError("out must be the dict of landmark_buffers (no %r)" % k)
-        _need_gpu(out[k], "out[%r]" % k)
-        want = torch.int32 if k in ("n_views", "status", "n_landmarks") else torch.float64
-        if k != "ws" and (out[k].dtype != want or tuple(out[k].shape) != shapes[k]):
-            raise ValueError("out[%r] must be %s %s" % (k, want, list(shapes[k])))
-    return out
+    return _check_family(out, what, LANDMARK_SPEC, (L, row_cap), keys, "landmark_buffers")
 
 
 def op_map_window(state, table, intrinsics, max_length, n_frames=None, out=None):
@@ -2144,23 +2111,30 @@ def op_map_window(state, table, intrinsics, max_length, n_frames=None, out=None)
     L = int(max_length)
     if not 2 <= L <= TRACK_MAX_LENGTH:
         raise ValueError("2 <= max_length <= %d required (got %d)" % (TRACK_MAX_LENGTH, L))
-    for t, nm in ((state, "state"), (table, "table"), (intrinsics, "intrinsics")):
-        _need_gpu(t, nm)
-    if state.dtype != torch.float64 or tuple(state.shape) != (POSE_STATE_WORDS,):
-        raise ValueError("state must be float64 [%d] (pose_state)" % POSE_STATE_WORDS)
-    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != POSE_ROW_WORDS:
-        raise ValueError("table must be float64 [capacity, %d] (pose_table)" % POSE_ROW_WORDS)
-    if intrinsics.dtype != torch.float64 or intrinsics.dim() != 2 or intrinsics.shape[1] != 4 or intrinsics.shape[0] not in (1, L):
-        raise ValueError("intrinsics must be float64 [1, 4] or [%d, 4] rows (fx, fy, cx, cy)" % L)
+    _tensor(state, "state", torch.float64, (POSE_STATE_WORDS,), "pose_state of one sequence")
+    _tensor(table, "table", torch.float64, (None, POSE_ROW_WORDS), "pose_table of one sequence")
+    n_intr = _intrinsics(intrinsics, "intrinsics", (4,), L)
     if n_frames is not None and int(n_frames) < 0:
         raise ValueError("n_frames must be non-negative (None: the state's count)")
     if out is None:
-        out = {"cams": torch.zeros(L, CAM_WORDS, dtype=torch.float64, device=state.device)}
-    cams = _landmark_out(out, ("cams",), L, 0, state.device)["cams"]
+        out = _alloc(LANDMARK_SPEC, (L, 0), state.device, ("cams",))
+    cams = _landmark_out(out, "out", ("cams",), L, 0, state.device)["cams"]
     with torch.cuda.device(state.device):
-        _check(lib.ssp_map_window(_ptr(state), _ptr(table), int(table.shape[0]), _ptr(intrinsics), int(intrinsics.shape[0]), L,
+        _check(lib.ssp_map_window(_ptr(state), _ptr(table), int(table.shape[0]), _ptr(intrinsics), n_intr, L,
                                   -1 if n_frames is None else int(n_frames), _ptr(cams), _stream()))
     return cams
+
+
+def _window_inputs(table, pts, first_slot, cams):
+    """A track table with its window's point ring and cameras, as the triangulation and the bundle adjustment take them."""
+    L, point_cap, row_cap = table["L"], table["point_cap"], table["row_cap"]
+    _tensor(table["ids"], "table['ids']", torch.int32, (row_cap, L), "track_table")
+    _count(table["state"], "table['state']", 2 + L)
+    _tensor(pts, "pts", torch.float64, (L, point_cap, 2), "L and point_cap of table")
+    _tensor(cams, "cams", torch.float64, (L, CAM_WORDS), "op_map_window")
+    if not 0 <= int(first_slot) < L:
+        raise ValueError("0 <= first_slot < %d required (got %d)" % (L, first_slot))
+    return L, point_cap, row_cap
 
 
 def op_triangulate_tracks(table, pts, first_slot, cams, min_views=2, min_parallax_deg=1.0, max_reproj=2.0, out=None):
@@ -2172,23 +2146,12 @@ def op_triangulate_tracks(table, pts, first_slot, cams, min_views=2, min_paralla
     "status": int32 [row_cap] (LANDMARK_OK, _FEW_VIEWS, _DEGENERATE, _BEHIND, _REPROJ)} aligned with the table's rows (`out`: a
     landmark_buffers dict; rows at or past the table's n_rows are left as they were).  No host synchronisation."""
     lib = load_library()
-    L, point_cap, row_cap = table["L"], table["point_cap"], table["row_cap"]
-    for t, nm in ((table["ids"], "table['ids']"), (table["state"], "table['state']"), (pts, "pts"), (cams, "cams")):
-        _need_gpu(t, nm)
-    if pts.dtype != torch.float64 or tuple(pts.shape) != (L, point_cap, 2):
-        raise ValueError("pts must be float64 [%d, %d, 2]" % (L, point_cap))
-    if cams.dtype != torch.float64 or tuple(cams.shape) != (L, CAM_WORDS):
-        raise ValueError("cams must be float64 [%d, %d] (op_map_window)" % (L, CAM_WORDS))
-    if table["ids"].dtype != torch.int32 or tuple(table["ids"].shape) != (row_cap, L) or table["state"].dtype != torch.int32 \
-            or table["state"].numel() != 2 + L:
-        raise ValueError("table must be a track table: ids int32 [%d, %d], state int32 [%d]" % (row_cap, L, 2 + L))
-    if not 0 <= int(first_slot) < L:
-        raise ValueError("0 <= first_slot < %d required (got %d)" % (L, first_slot))
+    L, point_cap, row_cap = _window_inputs(table, pts, first_slot, cams)
     if int(min_views) < 2:
         raise ValueError("min_views >= 2 required (got %d)" % min_views)
     if not (0.0 <= float(min_parallax_deg) <= 180.0) or not float(max_reproj) >= 0.0:
         raise ValueError("0 <= min_parallax_deg <= 180 and max_reproj >= 0 required")
-    out = _landmark_out(out, LANDMARK_ROW_KEYS, L, row_cap, pts.device)
+    out = _landmark_out(out, "out", LANDMARK_ROW_KEYS, L, row_cap, pts.device)
     with torch.cuda.device(pts.device):
         _check(lib.ssp_op_triangulate_tracks(_ptr(table["ids"]), _ptr(table["state"]), _ptr(pts), int(first_slot), _ptr(cams), L,
                                              point_cap, row_cap, int(min_views), math.cos(math.radians(float(min_parallax_deg))),
@@ -2204,12 +2167,15 @@ def op_landmarks_select(table, rows, out=None):
     lib = load_library()
     L, point_cap, row_cap = table["L"], table["point_cap"], table["row_cap"]
     dev = table["ids"].device
-    _landmark_out(rows, LANDMARK_ROW_KEYS, L, row_cap, dev)
+    _landmark_out(rows, "rows", LANDMARK_ROW_KEYS, L, row_cap, dev)
     for k in ("ids", "tid", "state"):
         _need_gpu(table[k], "table[%r]" % k)
     if out is None:
         out = landmark_buffers(L, row_cap, dev)
-    _landmark_out(out, ("landmarks", "n_landmarks", "ws"), L, row_cap, dev)
+    _landmark_out(out, "out", ("landmarks", "n_landmarks"), L, row_cap, dev)
+    if "ws" not in out:
+        raise ValueError("out must be the dict of landmark_buffers (no 'ws')")
+    _need_gpu(out["ws"], "out['ws']")
     if out["ws"].numel() < lib.ssp_landmark_workspace_bytes(L, row_cap):
         raise ValueError("out['ws'] is smaller than ssp_landmark_workspace_bytes(%d, %d)" % (L, row_cap))
     with torch.cuda.device(dev):
@@ -2227,6 +2193,10 @@ def landmarks_to_numpy(landmarks, n_landmarks):
 
 # ---- absolute pose from landmarks ----
 PNP_KEYS = ("Rw", "C", "mask", "n_inliers", "winner", "rms", "status")
+PNP_SPEC = (("P", "cap"), {"corr": (torch.float64, ("P", "cap", CORR_WORDS)), "n": (torch.int32, ("P", 2)),
+            "Rw": (torch.float64, ("P", 3, 3)),
+            "C": (torch.float64, ("P", 3)), "mask": (torch.uint8, ("P", "cap")), "n_inliers": (torch.int32, ("P",)),
+            "winner": (torch.int32, ("P",)), "rms": (torch.float64, ("P",)), "status": (torch.int32, ("P",))})
 
 
 def pnp_buffers(n_problems, cap, device):
@@ -2244,26 +2214,31 @@ def pnp_buffers(n_problems, cap, device):
     wsb = lib.ssp_pnp_workspace_bytes(P)
     if wsb == 0:
         _check(-1)
-    f64, i32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int32, device=device)
-    return {"corr": torch.zeros(P, cap, CORR_WORDS, **f64), "n": torch.zeros(P, 2, **i32), "Rw": torch.zeros(P, 3, 3, **f64),
-            "C": torch.zeros(P, 3, **f64), "mask": torch.zeros(P, cap, dtype=torch.uint8, device=device),
-            "n_inliers": torch.zeros(P, **i32), "winner": torch.zeros(P, **i32), "rms": torch.zeros(P, **f64),
-            "status": torch.zeros(P, **i32), "ws": torch.zeros(wsb, dtype=torch.uint8, device=device)}
+    out = _alloc(PNP_SPEC, (P, cap), device)
+    out["ws"] = torch.zeros(wsb, dtype=torch.uint8, device=device)
+    return out
 
 
-def _pnp_out(out, keys, P, cap, device):
+def _pnp_out(out, keys, P, cap, device, sizes):
     if out is None:
         return pnp_buffers(P, cap, device)
-    shapes = {"corr": (P, cap, CORR_WORDS), "n": (P, 2), "Rw": (P, 3, 3), "C": (P, 3), "mask": (P, cap), "n_inliers": (P,),
-              "winner": (P,), "rms": (P,), "status": (P,)}
-    for k in keys:
-        if k not in out:
-            raise ValueError("out must be the dict of pnp_buffers (no %r)" % k)
-        _need_gpu(out[k], "out[%r]" % k)
-        want = torch.uint8 if k == "mask" else (torch.int32 if k in ("n", "n_inliers", "winner", "status") else torch.float64)
-        if out[k].dtype != want or tuple(out[k].shape) != shapes[k] or not out[k].is_contiguous():
-            raise ValueError("out[%r] must be contiguous %s %s (pnp_buffers)" % (k, want, list(shapes[k])))
-    return out
+    return _check_family(out, "out", PNP_SPEC, (P, cap), keys, "pnp_buffers" + sizes)
+
+
+def _landmark_rows(landmarks, n_landmarks):
+    """(landmarks, n_landmarks) of op_landmarks_select; returns row_cap."""
+    _tensor(landmarks, "landmarks", torch.float64, (None, LANDMARK_WORDS), "op_landmarks_select")
+    _count(n_landmarks, "n_landmarks", 1)
+    return landmarks.shape[0]
+
+
+def _frame_matches(match, n_match, pts_new, cap=None):
+    """One pair's match rows against a frame's points: match float32 [cap, 3], n_match int32 [1], pts_new float64 [point_cap, >= 2];
+    returns (cap, point_cap)."""
+    _tensor(match, "match", torch.float32, (cap, 3), None if cap is None else "loop['cap'] rows")
+    _count(n_match, "n_match", 1)
+    _tensor(pts_new, "pts_new", torch.float64, (None, (2, None)), "rows starting (x, y)")
+    return match.shape[0], pts_new.shape[0]
 
 
 def op_landmark_matches(landmarks, n_landmarks, match, n_match, pts_new, out=None):
@@ -2275,21 +2250,11 @@ def op_landmark_matches(landmarks, n_landmarks, match, n_match, pts_new, out=Non
     int32 [2] = (rows, valid rows)); `out`: a pnp_buffers dict of one problem (its "corr" and "n" are filled and views of them
     returned).  No host synchronisation."""
     lib = load_library()
-    for t, nm in ((landmarks, "landmarks"), (n_landmarks, "n_landmarks"), (match, "match"), (n_match, "n_match"), (pts_new, "pts_new")):
-        _need_gpu(t, nm)
-    if landmarks.dtype != torch.float64 or landmarks.dim() != 2 or landmarks.shape[1] != LANDMARK_WORDS or not landmarks.is_contiguous():
-        raise ValueError("landmarks must be contiguous float64 [row_cap, %d] (op_landmarks_select)" % LANDMARK_WORDS)
-    if match.dtype != torch.float32 or match.dim() != 2 or match.shape[1] != 3 or not match.is_contiguous():
-        raise ValueError("match must be contiguous float32 [cap, 3]")
-    if pts_new.dtype != torch.float64 or pts_new.dim() != 2 or pts_new.shape[1] < 2 or not pts_new.is_contiguous():
-        raise ValueError("pts_new must be contiguous float64 [point_cap, >= 2]")
-    for t, nm in ((n_landmarks, "n_landmarks"), (n_match, "n_match")):
-        if t.dtype != torch.int32 or t.numel() != 1:
-            raise ValueError("%s must be int32 [1]" % nm)
-    row_cap, cap, point_cap = landmarks.shape[0], match.shape[0], pts_new.shape[0]
+    row_cap = _landmark_rows(landmarks, n_landmarks)
+    cap, point_cap = _frame_matches(match, n_match, pts_new)
     if not (1 <= cap <= MATCH_MAX_POINTS and 1 <= point_cap <= MATCH_MAX_POINTS and 1 <= row_cap <= TRACK_MAX_LENGTH * MATCH_MAX_POINTS):
         raise ValueError("1 <= cap, point_cap <= %d and 1 <= row_cap <= %d required" % (MATCH_MAX_POINTS, TRACK_MAX_LENGTH * MATCH_MAX_POINTS))
-    out = _pnp_out(out, ("corr", "n"), 1, cap, match.device)
+    out = _pnp_out(out, ("corr", "n"), 1, cap, match.device, " of one problem, cap from match")
     with torch.cuda.device(match.device):
         _check(lib.ssp_op_landmark_matches(_ptr(landmarks), _ptr(n_landmarks), row_cap, _ptr(match), _ptr(n_match), cap, _ptr(pts_new),
                                            int(pts_new.shape[1]), point_cap, _ptr(out["corr"]), _ptr(out["n"]), _stream()))
@@ -2306,30 +2271,38 @@ def op_pnp_ransac(corr, n, intrinsics, seeds, thresh=2.0, min_inliers=6, groups=
     int32 [P], "winner": int32 [P] (the hypothesis, -1), "rms": float64 [P] (pixels), "status": int32 [P] (1 = no pose: Rw = I,
     C = 0, empty mask)}; `out`: a pnp_buffers dict.  No host synchronisation."""
     lib = load_library()
-    for t, nm in ((corr, "corr"), (n, "n"), (intrinsics, "intrinsics"), (seeds, "seeds")):
-        _need_gpu(t, nm)
-    c3 = corr if corr.dim() == 3 else corr[None]
-    if c3.dtype != torch.float64 or c3.dim() != 3 or c3.shape[2] != CORR_WORDS or not c3.is_contiguous():
-        raise ValueError("corr must be contiguous float64 [P, cap, %d] or [cap, %d]" % (CORR_WORDS, CORR_WORDS))
+    _need_gpu(corr, "corr")
+    c3 = corr[None] if corr.dim() == 2 else corr
+    _tensor(c3, "corr", torch.float64, (None, None, CORR_WORDS), "[cap, CORR_WORDS] for one problem")
     P, cap = c3.shape[0], c3.shape[1]
     if not 1 <= cap <= MATCH_MAX_POINTS:
         raise ValueError("1 <= cap <= %d rows per problem (got %d)" % (MATCH_MAX_POINTS, cap))
-    if n.dtype != torch.int32 or n.numel() != P or not n.is_contiguous():
-        raise ValueError("n must be contiguous int32 [%d]" % P)
-    if seeds.dtype != torch.int64 or seeds.numel() != P or not seeds.is_contiguous():
-        raise ValueError("seeds must be contiguous int64 [%d]" % P)
-    if (intrinsics.dtype != torch.float64 or intrinsics.dim() != 2 or intrinsics.shape[1] != 4 or intrinsics.shape[0] not in (1, P)
-            or not intrinsics.is_contiguous()):
-        raise ValueError("intrinsics must be contiguous float64 [1, 4] or [%d, 4] rows (fx, fy, cx, cy)" % P)
+    _count(n, "n", P, hint="one per problem of corr")
+    _count(seeds, "seeds", P, torch.int64)
+    n_intr = _intrinsics(intrinsics, "intrinsics", (4,), P)
     if int(min_inliers) < 4:
         raise ValueError("min_inliers >= 4 required (got %d)" % int(min_inliers))
-    out = _pnp_out(out, PNP_KEYS, P, cap, c3.device)
+    out = _pnp_out(out, PNP_KEYS, P, cap, c3.device, ", P and cap from corr")
     if "ws" not in out or out["ws"].numel() < lib.ssp_pnp_workspace_bytes(P):
         raise ValueError("out['ws'] is smaller than ssp_pnp_workspace_bytes(%d)" % P)
     with torch.cuda.device(c3.device):
-        _check(lib.ssp_pnp_ransac(_ptr(c3), _ptr(n), cap, P, _ptr(intrinsics), int(intrinsics.shape[0]), _ptr(seeds), float(thresh),
+        _check(lib.ssp_pnp_ransac(_ptr(c3), _ptr(n), cap, P, _ptr(intrinsics), n_intr, _ptr(seeds), float(thresh),
                                   int(min_inliers), int(groups), _ptr(out["ws"]), *[_ptr(out[k]) for k in PNP_KEYS], _stream()))
     return {k: out[k] for k in PNP_KEYS}
+
+
+def _absolute_pose(absolute, S=None, keys=("Rw", "C", "status")):
+    """The op_pnp_ransac dict of S problems (None: as many as its "status" holds), its members held by their lengths; returns S."""
+    for k in keys:
+        if k not in absolute:
+            raise ValueError("absolute must be the dict of op_pnp_ransac (no %r)" % k)
+    if S is None:
+        _need_gpu(absolute["status"], "absolute['status']")
+        S = absolute["status"].numel()
+    _count(absolute["status"], "absolute['status']", S, hint="one per sequence")
+    _count(absolute["Rw"], "absolute['Rw']", S * 9, torch.float64, (S, 3, 3), "one per entry of absolute['status']")
+    _count(absolute["C"], "absolute['C']", S * 3, torch.float64, (S, 3), "one per entry of absolute['status']")
+    return S
 
 
 def op_pose_repair(absolute, state, table):
@@ -2342,31 +2315,18 @@ def op_pose_repair(absolute, state, table):
     POSE_FLAG_NO_POSE is cleared and POSE_FLAG_ABSOLUTE set.  Otherwise nothing changes.  Returns (state, table).  No host
     synchronisation."""
     lib = load_library()
-    for k in ("Rw", "C", "status"):
-        if k not in absolute:
-            raise ValueError("absolute must be the dict of op_pnp_ransac (no %r)" % k)
-        _need_gpu(absolute[k], "absolute[%r]" % k)
-    _need_gpu(state, "state")
-    _need_gpu(table, "table")
-    S = absolute["status"].numel()
-    if absolute["status"].dtype != torch.int32 or not absolute["status"].is_contiguous():
-        raise ValueError("absolute['status'] must be contiguous int32 [%d]" % S)
-    for k, m in (("Rw", 9), ("C", 3)):
-        if absolute[k].dtype != torch.float64 or absolute[k].numel() != S * m or not absolute[k].is_contiguous():
-            raise ValueError("absolute[%r] must be the contiguous float64 tensor of op_pnp_ransac" % k)
-    if state.dtype != torch.float64 or state.numel() != S * POSE_STATE_WORDS or not state.is_contiguous():
-        raise ValueError("state must be contiguous float64 [%d, %d] (pose_state)" % (S, POSE_STATE_WORDS))
-    if (table.dtype != torch.float64 or table.dim() not in (2, 3) or table.shape[-1] != POSE_ROW_WORDS or not table.is_contiguous()
-            or table.numel() != S * table.shape[-2] * POSE_ROW_WORDS):
-        raise ValueError("table must be contiguous float64 [%d, capacity, %d] (pose_table)" % (S, POSE_ROW_WORDS))
+    S = _absolute_pose(absolute)
+    capacity = _chain_arrays(state, table, S)
     with torch.cuda.device(state.device):
         _check(lib.ssp_pose_repair(_ptr(absolute["Rw"]), _ptr(absolute["C"]), _ptr(absolute["status"]), S, _ptr(state), _ptr(table),
-                                   int(table.shape[-2]), _stream()))
+                                   capacity, _stream()))
     return state, table
 
 
 # ---- windowed bundle adjustment (DESIGN.md section 28) ----
 BA_KEYS = ("cams", "X", "rms", "info")
+BA_SPEC = (("L", "row_cap"), {"cams": (torch.float64, ("L", CAM_WORDS)), "X": (torch.float64, ("row_cap", 3)),
+           "rms": (torch.float64, ("row_cap",)), "info": (torch.float64, (BA_INFO_WORDS,))})
 
 
 def ba_buffers(max_length, row_cap, device):
@@ -2381,9 +2341,9 @@ def ba_buffers(max_length, row_cap, device):
     wsb = lib.ssp_ba_workspace_bytes(L, row_cap)
     if wsb == 0:
         _check(-1)
-    f64 = dict(dtype=torch.float64, device=device)
-    return {"cams": torch.zeros(L, CAM_WORDS, **f64), "X": torch.zeros(row_cap, 3, **f64), "rms": torch.zeros(row_cap, **f64),
-            "info": torch.zeros(BA_INFO_WORDS, **f64), "ws": torch.zeros(wsb, dtype=torch.uint8, device=device)}
+    out = _alloc(BA_SPEC, (L, row_cap), device)
+    out["ws"] = torch.zeros(wsb, dtype=torch.uint8, device=device)
+    return out
 
 
 def op_bundle_adjust(table, pts, first_slot, cams, rows, iterations=10, out=None):
@@ -2397,37 +2357,17 @@ def op_bundle_adjust(table, pts, first_slot, cams, rows, iterations=10, out=None
     accepted): under the last two the outputs are copies of the inputs.  `out`: a ba_buffers dict (not the inputs' own arrays).
     No host synchronisation."""
     lib = load_library()
-    L, point_cap, row_cap = table["L"], table["point_cap"], table["row_cap"]
-    for k in ("X", "status"):
-        if k not in rows:
-            raise ValueError("rows must be the dict of op_triangulate_tracks (no %r)" % k)
-    for t, nm in ((table["ids"], "table['ids']"), (table["state"], "table['state']"), (pts, "pts"), (cams, "cams"), (rows["X"], "rows['X']"),
-                  (rows["status"], "rows['status']")):
-        _need_gpu(t, nm)
-    if pts.dtype != torch.float64 or tuple(pts.shape) != (L, point_cap, 2) or not pts.is_contiguous():
-        raise ValueError("pts must be contiguous float64 [%d, %d, 2]" % (L, point_cap))
-    if cams.dtype != torch.float64 or tuple(cams.shape) != (L, CAM_WORDS) or not cams.is_contiguous():
-        raise ValueError("cams must be contiguous float64 [%d, %d] (op_map_window)" % (L, CAM_WORDS))
-    if table["ids"].dtype != torch.int32 or tuple(table["ids"].shape) != (row_cap, L) or table["state"].dtype != torch.int32 \
-            or table["state"].numel() != 2 + L:
-        raise ValueError("table must be a track table: ids int32 [%d, %d], state int32 [%d]" % (row_cap, L, 2 + L))
-    if rows["X"].dtype != torch.float64 or tuple(rows["X"].shape) != (row_cap, 3) or not rows["X"].is_contiguous():
-        raise ValueError("rows['X'] must be contiguous float64 [%d, 3]" % row_cap)
-    if rows["status"].dtype != torch.int32 or tuple(rows["status"].shape) != (row_cap,) or not rows["status"].is_contiguous():
-        raise ValueError("rows['status'] must be contiguous int32 [%d]" % row_cap)
-    if not 0 <= int(first_slot) < L:
-        raise ValueError("0 <= first_slot < %d required (got %d)" % (L, first_slot))
+    L, point_cap, row_cap = _window_inputs(table, pts, first_slot, cams)
+    dims = (L, row_cap)
+    _check_family(rows, "rows", LANDMARK_SPEC, dims, ("X", "status"), "op_triangulate_tracks")
     if not 1 <= int(iterations) <= BA_MAX_ITERATIONS:
         raise ValueError("1 <= iterations <= %d required (got %d)" % (BA_MAX_ITERATIONS, int(iterations)))
     if out is None:
         out = ba_buffers(L, row_cap, pts.device)
-    shapes = {"cams": (L, CAM_WORDS), "X": (row_cap, 3), "rms": (row_cap,), "info": (BA_INFO_WORDS,)}
-    for k in BA_KEYS + ("ws",):
-        if k not in out:
-            raise ValueError("out must be the dict of ba_buffers (no %r)" % k)
-        _need_gpu(out[k], "out[%r]" % k)
-        if k != "ws" and (out[k].dtype != torch.float64 or tuple(out[k].shape) != shapes[k] or not out[k].is_contiguous()):
-            raise ValueError("out[%r] must be contiguous float64 %s (ba_buffers)" % (k, list(shapes[k])))
+    _check_family(out, "out", BA_SPEC, dims, BA_KEYS, "ba_buffers")
+    if "ws" not in out:
+        raise ValueError("out must be the dict of ba_buffers (no 'ws')")
+    _need_gpu(out["ws"], "out['ws']")
     if out["ws"].dtype != torch.uint8 or out["ws"].numel() < lib.ssp_ba_workspace_bytes(L, row_cap):
         raise ValueError("out['ws'] is smaller than ssp_ba_workspace_bytes(%d, %d)" % (L, row_cap))
     if out["cams"].data_ptr() == cams.data_ptr() or out["X"].data_ptr() == rows["X"].data_ptr():
@@ -2455,25 +2395,18 @@ def op_ba_apply(adjusted, state, table, max_length, n_frames=None):
     for k in ("info", "cams"):
         if k not in adjusted:
             raise ValueError("adjusted must be the dict of op_bundle_adjust (no %r)" % k)
-        _need_gpu(adjusted[k], "adjusted[%r]" % k)
-    _need_gpu(state, "state")
-    _need_gpu(table, "table")
     info, cams = adjusted["info"], adjusted["cams"]
-    if info.dtype != torch.float64 or info.numel() % BA_INFO_WORDS or info.numel() == 0 or not info.is_contiguous():
-        raise ValueError("adjusted['info'] must be contiguous float64 [S, %d]" % BA_INFO_WORDS)
+    _need_gpu(info, "adjusted['info']")
+    if info.dtype != torch.float64 or info.numel() % BA_INFO_WORDS or info.numel() == 0:
+        raise ValueError("adjusted['info'] must be float64 [S, %d]" % BA_INFO_WORDS)
     S = info.numel() // BA_INFO_WORDS
-    if cams.dtype != torch.float64 or cams.numel() != S * L * CAM_WORDS or not cams.is_contiguous():
-        raise ValueError("adjusted['cams'] must be contiguous float64 [%d, %d, %d]" % (S, L, CAM_WORDS))
-    if state.dtype != torch.float64 or state.numel() != S * POSE_STATE_WORDS or not state.is_contiguous():
-        raise ValueError("state must be contiguous float64 [%d, %d] (pose_state)" % (S, POSE_STATE_WORDS))
-    if (table.dtype != torch.float64 or table.dim() not in (2, 3) or table.shape[-1] != POSE_ROW_WORDS or not table.is_contiguous()
-            or table.numel() != S * table.shape[-2] * POSE_ROW_WORDS):
-        raise ValueError("table must be contiguous float64 [%d, capacity, %d] (pose_table)" % (S, POSE_ROW_WORDS))
+    _count(cams, "adjusted['cams']", S * L * CAM_WORDS, torch.float64, (S, L, CAM_WORDS), "S from adjusted['info'], L = max_length")
+    capacity = _chain_arrays(state, table, S)
     if n_frames is not None and int(n_frames) < 0:
         raise ValueError("n_frames must be non-negative (None: the states' counts)")
     with torch.cuda.device(state.device):
         _check(lib.ssp_ba_apply(_ptr(info), _ptr(cams), L, S, -1 if n_frames is None else int(n_frames), _ptr(state), _ptr(table),
-                                int(table.shape[-2]), _stream()))
+                                capacity, _stream()))
     return state, table
 
 
@@ -2482,6 +2415,10 @@ WORLD_MAX_ROWS = 65536  # SSP_WORLD_MAX_ROWS (include/ssp_hip.h)
 WORLD_STATE_WORDS = 8  # SSP_WORLD_STATE_WORDS: n_rows, anchored, lost_frames, streak, dropped (full), dropped (tid), appended, updated
 POSE_FLAG_WORLD = 16  # SSP_POSE_FLAG_WORLD: the trajectory row was rewritten from a pose against the world map
 WORLD_KEYS = ("X", "desc", "tid", "n_views", "first_frame", "last_frame", "rms", "slot_of_tid", "state")
+WORLD_SPEC = (("map_cap", "tid_cap"), {"X": (torch.float64, ("map_cap", 3)), "desc": (torch.float32, ("map_cap", 256)),
+              "tid": (torch.int32, ("map_cap",)),
+              "n_views": (torch.int32, ("map_cap",)), "first_frame": (torch.int32, ("map_cap",)), "last_frame": (torch.int32, ("map_cap",)),
+              "rms": (torch.float64, ("map_cap",)), "slot_of_tid": (torch.int32, ("tid_cap",)), "state": (torch.int32, (WORLD_STATE_WORDS,))})
 
 
 def world_buffers(map_cap=WORLD_MAX_ROWS, tid_cap=1 << 22, device="cuda"):
@@ -2504,12 +2441,9 @@ def world_buffers(map_cap=WORLD_MAX_ROWS, tid_cap=1 << 22, device="cuda"):
               lib.ssp_world_insert_workspace_bytes(TRACK_MAX_LENGTH * MATCH_MAX_POINTS))
     if wsb == 0:
         _check(-1)
-    f64, i32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int32, device=device)
-    return {"X": torch.zeros(map_cap, 3, **f64), "desc": torch.zeros(map_cap, 256, dtype=torch.float32, device=device),
-            "tid": torch.zeros(map_cap, **i32), "n_views": torch.zeros(map_cap, **i32), "first_frame": torch.zeros(map_cap, **i32),
-            "last_frame": torch.zeros(map_cap, **i32), "rms": torch.zeros(map_cap, **f64), "slot_of_tid": torch.zeros(tid_cap, **i32),
-            "state": torch.zeros(WORLD_STATE_WORDS, **i32), "ws": torch.zeros(wsb, dtype=torch.uint8, device=device),
-            "map_cap": map_cap, "tid_cap": tid_cap}
+    world = _alloc(WORLD_SPEC, (map_cap, tid_cap), device)
+    world.update(ws=torch.zeros(wsb, dtype=torch.uint8, device=device), map_cap=map_cap, tid_cap=tid_cap)
+    return world
 
 
 def _world_map(world):
@@ -2517,13 +2451,7 @@ def _world_map(world):
     if not isinstance(world, dict) or any(k not in world for k in WORLD_KEYS + ("ws", "map_cap", "tid_cap")):
         raise ValueError("world must be the dict of world_buffers")
     map_cap, tid_cap = int(world["map_cap"]), int(world["tid_cap"])
-    shapes = {"X": (map_cap, 3), "desc": (map_cap, 256), "tid": (map_cap,), "n_views": (map_cap,), "first_frame": (map_cap,),
-              "last_frame": (map_cap,), "rms": (map_cap,), "slot_of_tid": (tid_cap,), "state": (WORLD_STATE_WORDS,)}
-    for k in WORLD_KEYS:
-        _need_gpu(world[k], "world[%r]" % k)
-        want = torch.float64 if k in ("X", "rms") else (torch.float32 if k == "desc" else torch.int32)
-        if world[k].dtype != want or tuple(world[k].shape) != shapes[k]:
-            raise ValueError("world[%r] must be contiguous %s %s (world_buffers)" % (k, want, list(shapes[k])))
+    _check_family(world, "world", WORLD_SPEC, (map_cap, tid_cap), WORLD_KEYS, "world_buffers")
     _need_gpu(world["ws"], "world['ws']")
     if not 1 <= map_cap <= WORLD_MAX_ROWS or tid_cap < 1:
         raise ValueError("1 <= map_cap <= %d and tid_cap >= 1 required" % WORLD_MAX_ROWS)
@@ -2543,18 +2471,11 @@ def op_world_insert(world, landmarks, n_landmarks, desc_new, count_new, table, n
     synchronisation."""
     lib = load_library()
     map_cap, tid_cap = _world_map(world)
-    for t, nm in ((landmarks, "landmarks"), (n_landmarks, "n_landmarks"), (desc_new, "desc_new"), (count_new, "count_new"), (table, "table")):
-        _need_gpu(t, nm)
-    if landmarks.dtype != torch.float64 or landmarks.dim() != 2 or landmarks.shape[1] != LANDMARK_WORDS:
-        raise ValueError("landmarks must be contiguous float64 [row_cap, %d] (op_landmarks_select)" % LANDMARK_WORDS)
-    if desc_new.dtype != torch.float32 or desc_new.dim() != 2 or desc_new.shape[1] != 256:
-        raise ValueError("desc_new must be contiguous float32 [point_cap, 256]")
-    for t, nm in ((n_landmarks, "n_landmarks"), (count_new, "count_new")):
-        if t.dtype != torch.int32 or t.numel() != 1:
-            raise ValueError("%s must be int32 [1]" % nm)
-    if table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != POSE_ROW_WORDS:
-        raise ValueError("table must be contiguous float64 [capacity, %d] (pose_table of one sequence)" % POSE_ROW_WORDS)
-    row_cap, point_cap = landmarks.shape[0], desc_new.shape[0]
+    row_cap = _landmark_rows(landmarks, n_landmarks)
+    _tensor(desc_new, "desc_new", torch.float32, (None, 256), "unit rows of the newest frame")
+    _count(count_new, "count_new", 1)
+    _tensor(table, "table", torch.float64, (None, POSE_ROW_WORDS), "pose_table of one sequence")
+    point_cap = desc_new.shape[0]
     if not (1 <= row_cap <= TRACK_MAX_LENGTH * MATCH_MAX_POINTS and 1 <= point_cap <= MATCH_MAX_POINTS):
         raise ValueError("1 <= row_cap <= %d and 1 <= point_cap <= %d required" % (TRACK_MAX_LENGTH * MATCH_MAX_POINTS, MATCH_MAX_POINTS))
     if int(n_frames) < 0 or int(patience) < 0:
@@ -2580,24 +2501,18 @@ def op_match_world(world, desc2, count2, nn_thresh, out=None):
     map_cap, _ = _world_map(world)
     if nn_thresh < 0.0:
         raise ValueError("'nn_thresh' should be non-negative")
-    _need_gpu(desc2, "desc2")
-    _need_gpu(count2, "count2")
-    if desc2.dtype != torch.float32 or desc2.dim() != 2 or desc2.shape[1] != 256:
-        raise ValueError("desc2 must be contiguous float32 [cap, 256]")
+    _tensor(desc2, "desc2", torch.float32, (None, 256), "unit rows")
     cap = desc2.shape[0]
     if not 1 <= cap <= MATCH_MAX_POINTS:
         raise ValueError("1 <= cap <= %d frame rows (got %d)" % (MATCH_MAX_POINTS, cap))
-    if count2.dtype != torch.int32 or count2.numel() != 1:
-        raise ValueError("count2 must be int32 [1]")
+    _count(count2, "count2", 1)
     if world["ws"].numel() < lib.ssp_match_world_workspace_bytes(map_cap, cap):
         raise ValueError("world['ws'] is smaller than ssp_match_world_workspace_bytes(%d, %d)" % (map_cap, cap))
     if out is None:
         out = (torch.empty(cap, 3, dtype=torch.float32, device=desc2.device), torch.empty(1, dtype=torch.int32, device=desc2.device))
     match, n_match = out
-    _need_gpu(match, "out[0]")
-    _need_gpu(n_match, "out[1]")
-    if match.dtype != torch.float32 or tuple(match.shape) != (cap, 3) or n_match.dtype != torch.int32 or n_match.numel() != 1:
-        raise ValueError("out must be (float32 [%d, 3], int32 [1])" % cap)
+    _tensor(match, "out[0]", torch.float32, (cap, 3), "cap rows of desc2")
+    _count(n_match, "out[1]", 1)
     with torch.cuda.device(desc2.device):
         _check(lib.ssp_match_world(_ptr(world["desc"]), _ptr(world["state"]), map_cap, _ptr(desc2), _ptr(count2), cap,
                                    float(np.float32(nn_thresh)), _ptr(world["ws"]), _ptr(match), _ptr(n_match), _stream()))
@@ -2613,19 +2528,11 @@ def op_world_correspondences(world, match, n_match, pts_new, count_new, out=None
     finite; every other row is zero.  No host synchronisation."""
     lib = load_library()
     map_cap, _ = _world_map(world)
-    for t, nm in ((match, "match"), (n_match, "n_match"), (pts_new, "pts_new"), (count_new, "count_new")):
-        _need_gpu(t, nm)
-    if match.dtype != torch.float32 or match.dim() != 2 or match.shape[1] != 3:
-        raise ValueError("match must be contiguous float32 [cap, 3]")
-    if pts_new.dtype != torch.float64 or pts_new.dim() != 2 or pts_new.shape[1] < 2:
-        raise ValueError("pts_new must be contiguous float64 [point_cap, >= 2]")
-    for t, nm in ((n_match, "n_match"), (count_new, "count_new")):
-        if t.dtype != torch.int32 or t.numel() != 1:
-            raise ValueError("%s must be int32 [1]" % nm)
-    cap, point_cap = match.shape[0], pts_new.shape[0]
+    cap, point_cap = _frame_matches(match, n_match, pts_new)
+    _count(count_new, "count_new", 1)
     if not (1 <= cap <= MATCH_MAX_POINTS and 1 <= point_cap <= MATCH_MAX_POINTS):
         raise ValueError("1 <= cap, point_cap <= %d required" % MATCH_MAX_POINTS)
-    out = _pnp_out(out, ("corr", "n"), 1, cap, match.device)
+    out = _pnp_out(out, ("corr", "n"), 1, cap, match.device, " of one problem, cap from match")
     with torch.cuda.device(match.device):
         _check(lib.ssp_op_world_correspondences(_ptr(world["X"]), _ptr(world["state"]), map_cap, _ptr(match), _ptr(n_match), cap,
                                                 _ptr(pts_new), int(pts_new.shape[1]), _ptr(count_new), point_cap, _ptr(out["corr"]),
@@ -2642,24 +2549,11 @@ def op_world_repair(world, absolute, state, table):
     rewritten frames grows by one, and a call that writes nothing zeroes it.  Returns (state, table).  No host synchronisation."""
     lib = load_library()
     map_cap, _ = _world_map(world)
-    for k in ("Rw", "C", "status"):
-        if k not in absolute:
-            raise ValueError("absolute must be the dict of op_pnp_ransac (no %r)" % k)
-        _need_gpu(absolute[k], "absolute[%r]" % k)
-    _need_gpu(state, "state")
-    _need_gpu(table, "table")
-    if absolute["status"].dtype != torch.int32 or absolute["status"].numel() != 1:
-        raise ValueError("absolute['status'] must be int32 [1]: one sequence")
-    for k, m in (("Rw", 9), ("C", 3)):
-        if absolute[k].dtype != torch.float64 or absolute[k].numel() != m:
-            raise ValueError("absolute[%r] must be the contiguous float64 tensor of op_pnp_ransac for one problem" % k)
-    if state.dtype != torch.float64 or state.numel() != POSE_STATE_WORDS:
-        raise ValueError("state must be contiguous float64 [%d] (pose_state of one sequence)" % POSE_STATE_WORDS)
-    if table.dtype != torch.float64 or table.shape[-1] != POSE_ROW_WORDS or table.numel() != table.shape[-2] * POSE_ROW_WORDS:
-        raise ValueError("table must be contiguous float64 [capacity, %d] (pose_table of one sequence)" % POSE_ROW_WORDS)
+    _absolute_pose(absolute, 1)
+    capacity = _chain_arrays(state, table, 1)
     with torch.cuda.device(state.device):
         _check(lib.ssp_world_repair(_ptr(absolute["Rw"]), _ptr(absolute["C"]), _ptr(absolute["status"]), _ptr(state), _ptr(table),
-                                    int(table.shape[-2]), map_cap, _ptr(world["state"]), _stream()))
+                                    capacity, map_cap, _ptr(world["state"]), _stream()))
     return state, table
 
 
@@ -2673,6 +2567,10 @@ LOOP_INFO_WORDS = 8  # SSP_LOOP_INFO_WORDS: status, cost before, cost after, nod
 LOOP_MAX_ITERATIONS = 64  # SSP_LOOP_MAX_ITERATIONS
 POSE_FLAG_LOOP = 32  # SSP_POSE_FLAG_LOOP: the trajectory row was rewritten by a loop closure
 LOOP_KEYS = ("corr", "xnew", "n", "edges", "state", "cand", "Rw", "C", "sigma", "info")
+LOOP_SPEC = (("cap", "capacity"), {"corr": (torch.float64, ("cap", CORR_WORDS)), "xnew": (torch.float64, ("cap", 4)), "n": (torch.int32, (3,)),
+             "edges": (torch.float64, (LOOP_MAX_EDGES, LOOP_EDGE_WORDS)), "state": (torch.int32, (LOOP_STATE_WORDS,)),
+             "cand": (torch.float64, (LOOP_CAND_WORDS,)), "Rw": (torch.float64, ("capacity", 9)), "C": (torch.float64, ("capacity", 3)),
+             "sigma": (torch.float64, ("capacity",)), "info": (torch.float64, (LOOP_INFO_WORDS,))})
 
 
 def loop_buffers(cap, capacity, device="cuda"):
@@ -2693,12 +2591,9 @@ def loop_buffers(cap, capacity, device="cuda"):
     wsb = lib.ssp_pose_graph_workspace_bytes(capacity)
     if wsb == 0:
         _check(-1)
-    f64, i32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int32, device=device)
-    return {"corr": torch.zeros(cap, CORR_WORDS, **f64), "xnew": torch.zeros(cap, 4, **f64), "n": torch.zeros(3, **i32),
-            "edges": torch.zeros(LOOP_MAX_EDGES, LOOP_EDGE_WORDS, **f64), "state": torch.zeros(LOOP_STATE_WORDS, **i32),
-            "cand": torch.zeros(LOOP_CAND_WORDS, **f64), "Rw": torch.zeros(capacity, 9, **f64), "C": torch.zeros(capacity, 3, **f64),
-            "sigma": torch.zeros(capacity, **f64), "info": torch.zeros(LOOP_INFO_WORDS, **f64),
-            "ws": torch.zeros(wsb, dtype=torch.uint8, device=device), "cap": cap, "capacity": capacity}
+    loop = _alloc(LOOP_SPEC, (cap, capacity), device)
+    loop.update(ws=torch.zeros(wsb, dtype=torch.uint8, device=device), cap=cap, capacity=capacity)
+    return loop
 
 
 def _loop_bufs(loop):
@@ -2706,14 +2601,7 @@ def _loop_bufs(loop):
     if not isinstance(loop, dict) or any(k not in loop for k in LOOP_KEYS + ("ws", "cap", "capacity")):
         raise ValueError("loop must be the dict of loop_buffers")
     cap, capacity = int(loop["cap"]), int(loop["capacity"])
-    shapes = {"corr": (cap, CORR_WORDS), "xnew": (cap, 4), "n": (3,), "edges": (LOOP_MAX_EDGES, LOOP_EDGE_WORDS),
-              "state": (LOOP_STATE_WORDS,), "cand": (LOOP_CAND_WORDS,), "Rw": (capacity, 9), "C": (capacity, 3), "sigma": (capacity,),
-              "info": (LOOP_INFO_WORDS,)}
-    for k in LOOP_KEYS:
-        _need_gpu(loop[k], "loop[%r]" % k)
-        want = torch.int32 if k in ("n", "state") else torch.float64
-        if loop[k].dtype != want or tuple(loop[k].shape) != shapes[k] or not loop[k].is_contiguous():
-            raise ValueError("loop[%r] must be contiguous %s %s (loop_buffers)" % (k, want, list(shapes[k])))
+    _check_family(loop, "loop", LOOP_SPEC, (cap, capacity), LOOP_KEYS, "loop_buffers")
     _need_gpu(loop["ws"], "loop['ws']")
     if not 1 <= cap <= MATCH_MAX_POINTS or capacity < 2:
         raise ValueError("1 <= cap <= %d and capacity >= 2 required" % MATCH_MAX_POINTS)
@@ -2721,11 +2609,7 @@ def _loop_bufs(loop):
 
 
 def _loop_table(table, capacity):
-    _need_gpu(table, "table")
-    if (table.dtype != torch.float64 or table.dim() != 2 or tuple(table.shape) != (capacity, POSE_ROW_WORDS)
-            or not table.is_contiguous()):
-        raise ValueError("table must be contiguous float64 [%d, %d] (pose_table of one sequence, loop['capacity'] rows)"
-                         % (capacity, POSE_ROW_WORDS))
+    _tensor(table, "table", torch.float64, (capacity, POSE_ROW_WORDS), "pose_table of one sequence, loop['capacity'] rows")
 
 
 def op_loop_correspondences(world, match, n_match, pts_new, count_new, landmarks, n_landmarks, frame, min_gap, loop):
@@ -2738,19 +2622,9 @@ def op_loop_correspondences(world, match, n_match, pts_new, count_new, landmarks
     lib = load_library()
     map_cap, _ = _world_map(world)
     cap, _ = _loop_bufs(loop)
-    for t, nm in ((match, "match"), (n_match, "n_match"), (pts_new, "pts_new"), (count_new, "count_new"), (landmarks, "landmarks"),
-                  (n_landmarks, "n_landmarks")):
-        _need_gpu(t, nm)
-    if match.dtype != torch.float32 or tuple(match.shape) != (cap, 3) or not match.is_contiguous():
-        raise ValueError("match must be contiguous float32 [%d, 3] (loop['cap'] rows)" % cap)
-    if pts_new.dtype != torch.float64 or pts_new.dim() != 2 or pts_new.shape[1] < 2 or not pts_new.is_contiguous():
-        raise ValueError("pts_new must be contiguous float64 [point_cap, >= 2]")
-    if landmarks.dtype != torch.float64 or landmarks.dim() != 2 or landmarks.shape[1] != LANDMARK_WORDS or not landmarks.is_contiguous():
-        raise ValueError("landmarks must be contiguous float64 [row_cap, %d] (op_landmarks_select)" % LANDMARK_WORDS)
-    for t, nm in ((n_match, "n_match"), (count_new, "count_new"), (n_landmarks, "n_landmarks")):
-        if t.dtype != torch.int32 or t.numel() != 1:
-            raise ValueError("%s must be int32 [1]" % nm)
-    point_cap, row_cap = pts_new.shape[0], landmarks.shape[0]
+    _, point_cap = _frame_matches(match, n_match, pts_new, cap)
+    _count(count_new, "count_new", 1)
+    row_cap = _landmark_rows(landmarks, n_landmarks)
     if not (1 <= point_cap <= MATCH_MAX_POINTS and 1 <= row_cap <= TRACK_MAX_LENGTH * MATCH_MAX_POINTS):
         raise ValueError("1 <= point_cap <= %d and 1 <= row_cap <= %d required" % (MATCH_MAX_POINTS, TRACK_MAX_LENGTH * MATCH_MAX_POINTS))
     if int(frame) < 0 or int(min_gap) < 1:
@@ -2776,17 +2650,8 @@ def op_loop_edge(world, absolute, table, frame, loop, min_inliers=12, cooldown=3
     map_cap, _ = _world_map(world)
     cap, capacity = _loop_bufs(loop)
     _loop_table(table, capacity)
-    for k in ("Rw", "C", "mask", "status"):
-        if k not in absolute:
-            raise ValueError("absolute must be the dict of op_pnp_ransac (no %r)" % k)
-        _need_gpu(absolute[k], "absolute[%r]" % k)
-    if absolute["status"].dtype != torch.int32 or absolute["status"].numel() != 1:
-        raise ValueError("absolute['status'] must be int32 [1]: one sequence")
-    for k, m in (("Rw", 9), ("C", 3)):
-        if absolute[k].dtype != torch.float64 or absolute[k].numel() != m or not absolute[k].is_contiguous():
-            raise ValueError("absolute[%r] must be the contiguous float64 tensor of op_pnp_ransac for one problem" % k)
-    if absolute["mask"].dtype != torch.uint8 or absolute["mask"].numel() != cap or not absolute["mask"].is_contiguous():
-        raise ValueError("absolute['mask'] must be contiguous uint8 [%d]" % cap)
+    _absolute_pose(absolute, 1, ("Rw", "C", "mask", "status"))
+    _count(absolute["mask"], "absolute['mask']", cap, torch.uint8, hint="loop['cap'] rows")
     if int(frame) < 0 or int(min_inliers) < 4 or int(cooldown) < 0:
         raise ValueError("frame >= 0, min_inliers >= 4 and cooldown >= 0 required")
     if not (float(weight) > 0.0 and np.isfinite(float(weight))):
@@ -2833,9 +2698,7 @@ def op_loop_apply(world, state, table, frame, loop):
     map_cap, _ = _world_map(world)
     _, capacity = _loop_bufs(loop)
     _loop_table(table, capacity)
-    _need_gpu(state, "state")
-    if state.dtype != torch.float64 or state.numel() != POSE_STATE_WORDS or not state.is_contiguous():
-        raise ValueError("state must be contiguous float64 [%d] (pose_state of one sequence)" % POSE_STATE_WORDS)
+    _count(state, "state", POSE_STATE_WORDS, torch.float64, hint="pose_state of one sequence")
     if int(frame) < 0:
         raise ValueError("frame >= 0 required (got %d)" % int(frame))
     with torch.cuda.device(table.device):
@@ -2851,10 +2714,7 @@ def op_eval_pixel_homographies(hn, height, width):
     utils/utils.py:291-294, in closed form); hom_inv = adj(hom) / det(hom), which is not np.linalg.inv bit for bit
     (DESIGN.md section 21).  No host synchronisation."""
     lib = load_library()
-    _need_gpu(hn, "hn")
-    if hn.dtype != torch.float32 or hn.dim() != 3 or tuple(hn.shape[1:]) != (3, 3) or hn.shape[0] < 1:
-        raise ValueError("hn must be float32 [P,3,3] (got %s %s)" % (hn.dtype, tuple(hn.shape)))
-    hn = hn.contiguous()
+    _tensor(hn, "hn", torch.float32, ((1, None), 3, 3))
     P = hn.shape[0]
     hom = torch.empty(P, 3, 3, dtype=torch.float64, device=hn.device)
     inv = torch.empty(P, 3, 3, dtype=torch.float64, device=hn.device)
@@ -2883,12 +2743,8 @@ def op_eval_accumulate(rows, state, first_pair, rep=None, ransac=None, ap=None, 
     (float64 [P,3,3], the true pixel homographies), or None for all four (homography metrics off).  corner_shape: the
     (height, width) whose corners measure correctness.  Updates rows and state in place; no host synchronisation."""
     lib = load_library()
-    _need_gpu(rows, "rows")
-    _need_gpu(state, "state")
-    if rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[1] != EVAL_ROW_WORDS or rows.shape[0] < 1 or not rows.is_contiguous():
-        raise ValueError("rows must be contiguous float64 [capacity, %d] (eval_metrics_state)" % EVAL_ROW_WORDS)
-    if state.dtype != torch.float64 or tuple(state.shape) != (EVAL_STATE_WORDS,) or not state.is_contiguous():
-        raise ValueError("state must be float64 [%d] (eval_metrics_state)" % EVAL_STATE_WORDS)
+    _tensor(rows, "rows", torch.float64, ((1, None), EVAL_ROW_WORDS), "eval_metrics_state")
+    _tensor(state, "state", torch.float64, (EVAL_STATE_WORDS,), "eval_metrics_state")
     group = (ransac, ap, n1, hom)
     if any(g is None for g in group) and not all(g is None for g in group):
         raise ValueError("ransac, ap, n1 and hom come together or not at all")
@@ -2901,23 +2757,19 @@ def op_eval_accumulate(rows, state, first_pair, rep=None, ransac=None, ap=None, 
         raise ValueError("first_pair >= 0 required")
     if len(thresholds) != 6 or len(corner_shape) != 2:
         raise ValueError("six thresholds and a (height, width) corner shape are required")
+    src = "P from rep" if rep is not None else "P from ap"
     if rep is not None:
-        _need_gpu(rep, "rep")
-        if rep.dtype != torch.float64 or tuple(rep.shape) != (P, 8) or not rep.is_contiguous():
-            raise ValueError("rep must be contiguous float64 [%d,8]" % P)
+        _tensor(rep, "rep", torch.float64, (P, 8), "op_eval_repeatability")
     H = ninl = status = None
     if ransac is not None:
-        H, ninl, status = ransac["H"], ransac["n_inliers"], ransac["status"]
-        for t, nm, dt, shp in ((H, "H", torch.float64, (P, 3, 3)), (ninl, "n_inliers", torch.int32, (P,)),
-                               (status, "status", torch.int32, (P,)), (ap, "ap", torch.float64, (P,)),
-                               (hom, "hom", torch.float64, (P, 3, 3))):
-            _need_gpu(t, nm)
-            if t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
-                raise ValueError("%s must be contiguous %s %s" % (nm, dt, list(shp)))
-        _need_gpu(n1, "n1")
-        if n1.dtype != torch.int32 or n1.dim() != 1 or int(pair_stride) < 1 or n1.numel() < (P - 1) * int(pair_stride) + 1 \
-                or not n1.is_contiguous():
-            raise ValueError("n1 must be contiguous int32 with an entry at p * pair_stride for each of the %d pairs" % P)
+        H = _tensor(ransac["H"], "ransac['H']", torch.float64, (P, 3, 3), src)
+        ninl = _tensor(ransac["n_inliers"], "ransac['n_inliers']", torch.int32, (P,), src)
+        status = _tensor(ransac["status"], "ransac['status']", torch.int32, (P,), src)
+        _tensor(ap, "ap", torch.float64, (P,), src)
+        _tensor(hom, "hom", torch.float64, (P, 3, 3), src)
+        if int(pair_stride) < 1:
+            raise ValueError("pair_stride >= 1 required (got %d)" % int(pair_stride))
+        _tensor(n1, "n1", torch.int32, (((P - 1) * int(pair_stride) + 1, None),), "an entry at p * pair_stride for each pair; " + src)
     thr = (C.c_double * 6)(*[float(t) for t in thresholds])
     with torch.cuda.device(rows.device):
         _check(lib.ssp_eval_accumulate(_ptr(rep), _ptr(H), _ptr(ninl), _ptr(status), _ptr(ap), _ptr(n1), int(pair_stride),
