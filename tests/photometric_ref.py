@@ -373,7 +373,9 @@ def apply(img, row, tau=None, mutant=None):
 # blur: angle 0 / direction 0 gives the column [1/3, 1/3, 1/3], angle 90 / direction -1 the row [0, 1/3, 2/3]-type kernels:
 # sums of thirds are never within 1e-3 of .5.
 SHADE_ELLIPSES = {(240, 320): [(100.0, 90.0, 40.0, 25.0, 19.0), (220.0, 150.0, 30.0, 55.0, 72.0), (160.0, 120.0, 12.0, 17.0, 33.0)],
-                  (67, 93): [(40.0, 30.0, 14.0, 9.0, 17.0), (60.0, 40.0, 7.0, 16.0, 71.0)]}
+                  (67, 93): [(40.0, 30.0, 14.0, 9.0, 17.0), (60.0, 40.0, 7.0, 16.0, 71.0)],
+                  # the smallest height whose shade strip takes the 16-column tile (photo_shade_lds_bytes(388, 32) > 64 KiB), one tile wide
+                  (388, 16): [(8.0, 200.0, 5.0, 70.0, 19.0), (4.0, 90.0, 3.0, 40.0, 72.0)]}
 
 
 def _flag_off(row):

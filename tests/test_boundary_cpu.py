@@ -618,9 +618,10 @@ RETIRED_SWITCHES = ("SSP_BN_LAZY", "SSP_FUSE_APPLY", "SSP_TAIL_MERGE", "SSP_PACK
 
 
 def test_host_layer_reads_only_the_kept_switches_and_launches_lds_kernels_one_way():
-    """The host launch layer (csrc/ssp.hip, csrc/bf16_host.hip.h) reads exactly the kept SSP_* environment switches, each through
-    its one accessor on top of env_int (the only getenv of the library); no retired A/B switch is named anywhere in csrc/; and the
-    per-(kernel, device) dynamic-LDS attribute flag AttrOnce is used by launch_lds alone."""
+    """The host launch layer (csrc/ssp.hip, csrc/bf16_host.hip.h, csrc/ops_host.hip.h) reads exactly the kept SSP_* environment
+    switches, each through its one accessor on top of env_int (the only getenv of the library); no retired A/B switch is named
+    anywhere in csrc/; the per-(kernel, device) dynamic-LDS attribute flag AttrOnce is used by launch_lds alone, and
+    hipFuncSetAttribute is called by launch_lds and the occupancy probe alone."""
     csrc = os.path.join(ROOT, "semantic-superpoint_amd", "csrc")
     text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hip.h"))}
     code = {f: re.sub(r"//[^\n]*", "", t) for f, t in text.items()}   # (no /* */ comment in csrc holds code words)
@@ -643,3 +644,9 @@ def test_host_layer_reads_only_the_kept_switches_and_launches_lds_kernels_one_wa
     m = re.search(r"static int launch_lds\(.*?\n\}\n", src, re.S)
     assert m and m.start() < uses[1][1] < m.end()
     assert len(re.findall(r"\.need\(\)", whole)) == 1
+    # hipFuncSetAttribute: inside launch_lds and the occupancy probe ssp_debug_occupancy, nowhere else (no per-call site)
+    sets = [(f, m.start()) for f, t in code.items() for m in re.finditer(r"\bhipFuncSetAttribute\b", t)]
+    probe = re.search(r"int ssp_debug_occupancy\(.*?\n\}\n", src, re.S)
+    assert probe and sets and {f for f, _ in sets} == {"ssp.hip"}, sets
+    outside = [pos for _, pos in sets if not (m.start() < pos < m.end() or probe.start() < pos < probe.end())]
+    assert not outside and sum(m.start() < pos < m.end() for _, pos in sets) == 1, sets

@@ -163,7 +163,7 @@ def test_lane_order_sum_is_a_reordering():
 def test_lds_boundaries_of_the_launchers():
     """eval_ransac_kernel stages cap * (sizeof(double4) + 5) = 37 cap bytes; it needs more than the 64 KiB a kernel gets without
     asking from cap 1772 and leaves LDS for global memory from cap 3322 (EVAL_LDS_MAX); the caps of the GPU test sit on both."""
-    src = open(os.path.join(ROOT, "semantic-superpoint_amd", "csrc", "ssp.hip")).read()
+    src = open(os.path.join(ROOT, "semantic-superpoint_amd", "csrc", "ops_host.hip.h")).read()
     m = re.search(r"#define EVAL_LDS_MAX \((\d+) \* 1024\)", src)
     lds_max = int(m.group(1)) * 1024
     assert "const size_t small = (size_t)cap * (sizeof(float) + 1);" in src

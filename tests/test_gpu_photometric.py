@@ -27,7 +27,7 @@ def _aug(golden_dir):
         return json.load(f)
 
 
-@pytest.mark.parametrize("hw", [(240, 320), (67, 93)])
+@pytest.mark.parametrize("hw", [(240, 320), (67, 93), (388, 16)])
 def test_apply_matches_the_restatement(hw):
     """Stages 1-7 exactly (multiples of 1/255) outside the helper's tie set, which must stay under 0.1 % of the pixels and
     may differ by one level; the shade at SHADE_TOL absolute."""

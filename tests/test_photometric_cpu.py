@@ -105,7 +105,7 @@ def test_motion_blur_weights():
     assert np.allclose(R.motion_blur_weights(0.0, 0.0)[:, 1], 1 / 3) and np.allclose(R.motion_blur_weights(90.0, -1.0)[1], [2 / 3, 1 / 3, 0])
 
 
-@pytest.mark.parametrize("hw", [(240, 320), (67, 93)])
+@pytest.mark.parametrize("hw", [(240, 320), (67, 93), (388, 16)])
 def test_exact_cases_meet_their_conditions(hw):
     """The conditions the exact GPU comparison rests on, checked on the helper itself: fewer than 0.1 % of the pixels within
     1e-3 of a rounding tie, and no pixel centre within 2e-5 of an ellipse's edge in f = (x'/ax)^2 + (y'/ay)^2 (the fp32
@@ -122,3 +122,22 @@ def test_exact_cases_meet_their_conditions(hw):
         assert out.min() >= 0.0 and out.max() <= 1.0
         if row[R.KSIZE] > 0:
             assert R.ellipse_mask(row, *hw)[1] > 2e-5, name
+
+
+def test_tile_case_height_is_read_from_the_header():
+    """The (388, 16) case of the exact tests stands for the 16-column tile of ssp_op_photometric_apply: 388 is the smallest height
+    whose shade strip exceeds 64 KiB at 32 columns, by the header's own photo_shade_lds_bytes (its return expression, evaluated
+    here), and it fits at 16 columns."""
+    import re
+    from semantic_superpoint_amd import lib as L
+    with open(os.path.join(os.path.dirname(L.__file__), "csrc", "photo_kernels.hip.h")) as f:
+        src = f.read()
+    body = re.search(r"size_t photo_shade_lds_bytes\(int H, int tx\) \{\s*return (.*?);", src, re.S).group(1).replace("(size_t)", "")
+    ext = re.search(r"int photo_ext_width\(int tx\) \{ return (.*?); \}", src).group(1)
+    names = {"PHOTO_MAX_KSIZE": L.PHOTO_MAX_KSIZE, "PHOTO_MAX_ELLIPSES": L.PHOTO_MAX_ELLIPSES, "PHOTO_HALO": (L.PHOTO_MAX_KSIZE - 1) // 2,
+             "PHOTO_BAND": int(re.search(r"PHOTO_BAND = (\d+)", src).group(1))}
+    names["photo_ext_width"] = lambda tx: eval(ext, dict(names, tx=tx))
+    lds = lambda H, tx: eval("(%s)" % body, dict(names, H=H, tx=tx))  # noqa: E731
+    tall = [hw for hw in R.SHADE_ELLIPSES if lds(hw[0], 32) > 65536]
+    assert tall == [(388, 16)] and lds(387, 32) <= 65536 < lds(388, 32) and lds(388, 16) <= 65536
+    assert all(lds(hw[0], 32) <= 65536 for hw in R.SHADE_ELLIPSES if hw != (388, 16))
