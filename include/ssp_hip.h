@@ -849,6 +849,48 @@ int ssp_op_world_correspondences(const double* x_dev, const int32_t* state_dev, 
 int ssp_world_repair(const double* rw_dev, const double* c_dev, const int32_t* status_dev, double* state_dev, double* table_dev,
                      int capacity, int map_cap, int32_t* world_state_dev, void* stream);
 
+/* ---- world map upkeep ----------------------------------------------------------------------------
+ * One call per frame, right after ssp_op_world_insert and with the arrays that call got: it merges the row pair of a scene point
+ * that returned under a new track id, culls rows that never matured, evicts the least valuable rows when the map nears its
+ * capacity, and compacts the store, so that no dead row is ever visible between calls.  The rules are restated in numpy by
+ * tests/world_upkeep_ref.py.  No call synchronises with the host or allocates.
+ *   match_dev [cap][3] / n_match_dev [1]: the frame's ssp_match_world rows, computed before the insert (an anchored insert only
+ *   appends and updates, so they still name the same rows); landmarks_dev [row_cap][SSP_LANDMARK_WORDS] / n_landmarks_dev [1],
+ *   count_new_dev [1], point_cap: as given to the insert; pts_new_dev fp64 [point_cap][pt_stride]: the frame's points (x, y);
+ *   table_dev [capacity][SSP_POSE_ROW_WORDS] and n_frames: the newest row is f = n_frames - 1; intr_dev fp64 [4] = (fx, fy, cx, cy).
+ * The call does nothing, and sets report word 7, unless state[1] (anchored) == 1, n_rows > 0 and row f exists.  Four phases, each
+ * later one on the rows still alive:
+ *   merge (params->merge != 0): for match row (r, p), q = the lowest landmark row that passes the insert's test and names point p,
+ *     t' its track id, r' its slot; the pair merges iff r' >= 0, r' != r, last_frame[r] < f, last_frame[r'] == f, X[r] has a finite
+ *     positive depth under (Rw, C) of row f and its squared reprojection error against pts_new[p] is <= merge_thresh^2 (fp64,
+ *     ssp_pnp_ransac's residual).  The lower slot survives with r''s tid, X, rms, n_views, descriptor, last_frame = f and the
+ *     smaller first_frame; slot_of_tid[t'] names it; the other row dies.
+ *   cull (cull_age >= 0): a row dies iff last_frame < f - cull_age and n_views < cull_min_views.
+ *   evict (high_water >= 0; 0 <= low_water <= high_water <= map_cap): if the rows alive exceed high_water, the k = min(alive -
+ *     low_water, rows with last_frame != f) rows of smallest key (min(max(n_views, 0), 255), max(last_frame, 0), 65535 - slot) die.
+ *   compact: survivors keep their order; all nine arrays move, slot_of_tid is rewritten for the rows that moved, state[0] becomes the
+ *     new count.  When nothing died the store, slot_of_tid and state are left as they were.
+ * report_dev int32 [SSP_WORLD_UPKEEP_REPORT_WORDS] = (rows before, merged, culled, evicted, rows after, eviction fired, rows wanted
+ * but protected, skipped); totals_dev int64 [4] (or NULL) += (merged, culled, evicted, 1).
+ * workspace_dev: ssp_world_upkeep_workspace_bytes(map_cap) bytes (0 = bad arguments). */
+#define SSP_WORLD_UPKEEP_REPORT_WORDS 8
+typedef struct ssp_world_upkeep_params {
+  int merge;            /* 0: no merging */
+  double merge_thresh;  /* pixels */
+  int cull_age;         /* negative: no culling */
+  int cull_min_views;
+  int high_water;       /* negative: no eviction */
+  int low_water;
+} ssp_world_upkeep_params;
+size_t ssp_world_upkeep_workspace_bytes(int map_cap);
+int ssp_op_world_upkeep(const float* match_dev, const int32_t* n_match_dev, int cap, const double* landmarks_dev,
+                        const int32_t* n_landmarks_dev, int row_cap, const double* pts_new_dev, int pt_stride,
+                        const int32_t* count_new_dev, int point_cap, const double* table_dev, int capacity, int n_frames,
+                        const double* intr_dev, const ssp_world_upkeep_params* params, int map_cap, int tid_cap, double* x_dev,
+                        float* desc_dev, int32_t* tid_dev, int32_t* views_dev, int32_t* first_dev, int32_t* last_dev, double* rms_dev,
+                        int32_t* slot_of_tid_dev, int32_t* state_dev, int32_t* report_dev, int64_t* totals_dev, void* workspace_dev,
+                        void* stream);
+
 /* ---- loop closure --------------------------------------------------------------------------------
  * A frame's map matches against the OLD rows of the world map, the loop edge measured from the pose found against them, a Sim(3)
  * pose graph over the trajectory rows since the old place was last seen, and the write-back.  The rules are restated in numpy by

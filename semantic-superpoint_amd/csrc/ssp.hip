@@ -42,6 +42,7 @@
 #include "pnp_kernels.hip.h"
 #include "ba_kernels.hip.h"
 #include "world_kernels.hip.h"
+#include "world_upkeep_kernels.hip.h"
 #include "loop_kernels.hip.h"
 #include "detector_eval_kernels.hip.h"
 #include "sem_kernels.hip.h"
@@ -3211,4 +3212,5 @@ int ssp_debug_buffer(ssp_handle* h, int slot, const char* name, float** ptr, siz
 // ---- operator-level entry points ------------------------------------------------------------------
 extern "C" {
 #include "ops_host.hip.h"
+#include "world_upkeep_host.hip.h"
 }  // extern "C"

@@ -102,6 +102,11 @@ class SspDetEvalParams(C.Structure):
                 ("prob_thresh", C.c_float), ("simplified", C.c_int32)]
 
 
+class SspWorldUpkeepParams(C.Structure):
+    _fields_ = [("merge", C.c_int32), ("merge_thresh", C.c_double), ("cull_age", C.c_int32), ("cull_min_views", C.c_int32),
+                ("high_water", C.c_int32), ("low_water", C.c_int32)]
+
+
 class SspExportParams(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("conf_thresh", C.c_float),
                 ("nms_dist", C.c_int32), ("border_remove", C.c_int32), ("top_k", C.c_int32), ("subpixel", C.c_int32)]
@@ -216,6 +221,8 @@ def _signatures():
         "ssp_match_world": ([vp, vp, i, vp, vp, i, f, vp, vp, vp, vp], i),
         "ssp_op_world_correspondences": ([vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, vp], i),
         "ssp_world_repair": ([vp] * 5 + [i, i, vp, vp], i),
+        "ssp_world_upkeep_workspace_bytes": ([i], sz),
+        "ssp_op_world_upkeep": ([vp, vp, i, vp, vp, i, vp, i, vp, i, vp, i, i, vp, vp, i, i] + [vp] * 13, i),
         "ssp_pose_graph_workspace_bytes": ([i], sz),
         "ssp_op_loop_correspondences": ([vp, vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, i, i, i, vp, vp, vp, vp], i),
         "ssp_loop_edge": ([vp] * 7 + [i, vp, i, vp, i, i, i, i, d, vp, vp, vp, vp], i),
@@ -2555,6 +2562,83 @@ def op_world_repair(world, absolute, state, table):
         _check(lib.ssp_world_repair(_ptr(absolute["Rw"]), _ptr(absolute["C"]), _ptr(absolute["status"]), _ptr(state), _ptr(table),
                                     capacity, map_cap, _ptr(world["state"]), _stream()))
     return state, table
+
+
+# ---- world map upkeep ----
+WORLD_UPKEEP_REPORT_WORDS = 8  # SSP_WORLD_UPKEEP_REPORT_WORDS: rows before, merged, culled, evicted, rows after, fired, protected, skipped
+UPKEEP_KEYS = ("report", "totals")
+UPKEEP_SPEC = ((), {"report": (torch.int32, (WORLD_UPKEEP_REPORT_WORDS,)), "totals": (torch.int64, (4,))})
+
+
+def world_upkeep_buffers(map_cap=WORLD_MAX_ROWS, device="cuda"):
+    """The device arrays of op_world_upkeep for a map of map_cap rows, zeroed: {"ws": its scratch (the
+    staging store of the compaction: about 1.1 KB per row), "report": int32 [WORLD_UPKEEP_REPORT_WORDS] of the last call, "totals":
+    int64 [4] = the running sums of (merged, culled, evicted, calls), added to on the device} plus the host-known "map_cap"."""
+    lib = load_library()
+    map_cap = int(map_cap)
+    if not 1 <= map_cap <= WORLD_MAX_ROWS:
+        raise ValueError("1 <= map_cap <= %d required (got %d)" % (WORLD_MAX_ROWS, map_cap))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("world_upkeep_buffers needs a HIP device: the MI355X path has no CPU fallback")
+    wsb = lib.ssp_world_upkeep_workspace_bytes(map_cap)
+    if wsb == 0:
+        _check(-1)
+    upkeep = _alloc(UPKEEP_SPEC, (), device)
+    upkeep.update(ws=torch.zeros(wsb, dtype=torch.uint8, device=device), map_cap=map_cap)
+    return upkeep
+
+
+def op_world_upkeep(world, match, n_match, landmarks, n_landmarks, pts_new, count_new, table, n_frames, intrinsics, upkeep,
+                    merge=True, merge_thresh=2.0, cull_age=-1, cull_min_views=3, high_water=-1, low_water=0):
+    """Upkeep of the world map (ssp_op_world_upkeep), in place, right after op_world_insert and with its
+    arguments: world, landmarks, n_landmarks, count_new, table, n_frames as given to the insert; match float32 [cap, 3] / n_match
+    int32 [1] of op_match_world for this frame, computed before the insert; pts_new float64 [point_cap, >= 2], the frame's points;
+    intrinsics float64 of 4 entries (fx, fy, cx, cy); upkeep: the dict of world_upkeep_buffers(world["map_cap"]).  With f =
+    n_frames - 1, and only when the map is anchored, has rows and row f exists (else report[7] = 1 and nothing changes):
+    merge: match row (r, p) whose point p is the newest observation of landmark row q with track t', r' = the slot of t', merges iff
+    r' != r, last_frame[r] < f, last_frame[r'] == f and X[r] lies in front of frame f's camera and reprojects within merge_thresh
+    pixels of pts_new[p]; the lower slot survives with r''s row and the smaller first_frame.  cull (cull_age >= 0): a row dies iff
+    last_frame < f - cull_age and n_views < cull_min_views.  evict (high_water >= 0; 0 <= low_water <= high_water <= map_cap): when
+    more than high_water rows are alive, the min(alive - low_water, rows not seen in f) rows of smallest (min(n_views, 255),
+    last_frame, 65535 - slot) die.  compact: survivors keep their order, slot_of_tid follows, state[0] is the new count.
+    upkeep["report"] = (rows before, merged, culled, evicted, rows after, eviction fired, rows wanted but protected, skipped);
+    upkeep["totals"] += (merged, culled, evicted, 1).  Returns world.  No host synchronisation."""
+    lib = load_library()
+    map_cap, tid_cap = _world_map(world)
+    if not isinstance(upkeep, dict) or any(k not in upkeep for k in UPKEEP_KEYS + ("ws", "map_cap")):
+        raise ValueError("upkeep must be the dict of world_upkeep_buffers")
+    _check_family(upkeep, "upkeep", UPKEEP_SPEC, (), UPKEEP_KEYS, "world_upkeep_buffers")
+    _need_gpu(upkeep["ws"], "upkeep['ws']")
+    row_cap = _landmark_rows(landmarks, n_landmarks)
+    cap, point_cap = _frame_matches(match, n_match, pts_new)
+    _count(count_new, "count_new", 1)
+    _tensor(table, "table", torch.float64, (None, POSE_ROW_WORDS), "pose_table of one sequence")
+    _count(intrinsics, "intrinsics", 4, torch.float64, hint="(fx, fy, cx, cy) of the one camera")
+    if not (1 <= row_cap <= TRACK_MAX_LENGTH * MATCH_MAX_POINTS and 1 <= point_cap <= MATCH_MAX_POINTS and 1 <= cap <= MATCH_MAX_POINTS):
+        raise ValueError("1 <= row_cap <= %d and 1 <= cap, point_cap <= %d required" % (TRACK_MAX_LENGTH * MATCH_MAX_POINTS,
+                                                                                      MATCH_MAX_POINTS))
+    if int(n_frames) < 0:
+        raise ValueError("n_frames must be non-negative")
+    merge_thresh = float(merge_thresh)
+    if merge and not (merge_thresh >= 0.0 and np.isfinite(merge_thresh)):
+        raise ValueError("merge_thresh must be finite and non-negative")
+    high_water, low_water = int(high_water), int(low_water)
+    if high_water >= 0 and not 0 <= low_water <= high_water <= map_cap:
+        raise ValueError("0 <= low_water <= high_water <= map_cap required, or a negative high_water for no eviction (low_water %d, "
+                         "high_water %d, map_cap %d)" % (low_water, high_water, map_cap))
+    if upkeep["ws"].numel() < lib.ssp_world_upkeep_workspace_bytes(map_cap):
+        raise ValueError("upkeep['ws'] is smaller than ssp_world_upkeep_workspace_bytes(%d)" % map_cap)
+    prm = SspWorldUpkeepParams(1 if merge else 0, merge_thresh, int(cull_age), int(cull_min_views), high_water, low_water)
+    with torch.cuda.device(match.device):
+        _check(lib.ssp_op_world_upkeep(_ptr(match), _ptr(n_match), cap, _ptr(landmarks), _ptr(n_landmarks), row_cap, _ptr(pts_new),
+                                       int(pts_new.shape[1]), _ptr(count_new), point_cap, _ptr(table), int(table.shape[0]),
+                                       int(n_frames), _ptr(intrinsics), C.c_void_p(C.addressof(prm)), map_cap, tid_cap,
+                                       _ptr(world["X"]), _ptr(world["desc"]), _ptr(world["tid"]), _ptr(world["n_views"]),
+                                       _ptr(world["first_frame"]), _ptr(world["last_frame"]), _ptr(world["rms"]),
+                                       _ptr(world["slot_of_tid"]), _ptr(world["state"]), _ptr(upkeep["report"]),
+                                       _ptr(upkeep["totals"]), _ptr(upkeep["ws"]), _stream()))
+    return world
 
 
 # ---- loop closure (DESIGN.md section 31) ----

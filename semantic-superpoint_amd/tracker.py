@@ -118,14 +118,23 @@ class PointTracker(object):
     since the old place was last seen (loop_iterations Levenberg-Marquardt steps, loop edges weighted loop_weight).  Nothing is
     written into the trajectory or the map.  "apply" also writes the corrected rows, the chain state and the map rows of that span
     (lib.op_loop_apply; POSE_FLAG_LOOP) and selects the window's landmarks once more before the insert.  last_geometry() gains the
-    "loop_*" keys; loop_closures() and loop_edges_device() read the accepted edges."""
+    "loop_*" keys; loop_closures() and loop_edges_device() read the accepted edges.
+    world_upkeep (needs world_map): None runs none of it.  "on": right after every insert (and so after loop
+    closure and its write-back) lib.op_world_upkeep merges the row pair of a scene point that came back under a new track id
+    (world_merge, within world_merge_thresh pixels, default world_thresh), removes rows last seen more than world_cull_age frames
+    ago (default max_length) with fewer than world_cull_min_views views, and, once more than world_high_water rows are alive
+    (default world_cap - world_cap // 16), evicts the least seen, then oldest rows down to world_low_water (default world_cap -
+    world_cap // 8); a negative world_cull_age or world_high_water switches that phase off.  The map is compacted, so map rows
+    change their slots: last_geometry()["world_match"] indexes the map as it stood before the frame's upkeep.  last_geometry() gains
+    "world_upkeep_report"; world_upkeep_report() reads the running totals."""
 
     def __init__(self, max_length, nn_thresh, device=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
                  absolute_min_inliers=6, landmark_params=(2, 1.0, 2.0), bundle_adjust=None, bundle_iterations=10, bundle_every=1,
                  world_map=None, world_cap=65536, world_patience=30, world_thresh=2.0, world_min_inliers=6,
                  loop_closure=None, loop_min_gap=32, loop_min_inliers=12, loop_cooldown=32, loop_iterations=10, loop_weight=1.0,
-                 model_ratio=0.40, rotation_eps=0.02, normal_margin=0.01):
+                 model_ratio=0.40, rotation_eps=0.02, normal_margin=0.01, world_upkeep=None, world_merge=True, world_merge_thresh=None,
+                 world_cull_age=None, world_cull_min_views=3, world_high_water=None, world_low_water=None):
         stage = (intrinsics, geometric_check, landmark_params)
         _check_mode("geometric_check", geometric_check, "fundamental", "homography", "auto")
         if geometric_check == "auto":
@@ -140,6 +149,23 @@ class PointTracker(object):
                 "world_thresh must be finite and non-negative, world_min_inliers at least 4"), (
                 lambda: not 1 <= int(world_cap) <= L.WORLD_MAX_ROWS or int(world_patience) < 0,
                 "1 <= world_cap <= %d and world_patience >= 0 required" % L.WORLD_MAX_ROWS))
+        _check_mode("world_upkeep", world_upkeep, "on")
+        if world_upkeep is not None:
+            if world_map is None:
+                raise ValueError("world_upkeep needs world_map: it is the upkeep of that map")
+            if world_merge_thresh is None:
+                world_merge_thresh = world_thresh
+            if world_cull_age is None:
+                world_cull_age = max_length
+            if world_high_water is None:
+                world_high_water = int(world_cap) - int(world_cap) // 16
+            if world_low_water is None:
+                world_low_water = min(int(world_cap) - int(world_cap) // 8, int(world_high_water)) if world_high_water >= 0 else 0
+            _check_stage("world_upkeep", "the merge reprojects the map's points into the trajectory's newest camera", *stage, (
+                lambda: bool(world_merge) and not (world_merge_thresh >= 0.0 and np.isfinite(world_merge_thresh)),
+                "world_merge_thresh must be finite and non-negative"), (
+                lambda: world_high_water >= 0 and not 0 <= int(world_low_water) <= int(world_high_water) <= int(world_cap),
+                "0 <= world_low_water <= world_high_water <= world_cap required (or a negative world_high_water for no eviction)"))
         _check_mode("loop_closure", loop_closure, "observe", "apply")
         if loop_closure is not None:
             if world_map is None:
@@ -232,6 +258,12 @@ class PointTracker(object):
         self._world_pnp = None    # lib.pnp_buffers of one problem
         self._world_match = None  # (match [cap, 3], n_match [1]) of the newest frame against the map
         self._world_table = None  # float64 [trajectory_rows, POSE_ROW_WORDS]: world_trajectory()
+        self.world_upkeep = world_upkeep
+        if world_upkeep is not None:
+            self.world_upkeep_params = dict(merge=bool(world_merge), merge_thresh=float(world_merge_thresh), cull_age=int(world_cull_age),
+                                            cull_min_views=int(world_cull_min_views), high_water=int(world_high_water),
+                                            low_water=int(world_low_water))
+        self._upkeep = None       # lib.world_upkeep_buffers: the scratch, the last report, the running totals
         self.loop_closure = loop_closure
         self.loop_min_gap, self.loop_min_inliers, self.loop_cooldown = int(loop_min_gap), int(loop_min_inliers), int(loop_cooldown)
         self.loop_iterations, self.loop_weight = int(loop_iterations), float(loop_weight)
@@ -445,7 +477,7 @@ class PointTracker(object):
         adjustment): map window, triangulate, select, insert."""
         if self._frames < 2 or self._traj_table is None or self._world is None:
             return
-        _, dslot = self._slots()
+        slot, dslot = self._slots()
         lms, n_lms = self._window_landmarks("_world_lm", *self.landmark_params)
         if self.loop_closure is not None:
             self._loop_device(lms, n_lms)
@@ -453,6 +485,13 @@ class PointTracker(object):
                 lms, n_lms = self._window_landmarks("_world_lm", *self.landmark_params)
         L.op_world_insert(self._world, lms, n_lms, self._desc[dslot], self._counts[dslot:dslot + 1], self._traj_table, self._frames,
                           self.world_patience)
+        if self.world_upkeep is not None:         # after loop closure and its write-back: both saw the map the frame was matched with
+            if self._upkeep is None:
+                self._upkeep = L.world_upkeep_buffers(self.world_cap, self.device)
+            m, nm = self._world_match
+            L.op_world_upkeep(self._world, m, nm, lms, n_lms, self._pts[slot], self._counts[dslot:dslot + 1], self._traj_table,
+                              self._frames, self._intr[0, 1:2], self._upkeep, **self.world_upkeep_params)
+            self._geometry = dict(self._geometry, world_upkeep_report=self._upkeep["report"])
 
     def _loop_device(self, lms, n_lms):
         """Loop closure of the newest frame, between the select and the insert: the frame's map matches
@@ -518,6 +557,13 @@ class PointTracker(object):
         """The map's device buffers (the dict of lib.world_buffers; "state"[0] rows are in use), None without world_map or before
         the first frame.  No synchronisation."""
         return self._world
+
+    def world_upkeep_report(self):
+        """The running totals of the map's upkeep as numpy int64 [4] = (rows merged, culled, evicted, calls); one host
+        synchronisation.  Zeros without world_upkeep or before its first call."""
+        if self._upkeep is None:
+            return np.zeros(4, dtype=np.int64)
+        return self._upkeep["totals"].cpu().numpy()
 
     def world_map(self):
         """The map as numpy: (rows float64 [n_rows, 8] = (tid, X, Y, Z, n_views, rms, first_frame, last_frame), descriptors float32
@@ -618,7 +664,9 @@ class PointTracker(object):
     def last_geometry(self):
         """The device dict of the newest frame's geometric check (lib.op_epipolar_ransac or lib.op_eval_ransac), None before
         the first checked frame or without a check.  Its mask indexes the UNFILTERED matches of that frame.  With bundle_adjust
-        it also holds "ba_info" (float64 [lib.BA_INFO_WORDS]) of the newest adjustment (status lib.BA_NOTHING before the first)."""
+        it also holds "ba_info" (float64 [lib.BA_INFO_WORDS]) of the newest adjustment (status lib.BA_NOTHING before the first).
+        With world_upkeep it holds "world_upkeep_report" (int32 [lib.WORLD_UPKEEP_REPORT_WORDS]) once the upkeep has been called, and
+        the rows of "world_match" index the map as it stood before the frame's upkeep, which may have moved or removed them."""
         return self._geometry
 
     def _track_device(self, m, nm):
@@ -831,6 +879,9 @@ class SequenceTracker:
     loop_closure / loop_min_gap / loop_min_inliers / loop_cooldown / loop_iterations / loop_weight: PointTracker's loop closure
     over the world map (needs world_map); read it with tracker.last_geometry(), loop_closures() and
     loop_edges_device().
+    world_upkeep / world_merge / world_merge_thresh / world_cull_age / world_cull_min_views / world_high_water / world_low_water:
+    PointTracker's upkeep of the world map after every insert (needs world_map): revisits merged, weak rows
+    culled, the least valuable rows evicted before the map is full; read it with tracker.last_geometry() and world_upkeep_report().
     Everything from geometric_check on is given by keyword (`**tracker_options`) and goes to PointTracker as it is: its names,
     defaults and checks are PointTracker's."""
 
@@ -898,6 +949,9 @@ class SequenceTracker:
 
     def world_map(self):
         return self.tracker.world_map()
+
+    def world_upkeep_report(self):
+        return self.tracker.world_upkeep_report()
 
     def loop_edges_device(self):
         return self.tracker.loop_edges_device()
