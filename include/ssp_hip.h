@@ -891,6 +891,67 @@ int ssp_op_world_upkeep(const float* match_dev, const int32_t* n_match_dev, int 
                         int32_t* slot_of_tid_dev, int32_t* state_dev, int32_t* report_dev, int64_t* totals_dev, void* workspace_dev,
                         void* stream);
 
+/* ---- trajectory evaluation -----------------------------------------------------------------------
+ * A trajectory table against ground-truth poses: the alignment, the absolute and the relative pose errors, and their statistics.
+ * The rules are restated in numpy by tests/traj_eval_ref.py.  fp64 without contraction, no floating-point atomics, every sum in one
+ * fixed order (thread t of 256 takes the rows t, t + 256, ..., then the wave butterfly and the waves in order), one workgroup per
+ * problem wherever a sum is taken: a problem's result does not depend on its batch or on the run.  No call synchronises with the
+ * host, allocates or needs a workspace.
+ * The arguments every call shares: n_problems = P tables against one or P ground truths.
+ *   table_dev fp64 [P][table_stride][SSP_POSE_ROW_WORDS], table_stride >= capacity rows: rows (Rw [9], C [3], s, n_shared, flags,
+ *     ratio), Rw world-to-camera, so that the estimate's camera-to-world rotation is Rw^T; n_frames_dev int32 [P] on the device.
+ *   gt_dev fp64 [P or 1][gt_stride][SSP_TRAJ_GT_WORDS]: the row-major 3x4 camera-to-world matrix (R | C) per row, the layout of a
+ *     KITTI poses file; n_gt rows; gt_stride 0: one ground truth shared by all problems, else >= n_gt rows per problem.
+ *   index_dev int32 [capacity] or NULL: the ground-truth row of frame f, -1 for none; NULL: frame f is row f.
+ *   Frame f is valid iff f < min(n_frames, capacity), its ground-truth row g exists (0 <= g < n_gt), its flag word is an integer
+ *     in [0, 2^31) with (flags & skip_flags) == 0, and all 12 + 12 numbers (Rw, C; R, C of the truth) are finite.
+ * ssp_op_traj_align: sim_dev [P][SSP_TRAJ_SIM_WORDS] = (s, R [9], t [3], n_valid, status, sigma_p^2) of q ~ s R p + t over the valid
+ *   frames, p the estimated and q the true centres.  mode 0: SE(3) (s = 1), 1: Sim(3): two passes (the means; H = sum (q - mq)
+ *   (p - mp)^T, Sp = sum |p - mp|^2), eight cyclic Jacobi sweeps on H^T H, v0 / v1 the columns of the two largest diagonal
+ *   entries (the lowest index on ties), v2 = v0 x v1, u0 = H v0 / |.|, u1 = H v1 made orthogonal to u0 and normalised, u2 = u0 x u1,
+ *   R = sum u_k v_k^T, s = sum_ij R_ij H_ij / Sp, t = mq - s R mp; sigma_p^2 = Sp / n_valid.  mode 2: R = R_gt Rw and t = q - R p
+ *   of the first valid frame, s = 1; mode 3: the same R and s = sum q'.p' / sum p'.p', q' = q - q0, p' = R (p - p0).
+ *   status 1: fewer than 3 valid frames (mode 2: 1, mode 3: 2), Sp <= 0, a moment or a result that is not finite or s <= 0;
+ *   status 2: centres collinear (the second-largest diagonal entry <= 1e-24 x the largest).  Both write s = 1, R = I, t = 0.
+ * ssp_op_traj_ape: per frame err_t = |q - (s R p + t)|, err_r = the angle of R_gt^T (R Rw^T) in degrees, valid; [P][capacity],
+ *   every entry written; 0 / 0 / 0 for an invalid frame or a sim row with status != 0.  The angle of a rotation E is
+ *   atan2(0.5 sqrt((E21-E12)^2 + (E02-E20)^2 + (E10-E01)^2), 0.5 (tr E - 1)) everywhere.
+ * ssp_op_traj_rpe_delta: for f and f + delta both valid, E = (P_f^-1 P_g)^-1 (Q_f^-1 Q_g), Q the truth, P the estimate with centres
+ *   scaled by scale_dev[p * scale_stride] (NULL: 1; sim_dev with stride SSP_TRAJ_SIM_WORDS passes an alignment's s);
+ *   err_t = |trans E|, err_r = its angle in degrees, valid; [P][capacity].
+ * ssp_op_traj_rpe_segments (the KITTI devkit's rules): dist_dev [P][capacity] = the cumulative path length over the ground-truth
+ *   rows of frames 0..f (an order-defined scan; a frame without a row, or whose centre is not finite, repeats the value before it).
+ *   For every first frame f0 = 0, step, 2 step, ... below capacity and every length L of lengths_dev fp64 [n_len], f1 = the first
+ *   frame with dist[f1] > dist[f0] + L (binary search), -1 if none or f0 >= n_frames.  seg_dev [P][cdiv(capacity, step)][n_len][4]
+ *   = (f1, t_err / L, r_err / L, L) for a segment that counts (f1 >= 0, both ends valid; r_err in radians), (f1, 0, 0, 0)
+ *   otherwise.  summary_dev [P][2 + 3 n_len] = mean t_err / L, mean r_err / L over all counted segments, then (count, mean, mean)
+ *   per length.  info_dev int32 [P][SSP_TRAJ_INFO_WORDS] = (counted, segments whose end exists but an end is invalid, first frames
+ *   without an end, first frames inside the sequence).
+ * ssp_op_traj_stats: err_dev fp64 / valid_dev int32 [P][capacity] (errors non-negative and finite where valid) ->
+ *   stats_dev [P][SSP_TRAJ_STATS_WORDS] = (n, rmse, mean, std (population), min, max, median (numpy's: the mean of the two middle
+ *   order statistics), sse); the order statistics by an exact radix select over the bit patterns; n = 0 gives zeros. */
+#define SSP_TRAJ_GT_WORDS 12
+#define SSP_TRAJ_SIM_WORDS 16
+#define SSP_TRAJ_STATS_WORDS 8
+#define SSP_TRAJ_INFO_WORDS 4
+#define SSP_TRAJ_MAX_LENGTHS 8
+#define SSP_TRAJ_MAX_FRAMES (1 << 20)
+#define SSP_TRAJ_MAX_PROBLEMS 65535
+int ssp_op_traj_align(const double* table_dev, int table_stride, const int32_t* n_frames_dev, int capacity, const double* gt_dev,
+                      int gt_stride, int n_gt, const int32_t* index_dev, int skip_flags, int mode, int n_problems, double* sim_dev,
+                      void* stream);
+int ssp_op_traj_ape(const double* table_dev, int table_stride, const int32_t* n_frames_dev, int capacity, const double* gt_dev,
+                    int gt_stride, int n_gt, const int32_t* index_dev, int skip_flags, int n_problems, const double* sim_dev,
+                    double* err_t_dev, double* err_r_dev, int32_t* valid_dev, void* stream);
+int ssp_op_traj_rpe_delta(const double* table_dev, int table_stride, const int32_t* n_frames_dev, int capacity, const double* gt_dev,
+                          int gt_stride, int n_gt, const int32_t* index_dev, int skip_flags, int n_problems, const double* scale_dev,
+                          int scale_stride, int delta, double* err_t_dev, double* err_r_dev, int32_t* valid_dev, void* stream);
+int ssp_op_traj_rpe_segments(const double* table_dev, int table_stride, const int32_t* n_frames_dev, int capacity, const double* gt_dev,
+                             int gt_stride, int n_gt, const int32_t* index_dev, int skip_flags, int n_problems, const double* scale_dev,
+                             int scale_stride, const double* lengths_dev, int n_len, int step, double* dist_dev, double* seg_dev,
+                             double* summary_dev, int32_t* info_dev, void* stream);
+int ssp_op_traj_stats(const double* err_dev, const int32_t* valid_dev, int capacity, int n_problems, double* stats_dev, void* stream);
+
 /* ---- loop closure --------------------------------------------------------------------------------
  * A frame's map matches against the OLD rows of the world map, the loop edge measured from the pose found against them, a Sim(3)
  * pose graph over the trajectory rows since the old place was last seen, and the write-back.  The rules are restated in numpy by

@@ -223,6 +223,11 @@ def _signatures():
         "ssp_world_repair": ([vp] * 5 + [i, i, vp, vp], i),
         "ssp_world_upkeep_workspace_bytes": ([i], sz),
         "ssp_op_world_upkeep": ([vp, vp, i, vp, vp, i, vp, i, vp, i, vp, i, i, vp, vp, i, i] + [vp] * 13, i),
+        "ssp_op_traj_align": ([vp, i, vp, i, vp, i, i, vp, i, i, i, vp, vp], i),
+        "ssp_op_traj_ape": ([vp, i, vp, i, vp, i, i, vp, i, i, vp, vp, vp, vp, vp], i),
+        "ssp_op_traj_rpe_delta": ([vp, i, vp, i, vp, i, i, vp, i, i, vp, i, i, vp, vp, vp, vp], i),
+        "ssp_op_traj_rpe_segments": ([vp, i, vp, i, vp, i, i, vp, i, i, vp, i, vp, i, i, vp, vp, vp, vp, vp], i),
+        "ssp_op_traj_stats": ([vp, vp, i, i, vp, vp], i),
         "ssp_pose_graph_workspace_bytes": ([i], sz),
         "ssp_op_loop_correspondences": ([vp, vp, vp, i, vp, vp, i, vp, i, vp, i, vp, vp, i, i, i, vp, vp, vp, vp], i),
         "ssp_loop_edge": ([vp] * 7 + [i, vp, i, vp, i, i, i, i, d, vp, vp, vp, vp], i),
@@ -2639,6 +2644,169 @@ def op_world_upkeep(world, match, n_match, landmarks, n_landmarks, pts_new, coun
                                        _ptr(world["slot_of_tid"]), _ptr(world["state"]), _ptr(upkeep["report"]),
                                        _ptr(upkeep["totals"]), _ptr(upkeep["ws"]), _stream()))
     return world
+
+
+# ---- trajectory evaluation ----
+TRAJ_GT_WORDS = 12  # SSP_TRAJ_GT_WORDS: the row-major 3x4 camera-to-world matrix (R | C), a row of a KITTI poses file
+TRAJ_SIM_WORDS = 16  # SSP_TRAJ_SIM_WORDS: s, R [9], t [3], n_valid, status, sigma_p^2
+TRAJ_STATS_WORDS = 8  # SSP_TRAJ_STATS_WORDS: n, rmse, mean, std, min, max, median, sse
+TRAJ_INFO_WORDS = 4  # SSP_TRAJ_INFO_WORDS: counted, end invalid, no end, first frames inside the sequence
+TRAJ_MAX_LENGTHS = 8  # SSP_TRAJ_MAX_LENGTHS
+TRAJ_MAX_FRAMES = 1 << 20  # SSP_TRAJ_MAX_FRAMES
+TRAJ_MAX_PROBLEMS = 65535  # SSP_TRAJ_MAX_PROBLEMS
+TRAJ_MODES = {"se3": 0, "sim3": 1, "origin": 2, "origin_scale": 3}
+TRAJ_OK, TRAJ_FEW, TRAJ_COLLINEAR = 0, 1, 2  # sim[14]
+KITTI_LENGTHS = (100.0, 200.0, 300.0, 400.0, 500.0, 600.0, 700.0, 800.0)
+TRAJ_PAIR_KEYS = ("err_t", "err_r", "valid")
+TRAJ_SEG_KEYS = ("lengths", "dist", "seg", "summary", "info")
+TRAJ_SPEC = (("P", "capacity", "n_first", "n_len", "n_summary", "n_stat"),
+             {"sim": (torch.float64, ("P", TRAJ_SIM_WORDS)), "err_t": (torch.float64, ("P", "capacity")),
+              "err_r": (torch.float64, ("P", "capacity")), "valid": (torch.int32, ("P", "capacity")),
+              "lengths": (torch.float64, ("n_len",)), "dist": (torch.float64, ("P", "capacity")),
+              "seg": (torch.float64, ("P", "n_first", "n_len", 4)), "summary": (torch.float64, ("P", "n_summary")),
+              "info": (torch.int32, ("P", TRAJ_INFO_WORDS)), "stats": (torch.float64, ("n_stat", "P", TRAJ_STATS_WORDS))})
+
+
+def _traj_dims(traj):
+    if not isinstance(traj, dict) or any(k not in traj for k in ("capacity", "n_problems", "n_len", "step", "n_stat")):
+        raise ValueError("traj must be the dict of traj_eval_buffers")
+    n_len, step, capacity = int(traj["n_len"]), int(traj["step"]), int(traj["capacity"])
+    return (int(traj["n_problems"]), capacity, -(-capacity // step), n_len, 2 + 3 * n_len, int(traj["n_stat"]))
+
+
+def traj_eval_buffers(capacity, n_problems=1, n_len=len(KITTI_LENGTHS), step=10, device="cuda", n_stat=4):
+    """The device arrays of the trajectory evaluation for n_problems tables of capacity rows, zeroed: "sim"
+    [P, TRAJ_SIM_WORDS]; "err_t" / "err_r" float64 and "valid" int32 [P, capacity], the per-frame output of op_traj_ape or
+    op_traj_rpe_delta; "lengths" [n_len], "dist" [P, capacity], "seg" [P, cdiv(capacity, step), n_len, 4], "summary" [P, 2 + 3 n_len]
+    and "info" int32 [P, TRAJ_INFO_WORDS] of op_traj_rpe_segments; "stats" [n_stat, P, TRAJ_STATS_WORDS], a row of op_traj_stats per
+    slot; plus the host-known "capacity", "n_problems", "n_len", "step" and "n_stat"."""
+    capacity, n_problems, n_len, step, n_stat = int(capacity), int(n_problems), int(n_len), int(step), int(n_stat)
+    if not 1 <= capacity <= TRAJ_MAX_FRAMES:
+        raise ValueError("1 <= capacity <= %d required (got %d)" % (TRAJ_MAX_FRAMES, capacity))
+    if not 1 <= n_problems <= TRAJ_MAX_PROBLEMS:
+        raise ValueError("1 <= n_problems <= %d required (got %d)" % (TRAJ_MAX_PROBLEMS, n_problems))
+    if not 1 <= n_len <= TRAJ_MAX_LENGTHS:
+        raise ValueError("1 <= n_len <= %d required (got %d)" % (TRAJ_MAX_LENGTHS, n_len))
+    if not 1 <= step <= TRAJ_MAX_FRAMES or n_stat < 1:
+        raise ValueError("1 <= step <= %d and n_stat >= 1 required (got %d, %d)" % (TRAJ_MAX_FRAMES, step, n_stat))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("traj_eval_buffers needs a HIP device: the MI355X path has no CPU fallback")
+    traj = dict(capacity=capacity, n_problems=n_problems, n_len=n_len, step=step, n_stat=n_stat)
+    traj.update(_alloc(TRAJ_SPEC, _traj_dims(traj), device))
+    return traj
+
+
+def _traj_inputs(table, n_frames, gt, index, traj, skip_flags):
+    """The arguments the trajectory operators share, checked -> (P, capacity, n_gt, gt_stride).  table float64 [P, capacity,
+    POSE_ROW_WORDS] (or [capacity, .] for P = 1); n_frames int32 of P entries; gt float64 [n_gt, TRAJ_GT_WORDS] shared by all tables
+    or [P, n_gt, .]; index int32 [capacity] or None."""
+    dims = _traj_dims(traj)
+    P, capacity = dims[0], dims[1]
+    _need_gpu(table, "table")
+    if (table.dtype != torch.float64 or table.dim() not in (2, 3) or tuple(table.shape[-2:]) != (capacity, POSE_ROW_WORDS)
+            or table.numel() != P * capacity * POSE_ROW_WORDS):
+        raise ValueError("table must be float64 [%d, %d, %d] (n_problems and capacity of traj_eval_buffers; got %s %s)"
+                         % (P, capacity, POSE_ROW_WORDS, str(table.dtype)[6:], list(table.shape)))
+    _count(n_frames, "n_frames", P, hint="one per table")
+    _need_gpu(gt, "gt")
+    if gt.dtype != torch.float64 or gt.dim() not in (2, 3) or gt.shape[-1] != TRAJ_GT_WORDS or (gt.dim() == 3 and gt.shape[0] != P):
+        raise ValueError("gt must be float64 [n_gt, %d] or [%d, n_gt, %d] (got %s %s)" % (TRAJ_GT_WORDS, P, TRAJ_GT_WORDS,
+                                                                                       str(gt.dtype)[6:], list(gt.shape)))
+    n_gt = int(gt.shape[-2])
+    if not 1 <= n_gt <= TRAJ_MAX_FRAMES:
+        raise ValueError("1 <= n_gt <= %d ground-truth rows required (got %d)" % (TRAJ_MAX_FRAMES, n_gt))
+    if index is not None:
+        _tensor(index, "index", torch.int32, (capacity,), "the ground-truth row of each frame, -1 for none")
+    skip_flags = int(skip_flags)
+    if skip_flags < 0:
+        raise ValueError("skip_flags must be non-negative")
+    return P, capacity, n_gt, (n_gt if gt.dim() == 3 else 0), skip_flags
+
+
+def _traj_scale(scale, P):
+    """(pointer, stride) of the scales of P problems: None (1), a sim tensor [P, TRAJ_SIM_WORDS] (its first column) or float64 [P]."""
+    if scale is None:
+        return None, 0
+    _need_gpu(scale, "scale")
+    if scale.dtype == torch.float64 and tuple(scale.shape) == (P, TRAJ_SIM_WORDS):
+        return _ptr(scale), TRAJ_SIM_WORDS
+    _count(scale, "scale", P, torch.float64, hint="one per table, or the sim tensor of op_traj_align")
+    return _ptr(scale), 1
+
+
+def op_traj_align(table, n_frames, gt, traj, index=None, mode="sim3", skip_flags=POSE_FLAG_NO_POSE):
+    """The similarity between the estimated and the true camera centres (ssp_op_traj_align) -> traj["sim"]
+    [P, TRAJ_SIM_WORDS] = (s, R [9], t [3], n_valid, status, sigma_p^2) with q ~ s R p + t.  mode: "se3", "sim3", "origin" (the first
+    valid frame's pose) or "origin_scale".  status TRAJ_FEW / TRAJ_COLLINEAR give the identity.  No host synchronisation."""
+    lib = load_library()
+    if mode not in TRAJ_MODES:
+        raise ValueError("mode must be one of %s (got %r)" % (sorted(TRAJ_MODES), mode))
+    P, capacity, n_gt, gt_stride, skip_flags = _traj_inputs(table, n_frames, gt, index, traj, skip_flags)
+    _check_family(traj, "traj", TRAJ_SPEC, _traj_dims(traj), ("sim",), "traj_eval_buffers")
+    with torch.cuda.device(table.device):
+        _check(lib.ssp_op_traj_align(_ptr(table), capacity, _ptr(n_frames), capacity, _ptr(gt), gt_stride, n_gt, _ptr(index), skip_flags,
+                                     TRAJ_MODES[mode], P, _ptr(traj["sim"]), _stream()))
+    return traj["sim"]
+
+
+def op_traj_ape(table, n_frames, gt, traj, index=None, skip_flags=POSE_FLAG_NO_POSE):
+    """The absolute pose error of every frame under traj["sim"] (ssp_op_traj_ape) -> (traj["err_t"], traj["err_r"], traj["valid"]),
+    [P, capacity]: |q - (s R p + t)|, the angle of R_gt^T (R Rw^T) in degrees, and the frame's validity.  No host synchronisation."""
+    lib = load_library()
+    P, capacity, n_gt, gt_stride, skip_flags = _traj_inputs(table, n_frames, gt, index, traj, skip_flags)
+    _check_family(traj, "traj", TRAJ_SPEC, _traj_dims(traj), ("sim",) + TRAJ_PAIR_KEYS, "traj_eval_buffers")
+    with torch.cuda.device(table.device):
+        _check(lib.ssp_op_traj_ape(_ptr(table), capacity, _ptr(n_frames), capacity, _ptr(gt), gt_stride, n_gt, _ptr(index), skip_flags, P,
+                                   _ptr(traj["sim"]), _ptr(traj["err_t"]), _ptr(traj["err_r"]), _ptr(traj["valid"]), _stream()))
+    return traj["err_t"], traj["err_r"], traj["valid"]
+
+
+def op_traj_rpe_delta(table, n_frames, gt, traj, index=None, delta=1, scale=None, skip_flags=POSE_FLAG_NO_POSE):
+    """The relative pose error between frames f and f + delta (ssp_op_traj_rpe_delta) -> (traj["err_t"], traj["err_r"],
+    traj["valid"]), [P, capacity], the rotation in degrees.  scale: None (1), traj["sim"] (its s) or float64 [P]; of an alignment
+    only the scale enters.  No host synchronisation."""
+    lib = load_library()
+    P, capacity, n_gt, gt_stride, skip_flags = _traj_inputs(table, n_frames, gt, index, traj, skip_flags)
+    _check_family(traj, "traj", TRAJ_SPEC, _traj_dims(traj), TRAJ_PAIR_KEYS, "traj_eval_buffers")
+    delta = int(delta)
+    if not 1 <= delta <= capacity:
+        raise ValueError("1 <= delta <= capacity required (delta %d, capacity %d)" % (delta, capacity))
+    sp, ss = _traj_scale(scale, P)
+    with torch.cuda.device(table.device):
+        _check(lib.ssp_op_traj_rpe_delta(_ptr(table), capacity, _ptr(n_frames), capacity, _ptr(gt), gt_stride, n_gt, _ptr(index), skip_flags,
+                                         P, sp, ss, delta, _ptr(traj["err_t"]), _ptr(traj["err_r"]), _ptr(traj["valid"]), _stream()))
+    return traj["err_t"], traj["err_r"], traj["valid"]
+
+
+def op_traj_rpe_segments(table, n_frames, gt, traj, index=None, scale=None, skip_flags=POSE_FLAG_NO_POSE):
+    """The KITTI devkit's segment errors (ssp_op_traj_rpe_segments) for the lengths in traj["lengths"] and first frames every
+    traj["step"] -> (traj["seg"], traj["summary"], traj["info"]); traj["dist"] holds the cumulative ground-truth path length.
+    summary[:, 0] is the mean translation error per metre (x 100: percent), summary[:, 1] the mean rotation error in radians per
+    metre.  No host synchronisation."""
+    lib = load_library()
+    P, capacity, n_gt, gt_stride, skip_flags = _traj_inputs(table, n_frames, gt, index, traj, skip_flags)
+    _check_family(traj, "traj", TRAJ_SPEC, _traj_dims(traj), TRAJ_SEG_KEYS, "traj_eval_buffers")
+    sp, ss = _traj_scale(scale, P)
+    with torch.cuda.device(table.device):
+        _check(lib.ssp_op_traj_rpe_segments(_ptr(table), capacity, _ptr(n_frames), capacity, _ptr(gt), gt_stride, n_gt, _ptr(index),
+                                            skip_flags, P, sp, ss, _ptr(traj["lengths"]), int(traj["n_len"]), int(traj["step"]),
+                                            _ptr(traj["dist"]), _ptr(traj["seg"]), _ptr(traj["summary"]), _ptr(traj["info"]), _stream()))
+    return traj["seg"], traj["summary"], traj["info"]
+
+
+def op_traj_stats(err, valid, out):
+    """(n, rmse, mean, std, min, max, median, sse) of the valid entries of err (ssp_op_traj_stats): err float64 and valid int32
+    [P, capacity], out float64 [P, TRAJ_STATS_WORDS] (a slot of traj["stats"]).  The errors are non-negative and finite where valid;
+    the median is numpy.median's, selected exactly.  Returns out.  No host synchronisation."""
+    lib = load_library()
+    _tensor(err, "err", torch.float64, ((1, TRAJ_MAX_PROBLEMS), (1, TRAJ_MAX_FRAMES)), "[P, capacity]")
+    P, capacity = int(err.shape[0]), int(err.shape[1])
+    _tensor(valid, "valid", torch.int32, (P, capacity), "as err")
+    _tensor(out, "out", torch.float64, (P, TRAJ_STATS_WORDS), "a slot of traj['stats']")
+    with torch.cuda.device(err.device):
+        _check(lib.ssp_op_traj_stats(_ptr(err), _ptr(valid), capacity, P, _ptr(out), _stream()))
+    return out
 
 
 # ---- loop closure (DESIGN.md section 31) ----

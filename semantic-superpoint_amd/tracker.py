@@ -126,7 +126,14 @@ class PointTracker(object):
     (default world_cap - world_cap // 16), evicts the least seen, then oldest rows down to world_low_water (default world_cap -
     world_cap // 8); a negative world_cull_age or world_high_water switches that phase off.  The map is compacted, so map rows
     change their slots: last_geometry()["world_match"] indexes the map as it stood before the frame's upkeep.  last_geometry() gains
-    "world_upkeep_report"; world_upkeep_report() reads the running totals."""
+    "world_upkeep_report"; world_upkeep_report() reads the running totals.
+    ground_truth (needs intrinsics): float64 [N, 12] camera-to-world rows (R | C), the layout of a KITTI poses
+    file; gt_index: int32 [trajectory_rows], the ground-truth row of each frame (-1: none), or None when frame f is row f.
+    evaluate_trajectory(which, **options) scores trajectory(), absolute_trajectory() or world_trajectory() on demand (alignment, ATE,
+    RPE, the KITTI segments; trajectory_evaluation.TrajectoryEvaluator).  trajectory_eval="observe": every frame, after all of its
+    write-backs, appends a row (ATE rmse, mean, max of the frames so far under their own eval_align alignment, s, n_valid, status,
+    two spare) to a device log [trajectory_rows, 8] for eval_table = "trajectory" or "world", with no host copy or synchronisation;
+    trajectory_eval_log() reads it and last_geometry() gains "trajectory_eval".  With trajectory_eval=None no new code runs."""
 
     def __init__(self, max_length, nn_thresh, device=None, class_consistent=False, geometric_check=None, check_thresh=1.0,
                  min_inliers=16, check_seed=0, intrinsics=None, trajectory_rows=4096, absolute_pose=None, absolute_thresh=2.0,
@@ -134,8 +141,31 @@ class PointTracker(object):
                  world_map=None, world_cap=65536, world_patience=30, world_thresh=2.0, world_min_inliers=6,
                  loop_closure=None, loop_min_gap=32, loop_min_inliers=12, loop_cooldown=32, loop_iterations=10, loop_weight=1.0,
                  model_ratio=0.40, rotation_eps=0.02, normal_margin=0.01, world_upkeep=None, world_merge=True, world_merge_thresh=None,
-                 world_cull_age=None, world_cull_min_views=3, world_high_water=None, world_low_water=None):
+                 world_cull_age=None, world_cull_min_views=3, world_high_water=None, world_low_water=None, ground_truth=None,
+                 gt_index=None, trajectory_eval=None, eval_align="sim3", eval_table="trajectory"):
         stage = (intrinsics, geometric_check, landmark_params)
+        _check_mode("trajectory_eval", trajectory_eval, "observe")
+        if eval_table not in ("trajectory", "world"):
+            raise ValueError("eval_table must be 'trajectory' or 'world' (got %r)" % (eval_table,))
+        if eval_align not in L.TRAJ_MODES:
+            raise ValueError("eval_align must be one of %s (got %r)" % (sorted(L.TRAJ_MODES), eval_align))
+        if trajectory_eval is not None or ground_truth is not None:
+            if intrinsics is None:
+                raise ValueError("trajectory evaluation needs intrinsics: it scores the trajectory of a calibrated camera")
+            if ground_truth is None:
+                raise ValueError("trajectory_eval needs ground_truth: float64 [N, 12] camera-to-world rows (R | C)")
+            ground_truth = np.ascontiguousarray(ground_truth, dtype=np.float64)
+            if ground_truth.ndim != 2 or ground_truth.shape[1] != L.TRAJ_GT_WORDS or ground_truth.shape[0] < 1:
+                raise ValueError("ground_truth must be [N >= 1, %d] (got %s)" % (L.TRAJ_GT_WORDS, list(ground_truth.shape)))
+            if gt_index is not None:
+                gt_index = np.ascontiguousarray(gt_index, dtype=np.int32)
+                if gt_index.shape != (int(trajectory_rows),):
+                    raise ValueError("gt_index must hold trajectory_rows = %d entries (got %s)" % (int(trajectory_rows),
+                                                                                                 list(gt_index.shape)))
+            if trajectory_eval is not None and eval_table == "world" and world_map is None:
+                raise ValueError("eval_table='world' needs world_map: it scores world_trajectory()")
+        elif gt_index is not None:
+            raise ValueError("gt_index needs ground_truth")
         _check_mode("geometric_check", geometric_check, "fundamental", "homography", "auto")
         if geometric_check == "auto":
             if intrinsics is None:
@@ -271,6 +301,11 @@ class PointTracker(object):
         self._loop_pnp = None     # lib.pnp_buffers of one problem: the pose against the old rows
         self._loop_log = None     # float64 [trajectory_rows, 11]: the candidate record and the graph's costs and status per frame
         self._loop_seed = None    # the frame's check seed
+        self.ground_truth, self.gt_index = ground_truth, gt_index   # numpy, or None
+        self.trajectory_eval, self.eval_align, self.eval_table = trajectory_eval, eval_align, eval_table
+        self._evaluators = {}     # trajectory_evaluation.TrajectoryEvaluator per option set of evaluate_trajectory
+        self._eval = None         # the buffers of the per-frame log under trajectory_eval="observe"
+        self._eval_log = None     # float64 [trajectory_rows, 8]: ATE rmse, mean, max, s, n_valid, status, two spare
 
     # ---- device buffers -------------------------------------------------------------------------------------------
     def _ensure(self, n):
@@ -332,6 +367,8 @@ class PointTracker(object):
             self._keep_landmarks_device()
         if self.world_map_mode is not None:
             self._world_insert_device()
+        if self.trajectory_eval is not None:
+            self._eval_observe_device()
         had_prev, self._prev_ok = self._prev_ok, True
         return m, nm, had_prev
 
@@ -661,12 +698,78 @@ class PointTracker(object):
         """landmarks_device as numpy: float64 [M, lib.LANDMARK_WORDS] (one host synchronisation)."""
         return L.landmarks_to_numpy(*self.landmarks_device(min_views, min_parallax_deg, max_reproj))
 
+    # ---- trajectory evaluation (DESIGN.md section 40) ---------------------------------------------------------------------
+    def _eval_tables(self, which):
+        """(table, rows given so far) of trajectory() / absolute_trajectory() / world_trajectory(), or None before it exists"""
+        got = {"trajectory": self.trajectory, "absolute": self.absolute_trajectory, "world": self.world_trajectory}[which]()
+        return None if got is None else (got[0], min(self._frames, self.trajectory_rows))
+
+    def _eval_observe_device(self):
+        """One row of the log for the newest frame, after all of its write-backs: the alignment of the frames so far, their
+        absolute errors and the statistics of those (three launches and two small gathers; the first frame allocates, after it
+        there is no host copy or synchronisation).  A frame before the table exists, or past trajectory_rows, leaves no row."""
+        f = self._frames - 1
+        e = self._eval
+        if e is None:
+            dev, rows = self.device, self.trajectory_rows
+            e = self._eval = dict(traj=L.traj_eval_buffers(rows, 1, 1, rows, dev, n_stat=1),
+                                  gt=torch.as_tensor(self.ground_truth).to(dev),
+                                  index=None if self.gt_index is None else torch.as_tensor(self.gt_index).to(dev),
+                                  n_frames=torch.zeros(1, dtype=torch.int32, device=dev),
+                                  stat_words=torch.tensor([1, 2, 5], device=dev), sim_words=torch.tensor([0, 13, 14], device=dev))
+            self._eval_log = torch.zeros(rows, 8, dtype=torch.float64, device=dev)
+        got = self._eval_tables(self.eval_table)
+        if got is None or f >= self.trajectory_rows:
+            return
+        table, n = got
+        traj = e["traj"]
+        e["n_frames"].fill_(n)
+        sim = L.op_traj_align(table, e["n_frames"], e["gt"], traj, e["index"], self.eval_align)
+        err_t, _, valid = L.op_traj_ape(table, e["n_frames"], e["gt"], traj, e["index"])
+        stats = L.op_traj_stats(err_t, valid, traj["stats"][0])
+        row = self._eval_log[f]
+        row[0:3] = stats[0].index_select(0, e["stat_words"])
+        row[3:6] = sim[0].index_select(0, e["sim_words"])
+        if self._geometry is not None:
+            self._geometry = dict(self._geometry, trajectory_eval=row)
+
+    def trajectory_eval_log(self):
+        """The per-frame log of trajectory_eval="observe" as numpy float64 [frames, 8]: (ATE rmse, mean, max of the frames so far
+        under their own alignment, s, n_valid, status, two spare) per frame given so far; one host synchronisation.  Zero rows
+        without it or before the first frame."""
+        if self._eval_log is None:
+            return np.zeros((0, 8))
+        return self._eval_log[:min(self._frames, self.trajectory_rows)].cpu().numpy()
+
+    def evaluate_trajectory(self, which=None, **options):
+        """The trajectory so far against ground_truth, on demand: which = "trajectory" (default: eval_table), "absolute" or "world";
+        options are TrajectoryEvaluator's (align: default eval_align; lengths, step, deltas, skip_flags).  Returns
+        TrajectoryEvaluator.result()'s dict (one host copy), None before the table exists."""
+        from .trajectory_evaluation import TrajectoryEvaluator
+        if self.ground_truth is None:
+            raise ValueError("evaluate_trajectory needs ground_truth (and intrinsics)")
+        which = self.eval_table if which is None else which
+        if which not in ("trajectory", "absolute", "world"):
+            raise ValueError("which must be 'trajectory', 'absolute' or 'world' (got %r)" % (which,))
+        got = self._eval_tables(which)
+        if got is None:
+            return None
+        options.setdefault("align", self.eval_align)
+        key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple)) else v) for k, v in options.items()))
+        ev = self._evaluators.get(key)
+        if ev is None:
+            ev = self._evaluators[key] = TrajectoryEvaluator(self.ground_truth, self.gt_index, capacity=self.trajectory_rows,
+                                                             device=self.device, **options)
+        ev.evaluate(got[0], got[1])
+        return ev.result()
+
     def last_geometry(self):
         """The device dict of the newest frame's geometric check (lib.op_epipolar_ransac or lib.op_eval_ransac), None before
         the first checked frame or without a check.  Its mask indexes the UNFILTERED matches of that frame.  With bundle_adjust
         it also holds "ba_info" (float64 [lib.BA_INFO_WORDS]) of the newest adjustment (status lib.BA_NOTHING before the first).
         With world_upkeep it holds "world_upkeep_report" (int32 [lib.WORLD_UPKEEP_REPORT_WORDS]) once the upkeep has been called, and
-        the rows of "world_match" index the map as it stood before the frame's upkeep, which may have moved or removed them."""
+        the rows of "world_match" index the map as it stood before the frame's upkeep, which may have moved or removed them.
+        With trajectory_eval it holds "trajectory_eval" (float64 [8]): the frame's row of the log."""
         return self._geometry
 
     def _track_device(self, m, nm):
@@ -882,6 +985,9 @@ class SequenceTracker:
     world_upkeep / world_merge / world_merge_thresh / world_cull_age / world_cull_min_views / world_high_water / world_low_water:
     PointTracker's upkeep of the world map after every insert (needs world_map): revisits merged, weak rows
     culled, the least valuable rows evicted before the map is full; read it with tracker.last_geometry() and world_upkeep_report().
+    ground_truth / gt_index / trajectory_eval / eval_align / eval_table: PointTracker's trajectory evaluation against ground-truth
+    poses (needs intrinsics): evaluate_trajectory() on demand and, with "observe", a per-frame log on the
+    device; read it with trajectory_eval_log() and tracker.last_geometry().
     Everything from geometric_check on is given by keyword (`**tracker_options`) and goes to PointTracker as it is: its names,
     defaults and checks are PointTracker's."""
 
@@ -958,6 +1064,12 @@ class SequenceTracker:
 
     def loop_closures(self):
         return self.tracker.loop_closures()
+
+    def evaluate_trajectory(self, which=None, **options):
+        return self.tracker.evaluate_trajectory(which, **options)
+
+    def trajectory_eval_log(self):
+        return self.tracker.trajectory_eval_log()
 
     def landmarks_device(self, min_views=2, min_parallax_deg=1.0, max_reproj=2.0):
         return self.tracker.landmarks_device(min_views, min_parallax_deg, max_reproj)
