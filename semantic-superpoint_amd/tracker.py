@@ -440,7 +440,7 @@ class PointTracker(object):
             self._abs_table = L.pose_table(self.trajectory_rows, self.device)
         a = self._pnp_one("_abs", m.shape[0])
         g = dict(g)
-        if self._abs_have and self._abs_lm["landmarks"].shape[0] == self._table["row_cap"]:
+        if self._abs_have:            # (kept at the row_cap of the frame before: a landmark names its point by index, not by row)
             corr, n = L.op_landmark_matches(self._abs_lm["landmarks"], self._abs_lm["n_landmarks"], m, nm, pts_new, out=a)
             res = L.op_pnp_ransac(a["corr"], n[0:1], self._intr[0, 1:2], seed, thresh=self.absolute_thresh,
                                   min_inliers=self.absolute_min_inliers, out=a)
@@ -493,8 +493,10 @@ class PointTracker(object):
             self._world = L.world_buffers(self.world_cap, device=self.device)
             self._world_table = L.pose_table(self.trajectory_rows, self.device)
         if self._world_match is None or self._world_match[0].shape[0] != cap:
-            self._world_match = (torch.zeros(cap, 3, dtype=torch.float32, device=self.device),
-                                 torch.zeros(1, dtype=torch.int32, device=self.device))
+            old, self._world_match = self._world_match, (torch.zeros(cap, 3, dtype=torch.float32, device=self.device),
+                                                         torch.zeros(1, dtype=torch.int32, device=self.device))
+            if old is not None:       # grown by copying: the matcher leaves the rows past n_match as they were
+                self._world_match[0][:old[0].shape[0]] = old[0]
         w, a, count = self._world, self._pnp_one("_world_pnp", cap), self._counts[dslot:dslot + 1]
         self._loop_seed = seed
         m, nm = L.op_match_world(w, self._desc[dslot], count, self.nn_thresh, out=self._world_match)
@@ -617,11 +619,17 @@ class PointTracker(object):
         """The bundle adjustment of the window ending at the newest frame (after _track_device): map window, triangulate, adjust
         and, with "apply", the write-back into the trajectory."""
         row_cap = self._table["row_cap"]
-        if self._ba is None or self._ba["rms"].shape[0] != row_cap:
+        if self._ba is None:
             self._ba = L.ba_buffers(self.maxl, row_cap, self.device)
             self._ba["info"][0:1] = L.BA_NOTHING
             self._ba["info"][7:8] = 1e-4
-            self._ba_ran = False
+        elif self._ba["rms"].shape[0] != row_cap:   # the table grew (_ensure): so does the newest adjustment, its rows in their places
+            old, self._ba = self._ba, L.ba_buffers(self.maxl, row_cap, self.device)
+            rows = old["rms"].shape[0]
+            self._ba["info"].copy_(old["info"])
+            self._ba["cams"].copy_(old["cams"])
+            self._ba["X"][:rows] = old["X"]
+            self._ba["rms"][:rows] = old["rms"]
         if self._frames >= 2 and self._traj_table is not None and self._frames % self.bundle_every == 0:
             cams, rows = self._window_rows("_ba_lm", *self.landmark_params)
             res = L.op_bundle_adjust(self._table, self._pts, self._frames % self.maxl, cams, rows, self.bundle_iterations, out=self._ba)
@@ -892,10 +900,12 @@ class PointTracker(object):
         """The same update from device tensors, e.g. one image's slice of Engine.describe_points: pts [cap, >= 2] rows
         starting (x, y), count int32 [1] (or 0-d), desc float32 [cap, 256] unit rows.  Matching and the track update are
         queued on the current stream; nothing is copied to the host and the host is not synchronised (the first call, and a
-        call with a larger cap than any before, allocate).  A cap above lib.MATCH_MAX_POINTS is cut to that many rows (and the
-        count with it).  get_matches / get_mscores / all_pts read back on demand and describe the NEWEST frame: matches of
-        earlier frames that were never asked for are dropped, so get_mscores() is the last non-empty match set among the
-        frames it was asked about, not among all frames as after `update`.
+        call with a larger cap than any before, allocate).  A frame whose cap makes the buffers grow gives the results of a tracker
+        that had that capacity from the start: the table, the kept landmarks of absolute_pose, the newest bundle adjustment and the
+        loop edges are carried into the larger buffers, and no result depends on the capacity.  A cap above
+        lib.MATCH_MAX_POINTS is cut to that many rows (and the count with it).  get_matches / get_mscores / all_pts read back on
+        demand and describe the NEWEST frame: matches of earlier frames that were never asked for are dropped, so get_mscores()
+        is the last non-empty match set among the frames it was asked about, not among all frames as after `update`.
         cls: uint8 [cap] classes of the rows (Engine.describe_points(classes=True)); required by a class-consistent tracker,
         ignored by a plain one."""
         if self.class_consistent:
