@@ -891,6 +891,33 @@ int ssp_op_world_upkeep(const float* match_dev, const int32_t* n_match_dev, int 
                         int32_t* slot_of_tid_dev, int32_t* state_dev, int32_t* report_dev, int64_t* totals_dev, void* workspace_dev,
                         void* stream);
 
+/* ---- world map classes ---------------------------------------------------------------------------
+ * What every landmark lies on: a class vote per track, the map read out as a labelled point cloud, and ssp_match_world restricted
+ * to pairs of one known, kept class.  The rules are restated in numpy by tests/world_classes_ref.py.  No call synchronises with the
+ * host or allocates.
+ *   votes_dev uint16 [tid_cap], keyed by TRACK ID (map slots move under the upkeep): the low byte is the class, the high byte the
+ *   vote count; zeroed memory = no class yet.  The decoded class is SSP_CLASS_NONE when the count is 0, else the low byte.
+ * ssp_op_track_class_votes: once per frame, beside ssp_op_world_insert and with its landmarks_dev / n_landmarks_dev / row_cap /
+ *   count_new_dev / point_cap; cls_new_dev uint8 [point_cap]: the class of every point of the newest frame.  A landmark row (track
+ *   id t, newest-frame index p) takes part iff 0 <= p < count, 0 <= t < tid_cap and c = cls_new[p] != SSP_CLASS_NONE (the insert's
+ *   test without X).  Boyer-Moore majority step on votes[t]: count 0 -> (c, 1); the same class -> count = min(count + 1, 255);
+ *   another class -> count - 1, the class byte kept.  Track ids must be unique within a call.
+ * ssp_op_world_classes: out_dev uint8 [map_cap] = the decoded class of tid_dev[i] for i < n_rows (state_dev[0], clamped),
+ *   SSP_CLASS_NONE past that and for a track id outside [0, tid_cap).
+ * ssp_match_world_classes: ssp_match_world with one more condition.  With class(i) the decoded class of map row i's track, the pair
+ *   (i, j) is a candidate iff class(i) == cls2_dev[j], class(i) != SSP_CLASS_NONE and bit class(i) of keep_mask (256 bits on the
+ *   HOST, ssp_op_filter_points' layout) is set; any other pair takes part in neither arg-min, and a row or column without a
+ *   candidate gives no match.  With every class equal, known and kept the output is bit-identical to ssp_match_world's.
+ *   workspace_dev: ssp_match_world_workspace_bytes(map_cap, cap) bytes. */
+int ssp_op_track_class_votes(const double* landmarks_dev, const int32_t* n_landmarks_dev, int row_cap, const uint8_t* cls_new_dev,
+                             const int32_t* count_new_dev, int point_cap, uint16_t* votes_dev, int tid_cap, void* stream);
+int ssp_op_world_classes(const int32_t* tid_dev, const int32_t* state_dev, int map_cap, const uint16_t* votes_dev, int tid_cap,
+                         uint8_t* out_dev, void* stream);
+int ssp_match_world_classes(const float* desc_dev, const int32_t* tid_dev, const int32_t* state_dev, int map_cap,
+                            const uint16_t* votes_dev, int tid_cap, const float* desc2_dev, const uint8_t* cls2_dev,
+                            const int32_t* count2_dev, int cap, const uint32_t keep_mask[8], float nn_thresh, void* workspace_dev,
+                            float* match_dev, int32_t* n_match_dev, void* stream);
+
 /* ---- trajectory evaluation -----------------------------------------------------------------------
  * A trajectory table against ground-truth poses: the alignment, the absolute and the relative pose errors, and their statistics.
  * The rules are restated in numpy by tests/traj_eval_ref.py.  fp64 without contraction, no floating-point atomics, every sum in one

@@ -1008,8 +1008,8 @@ int ssp_match_world(const float* desc_dev, const int32_t* state_dev, int map_cap
   hipStream_t st = (hipStream_t)stream;
   const MatchWs w = match_carve(map_cap, cap, workspace_dev);
   HIPCHK(hipMemsetAsync(w.rowmin, 0xFF, w.keys * sizeof(uint64_t), st));
-  hipLaunchKernelGGL(world_match_kernel, dim3(cdiv(map_cap, WORLD_STRIP), WORLD_SPLIT_MAX), dim3(256), 0, st, desc_dev, state_dev, map_cap, desc2_dev,
-                     count2_dev, cap, w.rowmin, w.colmin);
+  hipLaunchKernelGGL(world_match_kernel<false>, dim3(cdiv(map_cap, WORLD_STRIP), WORLD_SPLIT_MAX), dim3(256), 0, st, desc_dev, state_dev, map_cap,
+                     desc2_dev, count2_dev, cap, w.rowmin, w.colmin, WorldClasses{});
   hipLaunchKernelGGL(world_compact_kernel, dim3(1), dim3(WORLD_BLOCK), 0, st, (const uint64_t*)w.rowmin, (const uint64_t*)w.colmin, state_dev,
                      map_cap, count2_dev, cap, nn_thresh, match_dev, n_match_dev);
   HIPCHK(hipGetLastError());

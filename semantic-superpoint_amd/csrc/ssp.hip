@@ -42,6 +42,7 @@
 #include "pnp_kernels.hip.h"
 #include "ba_kernels.hip.h"
 #include "world_kernels.hip.h"
+#include "world_class_kernels.hip.h"
 #include "world_upkeep_kernels.hip.h"
 #include "traj_eval_kernels.hip.h"
 #include "loop_kernels.hip.h"
@@ -3214,5 +3215,6 @@ int ssp_debug_buffer(ssp_handle* h, int slot, const char* name, float** ptr, siz
 extern "C" {
 #include "ops_host.hip.h"
 #include "world_upkeep_host.hip.h"
+#include "world_class_host.hip.h"
 #include "traj_eval_host.hip.h"
 }  // extern "C"

@@ -11,6 +11,11 @@
 //                          when a small map's sweep is split over several workgroups, decided on the device).  Column minima
 //                          cross strips by the 64-bit atomicMin of match_dist_kernel (a minimum of unique keys has no order to
 //                          depend on), issued only when the key is below the value already there: a stale read only costs an atomic.
+//                          CLASSES (ssp_match_world_classes): a pair (i, j) is a candidate iff the class voted
+//                          for map row i's track equals the frame row's, is known, and is kept by the mask; any other pair takes
+//                          part in neither arg-min.  The strip's 128 class codes (one byte each, WORLD_CLASS_NONE = never a candidate)
+//                          and every tile's 32 frame codes (an unknown frame class becomes 256, which no byte equals) go through
+//                          LDS beside the tile; the epilogue reads 4 + 1 words of them.  CLASSES = false reads none of it.
 //   world_compact_kernel   one workgroup: thread t owns the map rows [t c, (t + 1) c), c = ceil(n_rows / 1024); count, scan, write:
 //                          the mutual matches below the threshold in ascending map row
 //   world_anchor_kernel    one thread: the anchor rule (section 29) from the newest trajectory row's flags and the map's state; the
@@ -41,12 +46,34 @@ namespace sspk {
 #define WORLD_CLS_SKIP (-2)
 #define WORLD_CLS_NEW (-1)
 
+#define WORLD_CLASS_NONE 255
+
 typedef float world_floatx16 __attribute__((ext_vector_type(16)));
 
+// the class arguments of world_match_kernel<true> (section 42; the votes are kept by world_class_kernels.hip.h)
+struct WorldClasses {
+  const int32_t* map_tid;   // [map_cap]: the track id of every map slot
+  const uint16_t* votes;    // [tid_cap]
+  const uint8_t* cls2;      // [cap]: the class of every frame row
+  int tid_cap;
+  uint32_t keep[8];         // bit c of word c / 32: map rows of class c take part
+};
+
+__device__ __forceinline__ int world_class_decode(uint32_t v) { return (v >> 8) ? (int)(v & 255u) : WORLD_CLASS_NONE; }
+
+// the decoded class of track t; an id outside [0, tid_cap) has none
+__device__ __forceinline__ int world_class_of(const uint16_t* __restrict__ votes, int t, int tid_cap) {
+  return (t >= 0 && t < tid_cap) ? world_class_decode(votes[t]) : WORLD_CLASS_NONE;
+}
+
+template <bool CLASSES>
 __global__ __launch_bounds__(256, 2) void world_match_kernel(const float* __restrict__ map_desc, const int32_t* __restrict__ world_state,
                                                           int map_cap, const float* __restrict__ d2, const int32_t* __restrict__ count2,
-                                                          int cap, uint64_t* __restrict__ rowmin, uint64_t* __restrict__ colmin) {
+                                                          int cap, uint64_t* __restrict__ rowmin, uint64_t* __restrict__ colmin,
+                                                          const WorldClasses wc) {
   __shared__ float4 tile[2][WORLD_TILE * WORLD_LDS_ROW];
+  __shared__ uint32_t strip_cls[CLASSES ? WORLD_STRIP / 4 : 1];   // byte k: the class code of map row strip0 + k
+  __shared__ int tile_cls[2][CLASSES ? WORLD_TILE : 1];           // the class code of the staged tile's frame rows
   const int n1 = min(max(world_state[0], 0), map_cap), n2 = min(max(count2[0], 0), cap);
   const int strip0 = blockIdx.x * WORLD_STRIP;
   if (strip0 >= n1 || n2 <= 0) return;   // (the whole workgroup: no barrier is left waiting)
@@ -74,6 +101,18 @@ __global__ __launch_bounds__(256, 2) void world_match_kernel(const float* __rest
   for (int q = 0; q < 8; ++q)
     tile[0][(4 * q + wave) * WORLD_LDS_ROW + lane] =
         reinterpret_cast<const float4*>(d2 + (size_t)min(y * WORLD_TILE + 4 * q + wave, n2 - 1) * 256)[lane];
+  if (CLASSES) {
+    // the classes are loaded under the descriptors' clamp: a copy of row n1 - 1 (n2 - 1) is a candidate exactly where that row is
+    if (tid < WORLD_STRIP) {
+      const int c = world_class_of(wc.votes, wc.map_tid[min(strip0 + tid, n1 - 1)], wc.tid_cap);
+      const bool kept = c != WORLD_CLASS_NONE && ((wc.keep[c >> 5] >> (c & 31)) & 1u);
+      reinterpret_cast<uint8_t*>(strip_cls)[tid] = (uint8_t)(kept ? c : WORLD_CLASS_NONE);
+    }
+    if (tid < WORLD_TILE) {
+      const int c = wc.cls2[min(y * WORLD_TILE + tid, n2 - 1)];
+      tile_cls[0][tid] = c == WORLD_CLASS_NONE ? 256 : c;
+    }
+  }
   __syncthreads();
   int buf = 0;
   for (int tl = y; tl < n_tiles; tl += split, buf ^= 1) {
@@ -97,13 +136,20 @@ __global__ __launch_bounds__(256, 2) void world_match_kernel(const float* __rest
       // distance and a larger index, so it never is a minimum, and its own minimum is never stored.
       const int j = j0 + r;
       uint64_t cbest = ~0ull;
+      const int cj = CLASSES ? tile_cls[buf][r] : 0;
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
         const int i = wi + (t & 3) + 8 * (t >> 2) + 4 * h;
         const float dd = sqrtf(2.f - 2.f * fminf(fmaxf(acc[t], -1.f), 1.f));   // (the correctly rounded root: describe_kernels.hip.h)
         const uint64_t hi = (uint64_t)__float_as_uint(dd) << 32;
-        kr[t] = min_u64(kr[t], hi | (uint32_t)j);
-        cbest = min_u64(cbest, hi | (uint32_t)i);
+        if (CLASSES) {   // rows 8 (t >> 2) + 4h .. + 3 of the wave: one word, two addresses per wave
+          const bool ok = (int)((strip_cls[wave * 8 + 2 * (t >> 2) + h] >> (8 * (t & 3))) & 255u) == cj;
+          kr[t] = min_u64(kr[t], ok ? hi | (uint32_t)j : ~0ull);
+          cbest = min_u64(cbest, ok ? hi | (uint32_t)i : ~0ull);
+        } else {
+          kr[t] = min_u64(kr[t], hi | (uint32_t)j);
+          cbest = min_u64(cbest, hi | (uint32_t)i);
+        }
       }
       cbest = min_u64(cbest, shfl_xor_u64(cbest, 32));
       if (h == 0 && j < n2) {
@@ -118,6 +164,10 @@ __global__ __launch_bounds__(256, 2) void world_match_kernel(const float* __rest
 #pragma unroll
       for (int q = 0; q < 8; ++q)
         stage[q] = reinterpret_cast<const float4*>(d2 + (size_t)min(j0 + split * WORLD_TILE + 4 * q + wave, n2 - 1) * 256)[lane];
+      if (CLASSES && tid < WORLD_TILE) {
+        const int c = wc.cls2[min(j0 + split * WORLD_TILE + tid, n2 - 1)];
+        tile_cls[buf ^ 1][tid] = c == WORLD_CLASS_NONE ? 256 : c;
+      }
 #pragma unroll
       for (int q = 0; q < 8; ++q) tile[buf ^ 1][(4 * q + wave) * WORLD_LDS_ROW + lane] = stage[q];
     }

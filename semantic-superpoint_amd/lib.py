@@ -223,6 +223,9 @@ def _signatures():
         "ssp_world_repair": ([vp] * 5 + [i, i, vp, vp], i),
         "ssp_world_upkeep_workspace_bytes": ([i], sz),
         "ssp_op_world_upkeep": ([vp, vp, i, vp, vp, i, vp, i, vp, i, vp, i, i, vp, vp, i, i] + [vp] * 13, i),
+        "ssp_op_track_class_votes": ([vp, vp, i, vp, vp, i, vp, i, vp], i),
+        "ssp_op_world_classes": ([vp, vp, i, vp, i, vp, vp], i),
+        "ssp_match_world_classes": ([vp, vp, vp, i, vp, i, vp, vp, vp, i, P(u32), f, vp, vp, vp, vp], i),
         "ssp_op_traj_align": ([vp, i, vp, i, vp, i, i, vp, i, i, i, vp, vp], i),
         "ssp_op_traj_ape": ([vp, i, vp, i, vp, i, i, vp, i, i, vp, vp, vp, vp, vp], i),
         "ssp_op_traj_rpe_delta": ([vp, i, vp, i, vp, i, i, vp, i, i, vp, i, i, vp, vp, vp, vp], i),
@@ -2644,6 +2647,115 @@ def op_world_upkeep(world, match, n_match, landmarks, n_landmarks, pts_new, coun
                                        _ptr(world["slot_of_tid"]), _ptr(world["state"]), _ptr(upkeep["report"]),
                                        _ptr(upkeep["totals"]), _ptr(upkeep["ws"]), _stream()))
     return world
+
+
+# ---- world map classes ----
+WORLD_CLASS_KEYS = ("votes",)
+WORLD_CLASS_SPEC = (("tid_cap",), {"votes": (torch.uint16, ("tid_cap",))})
+
+
+def world_class_buffers(tid_cap=1 << 22, device="cuda"):
+    """The class votes of a world map, zeroed: {"votes": uint16 [tid_cap], one entry per TRACK ID: the low
+    byte is the class, the high byte the vote count; zero = no class yet} plus the host-known "tid_cap" (the map's)."""
+    tid_cap = int(tid_cap)
+    if not 1 <= tid_cap < 2 ** 31:
+        raise ValueError("1 <= tid_cap < 2^31 required (got %d)" % tid_cap)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("world_class_buffers needs a HIP device: the MI355X path has no CPU fallback")
+    classes = _alloc(WORLD_CLASS_SPEC, (tid_cap,), device)
+    classes.update(tid_cap=tid_cap)
+    return classes
+
+
+def _world_classes(classes, tid_cap=None):
+    """checks a world_class_buffers dict (against the map's tid_cap where given); -> tid_cap"""
+    if not isinstance(classes, dict) or any(k not in classes for k in WORLD_CLASS_KEYS + ("tid_cap",)):
+        raise ValueError("classes must be the dict of world_class_buffers")
+    own = int(classes["tid_cap"])
+    if own < 1 or (tid_cap is not None and own != tid_cap):
+        raise ValueError("classes must be the dict of world_class_buffers(tid_cap) with the map's tid_cap%s (got %d)"
+                         % ("" if tid_cap is None else " = %d" % tid_cap, own))
+    _check_family(classes, "classes", WORLD_CLASS_SPEC, (own,), WORLD_CLASS_KEYS, "world_class_buffers")
+    return own
+
+
+def _keep_words(mask, name="map_keep"):
+    """the eight 32-bit words of a class_mask as a ctypes array; None = every class"""
+    words = [0xFFFFFFFF] * 8 if mask is None else [int(w) for w in mask]
+    if len(words) != 8 or any(not 0 <= w < 1 << 32 for w in words):
+        raise ValueError("%s must be eight 32-bit words (class_mask)" % name)
+    return (C.c_uint32 * 8)(*words)
+
+
+def op_track_class_votes(classes, landmarks, n_landmarks, cls_new, count_new):
+    """One frame's class votes (ssp_op_track_class_votes), in place.  classes: the dict of
+    world_class_buffers; landmarks float64 [row_cap, LANDMARK_WORDS], n_landmarks int32 [1] and count_new int32 [1] as given to
+    op_world_insert; cls_new uint8 [point_cap]: the class of every point of the newest frame.  A landmark row of track t whose
+    newest-frame index p has 0 <= p < count, with 0 <= t < tid_cap and c = cls_new[p] != CLASS_NONE, votes: no votes yet -> (c, 1);
+    the same class -> one vote more (at most 255); another class -> one vote less, the class kept.  Track ids must be unique within
+    a call.  Returns classes.  No host synchronisation."""
+    lib = load_library()
+    tid_cap = _world_classes(classes)
+    row_cap = _landmark_rows(landmarks, n_landmarks)
+    _tensor(cls_new, "cls_new", torch.uint8, (None,), "the classes of the newest frame's points")
+    _count(count_new, "count_new", 1)
+    point_cap = cls_new.shape[0]
+    if not (1 <= row_cap <= TRACK_MAX_LENGTH * MATCH_MAX_POINTS and 1 <= point_cap <= MATCH_MAX_POINTS):
+        raise ValueError("1 <= row_cap <= %d and 1 <= point_cap <= %d required" % (TRACK_MAX_LENGTH * MATCH_MAX_POINTS, MATCH_MAX_POINTS))
+    with torch.cuda.device(landmarks.device):
+        _check(lib.ssp_op_track_class_votes(_ptr(landmarks), _ptr(n_landmarks), row_cap, _ptr(cls_new), _ptr(count_new), point_cap,
+                                            _ptr(classes["votes"]), tid_cap, _stream()))
+    return classes
+
+
+def op_world_classes(world, classes, out=None):
+    """The map as a labelled point cloud (ssp_op_world_classes): uint8 [map_cap], the voted class of the
+    track of every map row below n_rows (CLASS_NONE while it has no votes) and CLASS_NONE past that; `out`: such a tensor to fill.
+    No host synchronisation."""
+    lib = load_library()
+    map_cap, tid_cap = _world_map(world)
+    _world_classes(classes, tid_cap)
+    if out is None:
+        out = torch.empty(map_cap, dtype=torch.uint8, device=world["tid"].device)
+    _tensor(out, "out", torch.uint8, (map_cap,), "map_cap of world")
+    with torch.cuda.device(out.device):
+        _check(lib.ssp_op_world_classes(_ptr(world["tid"]), _ptr(world["state"]), map_cap, _ptr(classes["votes"]), tid_cap, _ptr(out),
+                                        _stream()))
+    return out
+
+
+def op_match_world_classes(world, classes, desc2, cls2, count2, nn_thresh, map_keep=None, out=None):
+    """op_match_world restricted to pairs of one class (ssp_match_world_classes).  classes: the dict of
+    world_class_buffers beside the map; cls2 uint8 [cap]: the class of every row of desc2; map_keep: a class_mask of the map classes
+    that take part (None: all).  Map row i and frame row j are a candidate iff the class voted for row i's track equals cls2[j], is
+    not CLASS_NONE and is kept; any other pair takes part in neither nearest-neighbour search.  With every class equal, known and
+    kept the result is bit-identical to op_match_world's.  Returns (match, n_match) as op_match_world does.  No host
+    synchronisation."""
+    lib = load_library()
+    map_cap, tid_cap = _world_map(world)
+    _world_classes(classes, tid_cap)
+    if nn_thresh < 0.0:
+        raise ValueError("'nn_thresh' should be non-negative")
+    keep = _keep_words(map_keep)
+    _tensor(desc2, "desc2", torch.float32, (None, 256), "unit rows")
+    cap = desc2.shape[0]
+    if not 1 <= cap <= MATCH_MAX_POINTS:
+        raise ValueError("1 <= cap <= %d frame rows (got %d)" % (MATCH_MAX_POINTS, cap))
+    _tensor(cls2, "cls2", torch.uint8, (cap,), "one class per row of desc2")
+    _count(count2, "count2", 1)
+    if world["ws"].numel() < lib.ssp_match_world_workspace_bytes(map_cap, cap):
+        raise ValueError("world['ws'] is smaller than ssp_match_world_workspace_bytes(%d, %d)" % (map_cap, cap))
+    if out is None:
+        out = (torch.empty(cap, 3, dtype=torch.float32, device=desc2.device), torch.empty(1, dtype=torch.int32, device=desc2.device))
+    match, n_match = out
+    _tensor(match, "out[0]", torch.float32, (cap, 3), "cap rows of desc2")
+    _count(n_match, "out[1]", 1)
+    with torch.cuda.device(desc2.device):
+        _check(lib.ssp_match_world_classes(_ptr(world["desc"]), _ptr(world["tid"]), _ptr(world["state"]), map_cap,
+                                           _ptr(classes["votes"]), tid_cap, _ptr(desc2), _ptr(cls2), _ptr(count2), cap, keep,
+                                           float(np.float32(nn_thresh)), _ptr(world["ws"]), _ptr(match), _ptr(n_match), _stream()))
+    return match, n_match
 
 
 # ---- trajectory evaluation (DESIGN.md section 40) ----

@@ -105,7 +105,7 @@ class PointTracker(object):
     frame's window (landmark_params, buffers of the tracker's own) enter a map of world_cap rows that keeps X and the newest
     descriptor of every track after the track has left the window (lib.op_world_insert, while the map is anchored to the
     trajectory; world_patience frames without an anchor clear it).  Every frame's unfiltered descriptors are matched against the
-    whole map (lib.op_match_world with nn_thresh; with class_consistent=True the map matcher still ignores the classes), joined
+    whole map (lib.op_match_world with nn_thresh; class_consistent does not reach the map matcher: world_classes="match" does), joined
     with its points (lib.op_world_correspondences) and given to the P3P RANSAC (world_thresh pixels, world_min_inliers, the frame's
     check seed): last_geometry() gains the "world_*" keys and world_trajectory() one row.  "relocalise" also rewrites the frame's
     trajectory row and the chain state from that pose (lib.op_world_repair) when the two-view chain could not determine them or
@@ -127,6 +127,15 @@ class PointTracker(object):
     world_cap // 8); a negative world_cull_age or world_high_water switches that phase off.  The map is compacted, so map rows
     change their slots: last_geometry()["world_match"] indexes the map as it stood before the frame's upkeep.  last_geometry() gains
     "world_upkeep_report"; world_upkeep_report() reads the running totals.
+    world_classes (needs world_map, and every frame's classes `cls` as class_consistent does; the two options
+    are independent): None runs none of it.  "observe": after every frame's landmark selection, beside the insert and before the
+    upkeep, each landmark's track takes a vote on its class from the class of its point in the newest frame
+    (lib.op_track_class_votes; votes per track id, so they survive the upkeep's moves and a cleared map); world_classes_device()
+    and world_map(classes=True) read the map as a labelled point cloud; every other output stays as it was.  "match": the frame is
+    also matched against the map by lib.op_match_world_classes: a map row takes part only with frame points of its own voted class,
+    and only when that class is known and kept by world_keep_classes / world_drop_classes (one of them, ids below 255; neither: all
+    classes), so the world pose, relocalisation, loop closure and the upkeep's merge, which all read these match rows, never join
+    across classes.  reset_world_classes() zeroes the votes.
     ground_truth (needs intrinsics): float64 [N, 12] camera-to-world rows (R | C), the layout of a KITTI poses
     file; gt_index: int32 [trajectory_rows], the ground-truth row of each frame (-1: none), or None when frame f is row f.
     evaluate_trajectory(which, **options) scores trajectory(), absolute_trajectory() or world_trajectory() on demand (alignment, ATE,
@@ -142,8 +151,20 @@ class PointTracker(object):
                  loop_closure=None, loop_min_gap=32, loop_min_inliers=12, loop_cooldown=32, loop_iterations=10, loop_weight=1.0,
                  model_ratio=0.40, rotation_eps=0.02, normal_margin=0.01, world_upkeep=None, world_merge=True, world_merge_thresh=None,
                  world_cull_age=None, world_cull_min_views=3, world_high_water=None, world_low_water=None, ground_truth=None,
-                 gt_index=None, trajectory_eval=None, eval_align="sim3", eval_table="trajectory"):
+                 gt_index=None, trajectory_eval=None, eval_align="sim3", eval_table="trajectory", world_classes=None,
+                 world_keep_classes=None, world_drop_classes=None):
         stage = (intrinsics, geometric_check, landmark_params)
+        _check_mode("world_classes", world_classes, "observe", "match")
+        if world_classes is None:
+            if world_keep_classes is not None or world_drop_classes is not None:
+                raise ValueError("world_keep_classes / world_drop_classes need world_classes='match'")
+        else:
+            if world_map is None:
+                raise ValueError("world_classes needs world_map: the votes are on that map's landmarks")
+            if world_keep_classes is not None or world_drop_classes is not None:
+                if world_classes != "match":
+                    raise ValueError("world_keep_classes / world_drop_classes need world_classes='match'")
+                world_keep_classes = L.class_mask(keep=world_keep_classes, drop=world_drop_classes, n_classes=L.CLASS_NONE)
         _check_mode("trajectory_eval", trajectory_eval, "observe")
         if eval_table not in ("trajectory", "world"):
             raise ValueError("eval_table must be 'trajectory' or 'world' (got %r)" % (eval_table,))
@@ -294,6 +315,10 @@ class PointTracker(object):
                                             cull_min_views=int(world_cull_min_views), high_water=int(world_high_water),
                                             low_water=int(world_low_water))
         self._upkeep = None       # lib.world_upkeep_buffers: the scratch, the last report, the running totals
+        self.world_classes = world_classes
+        self.world_keep_mask = world_keep_classes      # eight 32-bit words (lib.class_mask), or None: every class
+        self._world_votes = None  # lib.world_class_buffers: the class votes per track id
+        self._world_cls = None    # uint8 [cap]: the classes of the newest frame's points (world_classes only)
         self.loop_closure = loop_closure
         self.loop_min_gap, self.loop_min_inliers, self.loop_cooldown = int(loop_min_gap), int(loop_min_inliers), int(loop_cooldown)
         self.loop_iterations, self.loop_weight = int(loop_iterations), float(loop_weight)
@@ -333,6 +358,8 @@ class PointTracker(object):
             if self._cap:
                 cls[:, :self._cap] = self._cls
             self._cls = cls
+        if self.world_classes is not None:
+            self._world_cls = torch.full((cap,), L.CLASS_NONE, dtype=torch.uint8, device=dev)
         self._table, self._spare, self._pts, self._desc, self._counts, self._cap = table, spare, pts, desc, counts, cap
         self._zero = torch.zeros(1, dtype=torch.int32, device=dev)
 
@@ -357,6 +384,8 @@ class PointTracker(object):
         self._counts[dslot:dslot + 1] = count
         if self.class_consistent:
             self._cls[dslot, :n] = cls
+        if self.world_classes is not None:
+            self._world_cls[:n] = cls
         m, nm = self._match_device()
         if self.geometric_check is not None:
             m, nm = self._check_device(m, nm)
@@ -492,6 +521,8 @@ class PointTracker(object):
         if self._world is None:
             self._world = L.world_buffers(self.world_cap, device=self.device)
             self._world_table = L.pose_table(self.trajectory_rows, self.device)
+            if self.world_classes is not None:
+                self._world_votes = L.world_class_buffers(self._world["tid_cap"], self.device)
         if self._world_match is None or self._world_match[0].shape[0] != cap:
             old, self._world_match = self._world_match, (torch.zeros(cap, 3, dtype=torch.float32, device=self.device),
                                                          torch.zeros(1, dtype=torch.int32, device=self.device))
@@ -499,7 +530,11 @@ class PointTracker(object):
                 self._world_match[0][:old[0].shape[0]] = old[0]
         w, a, count = self._world, self._pnp_one("_world_pnp", cap), self._counts[dslot:dslot + 1]
         self._loop_seed = seed
-        m, nm = L.op_match_world(w, self._desc[dslot], count, self.nn_thresh, out=self._world_match)
+        if self.world_classes == "match":
+            m, nm = L.op_match_world_classes(w, self._world_votes, self._desc[dslot], self._world_cls, count, self.nn_thresh,
+                                             map_keep=self.world_keep_mask, out=self._world_match)
+        else:
+            m, nm = L.op_match_world(w, self._desc[dslot], count, self.nn_thresh, out=self._world_match)
         corr, n = L.op_world_correspondences(w, m, nm, pts_new, count, out=a)
         res = L.op_pnp_ransac(a["corr"], n[0:1], self._intr[0, 1:2], seed, thresh=self.world_thresh,
                               min_inliers=self.world_min_inliers, out=a)
@@ -524,6 +559,8 @@ class PointTracker(object):
                 lms, n_lms = self._window_landmarks("_world_lm", *self.landmark_params)
         L.op_world_insert(self._world, lms, n_lms, self._desc[dslot], self._counts[dslot:dslot + 1], self._traj_table, self._frames,
                           self.world_patience)
+        if self.world_classes is not None:        # beside the insert, before the upkeep: the votes are per track id, not per slot
+            L.op_track_class_votes(self._world_votes, lms, n_lms, self._world_cls, self._counts[dslot:dslot + 1])
         if self.world_upkeep is not None:         # after loop closure and its write-back: both saw the map the frame was matched with
             if self._upkeep is None:
                 self._upkeep = L.world_upkeep_buffers(self.world_cap, self.device)
@@ -604,16 +641,33 @@ class PointTracker(object):
             return np.zeros(4, dtype=np.int64)
         return self._upkeep["totals"].cpu().numpy()
 
-    def world_map(self):
+    def world_map(self, classes=False):
         """The map as numpy: (rows float64 [n_rows, 8] = (tid, X, Y, Z, n_views, rms, first_frame, last_frame), descriptors float32
-        [n_rows, 256]); one host synchronisation.  Zero rows without world_map or before the first frame."""
+        [n_rows, 256]); one host synchronisation.  Zero rows without world_map or before the first frame.  classes=True (needs
+        world_classes): the rows get a ninth column, the class voted for the row's track (lib.CLASS_NONE while it has none)."""
+        if classes and self.world_classes is None:
+            raise ValueError("world_map(classes=True) needs world_classes")
         if self._world is None:
-            return np.zeros((0, 8)), np.zeros((0, 256), dtype=np.float32)
+            return np.zeros((0, 9 if classes else 8)), np.zeros((0, 256), dtype=np.float32)
         w = self._world
         n = min(max(int(w["state"][0].item()), 0), w["map_cap"])
         cols = [w["tid"][:n].double()[:, None], w["X"][:n], w["n_views"][:n].double()[:, None], w["rms"][:n, None],
                 w["first_frame"][:n].double()[:, None], w["last_frame"][:n].double()[:, None]]
+        if classes:
+            cols.append(self.world_classes_device()[:n].double()[:, None])
         return torch.cat(cols, dim=1).cpu().numpy(), w["desc"][:n].cpu().numpy()
+
+    def world_classes_device(self):
+        """uint8 [world_cap] on the device: the class voted for the track of every map row in use, lib.CLASS_NONE while it has none and
+        past the rows in use (lib.op_world_classes); None without world_classes or before the first frame.  No synchronisation."""
+        if self._world_votes is None:
+            return None
+        return L.op_world_classes(self._world, self._world_votes)
+
+    def reset_world_classes(self):
+        """Zeroes the class votes (a cleared or re-anchored map keeps them: a track id names one scene track for its whole life)."""
+        if self._world_votes is not None:
+            self._world_votes["votes"].zero_()
 
     def _bundle_device(self):
         """The bundle adjustment of the window ending at the newest frame (after _track_device): map window, triangulate, adjust
@@ -876,8 +930,9 @@ class PointTracker(object):
         if pts is None or desc is None:
             print("PointTracker: Warning, no points were added to tracker.")
             return
-        if self.class_consistent:
-            raise ValueError("a class-consistent tracker takes its frames, with their classes, through update_device")
+        if self.class_consistent or self.world_classes is not None:
+            raise ValueError("a class-consistent tracker and one with world_classes take their frames, with their classes, through "
+                             "update_device")
         assert pts.shape[1] == desc.shape[1]
         n = pts.shape[1]
         if self.nn_thresh < 0.0 and n and self._prev_ok and self.all_pts[-1].shape[1]:
@@ -906,11 +961,11 @@ class PointTracker(object):
         lib.MATCH_MAX_POINTS is cut to that many rows (and the count with it).  get_matches / get_mscores / all_pts read back on
         demand and describe the NEWEST frame: matches of earlier frames that were never asked for are dropped, so get_mscores()
         is the last non-empty match set among the frames it was asked about, not among all frames as after `update`.
-        cls: uint8 [cap] classes of the rows (Engine.describe_points(classes=True)); required by a class-consistent tracker,
-        ignored by a plain one."""
-        if self.class_consistent:
+        cls: uint8 [cap] classes of the rows (Engine.describe_points(classes=True)); required by a class-consistent tracker and
+        by one with world_classes, ignored by a plain one."""
+        if self.class_consistent or self.world_classes is not None:
             if cls is None:
-                raise ValueError("a class-consistent tracker needs the classes of every frame (cls)")
+                raise ValueError("a class-consistent tracker and one with world_classes need the classes of every frame (cls)")
             if not cls.is_cuda:
                 raise RuntimeError("cls must live on a HIP device: the MI355X path has no CPU fallback")
             if cls.dtype != torch.uint8 or tuple(cls.shape) != (pts.shape[0],):
@@ -987,8 +1042,11 @@ class SequenceTracker:
     free of host copies and synchronisation.
     world_map / world_cap / world_patience / world_thresh / world_min_inliers: PointTracker's world map of landmarks that outlive
     their window, every frame's pose against it and, with "relocalise", the repair of the trajectory from it (DESIGN.md section
-    29; the map matcher ignores classes); read it with tracker.last_geometry(), world_trajectory(), world_map_device() and
-    world_map().  A step stays free of host copies and synchronisation once allocated.
+    29); read it with tracker.last_geometry(), world_trajectory(), world_map_device() and world_map().  A step stays free of host
+    copies and synchronisation once allocated.
+    world_classes / world_keep_classes / world_drop_classes: PointTracker's class votes on the map's landmarks and, with "match",
+    its class-aware map matcher (needs world_map and a model with a segmentation head); read them with
+    world_classes_device() and world_map(classes=True).  No host copy or synchronisation per step.
     loop_closure / loop_min_gap / loop_min_inliers / loop_cooldown / loop_iterations / loop_weight: PointTracker's loop closure
     over the world map (needs world_map); read it with tracker.last_geometry(), loop_closures() and
     loop_edges_device().
@@ -1007,9 +1065,10 @@ class SequenceTracker:
             raise ValueError("'nn_thresh' should be non-negative")
         self.class_consistent = bool(class_consistent)
         self._mask = None
-        if keep_classes is not None or drop_classes is not None or self.class_consistent:
+        self._with_cls = self.class_consistent or tracker_options.get("world_classes") is not None   # the tracker takes cls
+        if keep_classes is not None or drop_classes is not None or self._with_cls:
             if not hasattr(net, "convSout"):
-                raise ValueError("keep_classes / drop_classes / class_consistent need a model with a segmentation head")
+                raise ValueError("keep_classes / drop_classes / class_consistent / world_classes need a model with a segmentation head")
             if keep_classes is not None or drop_classes is not None:
                 self._mask = L.class_mask(keep=keep_classes, drop=drop_classes, n_classes=net.n_classes)
         self.net, self.device = net, torch.device(device)
@@ -1024,7 +1083,7 @@ class SequenceTracker:
         eng = self.net.engine(1, x.shape[2], x.shape[3], self.device)
         with torch.no_grad():
             eng.forward(x, slot=0, train=False, want=())
-        if self._mask is None and not self.class_consistent:
+        if self._mask is None and not self._with_cls:
             return eng.describe_points(0, 1, conf_thresh=self.conf_thresh, nms_dist=self.nms_dist, subpixel=self.subpixel,
                                        border_remove=self.border_remove)
         o = eng.describe_points(0, 1, conf_thresh=self.conf_thresh, nms_dist=self.nms_dist, subpixel=self.subpixel,
@@ -1039,7 +1098,7 @@ class SequenceTracker:
         xy = pts[:, :2].to(torch.float64)
         if self.subpixel:  # the same float64 sum as lib.points_to_numpy
             xy = xy + pts[:, 3:5].to(torch.float64) - 2
-        self.tracker.update_device(xy, o["count"][0:1], o["desc"][0], o["cls"][0] if self.class_consistent else None)
+        self.tracker.update_device(xy, o["count"][0:1], o["desc"][0], o["cls"][0] if self._with_cls else None)
         return o
 
     def get_tracks(self, min_length):
@@ -1063,8 +1122,11 @@ class SequenceTracker:
     def world_map_device(self):
         return self.tracker.world_map_device()
 
-    def world_map(self):
-        return self.tracker.world_map()
+    def world_map(self, classes=False):
+        return self.tracker.world_map(classes)
+
+    def world_classes_device(self):
+        return self.tracker.world_classes_device()
 
     def world_upkeep_report(self):
         return self.tracker.world_upkeep_report()
